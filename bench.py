@@ -20,6 +20,10 @@ N > 1 (configs[3]: the same 100 GB as ONE archive on N GPUs, size / N of the tex
     `decode_only_value` and `to_host_value` (per-GPU D2H, PCIe-inclusive, never `value`) beside it.  `--replicas` runs the round-1
     shape instead (one archive per GPU, no data-path collective).
 
+A plain run makes the text and its archive, warms up, times the steps and prints the line (`value`, `ms_per_step`); with
+`--dump-outputs DIR` it first writes what the last timed step decoded (dump_outputs).  Everything else above -- the encoder's own
+timing (`ennaf_value`), the full-size check, per-kernel times and `roofline`, the side legs and the reference -- runs with `--full`.
+
 Emits ONE JSON line on rank 0.
 """
 import argparse
@@ -572,11 +576,13 @@ def equal_in_chunks(a, b, step=1 << 30):
     return True
 
 
-def one_gpu_leg(ctx, dev, size, records, seed, steps, warmup, enc_reps=10):
+def one_gpu_leg(ctx, dev, size, records, seed, steps, warmup, enc_reps=10, full=True, dump=None):
     """ennaf then unnaf of `size` bytes of synthetic-ACGT FASTA on this GPU, everything resident in HBM: the archive is made by the GPU
-    encoder (timed on its own: `enc_reps` calls behind two untimed ones, one more instrumented), decoded once untimed and checked at full
-    size (bit-exact in chunks + the position-weighted checksum), then `warmup` - 1 more untimed steps and EXACTLY `steps` timed ones between
-    two device synchronisations, then one instrumented step.  Returns the measurements; text and archive stay alive in the result."""
+    encoder, the first step is untimed, then `warmup` - 1 more untimed steps and EXACTLY `steps` timed ones between two device
+    synchronisations; `dump(r)` takes what the last timed step returned.  With `full`, the encoder is timed on its own (`enc_reps` calls
+    behind two untimed ones, one more instrumented), the first step's text is checked at full size (bit-exact in chunks + the
+    position-weighted checksum) and one instrumented step follows the timed ones.  Returns the measurements; text and archive stay
+    alive in the result."""
     import torch
     from naf_amd import capi, synth
     text = synth.fasta_acgt_device(size, n_records=records, width=80, seed=seed, device=dev)
@@ -588,36 +594,43 @@ def one_gpu_leg(ctx, dev, size, records, seed, steps, warmup, enc_reps=10):
     res_e = [None]
     def enc():
         res_e[0] = ctx.ennaf(text, out=naf_buf)
-    enc_times = timed_calls(enc, enc_reps)                        # two untimed calls first (arena growth, lazy initialisation)
+    res = {}
+    if full:
+        enc_times = timed_calls(enc, enc_reps)                    # two untimed calls first (arena growth, lazy initialisation)
+        _top, enc_all, enc_streams = instrumented(ctx, enc)
+        res.update({"enc_times": enc_times, "enc_kt": {n: (ms, k) for n, ms, k in enc_all}, "enc_streams": enc_streams,
+                    "free_after_encode": torch.cuda.mem_get_info()[0]})
+    else:
+        enc()                                                     # the archive the steps decode
     d_naf, rep = res_e[0]
-    _top, enc_all, enc_streams = instrumented(ctx, enc)
-    free_after_encode = torch.cuda.mem_get_info()[0]
     if big:
         torch.cuda.synchronize(); ctx.release_scratch()        # the encoder's arena (the codes of 100 GB of text among it) before the text is made a second time
     out = torch.empty(n_text + 64, dtype=torch.uint8, device=dev)
     step = lambda: ctx.unnaf(d_naf, capi.OUT_FASTA, out=out)
     r = step()                                                    # untimed: the round trip at full size (size-independent properties)
     torch.cuda.synchronize()
-    ok = equal_in_chunks(r, text)
-    wsum = weighted_sum(text, 0)
-    wsum_ok = wsum == weighted_sum(r, 0)
+    if full:
+        wsum = weighted_sum(text, 0)
+        res.update({"ok": equal_in_chunks(r, text), "wsum": wsum, "wsum_ok": wsum == weighted_sum(r, 0)})
     for _ in range(max(0, warmup - 1)):
         step()
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for _ in range(steps):
-        step()
+        r = step()
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
-    ctx.set_timing(True)
-    step()
-    kt = {n: (ms, k) for n, ms, k in ctx.get_timing()}
-    step_streams = ctx.get_timing_streams()
-    ctx.set_timing(False)
+    if dump is not None:
+        dump(r)
+    if full:
+        ctx.set_timing(True)
+        step()
+        res.update({"kt": {n: (ms, k) for n, ms, k in ctx.get_timing()}, "step_streams": ctx.get_timing_streams()})
+        ctx.set_timing(False)
     del out, r
-    return {"text": text, "d_naf": d_naf, "naf_buf": naf_buf, "rep": rep, "n_text": n_text, "n_naf": int(d_naf.numel()), "ok": ok, "wsum": wsum, "wsum_ok": wsum_ok,
-            "dt": dt, "ms_per_step": dt / steps * 1e3, "value": n_text * steps / dt / 1e9, "kt": kt, "step_streams": step_streams,
-            "enc_times": enc_times, "enc_kt": {n: (ms, k) for n, ms, k in enc_all}, "enc_streams": enc_streams, "free_after_encode": free_after_encode}
+    res.update({"text": text, "d_naf": d_naf, "naf_buf": naf_buf, "rep": rep, "n_text": n_text, "n_naf": int(d_naf.numel()),
+                "dt": dt, "ms_per_step": dt / steps * 1e3, "value": n_text * steps / dt / 1e9})
+    return res
 
 
 def decode_roofline(leg, ms_per_step, my_text=None, frac_mine=1.0, n_naf=None):
@@ -660,6 +673,37 @@ def encode_roofline(leg):
     return er
 
 
+DUMP_BLOCK = 1 << 20         # --dump-outputs: bytes per block sum of the decoded text
+DUMP_SAMPLE = 1 << 22        # --dump-outputs: bytes of the decoded text sampled at positions drawn with a fixed seed
+
+
+def dump_outputs(r, out_dir):
+    """--dump-outputs: what the timed step returned, the decoded text `r`, as float arrays under `out_dir` (about 49 MB
+    at 100 GB): its length, the byte sum of every 1 MiB block (the last one shorter), and the bytes at 4 Mi positions drawn with seed
+    2024 (the same positions in every run of the same size) beside those positions."""
+    import numpy as np
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    n = int(r.numel())
+    sums = []
+    seg_bytes = 32 * DUMP_BLOCK                                   # a multiple of the block: int64 copies of 256 MiB at most
+    for a in range(0, n, seg_bytes):
+        seg = r[a:min(n, a + seg_bytes)]
+        m = int(seg.numel()) // DUMP_BLOCK
+        if m:
+            sums.append(seg[:m * DUMP_BLOCK].view(m, DUMP_BLOCK).sum(dim=1, dtype=torch.int64))
+        if int(seg.numel()) > m * DUMP_BLOCK:
+            sums.append(seg[m * DUMP_BLOCK:].sum(dtype=torch.int64).view(1))
+    pos = np.sort(np.random.default_rng(2024).integers(0, n, DUMP_SAMPLE))
+    sample = r[torch.from_numpy(pos).to(r.device)].cpu().numpy()
+    arrays = {"unnaf_text_bytes": np.array([n], dtype=np.float64),
+              "unnaf_text_block_sums": torch.cat(sums).cpu().numpy().astype(np.float64),
+              "unnaf_text_sample_pos": pos.astype(np.float64),
+              "unnaf_text_sample": sample.astype(np.float32)}
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -680,7 +724,13 @@ def main():
     ap.add_argument("--fastq-size", type=float, default=12.5e9, help="N > 1: FASTQ bytes per GPU for the sharded FASTQ encode (configs[4] = 100 GB over 8 GPUs; 0: skip)")
     ap.add_argument("--no-ref-full", dest="ref_full", action="store_false", help="N = 1: skip the reference's archives of the WHOLE FASTQ / realistic texts (half a minute of the reference's ennaf)")
     ap.add_argument("--levels-size", type=float, default=1e9, help="N = 1: bytes of a repeat-rich genome encoded at -19 and -3 --long 27 beside the reference with the same flags (0: skip)")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: the encoder's own timing, the full-size round-trip check, per-kernel times and roofline, "
+                         "and (N = 1) every side leg above; without it a run times the headline steps alone")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write what the last timed step decoded to DIR/*.npy (dump_outputs)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     import torch
     import torch.distributed as dist
@@ -701,12 +751,16 @@ def main():
     cfg10 = None
     cb = None
     ennaf_roofline = None
+    roofline = None
 
     if not multi:
         # ---- N = 1: the metric's own size on the one GPU (text, archive and decoded text resident: 225 of the 288 GB)
-        leg = one_gpu_leg(ctx, dev, int(args.size), args.records, 2024, args.steps, args.warmup)
+        dump = (lambda r: dump_outputs(r, args.dump_outputs)) if args.dump_outputs else None
+        leg = one_gpu_leg(ctx, dev, int(args.size), args.records, 2024, args.steps, args.warmup, full=args.full, dump=dump)
         n_text, n_naf, total_text, rep = leg["n_text"], leg["n_naf"], leg["n_text"], leg["rep"]
-        value, ms_per_step, ok = leg["value"], leg["ms_per_step"], leg["ok"] and leg["wsum_ok"]
+        value, ms_per_step = leg["value"], leg["ms_per_step"]
+    if not multi and args.full:
+        ok = leg["ok"] and leg["wsum_ok"]
         enc_times = leg["enc_times"]
         roofline = decode_roofline(leg, ms_per_step)
         hl_enc = encode_roofline(leg)
@@ -738,7 +792,7 @@ def main():
                 cb = cpu_baseline(c["text"], int(min(args.cpu_sample, c["n_text"])), ctx, e2e_bytes=int(min(args.e2e_size, c["n_text"])))
             del c
             torch.cuda.synchronize(); ctx.release_scratch(); torch.cuda.empty_cache()
-    else:
+    if multi:
         size = int(args.size) // (world if sharded else 1) if world > 1 else int(args.size)
         spare = 1 << 20                                                    # room behind a slice for what a shard borrows from the next one
         text = synth.fasta_acgt_device(size, n_records=args.records, width=80, seed=2024 + rank, device=dev)
@@ -758,7 +812,10 @@ def main():
             res_e = [None]
             def enc():
                 res_e[0] = ctx.ennaf(text, out=naf_buf)
-            enc_times = timed_calls(enc, 5)
+            if args.full:
+                enc_times = timed_calls(enc, 5)
+            else:
+                enc()                                                  # the archive the steps decode
             d_naf, rep = res_e[0]
             n_naf = int(d_naf.numel())
             total_text = n_text
@@ -767,19 +824,21 @@ def main():
             step = lambda: ctx.unnaf(d_naf, capi.OUT_FASTA, out=out)
             r = step()
             torch.cuda.synchronize()
-            ok = equal_in_chunks(r, text)
+            if args.full:
+                ok = equal_in_chunks(r, text)
         else:
             # ---- ONE archive of the whole job's text, made by the sharded encoder; every rank keeps a copy (a quarter of the text)
             opts = shard.make_opts()
             d_naf, rep, sinfo = shard.ennaf_sharded(ctx, text_buf, n_text, opts, dst=0, everywhere=True)
             torch.cuda.synchronize(); dist.barrier()
-            enc_times = []
-            for _ in range(5):
-                torch.cuda.synchronize(); dist.barrier()
-                t0 = time.perf_counter()
-                shard.ennaf_sharded(ctx, text_buf, n_text, opts, dst=0, everywhere=False)
-                torch.cuda.synchronize(); dist.barrier()
-                enc_times.append(time.perf_counter() - t0)
+            if args.full:
+                enc_times = []
+                for _ in range(5):
+                    torch.cuda.synchronize(); dist.barrier()
+                    t0 = time.perf_counter()
+                    shard.ennaf_sharded(ctx, text_buf, n_text, opts, dst=0, everywhere=False)
+                    torch.cuda.synchronize(); dist.barrier()
+                    enc_times.append(time.perf_counter() - t0)
             n_naf = int(d_naf.numel())
             torch.cuda.synchronize(); ctx.release_scratch(); torch.cuda.empty_cache()
             total_text = ctx.unnaf_size(d_naf, capi.OUT_FASTA)
@@ -791,16 +850,17 @@ def main():
             step = lambda: shard.unnaf_sharded(ctx, d_naf, capi.OUT_FASTA, dst=0, out=out, total=total_text, scratch=scratch, self_exchange=(world == 1))
             r = step()
             torch.cuda.synchronize()
-            # full-size check: sum over ranks of the weighted sum of every slice == weighted sum of the gathered text on rank 0, and
-            # every rank's own decoded range against the same positions of the text it holds (where they overlap)
-            off = n_text * rank                                      # slices are equal-sized by construction
-            mine = torch.tensor([weighted_sum(text, off), n_text], dtype=torch.int64, device=dev)
-            dist.all_reduce(mine, op=dist.ReduceOp.SUM)
-            ok = True
-            if rank == 0:
-                ok = int(mine[1].item()) == total_text and int(mine[0].item()) == weighted_sum(r, 0) and equal_in_chunks(r[:n_text], text)
-            extra["sharded_ennaf"] = {"value": round(total_text / median(enc_times) / 1e9, 3), "unit": "GB/s FASTA in, whole job: split + streams + zstd on every rank, parts gathered to rank 0 (BASELINE configs[4] shape on FASTA)",
-                                      "borrowed_bytes": sinfo["halo"], "given_bytes": sinfo["cut"]}
+            if args.full:
+                # full-size check: sum over ranks of the weighted sum of every slice == weighted sum of the gathered text on rank 0, and
+                # every rank's own decoded range against the same positions of the text it holds (where they overlap)
+                off = n_text * rank                                      # slices are equal-sized by construction
+                mine = torch.tensor([weighted_sum(text, off), n_text], dtype=torch.int64, device=dev)
+                dist.all_reduce(mine, op=dist.ReduceOp.SUM)
+                ok = True
+                if rank == 0:
+                    ok = int(mine[1].item()) == total_text and int(mine[0].item()) == weighted_sum(r, 0) and equal_in_chunks(r[:n_text], text)
+                extra["sharded_ennaf"] = {"value": round(total_text / median(enc_times) / 1e9, 3), "unit": "GB/s FASTA in, whole job: split + streams + zstd on every rank, parts gathered to rank 0 (BASELINE configs[4] shape on FASTA)",
+                                          "borrowed_bytes": sinfo["halo"], "given_bytes": sinfo["cut"]}
         for _ in range(max(0, args.warmup - 1)):
             step()
         torch.cuda.synchronize()
@@ -808,7 +868,7 @@ def main():
         torch.cuda.synchronize()
         t0 = time.perf_counter()
         for _ in range(args.steps):
-            step()
+            r = step()
         torch.cuda.synchronize()
         dist.barrier()
         dt = time.perf_counter() - t0
@@ -821,8 +881,10 @@ def main():
             total_text = float(tot.item())
         ms_per_step = dt / args.steps * 1e3
         value = float(total_text) * args.steps / dt / 1e9
+        if args.dump_outputs and rank == 0:
+            dump_outputs(r, args.dump_outputs)
 
-        if sharded:
+        if sharded and args.full:
             # the two halves of a step on their own: range decode (max over ranks), then the gather of already decoded ranges
             b, e = shard.byte_range(total_text, rank, world)
             buf = out[b:e] if rank == 0 else scratch
@@ -894,28 +956,29 @@ def main():
                 else:
                     scratch = torch.empty(e - b + 64, dtype=torch.uint8, device=dev)
 
-        # ---- per-kernel device time (HIP events on the stream the kernels run on), one extra instrumented step
-        ctx.set_timing(True)
-        if sharded:
-            b, e = shard.byte_range(total_text, rank, world)
-            ctx.unnaf_range(d_naf, b, e, capi.OUT_FASTA, out=(out[: e - b + 64] if rank == 0 else scratch))
-            my_text = e - b
-        else:
-            ctx.unnaf(d_naf, capi.OUT_FASTA, out=out)
-            my_text = n_text
-        legm = {"rep": rep, "n_text": n_text, "n_naf": n_naf, "kt": {n: (ms, k) for n, ms, k in ctx.get_timing()}, "step_streams": ctx.get_timing_streams()}
-        ctx.set_timing(False)
-        frac_mine = my_text / float(total_text) if sharded else 1.0
-        roofline = decode_roofline(legm, ms_per_step if not sharded else extra["range_decode_ms"], my_text=my_text, frac_mine=frac_mine)
-        if roofline and sharded:
-            # gather-to-root is bound by the root's xGMI ingress, below what one GPU decodes on its own: the other two
-            # figures of the step beside `value`, where the driver keeps scalars
-            roofline.update({"decode_only_value": extra["decode_only_value"], "to_host_value": extra["to_host_value"], "range_decode_ms": extra["range_decode_ms"],
-                             "gather_ms": extra["gather_ms"], "roundtrip_bit_exact": bool(ok),
-                             "sharded_ennaf_gbps": extra["sharded_ennaf"]["value"],
-                             "sharded_ennaf_fastq_gbps": (extra.get("sharded_ennaf_fastq") or {}).get("value")})
+        if args.full:
+            # ---- per-kernel device time (HIP events on the stream the kernels run on), one extra instrumented step
+            ctx.set_timing(True)
+            if sharded:
+                b, e = shard.byte_range(total_text, rank, world)
+                ctx.unnaf_range(d_naf, b, e, capi.OUT_FASTA, out=(out[: e - b + 64] if rank == 0 else scratch))
+                my_text = e - b
+            else:
+                ctx.unnaf(d_naf, capi.OUT_FASTA, out=out)
+                my_text = n_text
+            legm = {"rep": rep, "n_text": n_text, "n_naf": n_naf, "kt": {n: (ms, k) for n, ms, k in ctx.get_timing()}, "step_streams": ctx.get_timing_streams()}
+            ctx.set_timing(False)
+            frac_mine = my_text / float(total_text) if sharded else 1.0
+            roofline = decode_roofline(legm, ms_per_step if not sharded else extra["range_decode_ms"], my_text=my_text, frac_mine=frac_mine)
+            if roofline and sharded:
+                # gather-to-root is bound by the root's xGMI ingress, below what one GPU decodes on its own: the other two
+                # figures of the step beside `value`, where the driver keeps scalars
+                roofline.update({"decode_only_value": extra["decode_only_value"], "to_host_value": extra["to_host_value"], "range_decode_ms": extra["range_decode_ms"],
+                                 "gather_ms": extra["gather_ms"], "roundtrip_bit_exact": bool(ok),
+                                 "sharded_ennaf_gbps": extra["sharded_ennaf"]["value"],
+                                 "sharded_ennaf_fastq_gbps": (extra.get("sharded_ennaf_fastq") or {}).get("value")})
 
-    if rank == 0 and not multi:
+    if rank == 0 and not multi and args.full:
         # ---- the other workloads of north_star, on this GPU, in this line (none of them is `value`)
         if args.softmask_size > 0:
             # the mask stream and the toggles of every tile are real work here (they are empty in the headline config)
@@ -1016,14 +1079,15 @@ def main():
             "value": round(value, 3), "unit": "GB/s",
             "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(ms_per_step, 3),
             "higher_is_better": True, "scaling": "strong" if sharded else "weak", "vs_baseline": None, "dtype": "u8", "data": "synthetic",
-            "config": {"workload": workload, "parallelism": par},
-            "roundtrip_bit_exact": bool(ok),
-            "ennaf_value": round(float(total_text) / median(enc_times) / 1e9, 3),
-            "ennaf_unit": "GB/s FASTA in (device-resident, same data%s; median of %d calls)" % (", sharded over the ranks, parts gathered to rank 0" if sharded else "", len(enc_times)),
-            "box": box_id(),
-            "naf_ratio": round(n_naf / float(total_text), 4),
-            "roofline": roofline, "ennaf_roofline": ennaf_roofline, "cpu_baseline": cb,
+            "config": {"workload": workload, "parallelism": par}, "full": bool(args.full),
         }
+        if args.full:
+            line.update({"roundtrip_bit_exact": bool(ok),
+                         "ennaf_value": round(float(total_text) / median(enc_times) / 1e9, 3),
+                         "ennaf_unit": "GB/s FASTA in (device-resident, same data%s; median of %d calls)" % (", sharded over the ranks, parts gathered to rank 0" if sharded else "", len(enc_times))})
+        line.update({"box": box_id(), "naf_ratio": round(n_naf / float(total_text), 4)})
+        if args.full:
+            line.update({"roofline": roofline, "ennaf_roofline": ennaf_roofline, "cpu_baseline": cb})
         line.update(extra)
     if multi:
         dist.destroy_process_group()

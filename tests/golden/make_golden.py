@@ -9,6 +9,7 @@ What it writes (all DATA: inputs, reference-made archives, expected outputs / th
   naf_cases.json           per case: ennaf args, sizes and SHA-256 of reference unnaf outputs per mode
   zstd/<case>.zst          frames made by the image's libzstd 1.4.9 (library + CLI)
   zstd_cases.json          per frame: raw length + SHA-256 of the content, and its feature class
+  ref_fuzz.json            random malformed-ish FASTA texts with the reference's archive and decode of each
 Nothing here is imported by the product.
 """
 import hashlib
@@ -199,11 +200,30 @@ def zstd_cases():
     json.dump(meta, open(os.path.join(HERE, "zstd_cases.json"), "w"), indent=1)
 
 
+def ref_fuzz():
+    """ref_fuzz.json: 40 random malformed-ish FASTA texts (seed 11), the reference ennaf's archive of each and, where its
+    sequence lengths add up, the reference unnaf's `--fasta` output of that archive (hex strings; null when not decoded)."""
+    rng = np.random.default_rng(11)
+    alphabet = np.frombuffer(b">>\n\n\r\t ACGTNacgtn-XZ*\x00\x7f\xff\x0b", dtype=np.uint8)
+    cases = []
+    for i in range(40):
+        t = b">" + alphabet[rng.integers(0, len(alphabet), int(rng.integers(1, 300)))].tobytes()
+        naf = O.ref_ennaf(t)
+        h = O.parse_naf(naf)
+        sp = O.split_text(t)
+        out = None
+        if h.n_sequences and h.orig[O.SEQ] == sum(np.frombuffer(sp.lengths, dtype="<u4").astype(int)):
+            out = O.ref_unnaf(naf, ("--fasta",)).hex()
+        cases.append({"text": t.hex(), "naf": naf.hex(), "unnaf_fasta": out})
+    json.dump({"seed": 11, "cases": cases}, open(os.path.join(HERE, "ref_fuzz.json"), "w"), indent=1)
+
+
 if __name__ == "__main__":
     assert O.have_ref(), "build oracle/_ref first (make -C oracle ref)"
     copy_ref_tests()
     naf_cases()
     zstd_cases()
+    ref_fuzz()
     tot = 0
     for dp, _, fs in os.walk(HERE):
         tot += sum(os.path.getsize(os.path.join(dp, f)) for f in fs)

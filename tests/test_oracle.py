@@ -2,6 +2,7 @@
 vectors produced by the real reference binaries / the image's libzstd (tests/golden/make_golden.py).
 """
 import hashlib
+import json
 
 import numpy as np
 import pytest
@@ -228,21 +229,29 @@ def test_fastq_error_messages(oracle):
     assert oracle.split_text(b"").format == oracle.FMT_UNKNOWN
 
 
-@pytest.mark.skipif(not __import__("oracle.oracle", fromlist=["x"]).have_ref(), reason="oracle/_ref not built")
 def test_oracle_against_live_reference_fuzz(oracle):
-    """Only where oracle/_ref exists (build container, GPU box): random malformed-ish FASTA."""
+    """Random malformed-ish FASTA: the reference's archives of them and its decodes, recorded in golden/ref_fuzz.json
+    (make_golden.py), and -- where oracle/_ref exists -- the live reference on the same texts."""
     O = oracle
-    rng = np.random.default_rng(11)
-    alphabet = np.frombuffer(b">>\n\n\r\t ACGTNacgtn-XZ*\x00\x7f\xff\x0b", dtype=np.uint8)
-    for i in range(40):
-        t = b">" + alphabet[rng.integers(0, len(alphabet), int(rng.integers(1, 300)))].tobytes()
-        naf = O.ref_ennaf(t)
-        h = O.parse_naf(naf)
+    cases = json.loads(golden_bytes("ref_fuzz.json"))["cases"]
+    assert len(cases) == 40
+    for c in cases:
+        t = bytes.fromhex(c["text"])
         sp = O.split_text(t)
-        for k, s in enumerate([sp.ids, sp.comments, sp.lengths, sp.mask, sp.seq]):
-            assert O.zstd_decompress(h.frame(naf, k)) == s
-        if h.n_sequences and h.orig[O.SEQ] == sum(np.frombuffer(sp.lengths, dtype="<u4").astype(int)):
-            assert O.ref_unnaf(naf, ("--fasta",)) == O.unnaf(naf, O.MODE_FASTA)
+        archives = [(bytes.fromhex(c["naf"]), False)]
+        if O.have_ref():
+            archives.append((O.ref_ennaf(t), True))
+        for naf, live in archives:
+            h = O.parse_naf(naf)
+            for k, s in enumerate([sp.ids, sp.comments, sp.lengths, sp.mask, sp.seq]):
+                assert O.zstd_decompress(h.frame(naf, k)) == s
+            decodable = bool(h.n_sequences) and h.orig[O.SEQ] == sum(np.frombuffer(sp.lengths, dtype="<u4").astype(int))
+            if not live:
+                assert (c["unnaf_fasta"] is not None) == decodable
+                if decodable:
+                    assert bytes.fromhex(c["unnaf_fasta"]) == O.unnaf(naf, O.MODE_FASTA)
+            if decodable and O.have_ref():
+                assert O.ref_unnaf(naf, ("--fasta",)) == O.unnaf(naf, O.MODE_FASTA)
 
 
 def test_cfg1_ten_megabases_cpu_round_trip(oracle):

@@ -1,7 +1,7 @@
 #!/bin/bash
 # Produces the files under profiles/ for one round:  tools/profile_bench.sh r06   (run on the GPU box, from the repo root)
-#   <tag>_bench_line.json                     the JSON line of a plain `python bench.py` (100 GB headline, every side leg)
-#   <tag>_bench_rocprofv3_kernel_stats.csv    rocprofv3 --kernel-trace --stats of the headline alone: `python bench.py --steps 3 --no-cpu` + SIDE0 (below)
+#   <tag>_bench_line.json                     the JSON line of `python bench.py --full` (100 GB headline, every side leg)
+#   <tag>_bench_rocprofv3_kernel_stats.csv    rocprofv3 --kernel-trace --stats of the headline alone: `python bench.py --full --steps 3` + SIDE0 (below)
 #   <tag>_cfg10_rocprofv3_kernel_stats.csv    the same at BASELINE configs[1]'s 10 GB (`--size 10e9`)
 #   pmc_traffic_100gb.json / pmc_traffic.json / pmc_traffic_ennaf(_100gb).json   PMC traffic per kernel and call at 100 GB and at 10 GB
 #   <tag>_realistic_rocprofv3_kernel_stats.csv  the same of `tools/perf_side.py realistic` (mostly-flat frame: flat tiles in place, the other blocks decoded beside them)
@@ -15,8 +15,8 @@ export TMPDIR=/tmp
 # the box these files come from (bench.py prints the same stamp as "box" in its line: a `frac` recomputed from the CSVs below and the
 # line's own can be matched, or known to come from two boxes)
 python -c "import bench; print(bench.box_id())" > $out/${tag}_box.txt
-SIDE0="--no-cpu --softmask-size 0 --realistic-size 0 --fastq1-size 0 --levels-size 0 --cfg10-size 0"     # the headline leg alone
-python bench.py > $out/${tag}_bench_line.json 2> $out/bench.err
+SIDE0="--full --no-cpu --softmask-size 0 --realistic-size 0 --fastq1-size 0 --levels-size 0 --cfg10-size 0"     # the headline leg alone
+python bench.py --full > $out/${tag}_bench_line.json 2> $out/bench.err
 tail -c 400 $out/bench.err
 rocprofv3 --kernel-trace --stats --output-format csv -d $out/stats -- python bench.py --steps 3 $SIDE0 > $out/stats.log 2>&1
 cp $(ls $out/stats/*/*kernel_stats.csv | head -1) $out/${tag}_bench_rocprofv3_kernel_stats.csv
