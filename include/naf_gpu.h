@@ -156,6 +156,41 @@ int  naf_gpu_unnaf(naf_gpu_ctx *ctx, const void *d_naf, size_t naf_len, const na
 int  naf_gpu_unnaf_range(naf_gpu_ctx *ctx, const void *d_naf, size_t naf_len, const naf_gpu_unnaf_opts *opts,
                          uint64_t out_begin, uint64_t out_end, void *d_out, size_t out_cap, size_t *out_len);
 
+/* ---- unnaf: records and regions by number, id or range ---------------------------------------------------
+ * A .naf has no index and the reference's unnaf is one sequential pass (it has no call site for any of this); here the record
+ * tables are made on the device per call, so a selection costs the side sections plus the zstd blocks behind the bases it names.
+ * A segment is bases [begin, end) of a record, 0-based; begin = 0 with end = NAF_GPU_WHOLE is the record as stored. */
+typedef struct { uint64_t record, begin, end; } naf_gpu_segment;
+#define NAF_GPU_WHOLE UINT64_MAX
+
+/* ids -> record numbers.  h_ids: n_ids zero-terminated strings laid end to end in HOST memory (ids_bytes in all).
+ * records[k] = number of the FIRST record (archive order) whose id equals string k byte for byte, or UINT64_MAX.
+ * NAF_GPU_EARG on an archive without an ids section. */
+int  naf_gpu_unnaf_find(naf_gpu_ctx *ctx, const void *d_naf, size_t naf_len, const char *h_ids, size_t ids_bytes, size_t n_ids,
+                        uint64_t *records);
+/* Lengths and text offsets of records [first, first + count) under opts, into host arrays: n_bases (count entries, may be NULL) and
+ * text_off (count + 1 entries; text_off[k] .. text_off[k + 1] is what naf_gpu_unnaf_range takes for record first + k). */
+int  naf_gpu_unnaf_record_table(naf_gpu_ctx *ctx, const void *d_naf, size_t naf_len, const naf_gpu_unnaf_opts *opts,
+                                uint64_t first, uint64_t count, uint64_t *n_bases, uint64_t *text_off);
+/* The texts of n_segs segments (a HOST array) laid end to end in the order given; segments may repeat, overlap and come in any order.
+ * A whole-record segment is exactly the bytes the record occupies in the text of naf_gpu_unnaf under the same opts.  A sub-range is
+ *   FASTA:      '>' id ':' begin+1 '-' end '\n', the bases wrapped at the effective line length (wrapping restarts at the
+ *               segment's first base; 0 = one line), a final '\n'   (id: the record's entry of the ids section, empty without one)
+ *   SEQUENCES:  the bases and '\n'          SEQ: the bases          FASTQ, 4BIT: NAF_GPU_EARG (4BIT also for whole records)
+ * with mask, RNA / protein / text handling as for those bases in the whole text.  `end` beyond the record is clamped to its length;
+ * after that begin >= end is NAF_GPU_EARG unless the segment is a whole-record one, and so is record >= n_sequences; last_error
+ * names the segment.  Bases behind the last record of a malformed archive are not addressable.  n_segs = 0 gives
+ * *out_len = 0; too small a capacity gives NAF_GPU_ECAP and the needed size.  The side sections are decoded once per call, the
+ * sequence (and quality) stream only in the blocks behind the segments. */
+int  naf_gpu_unnaf_select_size(naf_gpu_ctx *ctx, const void *d_naf, size_t naf_len, const naf_gpu_unnaf_opts *opts,
+                               const naf_gpu_segment *segs, size_t n_segs, size_t *out_len);
+int  naf_gpu_unnaf_select(naf_gpu_ctx *ctx, const void *d_naf, size_t naf_len, const naf_gpu_unnaf_opts *opts,
+                          const naf_gpu_segment *segs, size_t n_segs, void *d_out, size_t out_cap, size_t *out_len);
+/* Host only, no device needed: "ID", "ID:a-b", "ID:a-", "ID:a" (1-based, inclusive, commas in numbers ignored).  The LAST ':' splits
+ * when only digits, commas and '-' follow it, so ids that contain ':' work; what follows must then be a range with 1 <= a <= b.
+ * Returns the id's length and begin / end 0-based half-open ("ID": 0 / NAF_GPU_WHOLE; "ID:a-": a - 1 / NAF_GPU_WHOLE). */
+int  naf_gpu_parse_region(const char *text, size_t *id_len, uint64_t *begin, uint64_t *end);
+
 /* ---- ennaf ------------------------------------------------------------------------------------------ */
 typedef struct {
     int      format;            /* NAF_FMT_* (AUTO = sniff, process.c:547-583) */

@@ -27,7 +27,9 @@ EXPORTS = [
     "naf_gpu_ennaf_shard_finish", "naf_gpu_ennaf_shard_carry", "naf_gpu_ennaf_stitch_plan", "naf_gpu_ennaf_stitch",
     "naf_gpu_read_file", "naf_gpu_write_file", "naf_gpu_copy", "naf_gpu_gather_ranges", "naf_gpu_get_timing_streams",
     "naf_gpu_set_option", "naf_gpu_get_trace", "naf_gpu_clear_trace", "naf_gpu_write_fd",
+    "naf_gpu_unnaf_find", "naf_gpu_unnaf_record_table", "naf_gpu_unnaf_select_size", "naf_gpu_unnaf_select", "naf_gpu_parse_region",
 ]
+WHOLE = 2 ** 64 - 1                     # NAF_GPU_WHOLE: (record, 0, WHOLE) is the record as stored
 MAX_SHARDS = 64
 
 
@@ -75,6 +77,11 @@ class ShardCarry(C.Structure):
 
 class StitchSeg(C.Structure):
     _fields_ = [("dst_off", C.c_uint64), ("len", C.c_uint64), ("src_off", C.c_uint64), ("shard", C.c_int32), ("stream", C.c_int32)]
+
+
+class Segment(C.Structure):
+    """naf_gpu_segment: bases [begin, end) of a record, 0-based."""
+    _fields_ = [("record", C.c_uint64), ("begin", C.c_uint64), ("end", C.c_uint64)]
 
 
 class NafGpuError(RuntimeError):
@@ -155,8 +162,24 @@ def load():
         L.naf_gpu_get_trace.restype = C.c_char_p
         L.naf_gpu_clear_trace.argtypes = [vp]
         L.naf_gpu_clear_trace.restype = None
+        L.naf_gpu_unnaf_find.argtypes = [vp, vp, sz, C.c_char_p, sz, sz, u64p]
+        L.naf_gpu_unnaf_record_table.argtypes = [vp, vp, sz, C.POINTER(UnnafOpts), C.c_uint64, C.c_uint64, u64p, u64p]
+        L.naf_gpu_unnaf_select_size.argtypes = [vp, vp, sz, C.POINTER(UnnafOpts), C.POINTER(Segment), sz, C.POINTER(sz)]
+        L.naf_gpu_unnaf_select.argtypes = [vp, vp, sz, C.POINTER(UnnafOpts), C.POINTER(Segment), sz, vp, sz, C.POINTER(sz)]
+        L.naf_gpu_parse_region.argtypes = [C.c_char_p, C.POINTER(sz), u64p, u64p]
         _lib = L
     return _lib
+
+
+def parse_region(text):
+    """Host-only: "ID", "ID:a-b", "ID:a-", "ID:a" (1-based, inclusive) -> (id, begin, end), 0-based half-open; a whole record is
+    (id, 0, WHOLE).  ValueError when the text is no region (naf_gpu_parse_region)."""
+    b = text.encode("latin1") if isinstance(text, str) else bytes(text)
+    n, lo, hi = C.c_size_t(), C.c_uint64(), C.c_uint64()
+    if load().naf_gpu_parse_region(b, C.byref(n), C.byref(lo), C.byref(hi)):
+        raise ValueError("not a region: %r" % (text,))
+    rid = b[:n.value]
+    return (rid.decode("latin1") if isinstance(text, str) else rid), lo.value, hi.value
 
 
 def shard_carry(infos, k):
@@ -355,6 +378,52 @@ class Context:
             out = torch.empty(max(end - begin, 1), dtype=torch.uint8, device=self.device)
         n = C.c_size_t()
         self._check(self.L.naf_gpu_unnaf_range(self.h, _ptr(d_naf), d_naf.numel(), C.byref(o), begin, end, _ptr(out), out.numel(), C.byref(n)))
+        return out[:n.value]
+
+    def unnaf_find(self, d_naf, ids):
+        """Record numbers of the given ids (str or bytes): the first record whose id equals each one, None where there is none."""
+        raw = [i.encode("latin1") if isinstance(i, str) else bytes(i) for i in ids]
+        if any(b"\0" in i for i in raw):
+            raise ValueError("an id cannot hold a zero byte")
+        blob = b"".join(i + b"\0" for i in raw)
+        rec = (C.c_uint64 * max(len(raw), 1))()
+        self._check(self.L.naf_gpu_unnaf_find(self.h, _ptr(d_naf), d_naf.numel(), blob, len(blob), len(raw), rec))
+        return [None if rec[k] == WHOLE else int(rec[k]) for k in range(len(raw))]
+
+    def unnaf_record_table(self, d_naf, first=0, count=None, out_type=OUT_DEFAULT, use_mask=True, line_length=-1):
+        """(n_bases, text_off) of records [first, first + count): text_off has count + 1 entries, consecutive pairs are what
+        unnaf_range takes for a record.  count=None: up to the last record."""
+        o = UnnafOpts(out_type, int(use_mask), line_length)
+        if count is None:
+            count = int(self.parse_header(d_naf).n_sequences) - first
+        nb, off = (C.c_uint64 * max(count, 1))(), (C.c_uint64 * (count + 1))()
+        self._check(self.L.naf_gpu_unnaf_record_table(self.h, _ptr(d_naf), d_naf.numel(), C.byref(o), first, count, nb, off))
+        return [int(nb[k]) for k in range(count)], [int(off[k]) for k in range(count + 1)]
+
+    @staticmethod
+    def _segments(segments):
+        segs = (Segment * max(len(segments), 1))()
+        for k, s in enumerate(segments):
+            segs[k] = Segment(int(s), 0, WHOLE) if isinstance(s, int) else Segment(int(s[0]), int(s[1]), int(s[2]))
+        return segs
+
+    def unnaf_select_size(self, d_naf, segments, out_type=OUT_DEFAULT, use_mask=True, line_length=-1):
+        o = UnnafOpts(out_type, int(use_mask), line_length)
+        n = C.c_size_t()
+        self._check(self.L.naf_gpu_unnaf_select_size(self.h, _ptr(d_naf), d_naf.numel(), C.byref(o), self._segments(segments), len(segments), C.byref(n)))
+        return n.value
+
+    def unnaf_select(self, d_naf, segments, out_type=OUT_DEFAULT, use_mask=True, line_length=-1, out=None):
+        """The texts of the segments -- (record, begin, end) tuples, 0-based half-open, or record numbers for whole records -- laid
+        end to end in the order given (naf_gpu_unnaf_select)."""
+        import torch
+        o = UnnafOpts(out_type, int(use_mask), line_length)
+        segs = self._segments(segments)
+        n = C.c_size_t()
+        if out is None:
+            self._check(self.L.naf_gpu_unnaf_select_size(self.h, _ptr(d_naf), d_naf.numel(), C.byref(o), segs, len(segments), C.byref(n)))
+            out = torch.empty(max(n.value, 1), dtype=torch.uint8, device=self.device)
+        self._check(self.L.naf_gpu_unnaf_select(self.h, _ptr(d_naf), d_naf.numel(), C.byref(o), segs, len(segments), _ptr(out), out.numel(), C.byref(n)))
         return out[:n.value]
 
     def histogram(self, d_buf):
