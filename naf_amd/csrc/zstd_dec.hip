@@ -1889,7 +1889,7 @@ struct UniInfo { u32 ok, bad, np, nblk, nhb, regen0, nstreams0, hso0, front, pos
 __global__ __launch_bounds__(64) void k_uni_head(const u8 *src, u64 off0, u32 S, u32 h0, u32 nmax, const u32 *res, const ZBlock *sblk, const ZStat *st, UniInfo *U, ZBlock *ublk, u32 spec_min)
 {
     const u32 lane = threadIdx.x;
-    if (lane == 0) { U->ok = 0; U->bad = 0; }
+    if (lane == 0) { UniInfo z; memset(&z, 0, sizeof z); *U = z; }      // (ok = bad = 0; the rest for the host's trace when the frame is declined)
     if (res[1] != 1) return;
     const u32 np = res[0], nblk = st->nblk;
     if (np < 1 || np > nmax || nblk <= spec_min || nblk < np || nblk - np > STRIDE_TAIL) return;
@@ -2047,7 +2047,7 @@ __global__ void k_runs_probe(const u8 *src, u64 len, u32 S, u32 h0, const UniRun
 __global__ __launch_bounds__(64) void k_uni_head_runs(const u8 *src, u64 off0, u32 h0, UniRuns *R, ZBlock *odd, UniInfo *U, ZBlock *ublk0, u32 spec_min)
 {
     const u32 lane = threadIdx.x;
-    if (lane == 0) { U->ok = 0; U->bad = 0; }
+    if (lane == 0) { UniInfo z; memset(&z, 0, sizeof z); *U = z; }      // (ok = bad = 0; the rest for the host's trace when the frame is declined)
     if (!R->done || R->fail || R->nblk <= spec_min) return;
     const u32 n_odd = R->n_odd;
     if (lane < n_odd) { ZBlock b = odd[lane]; zstd_parse_block(src + b.src_off, b); odd[lane] = b; }
