@@ -186,6 +186,20 @@ int  naf_gpu_unnaf_select_size(naf_gpu_ctx *ctx, const void *d_naf, size_t naf_l
                                const naf_gpu_segment *segs, size_t n_segs, size_t *out_len);
 int  naf_gpu_unnaf_select(naf_gpu_ctx *ctx, const void *d_naf, size_t naf_len, const naf_gpu_unnaf_opts *opts,
                           const naf_gpu_segment *segs, size_t n_segs, void *d_out, size_t out_cap, size_t *out_len);
+/* The same with a strand per segment.  strand: a HOST array of n_segs bytes, 0 = as stored, 1 = the reverse complement of segment k;
+ * NULL = all 0, and then (as with all bytes 0) the call is exactly naf_gpu_unnaf_select.  The text of a reverse segment is the text of
+ * a record whose bases are the complements of bases [begin, end) read from end - 1 down to begin: complemented per IUPAC (A<>T, C<>G,
+ * M<>K, R<>Y, B<>V, D<>H; S W N - stay; U for T in an RNA archive), every base with its own case, mask and line length applied as for
+ * a forward segment (wrapping restarts at the first emitted base).  Its header carries "/rc" directly behind the id:
+ *   a sub-range '>' id ':' begin+1 '-' end "/rc" (the forward coordinates);  a whole record '>' id "/rc", then the separator and the
+ *   stored name if there is one;  an archive without ids: the stored name, then "/rc";  '@' for FASTQ.
+ * A whole FASTQ record has its quality string reversed and its '+' line as in the whole text.  A reverse segment of a protein or text
+ * archive and a strand byte other than 0 or 1 are NAF_GPU_EARG (last_error names the segment); everything naf_gpu_unnaf_select
+ * rejects is rejected the same way.  A reverse segment decodes the blocks its forward twin decodes. */
+int  naf_gpu_unnaf_select_stranded_size(naf_gpu_ctx *ctx, const void *d_naf, size_t naf_len, const naf_gpu_unnaf_opts *opts,
+                                        const naf_gpu_segment *segs, const uint8_t *strand, size_t n_segs, size_t *out_len);
+int  naf_gpu_unnaf_select_stranded(naf_gpu_ctx *ctx, const void *d_naf, size_t naf_len, const naf_gpu_unnaf_opts *opts,
+                                   const naf_gpu_segment *segs, const uint8_t *strand, size_t n_segs, void *d_out, size_t out_cap, size_t *out_len);
 /* Host only, no device needed: "ID", "ID:a-b", "ID:a-", "ID:a" (1-based, inclusive, commas in numbers ignored).  The LAST ':' splits
  * when only digits, commas and '-' follow it, so ids that contain ':' work; what follows must then be a range with 1 <= a <= b.
  * Returns the id's length and begin / end 0-based half-open ("ID": 0 / NAF_GPU_WHOLE; "ID:a-": a - 1 / NAF_GPU_WHOLE). */

@@ -28,6 +28,7 @@ EXPORTS = [
     "naf_gpu_read_file", "naf_gpu_write_file", "naf_gpu_copy", "naf_gpu_gather_ranges", "naf_gpu_get_timing_streams",
     "naf_gpu_set_option", "naf_gpu_get_trace", "naf_gpu_clear_trace", "naf_gpu_write_fd",
     "naf_gpu_unnaf_find", "naf_gpu_unnaf_record_table", "naf_gpu_unnaf_select_size", "naf_gpu_unnaf_select", "naf_gpu_parse_region",
+    "naf_gpu_unnaf_select_stranded_size", "naf_gpu_unnaf_select_stranded",
 ]
 WHOLE = 2 ** 64 - 1                     # NAF_GPU_WHOLE: (record, 0, WHOLE) is the record as stored
 MAX_SHARDS = 64
@@ -167,6 +168,9 @@ def load():
         L.naf_gpu_unnaf_select_size.argtypes = [vp, vp, sz, C.POINTER(UnnafOpts), C.POINTER(Segment), sz, C.POINTER(sz)]
         L.naf_gpu_unnaf_select.argtypes = [vp, vp, sz, C.POINTER(UnnafOpts), C.POINTER(Segment), sz, vp, sz, C.POINTER(sz)]
         L.naf_gpu_parse_region.argtypes = [C.c_char_p, C.POINTER(sz), u64p, u64p]
+        u8p = C.POINTER(C.c_uint8)
+        L.naf_gpu_unnaf_select_stranded_size.argtypes = [vp, vp, sz, C.POINTER(UnnafOpts), C.POINTER(Segment), u8p, sz, C.POINTER(sz)]
+        L.naf_gpu_unnaf_select_stranded.argtypes = [vp, vp, sz, C.POINTER(UnnafOpts), C.POINTER(Segment), u8p, sz, vp, sz, C.POINTER(sz)]
         _lib = L
     return _lib
 
@@ -407,23 +411,44 @@ class Context:
             segs[k] = Segment(int(s), 0, WHOLE) if isinstance(s, int) else Segment(int(s[0]), int(s[1]), int(s[2]))
         return segs
 
+    @staticmethod
+    def _strands(segments):
+        """The strand bytes of a list that holds 4-tuples (record, begin, end, reverse); None when it holds none."""
+        if not any(not isinstance(s, int) and len(s) == 4 for s in segments):
+            return None
+        st = (C.c_uint8 * len(segments))()
+        for k, s in enumerate(segments):
+            if not isinstance(s, int) and len(s) == 4:
+                st[k] = int(s[3])
+        return st
+
+    def _select_size(self, d_naf, o, segs, strands, n_segs, n):
+        if strands is None:
+            self._check(self.L.naf_gpu_unnaf_select_size(self.h, _ptr(d_naf), d_naf.numel(), C.byref(o), segs, n_segs, C.byref(n)))
+        else:
+            self._check(self.L.naf_gpu_unnaf_select_stranded_size(self.h, _ptr(d_naf), d_naf.numel(), C.byref(o), segs, strands, n_segs, C.byref(n)))
+
     def unnaf_select_size(self, d_naf, segments, out_type=OUT_DEFAULT, use_mask=True, line_length=-1):
         o = UnnafOpts(out_type, int(use_mask), line_length)
         n = C.c_size_t()
-        self._check(self.L.naf_gpu_unnaf_select_size(self.h, _ptr(d_naf), d_naf.numel(), C.byref(o), self._segments(segments), len(segments), C.byref(n)))
+        self._select_size(d_naf, o, self._segments(segments), self._strands(segments), len(segments), n)
         return n.value
 
     def unnaf_select(self, d_naf, segments, out_type=OUT_DEFAULT, use_mask=True, line_length=-1, out=None):
         """The texts of the segments -- (record, begin, end) tuples, 0-based half-open, or record numbers for whole records -- laid
-        end to end in the order given (naf_gpu_unnaf_select)."""
+        end to end in the order given (naf_gpu_unnaf_select).  A 4-tuple (record, begin, end, reverse) gives a strand: reverse = 1 is
+        the segment's reverse complement; a list that holds one goes through naf_gpu_unnaf_select_stranded."""
         import torch
         o = UnnafOpts(out_type, int(use_mask), line_length)
-        segs = self._segments(segments)
+        segs, strands = self._segments(segments), self._strands(segments)
         n = C.c_size_t()
         if out is None:
-            self._check(self.L.naf_gpu_unnaf_select_size(self.h, _ptr(d_naf), d_naf.numel(), C.byref(o), segs, len(segments), C.byref(n)))
+            self._select_size(d_naf, o, segs, strands, len(segments), n)
             out = torch.empty(max(n.value, 1), dtype=torch.uint8, device=self.device)
-        self._check(self.L.naf_gpu_unnaf_select(self.h, _ptr(d_naf), d_naf.numel(), C.byref(o), segs, len(segments), _ptr(out), out.numel(), C.byref(n)))
+        if strands is None:
+            self._check(self.L.naf_gpu_unnaf_select(self.h, _ptr(d_naf), d_naf.numel(), C.byref(o), segs, len(segments), _ptr(out), out.numel(), C.byref(n)))
+        else:
+            self._check(self.L.naf_gpu_unnaf_select_stranded(self.h, _ptr(d_naf), d_naf.numel(), C.byref(o), segs, strands, len(segments), _ptr(out), out.numel(), C.byref(n)))
         return out[:n.value]
 
     def histogram(self, d_buf):

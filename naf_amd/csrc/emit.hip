@@ -1640,6 +1640,8 @@ static int unnaf_prepare(naf_gpu_ctx *c, const u8 *d_naf, size_t naf_len, const 
     P.upper = !pl.fourbit && !o->use_mask;
     const char *tab = h.seq_type == NAF_SEQ_RNA ? "-UGKCYSBAWRDMHVN" : "-TGKCYSBAWRDMHVN";   // unnaf.c:13,369
     memcpy(P.lut, tab, 16);
+    // the complement of a code is the code with its four bits reversed (T 0001 <-> A 1000, G 0010 <-> C 0100, K <-> M, Y <-> R, B <-> V, D <-> H)
+    for (u32 k = 0; k < 16; k++) ((u8 *)P.lutc)[k] = (u8)tab[((k & 1) << 3) | ((k & 2) << 1) | ((k & 4) >> 1) | (k >> 3)];
     const char *fs = ctx_opt(c, "FORCE_SLOW"); P.force_slow = fs && fs[0] == '1';
     P.nt_store = 1;
     pl.need_qual = P.mode == EM_FASTQ;

@@ -19,6 +19,7 @@ struct EmitP {
     u64 N, T, L;
     u64 out_begin, out_end;            // byte range of the full text to produce; out[0] = byte out_begin
     u32 lut[4];                        // 16-entry code -> ASCII table as four dwords
+    u32 lutc[4];                       // code -> ASCII of the complement: lut[] indexed by the code with its four bits reversed (the selection's reverse strand)
     u32 Ldiv_magic;                    // unused when L+1 >= 2^32
     int mode, has_ids, has_names, masking, upper;
     u8 sep, hdr_char;

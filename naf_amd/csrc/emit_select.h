@@ -1,5 +1,5 @@
 // emit_select.h -- the selection path of unnaf: records and regions by number, id or range (naf_gpu_unnaf_find,
-// naf_gpu_unnaf_record_table, naf_gpu_unnaf_select).  Part of emit.hip (included by it, behind unnaf_run): it uses that file's
+// naf_gpu_unnaf_record_table, naf_gpu_unnaf_select, naf_gpu_unnaf_select_stranded).  Part of emit.hip (included by it, behind unnaf_run): it uses that file's
 // side-section chain (unnaf_prepare, unnaf_sections) and device helpers as they are, and adds kernels of its own.
 //
 // A selection is a list of SEGMENTS -- bases [begin, end) of a record -- whose texts are laid end to end in the order given.  The
@@ -8,6 +8,13 @@
 // and a tile kernel composes 4 KiB of output per wavefront from them (k_emit_select).  The sequence stream is decoded only where
 // the segments lie: their base intervals are sorted and merged on the host and every merged interval is one zstd_decode_range;
 // every segment carries the pointers of the range that holds its bases (k_select_bind).
+//
+// A segment may be asked for as its REVERSE COMPLEMENT (naf_gpu_unnaf_select_stranded): the same record text with the bases read from
+// end - 1 down to begin and complemented, "/rc" behind the id.  In the code table "-TGKCYSBAWRDMHVN" the complement of a code is the
+// code with its four bits reversed, so the complement is a second 16-entry table (P.lutc) through the same expand16; the chunk
+// composer loads the 16 forward bases (or quality bytes) that end where the chunk begins, expands and masks them at their forward
+// positions -- a base keeps its own case -- and turns the 16 bytes round in registers (k_emit_select<true, true>, launched only for a
+// call that holds such a segment).  Everything on the host, the decoded blocks among it, is the same for both strands.
 #pragma once
 #include <algorithm>
 
@@ -20,30 +27,33 @@ struct SelSeg {
     u64 klo, khi;                            // mask toggles that can fall inside it: toggles[klo .. khi)
     u64 rec, begin;                          // record and 0-based first base inside it
     const u8 *seq, *qual;                    // the decoded range that holds its bases, as pointers to stream byte 0 / quality byte 0
-    u32 hl, sub;                             // header length; 1 = a sub-range (header '>' id ':' begin+1 '-' end)
+    u32 hl, sub;                             // header length; SEL_SUB = a sub-range (header '>' id ':' begin+1 '-' end), SEL_RC = reverse complement ("/rc" behind it)
 };
+#define SEL_SUB 1u
+#define SEL_RC 2u
 struct SelRange { u64 g_lo, g_hi; const u8 *seq, *qual; };
 
 __device__ __forceinline__ u32 dec_digits(u64 v) { u32 n = 1; while (v >= 10) { v /= 10; n++; } return n; }
 
 // One lane per segment: validation, geometry, text size.  status[0] receives the number of the first segment that cannot be
 // produced (atomicMin; ~0 = none).  size[] / hsize[] are scanned into the text offsets and the header stream offsets.
-__global__ __launch_bounds__(256) void k_select_layout(EmitP P, const naf_gpu_segment *in, u64 S, SelSeg *sg, u64 *size, u64 *hsize, u64 *iv, unsigned long long *status)
+__global__ __launch_bounds__(256) void k_select_layout(EmitP P, const naf_gpu_segment *in, const u8 *strand, u64 S, SelSeg *sg, u64 *size, u64 *hsize, u64 *iv, unsigned long long *status)
 {
     const u64 s = (u64)blockIdx.x * 256 + threadIdx.x;
     if (s >= S) return;
     const u64 rec = in[s].record, b = in[s].begin; u64 e = in[s].end;
-    const bool whole = b == 0 && e == ~0ull;
+    const bool whole = b == 0 && e == ~0ull, rc = strand && strand[s];          // (strand: nullptr when the call has no reverse segment)
     SelSeg g; memset(&g, 0, sizeof g);
     bool bad = rec >= P.N;
     u64 len = 0;
     if (!bad) { len = P.rec_len[rec]; if (e > len) e = len; bad = !whole && (b >= e || P.mode == EM_FASTQ); }
     if (bad) { atomicMin(status, (unsigned long long)s); size[s] = 0; hsize[s] = 0; iv[2 * s] = iv[2 * s + 1] = 0; sg[s] = g; return; }
-    g.rec = rec; g.begin = whole ? 0 : b; g.n = whole ? len : e - b; g.g0 = P.rec_base[rec] + g.begin; g.sub = whole ? 0u : 1u;
+    g.rec = rec; g.begin = whole ? 0 : b; g.n = whole ? len : e - b; g.g0 = P.rec_base[rec] + g.begin; g.sub = (whole ? 0u : SEL_SUB) | (rc ? SEL_RC : 0u);
     u64 h = 0;
     if (P.mode == EM_FASTA || P.mode == EM_FASTQ) {
         if (whole) h = P.hdr_len[rec];
         else { const u64 idl = P.has_ids ? P.idz[rec] - (rec ? P.idz[rec - 1] + 1 : 0) : 0; h = 1 + idl + 1 + dec_digits(b + 1) + 1 + dec_digits(e) + 1; }
+        if (rc) h += 3;                                                           // "/rc"
     }
     g.hl = (u32)h;
     u64 body;
@@ -58,13 +68,14 @@ __global__ __launch_bounds__(256) void k_select_layout(EmitP P, const naf_gpu_se
 }
 
 // Header lines of the segments as one byte stream, eight lanes per segment (k_hdr_build's shape): a whole record's line from its id
-// and name, a sub-range's from its id and the two numbers.
+// and name, a sub-range's from its id and the two numbers; "/rc" directly behind the id (behind the range; behind the name of an archive
+// without ids) for a reverse segment.
 __global__ __launch_bounds__(256) void k_select_hdr(EmitP P, SelSeg *sg, u64 S, const u64 *hoff, u8 *text)
 {
     const u64 s = (u64)blockIdx.x * 32 + (threadIdx.x >> 3);
     const u32 g = threadIdx.x & 7;
     if (s >= S) return;
-    const u64 r = sg[s].rec; const u32 hl = sg[s].hl;
+    const u64 r = sg[s].rec; const u32 hl = sg[s].hl, rc = sg[s].sub & SEL_RC ? 3u : 0u;
     if (g == 0) sg[s].ho = hoff[s];
     if (!hl) return;
     u8 *o = text + hoff[s];
@@ -72,10 +83,11 @@ __global__ __launch_bounds__(256) void k_select_hdr(EmitP P, SelSeg *sg, u64 S, 
     if (P.has_ids) { ids0 = r ? P.idz[r - 1] + 1 : 0; idl = P.idz[r] - ids0; }
     if (P.has_names) { nm0 = r ? P.nmz[r - 1] + 1 : 0; nml = P.nmz[r] - nm0; }
     if (g == 0) { o[0] = P.hdr_char; o[hl - 1] = '\n'; }
-    if (sg[s].sub) {
+    if (sg[s].sub & SEL_SUB) {
         if (P.has_ids) group_copy<8>(o + 1, P.ids + ids0, idl, g);
         if (g == 0) {                                                             // ':' a '-' b, written backwards from the line's end
             u8 *q = o + hl - 1;
+            if (rc) { *--q = 'c'; *--q = 'r'; *--q = '/'; }
             u64 v = sg[s].begin + sg[s].n; do { *--q = (u8)('0' + v % 10); v /= 10; } while (v);
             *--q = '-';
             v = sg[s].begin + 1; do { *--q = (u8)('0' + v % 10); v /= 10; } while (v);
@@ -83,8 +95,12 @@ __global__ __launch_bounds__(256) void k_select_hdr(EmitP P, SelSeg *sg, u64 S, 
         }
     } else if (P.has_ids) {
         group_copy<8>(o + 1, P.ids + ids0, idl, g);
-        if (P.has_names && nml) { if (g == 0) o[1 + idl] = P.sep; group_copy<8>(o + 2 + idl, P.names + nm0, nml, g); }
-    } else group_copy<8>(o + 1, P.names + nm0, nml, g);
+        if (rc && g == 0) { o[1 + idl] = '/'; o[2 + idl] = 'r'; o[3 + idl] = 'c'; }
+        if (P.has_names && nml) { if (g == 0) o[1 + idl + rc] = P.sep; group_copy<8>(o + 2 + idl + rc, P.names + nm0, nml, g); }
+    } else {
+        group_copy<8>(o + 1, P.names + nm0, nml, g);
+        if (rc && g == 0) { o[hl - 4] = '/'; o[hl - 3] = 'r'; o[hl - 2] = 'c'; }
+    }
 }
 
 // Every segment takes the pointers of the decoded range that holds its bases (ranges sorted by g_lo, disjoint).
@@ -100,7 +116,7 @@ __global__ __launch_bounds__(256) void k_select_bind(SelSeg *sg, u64 S, const Se
 
 // 16 bases from base index g of the stream at `seq` (bases16 without the flat-frame source, which this path never has)
 template <bool FOURBIT>
-__device__ __forceinline__ void sel_bases16(const EmitP &P, const u8 *seq, u64 g, u64 &lo, u64 &hi)
+__device__ __forceinline__ void sel_bases16(const EmitP &P, const u32 lut[4], const u8 *seq, u64 g, u64 &lo, u64 &hi)
 {
     if (!FOURBIT) {
         lo = ld64(seq + g); hi = ld64(seq + g + 8);
@@ -113,12 +129,26 @@ __device__ __forceinline__ void sel_bases16(const EmitP &P, const u8 *seq, u64 g
     const u8 *a = seq + (g >> 1);
     u64 nib = ld64(a);
     if (g & 1) nib = (nib >> 4) | ((u64)a[8] << 60);                               // a region that starts on a low nibble
-    expand16(P.lut, nib, lo, hi);
+    expand16(lut, nib, lo, hi);
+}
+
+// The first c (1 .. 16) bytes of {lo,hi} in reverse order, from byte 0 on: all sixteen turned round, the 16 - c that do not belong
+// shifted out.
+__device__ __forceinline__ void reverse16(u64 &lo, u64 &hi, u32 c)
+{
+    u64 a = __builtin_bswap64(hi), b = __builtin_bswap64(lo);
+    const u32 sh = 8 * (16 - c);
+    if (sh >= 64) { a = b >> (sh - 64); b = 0; } else if (sh) { a = (a >> sh) | (b << (64 - sh)); b >>= sh; }
+    lo = a; hi = b;
 }
 
 // One 16-byte chunk of the selection's text, composed piece by piece as compose_chunk composes a chunk of the whole text: a piece
 // is n_main bytes of header, bases or qualities followed by up to three constant bytes.  s: the segment that holds byte p0.
-template <bool FOURBIT>
+// RC: the call holds reverse segments.  Output base j of one is stream base g0 + len - 1 - j, so a piece that starts at base j takes
+// the c = min(16, len - j) bases that end there -- one forward load from g0 + len - j - c, which never starts before the segment and
+// reads past the piece no further than a forward piece does -- complemented by the table, masked where they stand, then reversed.
+// The qualities of a reverse read likewise.
+template <bool FOURBIT, bool RC>
 __device__ __forceinline__ void select_chunk(const EmitP &P, const SelSeg *sg, const u64 *seg_out, const u8 *hdr_text, u64 p0, u32 nbytes, u64 s, u32 Lp1_32, u8 *o)
 {
     u64 so = seg_out[s], sn = seg_out[s + 1];
@@ -130,6 +160,7 @@ __device__ __forceinline__ void select_chunk(const EmitP &P, const SelSeg *sg, c
         const u64 off = p - so, len = g.n;
         const u8 *src = nullptr; u64 gi = 0; bool is_bases = false;
         u64 n_main = 0; u32 tc = 0, n_tc = 0;
+        u32 rc_c = 0;                                                             // RC: source bytes to reverse into this piece (0: a forward piece)
         if (off < g.hl) { src = hdr_text + g.ho + off; n_main = g.hl - off; }
         else {
             const u64 q = off - g.hl;
@@ -138,7 +169,10 @@ __device__ __forceinline__ void select_chunk(const EmitP &P, const SelSeg *sg, c
                     u64 skip = 0;
                     if (q < len) { is_bases = true; gi = g.g0 + q; n_main = len - q; } else skip = q - len;
                     tc = 0x0A2B0Au >> (8 * (u32)skip); n_tc = 3 - (u32)skip;
-                } else { src = g.qual + g.g0 + (q - len - 3); n_main = 2 * len + 3 - q; tc = '\n'; n_tc = 1; }
+                } else {
+                    src = g.qual + g.g0 + (q - len - 3); n_main = 2 * len + 3 - q; tc = '\n'; n_tc = 1;
+                    if (RC && (g.sub & SEL_RC)) { rc_c = n_main < 16 ? (u32)n_main : 16u; src = g.qual + g.g0 + n_main - rc_c; }
+                }
             } else if (P.mode == EM_SEQ) { is_bases = true; gi = g.g0 + q; n_main = len - q; }
             else {
                 tc = '\n'; n_tc = 1;
@@ -157,7 +191,13 @@ __device__ __forceinline__ void select_chunk(const EmitP &P, const SelSeg *sg, c
         if (n1) {
             u64 slo, shi;
             if (is_bases) {
-                sel_bases16<FOURBIT>(P, g.seq, gi, slo, shi);
+                if (RC && (g.sub & SEL_RC)) {
+                    const u64 left = g.g0 + len - gi;                             // bases of the segment from this output base on
+                    rc_c = left < 16 ? (u32)left : 16u; gi = g.g0 + left - rc_c;
+                    const u32 lc[4] = { P.lutc[0], P.lutc[1], P.lutc[2], P.lutc[3] };
+                    sel_bases16<FOURBIT>(P, lc, g.seq, gi, slo, shi);
+                }
+                else sel_bases16<FOURBIT>(P, P.lut, g.seq, gi, slo, shi);
                 if (P.masking) {
                     u64 klo = g.klo, khi = g.khi;
                     if (khi - klo > 0x7FFFFFFFull) { klo = upper_bound_u64(P.toggles, klo, khi, gi); if (khi - klo > 17) khi = klo + 17; }   // at most 16 toggles inside 16 bases
@@ -165,7 +205,8 @@ __device__ __forceinline__ void select_chunk(const EmitP &P, const SelSeg *sg, c
                     else if (klo & 1) { slo += 0x2020202020202020ull; shi += 0x2020202020202020ull; }
                 }
             }
-            else { slo = ld64(src); shi = n1 > 8 ? ld64(src + 8) : 0; }
+            else { slo = ld64(src); shi = (RC && rc_c ? rc_c : n1) > 8 ? ld64(src + 8) : 0; }
+            if (RC && rc_c) reverse16(slo, shi, rc_c);
             place16(lo, hi, slo, shi, pos, n1);
             pos += n1; rem -= n1;
         }
@@ -177,7 +218,8 @@ __device__ __forceinline__ void select_chunk(const EmitP &P, const SelSeg *sg, c
 // One wavefront per 4 KiB tile of the output, four rounds of 64 lanes x 16 bytes: a round is one KiB of consecutive 16-byte stores.
 // The tile's first and last segment are found once (the same in every lane: scalar loads); a lane searches between them only when
 // the tile spans several segments (short reads: ~300 bytes of text each).
-template <bool FOURBIT>
+// RC = true is the instantiation of a call with reverse segments (4-bit streams only); a call without one runs <FOURBIT, false>.
+template <bool FOURBIT, bool RC = false>
 __global__ __launch_bounds__(64) void k_emit_select(EmitP P, const SelSeg *sg, const u64 *seg_out, u64 S, const u8 *hdr_text, u64 total, u8 *out)
 {
     const u64 t0 = (u64)xcd_block() * 4096, t1 = t0 + 4096 < total ? t0 + 4096 : total;
@@ -190,7 +232,7 @@ __global__ __launch_bounds__(64) void k_emit_select(EmitP P, const SelSeg *sg, c
         if (p0 >= t1) break;
         const u32 nbytes = t1 - p0 < 16 ? (u32)(t1 - p0) : 16u;
         const u64 s = s_lo == s_hi ? s_lo : upper_bound_u64(seg_out, s_lo, s_hi + 1, p0) - 1;
-        select_chunk<FOURBIT>(P, sg, seg_out, hdr_text, p0, nbytes, s, Lp1_32, out + p0);
+        select_chunk<FOURBIT, RC>(P, sg, seg_out, hdr_text, p0, nbytes, s, Lp1_32, out + p0);
     }
 }
 
@@ -372,14 +414,22 @@ extern "C" int naf_gpu_unnaf_record_table(naf_gpu_ctx *c, const void *d_naf, siz
     return 0;
 }
 
-static int select_run(naf_gpu_ctx *c, const u8 *d_naf, size_t naf_len, const naf_gpu_unnaf_opts *o, const naf_gpu_segment *h_segs, size_t S,
+// h_strand: one byte per segment, 1 = its reverse complement; nullptr = none
+static int select_run(naf_gpu_ctx *c, const u8 *d_naf, size_t naf_len, const naf_gpu_unnaf_opts *o, const naf_gpu_segment *h_segs, const u8 *h_strand, size_t S,
                       u8 *d_out, size_t out_cap, size_t *out_len, bool size_only)
 {
     if (!c || !d_naf || !o || !out_len || (S && !h_segs)) return NAF_GPU_EARG;
     arena_reset(c);
     *out_len = 0;
+    size_t first_rc = S;
+    if (h_strand) for (size_t k = 0; k < S; k++) {
+        if (h_strand[k] > 1) return ctx_fail(c, NAF_GPU_EARG, "segment %zu: strand %u is neither 0 (as stored) nor 1 (reverse complement)", k, (unsigned)h_strand[k]);
+        if (h_strand[k] && first_rc == S) first_rc = k;
+    }
+    const bool any_rc = first_rc < S;
     UnnafPlan pl;
     int rc = select_tables(c, d_naf, naf_len, o, pl); if (rc) return rc;
+    if (any_rc && !pl.fourbit) return ctx_fail(c, NAF_GPU_EARG, "segment %zu: a %s sequence has no reverse complement", first_rc, pl.h.seq_type == NAF_SEQ_PROTEIN ? "protein" : "text");
     if (S == 0) return 0;
     const naf_gpu_header &h = pl.h;
     EmitP &P = pl.P;
@@ -392,12 +442,14 @@ static int select_run(naf_gpu_ctx *c, const u8 *d_naf, size_t naf_len, const naf
     SelSeg *sg = arena_new<SelSeg>(c, S + 1);
     u64 *seg_out = arena_new<u64>(c, S + 2), *hoff = arena_new<u64>(c, S + 2), *iv = arena_new<u64>(c, 2 * S);
     unsigned long long *d_status = arena_new<unsigned long long>(c, 1);
-    if (!d_in || !sg || !seg_out || !hoff || !iv || !d_status) return NAF_GPU_ENOMEM;
+    u8 *d_strand = any_rc ? (u8 *)arena_alloc(c, S) : nullptr;
+    if (!d_in || !sg || !seg_out || !hoff || !iv || !d_status || (any_rc && !d_strand)) return NAF_GPU_ENOMEM;
+    if (any_rc) HIP_TRY(c, hipMemcpyAsync(d_strand, h_strand, S, hipMemcpyHostToDevice, c->stream));
     HIP_TRY(c, hipMemcpyAsync(d_in, h_segs, S * sizeof *h_segs, hipMemcpyHostToDevice, c->stream));
     HIP_TRY(c, hipMemsetAsync(d_status, 0xFF, 8, c->stream));
     HIP_TRY(c, hipMemsetAsync(seg_out + S, 0, 8, c->stream));
     HIP_TRY(c, hipMemsetAsync(hoff + S, 0, 8, c->stream));
-    LAUNCH(c, "unnaf_select_layout", k_select_layout, cdiv(S, 256), 256, 0, P, (const naf_gpu_segment *)d_in, (u64)S, sg, seg_out, hoff, iv, d_status);
+    LAUNCH(c, "unnaf_select_layout", k_select_layout, cdiv(S, 256), 256, 0, P, (const naf_gpu_segment *)d_in, (const u8 *)d_strand, (u64)S, sg, seg_out, hoff, iv, d_status);
     if ((rc = scan_exclusive_u64(c, seg_out, S + 1, (u64 *)nullptr))) return rc;
     if ((rc = scan_exclusive_u64(c, hoff, S + 1, (u64 *)nullptr))) return rc;
     u64 first_bad = 0, total = 0, htotal = 0;
@@ -483,7 +535,8 @@ static int select_run(naf_gpu_ctx *c, const u8 *d_naf, size_t naf_len, const naf
         LAUNCH(c, "unnaf_select_bind", k_select_bind, cdiv(S, 256), 256, 0, sg, (u64)S, (const SelRange *)d_rg, (u32)hr.size());
     }
     const u32 grid = cdiv(total, 4096);
-    if (pl.fourbit) LAUNCH(c, "unnaf_emit_select", k_emit_select<true>, grid, 64, 0, P, (const SelSeg *)sg, (const u64 *)seg_out, (u64)S, (const u8 *)hdr_text, total, d_out);
+    if (any_rc) LAUNCH(c, "unnaf_emit_select_rc", (k_emit_select<true, true>), grid, 64, 0, P, (const SelSeg *)sg, (const u64 *)seg_out, (u64)S, (const u8 *)hdr_text, total, d_out);
+    else if (pl.fourbit) LAUNCH(c, "unnaf_emit_select", k_emit_select<true>, grid, 64, 0, P, (const SelSeg *)sg, (const u64 *)seg_out, (u64)S, (const u8 *)hdr_text, total, d_out);
     else LAUNCH(c, "unnaf_emit_select", k_emit_select<false>, grid, 64, 0, P, (const SelSeg *)sg, (const u64 *)seg_out, (u64)S, (const u8 *)hdr_text, total, d_out);
     HIP_TRY(c, hipGetLastError());
     HIP_TRY(c, hipStreamSynchronize(c->stream));                                 // (hr, the uploaded table, is this call's)
@@ -494,12 +547,24 @@ static int select_run(naf_gpu_ctx *c, const u8 *d_naf, size_t naf_len, const naf
 extern "C" int naf_gpu_unnaf_select_size(naf_gpu_ctx *c, const void *d_naf, size_t naf_len, const naf_gpu_unnaf_opts *o,
                                          const naf_gpu_segment *segs, size_t n_segs, size_t *out_len)
 {
-    return select_run(c, (const u8 *)d_naf, naf_len, o, segs, n_segs, nullptr, 0, out_len, true);
+    return select_run(c, (const u8 *)d_naf, naf_len, o, segs, nullptr, n_segs, nullptr, 0, out_len, true);
 }
 extern "C" int naf_gpu_unnaf_select(naf_gpu_ctx *c, const void *d_naf, size_t naf_len, const naf_gpu_unnaf_opts *o,
                                     const naf_gpu_segment *segs, size_t n_segs, void *d_out, size_t out_cap, size_t *out_len)
 {
-    int rc = select_run(c, (const u8 *)d_naf, naf_len, o, segs, n_segs, (u8 *)d_out, out_cap, out_len, false);
+    int rc = select_run(c, (const u8 *)d_naf, naf_len, o, segs, nullptr, n_segs, (u8 *)d_out, out_cap, out_len, false);
+    if (c) arena_settle(c);
+    return rc;
+}
+extern "C" int naf_gpu_unnaf_select_stranded_size(naf_gpu_ctx *c, const void *d_naf, size_t naf_len, const naf_gpu_unnaf_opts *o,
+                                                  const naf_gpu_segment *segs, const uint8_t *strand, size_t n_segs, size_t *out_len)
+{
+    return select_run(c, (const u8 *)d_naf, naf_len, o, segs, strand, n_segs, nullptr, 0, out_len, true);
+}
+extern "C" int naf_gpu_unnaf_select_stranded(naf_gpu_ctx *c, const void *d_naf, size_t naf_len, const naf_gpu_unnaf_opts *o,
+                                             const naf_gpu_segment *segs, const uint8_t *strand, size_t n_segs, void *d_out, size_t out_cap, size_t *out_len)
+{
+    int rc = select_run(c, (const u8 *)d_naf, naf_len, o, segs, strand, n_segs, (u8 *)d_out, out_cap, out_len, false);
     if (c) arena_settle(c);
     return rc;
 }

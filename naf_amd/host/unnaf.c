@@ -12,9 +12,10 @@ static bool use_mask = true, force_stdout = false, verbose = false;
 static char *in_file_path = NULL, *out_file_path = NULL;
 static bool line_length_is_specified = false; static long long requested_line_length = 0;
 static FILE *OUT = NULL; static bool created_output_file = false, success = false;
-/* --region / --records, in command-line order (this implementation only: the reference has no selection) */
-typedef struct { const char *region; unsigned long long first, last; } selection;      /* region, or records first..last (1-based, inclusive) */
+/* --region / --rc-region / --records, in command-line order (this implementation only: the reference has no selection) */
+typedef struct { const char *region; unsigned long long first, last; bool rc; } selection;      /* region, or records first..last (1-based, inclusive); rc: its reverse complement */
 static selection *selections = NULL; static size_t n_selections = 0;
+static bool revcomp = false;                                      /* --revcomp: every selection of the call as its reverse complement */
 
 static void done(int status, void *arg)
 {
@@ -36,17 +37,17 @@ static void set_line_length(char *str)
     requested_line_length = a; line_length_is_specified = true;
 }
 
-static void add_selection(const char *region, unsigned long long first, unsigned long long last)
+static void add_selection(const char *region, unsigned long long first, unsigned long long last, bool rc)
 {
     selections = (selection *)realloc(selections, (n_selections + 1) * sizeof *selections);
     if (!selections) die("can't allocate memory\n");
-    selections[n_selections++] = (selection){ region, first, last };
+    selections[n_selections++] = (selection){ region, first, last, rc };
 }
-static void add_region(const char *spec)
+static void add_region(const char *spec, bool rc)
 {
     size_t id_len; uint64_t b, e;
-    if (naf_gpu_parse_region(spec, &id_len, &b, &e)) die("can't parse the value of --region parameter\n");
-    add_selection(spec, 0, 0);
+    if (naf_gpu_parse_region(spec, &id_len, &b, &e)) die("can't parse the value of %s parameter\n", rc ? "--rc-region" : "--region");
+    add_selection(spec, 0, 0, rc);
 }
 static void add_records(const char *spec)
 {
@@ -55,7 +56,7 @@ static void add_records(const char *spec)
     unsigned long long a = strtoull(spec, &end, 10), b = a;
     if (*end == '-') { const char *q = end + 1; if (*q < '0' || *q > '9') die("can't parse the value of --records parameter\n"); b = strtoull(q, &end, 10); }
     if (*end || a == 0 || b < a) die("can't parse the value of --records parameter\n");
-    add_selection(NULL, a, b);
+    add_selection(NULL, a, b, false);
 }
 
 static void show_help(void)
@@ -74,7 +75,9 @@ static void show_help(void)
         "  --binary        - Shortcut for \"--binary-stdout --binary-stderr\"\n  -h, --help      - Show help\n  -V, --version   - Show version\n"
         "Options for selecting records (with --fasta, --fastq, --seq, --sequences; repeatable, output in the order given):\n"
         "  --region ID[:A-B] - Sequence ID, or its bases A to B (1-based, inclusive; \"ID:A-\" = to its end)\n"
-        "  --records A-B   - Sequences number A to B (1-based, inclusive)\n");
+        "  --records A-B   - Sequences number A to B (1-based, inclusive)\n"
+        "  --rc-region ID[:A-B] - The same region as its reverse complement (header \"ID:A-B/rc\"; DNA and RNA only)\n"
+        "  --revcomp       - Every selected sequence and region as its reverse complement\n");
 }
 
 static void parse_command_line(int argc, char **argv)
@@ -87,12 +90,12 @@ static void parse_command_line(int argc, char **argv)
         {"--fasta", FASTA}, {"--fastq", FASTQ}, {"--dna", DNA}, {"--masked-dna", MASKED_DNA}, {"--unmasked-dna", UNMASKED_DNA},
         {"--masked-fasta", MASKED_FASTA}, {"--unmasked-fasta", UNMASKED_FASTA} };
     /* the other options (unnaf/src/unnaf.c:282-353), as a table: one that takes a value is only recognised with an argument behind it */
-    enum { OP_LINE_LENGTH, OP_OUT, OP_NO_MASK, OP_IGNORED, OP_HELP, OP_VERBOSE, OP_VERSION, OP_STDOUT, OP_REGION, OP_RECORDS };
+    enum { OP_LINE_LENGTH, OP_OUT, OP_NO_MASK, OP_IGNORED, OP_HELP, OP_VERBOSE, OP_VERSION, OP_STDOUT, OP_REGION, OP_RECORDS, OP_RC_REGION, OP_REVCOMP };
     static const struct { const char *name; int op; bool value; } option_table[] = {
         { "--line-length", OP_LINE_LENGTH, true }, { "-o", OP_OUT, true }, { "--no-mask", OP_NO_MASK, false }, { "--binary-stdout", OP_IGNORED, false },
         { "--binary-stderr", OP_IGNORED, false }, { "--binary", OP_IGNORED, false }, { "--help", OP_HELP, false }, { "-h", OP_HELP, false },
         { "--verbose", OP_VERBOSE, false }, { "--version", OP_VERSION, false }, { "-V", OP_VERSION, false }, { "-c", OP_STDOUT, false },
-        { "--region", OP_REGION, true }, { "--records", OP_RECORDS, true } };
+        { "--region", OP_REGION, true }, { "--records", OP_RECORDS, true }, { "--rc-region", OP_RC_REGION, true }, { "--revcomp", OP_REVCOMP, false } };
     for (int i = 1; i < argc; i++) {
         char *arg = argv[i];
         if (arg[0] != '-') {
@@ -117,7 +120,9 @@ static void parse_command_line(int argc, char **argv)
         case OP_VERBOSE: verbose = true; break;
         case OP_VERSION: print_version = true; break;
         case OP_STDOUT: force_stdout = true; break;
-        case OP_REGION: add_region(v); break;
+        case OP_REGION: add_region(v, false); break;
+        case OP_RC_REGION: add_region(v, true); break;
+        case OP_REVCOMP: revcomp = true; break;
         case OP_RECORDS: add_records(v); break;
         }
     }
@@ -127,8 +132,10 @@ static void parse_command_line(int argc, char **argv)
         exit(0);
     }
     if (force_stdout && out_file_path) die("-c and -o arguments can't be used together\n");
-    if (n_selections && !(out_type == UNDECIDED || out_type == FASTA || out_type == FASTQ || out_type == SEQ || out_type == SEQUENCES))
+    if ((n_selections || revcomp) && !(out_type == UNDECIDED || out_type == FASTA || out_type == FASTQ || out_type == SEQ || out_type == SEQUENCES))
         die("--region can be used only with sequence output\n");
+    if (revcomp && !n_selections) die("--revcomp can be used only with --region or --records\n");
+    if (revcomp) for (size_t k = 0; k < n_selections; k++) selections[k].rc = true;        /* (an --rc-region stays reverse: no double flip) */
 }
 
 static const unsigned char *naf; static size_t naf_len; static naf_gpu_header H; static void *d_naf = NULL;
@@ -248,16 +255,16 @@ static void run_text(int mode, int masking_allowed)
 }
 
 /* --region / --records: ids to record numbers (naf_gpu_unnaf_find), then the segments' texts in command-line order
- * (naf_gpu_unnaf_select), on the first device.  Nothing is written before every id is found. */
+ * (naf_gpu_unnaf_select_stranded: --rc-region / --revcomp give a segment's reverse complement), on the first device.  Nothing is written before every id is found. */
 static void *sel_buf = NULL; static size_t sel_cap = 0;
-static void emit_segments(const naf_gpu_unnaf_opts *o, const naf_gpu_segment *segs, size_t n)
+static void emit_segments(const naf_gpu_unnaf_opts *o, const naf_gpu_segment *segs, const uint8_t *strand, size_t n)
 {
     /* a selection larger than the range buffer is produced in pieces of whole segments: halves until a piece fits (or is one segment) */
-    size_t need = 0; GPU_TRY(naf_gpu_unnaf_select_size(gpu, d_naf, naf_len, o, segs, n, &need));
+    size_t need = 0; GPU_TRY(naf_gpu_unnaf_select_stranded_size(gpu, d_naf, naf_len, o, segs, strand, n, &need));
     if (!need) return;
-    if (need > range_bytes() && n > 1) { emit_segments(o, segs, n / 2); emit_segments(o, segs + n / 2, n - n / 2); return; }
+    if (need > range_bytes() && n > 1) { emit_segments(o, segs, strand, n / 2); emit_segments(o, segs + n / 2, strand ? strand + n / 2 : NULL, n - n / 2); return; }
     if (need > sel_cap) { if (sel_buf) naf_gpu_free(gpu, sel_buf); GPU_TRY(naf_gpu_malloc(gpu, need + 64, &sel_buf)); sel_cap = need; }
-    size_t got = 0; GPU_TRY(naf_gpu_unnaf_select(gpu, d_naf, naf_len, o, segs, n, sel_buf, sel_cap, &got));
+    size_t got = 0; GPU_TRY(naf_gpu_unnaf_select_stranded(gpu, d_naf, naf_len, o, segs, strand, n, sel_buf, sel_cap, &got));
     if (got != need) die("can't decompress sequence\n");
     write_from_device(OUT, sel_buf, got);
 }
@@ -277,7 +284,8 @@ static void run_select(int mode, bool has_ids)
     }
     char *ids = (char *)malloc(ids_bytes + 1); uint64_t *recs = (uint64_t *)malloc((n_regions + 1) * sizeof *recs);
     naf_gpu_segment *segs = (naf_gpu_segment *)malloc((n_segs + 1) * sizeof *segs);
-    if (!ids || !recs || !segs) die("can't allocate memory\n");
+    uint8_t *strand = (uint8_t *)malloc(n_segs + 1); bool any_rc = false;
+    if (!ids || !recs || !segs || !strand) die("can't allocate memory\n");
     size_t at = 0;
     for (size_t k = 0; k < n_selections; k++) if (selections[k].region) {
         size_t l; uint64_t b, e; naf_gpu_parse_region(selections[k].region, &l, &b, &e);
@@ -293,14 +301,15 @@ static void run_select(int mode, bool has_ids)
         if (s->region) {
             size_t l; uint64_t b, e; naf_gpu_parse_region(s->region, &l, &b, &e);
             if (recs[q] == UINT64_MAX) die("sequence \"%.*s\" not found\n", (int)l, s->region);
-            segs[m++] = (naf_gpu_segment){ recs[q++], b, e };
-        } else for (unsigned long long r = s->first; r <= s->last; r++) segs[m++] = (naf_gpu_segment){ r - 1, 0, NAF_GPU_WHOLE };
+            strand[m] = s->rc; segs[m++] = (naf_gpu_segment){ recs[q++], b, e };
+        } else for (unsigned long long r = s->first; r <= s->last; r++) { strand[m] = s->rc; segs[m++] = (naf_gpu_segment){ r - 1, 0, NAF_GPU_WHOLE }; }
+        any_rc = any_rc || s->rc;
     }
     naf_gpu_unnaf_opts o = { mode, mode != NAF_OUT_FASTQ && use_mask, line_length_is_specified ? requested_line_length : -1 };
     fflush(OUT);
-    emit_segments(&o, segs, n_segs);
+    emit_segments(&o, segs, any_rc ? strand : NULL, n_segs);
     if (sel_buf) { naf_gpu_free(gpu, sel_buf); sel_buf = NULL; sel_cap = 0; }
-    free(ids); free(recs); free(segs);
+    free(ids); free(recs); free(segs); free(strand);
 }
 
 int main(int argc, char **argv)
@@ -350,6 +359,7 @@ int main(int argc, char **argv)
     unsigned long long N = H.n_sequences;
     if (n_selections) {
         if (out_type == FASTQ && !has_quality) die("FASTQ output requested, but input has no qualities\n");
+        for (size_t k = 0; k < n_selections; k++) if (selections[k].rc && H.seq_type >= NAF_SEQ_PROTEIN) die("%s sequences have no reverse complement\n", tn[H.seq_type]);
         run_select(out_type == FASTA ? NAF_OUT_FASTA : out_type == FASTQ ? NAF_OUT_FASTQ : out_type == SEQ ? NAF_OUT_SEQ : NAF_OUT_SEQUENCES, has_ids);
     }
     else if (out_type == FORMAT_NAME) fprintf(OUT, "%s sequences%s in NAF format version %d\n", tn[H.seq_type], has_quality ? " with qualities" : "", H.version);

@@ -2,7 +2,9 @@
 """Selection beside the whole text: tools/perf_select.py [genome bytes] [read-set bytes] -- on the realistic genome (default 4 GB) and
 the read set (default 12.5 GB) of the bench configs, per-call times of (a) one whole record, (b) a 1 Mb region, (c) 1 000 scattered
 10 kb regions (reads: 1 000 scattered reads), (d) find of 1 000 ids, each beside naf_gpu_unnaf of the same archive; then the kernel
-list of every call.  Warm-up 3, median / min / max of 10, the host clock around calls that end in a device synchronise."""
+list of every call.  Rows (a), (b), (c) are followed by their reverse twins -- the same segments as their reverse complements
+(naf_gpu_unnaf_select_stranded) -- with the ratio to the forward row of the same run, for the call and for the emit kernel alone.
+Warm-up 3, median / min / max of 10, the host clock around calls that end in a device synchronise."""
 import os
 import subprocess
 import sys
@@ -29,10 +31,24 @@ def timed(label, fn):
     ts.sort()
     print("%-44s median %9.3f ms  min %9.3f  max %9.3f" % (label, ts[5] * 1e3, ts[0] * 1e3, ts[-1] * 1e3))
     ctx.set_timing(True); fn(); torch.cuda.synchronize()
-    for nm, ms, k in sorted(ctx.get_timing(), key=lambda x: -x[1])[:8]:
+    kernels = ctx.get_timing()
+    for nm, ms, k in sorted(kernels, key=lambda x: -x[1])[:8]:
         print("      %-28s %8.3f ms x%d" % (nm, ms, k))
     ctx.set_timing(False)
+    timed.last = (ts[5] * 1e3, sum(ms for nm, ms, k in kernels if nm.startswith("unnaf_emit_select")))
     return r
+
+
+def both_strands(label, naf, segs, mode, out):
+    """A row and its reverse twin: the same segments forward, then as reverse complements, and the ratios reverse / forward."""
+    W = capi.WHOLE
+    fwd = [(s, 0, W) if isinstance(s, int) else s for s in segs]
+    timed(label, lambda: ctx.unnaf_select(naf, fwd, mode, out=out))
+    f_call, f_emit = timed.last
+    rev = [s + (1,) for s in fwd]
+    timed(label + ", reverse", lambda: ctx.unnaf_select(naf, rev, mode, out=out))
+    r_call, r_emit = timed.last
+    print("      reverse / forward: call %.2f, emit kernel %.3f / %.3f ms = %.2f" % (r_call / f_call, r_emit, f_emit, r_emit / f_emit))
 
 
 def run(kind, text, mode):
@@ -48,18 +64,18 @@ def run(kind, text, mode):
     timed("whole text (naf_gpu_unnaf)", lambda: ctx.unnaf(naf, mode, out=out))
     rng = np.random.default_rng(1)
     r17 = min(17, N - 1)
-    timed("(a) one whole record", lambda: ctx.unnaf_select(naf, [r17], mode, out=out))
+    both_strands("(a) one whole record", naf, [r17], mode, out)
     if mode == capi.OUT_FASTA:
         r3 = min(3, N - 1)
         b = int(nb[r3] // 3)
-        timed("(b) a 1 Mb region", lambda: ctx.unnaf_select(naf, [(r3, b, b + 1_000_000)], mode, out=out))
+        both_strands("(b) a 1 Mb region", naf, [(r3, b, b + 1_000_000)], mode, out)
         segs = []
         for k in range(1000):
             r = int(rng.integers(0, N)); s = int(rng.integers(0, max(1, nb[r] - 10_000))); segs.append((r, s, s + 10_000))
     else:
-        timed("(b) 100 000 consecutive reads", lambda: ctx.unnaf_select(naf, list(range(N // 2, N // 2 + 100_000)), mode, out=out))
+        both_strands("(b) 100 000 consecutive reads", naf, list(range(N // 2, N // 2 + 100_000)), mode, out)
         segs = [int(r) for r in rng.integers(0, N, 1000)]
-    timed("(c) 1 000 scattered", lambda: ctx.unnaf_select(naf, segs, mode, out=out))
+    both_strands("(c) 1 000 scattered", naf, segs, mode, out)
     # the ids of 1 000 records, read out of the whole text
     recs = sorted(int(r) for r in rng.integers(0, N, 1000))
     ids = []
