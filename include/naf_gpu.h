@@ -21,7 +21,9 @@
  * on success or a negative NAF_GPU_E* code; naf_gpu_last_error(ctx) gives the text (for parity with
  * the reference's die() strings where the reference defines one).  One ctx per device and per host
  * thread; calls on a ctx are serialised on its HIP stream.  "d_" pointers are device (HBM) addresses,
- * "h_" pointers are host addresses.  There is NO CPU fallback: without a usable gfx950 device
+ * "h_" pointers are host addresses.  "d_" pointers may have any alignment; a call writes only inside
+ * [d_out, d_out + capacity), its result depends only on [d_src, d_src + len), and with NAF_GPU_ECAP
+ * *out_len (where the call has one that reports it) is the size of the whole result.  There is NO CPU fallback: without a usable gfx950 device
  * naf_gpu_init fails with NAF_GPU_ENODEV.
  */
 #ifndef NAF_GPU_H
@@ -120,7 +122,8 @@ int  naf_gpu_zstd_decompress(naf_gpu_ctx *ctx, const void *d_src, size_t src_len
 /* Compress d_src into ONE zstd frame made of independently coded blocks (single frame: SURVEY.md R1).
  * level <= 1: entropy-only blocks (Huffman literals, RLE, raw), Huffman weights written directly wherever the format allows
  * (up to 128 weights); level >= 2 adds the LZ stage (matches inside a block, coded with the predefined FSE sequence tables)
- * and FSE-codes the Huffman weights when that is smaller.  Blocks never depend on each other at any level. */
+ * and FSE-codes the Huffman weights when that is smaller.  Blocks never depend on each other at any level.
+ * dst_cap must be at least naf_gpu_zstd_compress_bound(src_len); less is NAF_GPU_ECAP and nothing is written. */
 int  naf_gpu_zstd_compress(naf_gpu_ctx *ctx, const void *d_src, size_t src_len, int level,
                            void *d_dst, size_t dst_cap, size_t *out_len);
 size_t naf_gpu_zstd_compress_bound(size_t src_len);

@@ -4532,6 +4532,7 @@ int zstd_decode_fused_fasta(naf_gpu_ctx *c, const u8 *d_src, size_t src_len, int
 int zstd_decode_range(naf_gpu_ctx *c, const u8 *d_src, size_t src_len, int has_magic, u8 *d_dst, size_t dst_cap, size_t *out_len, ZRange *rg, const u8 *head)
 {
     size_t pos = 0, out = 0; bool first = true;
+    bool short_of = false;                                   // a frame did not fit: the frames behind it are indexed for their sizes, not decoded
     *out_len = 0;
     while (pos < src_len || first) {
         if (!(first && !has_magic)) {
@@ -4550,14 +4551,16 @@ int zstd_decode_range(naf_gpu_ctx *c, const u8 *d_src, size_t src_len, int has_m
         }
         first = false;
         size_t n = 0, used = 0;
-        int rc = zstd_decode_one(c, d_src + pos, src_len - pos, d_dst + out, dst_cap > out ? dst_cap - out : 0, &n, &used, out == 0 ? rg : nullptr, nullptr, nullptr,
+        int rc = zstd_decode_one(c, d_src + pos, src_len - pos, short_of ? nullptr : d_dst + out, !short_of && dst_cap > out ? dst_cap - out : 0, &n, &used, out == 0 ? rg : nullptr, nullptr, nullptr,
                                  (head && pos == 0 && !has_magic) ? head : nullptr);
         if (rg && rg->ranged && pos + used < src_len) return ctx_fail(c, NAF_GPU_EZSTD, "range decode needs a single-frame stream");
-        if (rc == NAF_GPU_ECAP) { *out_len = out + n; return rc; }
+        // the capacity error reports the size of the WHOLE result (naf_gpu.h): a frame's size and length are known before its blocks are decoded
+        if (rc == NAF_GPU_ECAP) { short_of = true; rc = 0; }
         if (rc) return rc;
         out += n; pos += used;
     }
     *out_len = out;
+    if (short_of) return ctx_fail(c, NAF_GPU_ECAP, "zstd output needs %zu bytes, capacity %zu", out, dst_cap);
     return 0;
 }
 

@@ -1856,6 +1856,8 @@ int zstd_encode(naf_gpu_ctx *c, const u8 *d_src, size_t n, int level, u8 *d_dst,
 extern "C" int naf_gpu_zstd_compress(naf_gpu_ctx *c, const void *d_src, size_t n, int level, void *d_dst, size_t cap, size_t *out_len)
 {
     if (!c || !d_dst || !out_len || (!d_src && n)) return NAF_GPU_EARG;
+    // the capacity contract is the bound, whatever blocks this input is cut into (the plan's own worst case is a little less)
+    if (cap < naf_gpu_zstd_compress_bound(n)) return ctx_fail(c, NAF_GPU_ECAP, "zstd_compress capacity %zu is less than the bound %zu", cap, naf_gpu_zstd_compress_bound(n));
     arena_reset(c);
     return zstd_encode(c, (const u8 *)d_src, n, level, (u8 *)d_dst, cap, out_len, 1, 0, 0, zenc_level_window(level));
 }
