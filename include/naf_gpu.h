@@ -208,6 +208,41 @@ int  naf_gpu_unnaf_select_stranded(naf_gpu_ctx *ctx, const void *d_naf, size_t n
  * Returns the id's length and begin / end 0-based half-open ("ID": 0 / NAF_GPU_WHOLE; "ID:a-": a - 1 / NAF_GPU_WHOLE). */
 int  naf_gpu_parse_region(const char *text, size_t *id_len, uint64_t *begin, uint64_t *end);
 
+/* ---- unnaf: IUPAC motifs on either strand, searched in the packed stream -------------------------------------
+ * The reference has nothing of the kind (its users pipe the whole text into a searcher).  In the 4-bit code "-TGKCYSBAWRDMHVN" a base is
+ * a set of nucleotides (A = 8, C = 4, G = 2, T/U = 1, N = 15, '-' = 0): a stored base c matches a pattern letter p if and only if
+ * c != 0 && (c & ~p) == 0, and the complement of a code is its nibble with the bits reversed.
+ *   Patterns  1 to 32 letters of ACGTU RYSWKM BDHV N, either case; U and T are one letter in DNA and RNA archives alike; '-', the empty
+ *             string, more than 32 letters and anything else are rejected.
+ *   Matching  pattern letter j against stored base g + j.  A stored ambiguous base matches only letters that contain all of it (stored N:
+ *             pattern N only; stored R: R D V N); a gap matches nothing.  Case (the soft mask) plays no part; the mask is not decoded.  A
+ *             hit lies inside one record.  Bases behind the last record of a malformed archive and the padding nibble of an
+ *             odd stream are never matched.  Every start position is a hit: AAA in a run of ten A gives eight.
+ *   Strands   mask 1 = as stored, 2 = reverse, 3 = both.  A reverse hit at [begin, begin + m) means that the reverse complement of those
+ *             stored bases matches the pattern; coordinates are always the forward ones, as naf_gpu_unnaf_select_stranded takes them.  A
+ *             pattern equal to its own reverse complement, searched on both strands, gives two hits at each place.
+ *   Archives  FASTA and FASTQ archives alike; protein and text archives, and an archive without a sequence section, are NAF_GPU_EARG.
+ *             An archive without records gives 0 hits.
+ *   Order     ascending (record, begin), then pattern number, then strand (0 before 1); the same on every run.
+ * A hit is exactly the (record, begin, begin + length of the pattern, strand) that naf_gpu_unnaf_select_stranded takes. */
+typedef struct { uint64_t record, begin; uint32_t pattern, strand; } naf_gpu_hit;   /* 24 bytes; end = begin + length of pattern */
+
+/* host only, no device: the 4-bit sets of a pattern and of its reverse complement (rev[j] = fwd[len - 1 - j] with its bits reversed), and
+ * its length; entries behind the length are 0.  NAF_GPU_EARG for what is no pattern. */
+int  naf_gpu_compile_motif(const char *text, uint8_t fwd[32], uint8_t rev[32], size_t *len);
+
+/* h_patterns: n_patterns (1..16) zero-terminated strings laid end to end in HOST memory.  Records [first, first + count) are searched
+ * (count = NAF_GPU_WHOLE: to the last record); only the zstd blocks behind their bases are decoded when the frame allows it.
+ * *n_hits is always the whole count; per_pattern (HOST, n_patterns x 2 entries, may be NULL) receives the count of pattern k on strand s
+ * at [2 k + s].  d_hits is DEVICE memory of any alignment: with hit_cap too small the call returns NAF_GPU_ECAP and writes nothing.
+ * NAF_GPU_EARG (last_error names the pattern number and the offending letter): a string that is no pattern, first > n_sequences, a range
+ * past the last record, n_patterns outside 1..16, strands outside 1..3.  A search of more bases than NAF_GPU_LOCATE_PIECE (default 2^31) is
+ * decoded and scanned in pieces of whole records; the result does not depend on the piece size. */
+int  naf_gpu_unnaf_locate_count(naf_gpu_ctx *ctx, const void *d_naf, size_t naf_len, const char *h_patterns, size_t patterns_bytes, size_t n_patterns,
+                                int strands, uint64_t first, uint64_t count, uint64_t *n_hits, uint64_t *per_pattern);
+int  naf_gpu_unnaf_locate(naf_gpu_ctx *ctx, const void *d_naf, size_t naf_len, const char *h_patterns, size_t patterns_bytes, size_t n_patterns,
+                          int strands, uint64_t first, uint64_t count, naf_gpu_hit *d_hits, size_t hit_cap, uint64_t *n_hits);
+
 /* ---- ennaf ------------------------------------------------------------------------------------------ */
 typedef struct {
     int      format;            /* NAF_FMT_* (AUTO = sniff, process.c:547-583) */

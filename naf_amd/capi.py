@@ -29,6 +29,7 @@ EXPORTS = [
     "naf_gpu_set_option", "naf_gpu_get_trace", "naf_gpu_clear_trace", "naf_gpu_write_fd",
     "naf_gpu_unnaf_find", "naf_gpu_unnaf_record_table", "naf_gpu_unnaf_select_size", "naf_gpu_unnaf_select", "naf_gpu_parse_region",
     "naf_gpu_unnaf_select_stranded_size", "naf_gpu_unnaf_select_stranded",
+    "naf_gpu_compile_motif", "naf_gpu_unnaf_locate_count", "naf_gpu_unnaf_locate",
 ]
 WHOLE = 2 ** 64 - 1                     # NAF_GPU_WHOLE: (record, 0, WHOLE) is the record as stored
 MAX_SHARDS = 64
@@ -83,6 +84,16 @@ class StitchSeg(C.Structure):
 class Segment(C.Structure):
     """naf_gpu_segment: bases [begin, end) of a record, 0-based."""
     _fields_ = [("record", C.c_uint64), ("begin", C.c_uint64), ("end", C.c_uint64)]
+
+
+class Hit(C.Structure):
+    """naf_gpu_hit: pattern number `pattern` matches at bases [begin, begin + its length) of `record`; strand 1 = the reverse complement
+    of those bases does."""
+    _fields_ = [("record", C.c_uint64), ("begin", C.c_uint64), ("pattern", C.c_uint32), ("strand", C.c_uint32)]
+
+
+HIT_DTYPE = [("record", "<u8"), ("begin", "<u8"), ("pattern", "<u4"), ("strand", "<u4")]      # numpy's view of a table of hits
+STRAND_FORWARD, STRAND_REVERSE, STRAND_BOTH = 1, 2, 3
 
 
 class NafGpuError(RuntimeError):
@@ -171,6 +182,9 @@ def load():
         u8p = C.POINTER(C.c_uint8)
         L.naf_gpu_unnaf_select_stranded_size.argtypes = [vp, vp, sz, C.POINTER(UnnafOpts), C.POINTER(Segment), u8p, sz, C.POINTER(sz)]
         L.naf_gpu_unnaf_select_stranded.argtypes = [vp, vp, sz, C.POINTER(UnnafOpts), C.POINTER(Segment), u8p, sz, vp, sz, C.POINTER(sz)]
+        L.naf_gpu_compile_motif.argtypes = [C.c_char_p, u8p, u8p, C.POINTER(sz)]
+        L.naf_gpu_unnaf_locate_count.argtypes = [vp, vp, sz, C.c_char_p, sz, sz, i, C.c_uint64, C.c_uint64, u64p, u64p]
+        L.naf_gpu_unnaf_locate.argtypes = [vp, vp, sz, C.c_char_p, sz, sz, i, C.c_uint64, C.c_uint64, vp, sz, u64p]
         _lib = L
     return _lib
 
@@ -184,6 +198,32 @@ def parse_region(text):
         raise ValueError("not a region: %r" % (text,))
     rid = b[:n.value]
     return (rid.decode("latin1") if isinstance(text, str) else rid), lo.value, hi.value
+
+
+def compile_motif(text):
+    """Host-only: (fwd, rev) -- the 4-bit sets of an IUPAC pattern and of its reverse complement, as bytes of the pattern's length
+    (naf_gpu_compile_motif).  ValueError for what is no pattern."""
+    b = text.encode("latin1") if isinstance(text, str) else bytes(text)
+    if b"\0" in b:
+        raise ValueError("not a pattern: %r" % (text,))
+    fwd, rev, n = (C.c_uint8 * 32)(), (C.c_uint8 * 32)(), C.c_size_t()
+    if load().naf_gpu_compile_motif(b, fwd, rev, C.byref(n)):
+        raise ValueError("not a pattern: %r" % (text,))
+    return bytes(fwd[:n.value]), bytes(rev[:n.value])
+
+
+def hits_to_segments(hits, patterns, flank=0, lengths=None):
+    """The (record, begin, end, reverse) tuples unnaf_select takes, one per hit (rows of the table unnaf_locate returns), for the patterns
+    the search was made with.  flank: that many bases more on either side, clamped to the record -- to its start always, to its end when
+    `lengths` (the n_bases of unnaf_record_table, indexed by record number) is given; unnaf_select clamps an end beyond the record itself."""
+    out = []
+    for h in hits:
+        r, b, e = int(h["record"]), int(h["begin"]), int(h["begin"]) + len(patterns[int(h["pattern"])])
+        b, e = max(0, b - flank), e + flank
+        if lengths is not None:
+            e = min(e, int(lengths[r]))
+        out.append((r, b, e, int(h["strand"])))
+    return out
 
 
 def shard_carry(infos, k):
@@ -450,6 +490,41 @@ class Context:
         else:
             self._check(self.L.naf_gpu_unnaf_select_stranded(self.h, _ptr(d_naf), d_naf.numel(), C.byref(o), segs, strands, len(segments), _ptr(out), out.numel(), C.byref(n)))
         return out[:n.value]
+
+    @staticmethod
+    def _patterns(patterns):
+        raw = [p.encode("latin1") if isinstance(p, str) else bytes(p) for p in patterns]
+        if any(b"\0" in p for p in raw):
+            raise ValueError("a pattern cannot hold a zero byte")
+        return b"".join(p + b"\0" for p in raw), len(raw)
+
+    def unnaf_locate_count(self, d_naf, patterns, strands=3, first=0, count=None):
+        """(hits in all, [[forward, reverse] per pattern]) of IUPAC patterns in records [first, first + count) -- count=None: to the last
+        record; strands: 1 as stored, 2 reverse, 3 both (naf_gpu_unnaf_locate_count)."""
+        blob, n = self._patterns(patterns)
+        total, per = C.c_uint64(), (C.c_uint64 * max(2 * n, 1))()
+        self._check(self.L.naf_gpu_unnaf_locate_count(self.h, _ptr(d_naf), d_naf.numel(), blob, len(blob), n, int(strands), int(first),
+                                                      WHOLE if count is None else int(count), C.byref(total), per))
+        return total.value, [[int(per[2 * k]), int(per[2 * k + 1])] for k in range(n)]
+
+    def unnaf_locate(self, d_naf, patterns, strands=3, first=0, count=None, out=None):
+        """(hits, total): the hits as a structured numpy array (HIT_DTYPE: record, begin, pattern, strand) in the order of the contract --
+        (record, begin), pattern number, strand.  out: a uint8 device tensor to take the table (24 bytes a hit); then `hits` is the torch
+        view of its first 24 * total bytes and too small a tensor raises NafGpuError(E_CAP).  Without it the table is counted first."""
+        import numpy as np
+        import torch
+        blob, n = self._patterns(patterns)
+        total = C.c_uint64()
+        cnt = WHOLE if count is None else int(count)
+        if out is not None:
+            self._check(self.L.naf_gpu_unnaf_locate(self.h, _ptr(d_naf), d_naf.numel(), blob, len(blob), n, int(strands), int(first), cnt,
+                                                    _ptr(out), out.numel() // 24, C.byref(total)))
+            return out[:24 * total.value], total.value
+        self._check(self.L.naf_gpu_unnaf_locate_count(self.h, _ptr(d_naf), d_naf.numel(), blob, len(blob), n, int(strands), int(first), cnt, C.byref(total), None))
+        buf = torch.empty(max(24 * total.value, 1), dtype=torch.uint8, device=self.device)
+        self._check(self.L.naf_gpu_unnaf_locate(self.h, _ptr(d_naf), d_naf.numel(), blob, len(blob), n, int(strands), int(first), cnt,
+                                                _ptr(buf), total.value, C.byref(total)))
+        return np.frombuffer(buf[:24 * total.value].cpu().numpy().tobytes(), dtype=HIT_DTYPE), total.value
 
     def histogram(self, d_buf):
         """Byte counts of a device buffer (unnaf --charcount)."""

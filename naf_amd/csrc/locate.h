@@ -1,0 +1,324 @@
+// locate.h -- IUPAC motifs on either strand, searched in the packed 4-bit stream (naf_gpu_compile_motif, naf_gpu_unnaf_locate_count,
+// naf_gpu_unnaf_locate).  Part of emit.hip (included by it, behind emit_select.h): it uses that file's side-section chain for the
+// record tables and the range decode of the selection path, and adds two kernels of its own.
+//
+// In the code table "-TGKCYSBAWRDMHVN" a base is a SET of nucleotides (A = 8, C = 4, G = 2, T/U = 1, N = 15, '-' = 0), so
+//   a stored base c matches a pattern letter p   <=>   c != 0 && (c & ~p) == 0
+// and the complement of a code is the code with its four bits reversed.  The contract (include/naf_gpu.h carries it too):
+//   patterns   1 .. 32 letters of ACGTU RYSWKM BDHV N in either case, U = T in DNA and RNA archives alike; '-', the empty string and
+//              anything else are rejected.
+//   matching   letter j against stored base g + j.  A stored ambiguous base matches only letters that contain all of it (stored N:
+//              pattern N only; a gap: nothing).  The soft mask plays no part and is not decoded.  A hit lies inside ONE record; bases
+//              behind the last record of a malformed archive and the padding nibble of an odd stream are never matched.  Every start
+//              position is a hit, overlapping ones too.
+//   strands    mask 1 = as stored, 2 = reverse, 3 = both.  A reverse hit at [begin, begin + m) says that the reverse complement of
+//              those stored bases matches the pattern -- the stored bases match the pattern reversed with every code bit-reversed.
+//              Coordinates are the forward ones.  A pattern that is its own reverse complement gives two hits a place on both strands.
+//   order      ascending (record, begin), then pattern number, then strand (0 before 1); the same on every run.
+//
+// A window of 32 bases is 128 bits, base j in bits 4j .. 4j + 3 (the stream's own order: the first base of a byte is its low nibble).
+// One combination of pattern and strand is four 64-bit masks: ~p in the nibbles of its letters (0 behind them) and a 1 in the lowest
+// bit of each of those nibbles; against a window W and the "this nibble is zero" flags Z of W (made once per window)
+//   hit  <=>  ((W & ~p) | (Z & ones)) == 0
+// Two passes over the packed bytes, a wavefront per tile of 4096 bases, 64 positions a lane: a lane loads its 32 bytes and the 16
+// behind them and moves the window on by a 128-bit funnel shift of one nibble a step.  k_locate<false> counts -- per tile, per lane
+// and per combination (a ballot per test, summed in the lane that owns the combination; one atomic a tile and combination at the
+// end) --, the tile counts are scanned, and k_locate<true> recomputes the hits of the tiles that have any and stores them at the place
+// a wave prefix sum over the lanes' counts gives.  Tiles start at the searched range's first base rounded down to an even one, so a
+// lane's bases always start on a byte.
+#pragma once
+
+#define LOC_TILE 4096u
+#define LOC_MAX_PATTERNS 16
+#define LOC_MAX_COMBOS 32
+#define LOC_PIECE_DEFAULT (1ull << 31)       // bases searched per decode of a whole-archive search (NAF_GPU_LOCATE_PIECE)
+
+struct LocCombo { u64 nl, nh, ol, oh; };     // ~p of letters 0..15 / 16..31 (0 behind the pattern); 1 in bit 0 of every nibble that holds a letter
+struct LocPats { LocCombo c[LOC_MAX_COMBOS]; u32 len[LOC_MAX_COMBOS]; u8 pat[LOC_MAX_COMBOS], strand[LOC_MAX_COMBOS]; u32 n; };
+
+__device__ __forceinline__ u32 wave_sum_u32(u32 v) { for (int d = 32; d; d >>= 1) v += (u32)__shfl_xor((int)v, d); return v; }
+__device__ __forceinline__ u32 wave_prefix_u32(u32 v, u32 lane)                 // exclusive
+{
+    u32 s = v;
+    for (int d = 1; d < 64; d <<= 1) { const u32 o = (u32)__shfl_up((int)s, d); if (lane >= (u32)d) s += o; }
+    return s - v;
+}
+// bit 4j set where nibble j of w is zero
+__device__ __forceinline__ u64 zero_nibbles(u64 w) { u64 t = w | (w >> 1); t |= t >> 2; return ~t & 0x1111111111111111ull; }
+
+// WRITE = false: tile_cnt[t] = hits of tile t, lane_cnt[64 t + lane] = hits of a lane (written for tiles that have hits),
+//                combo_cnt[k] += hits of combination k.
+// WRITE = true:  the hits of tile t at hits[out_base + tile_off[t] ...], in position order; a tile without hits returns at once.
+// LONG: a pattern is longer than 16 letters (the upper half of the window takes part).
+// seq: pointer to packed byte 0 of the stream; bytes [.., b_end) of it may be read (the lanes at the range's end load byte by byte).
+// Records [r_lo, r_hi) are searched: rec_base[r_lo] = p_lo, rec_base[r_hi] = p_hi.  t0: first base of tile 0, even, <= p_lo.
+template <bool WRITE, bool LONG>
+__global__ __launch_bounds__(64) void k_locate(LocPats Q, const u8 *seq, u64 b_end, const u64 *rec_base, u64 r_lo, u64 r_hi, u64 p_lo, u64 p_hi, u64 t0,
+                                               u64 *tile_cnt, u32 *lane_cnt, unsigned long long *combo_cnt,
+                                               const u64 *tile_off, u64 out_base, u8 *hits, u64 hit_cap)
+{
+    const u32 lane = threadIdx.x;
+    const u64 t = xcd_block();
+    u64 at = 0;
+    if (WRITE) {
+        const u64 o0 = tile_off[t], o1 = tile_off[t + 1];
+        if (o0 == o1) return;
+        at = out_base + o0 + wave_prefix_u32(lane_cnt[t * 64 + lane], lane);
+    }
+    const u64 g = t0 + t * LOC_TILE + lane * 64;                                  // the lane's first position
+    const bool active = g < p_hi && g + 64 > p_lo;
+    u64 w[6] = { 0, 0, 0, 0, 0, 0 };
+    u64 r = 0, rbase = 0, rend = 0;
+    if (active) {
+        const u64 b0 = g >> 1;
+        const u32 nb = LONG ? 48u : 40u;
+        if (b0 + nb <= b_end) {
+#pragma unroll
+            for (u32 k = 0; k < nb / 8; k++) w[k] = ld64(seq + b0 + 8 * k);
+        } else {
+#pragma unroll
+            for (u32 k = 0; k < nb / 8; k++) {
+                u64 v = 0;
+                for (u32 i = 0; i < 8; i++) if (b0 + 8 * k + i < b_end) v |= (u64)seq[b0 + 8 * k + i] << (8 * i);
+                w[k] = v;
+            }
+        }
+        const u64 x0 = g > p_lo ? g : p_lo;
+        r = upper_bound_u64(rec_base, r_lo, r_hi + 1, x0) - 1;                    // rec_base[r_lo] <= x0 < rec_base[r_hi]: r_lo <= r < r_hi
+        rbase = rec_base[r]; rend = rec_base[r + 1];
+    }
+    u32 own = 0, mine = 0;
+#pragma unroll
+    for (u32 k = 0; k < 4; k++) {
+        u64 lo = w[k], hi = w[k + 1], nx = LONG ? w[k + 2] : 0;
+#pragma unroll 1
+        for (u32 j = 0; j < 16; j++) {
+            const u64 x = g + 16 * k + j;
+            const bool in = active && x >= p_lo && x < p_hi;
+            if (in) while (x >= rend && r + 1 < r_hi) { r++; rbase = rend; rend = rec_base[r + 1]; }   // (empty records share a base: the last of them holds x)
+            const u32 room = !in || x >= rend ? 0u : (rend - x < 32 ? (u32)(rend - x) : 32u);
+            const u64 zl = zero_nibbles(lo), zh = LONG ? zero_nibbles(hi) : 0;
+            for (u32 q = 0; q < Q.n; q++) {
+                u64 miss = (lo & Q.c[q].nl) | (zl & Q.c[q].ol);
+                if (LONG) miss |= (hi & Q.c[q].nh) | (zh & Q.c[q].oh);
+                const bool hit = miss == 0 && Q.len[q] <= room;
+                if (!WRITE) {
+                    const u32 n = (u32)__popcll(__ballot(hit));
+                    if (lane == q) mine += n;
+                    own += hit;
+                } else if (hit) {
+                    if (at < hit_cap) { u8 *o = hits + at * 24; st64(o, r); st64(o + 8, x - rbase); st32(o + 16, Q.pat[q]); st32(o + 20, Q.strand[q]); }
+                    at++;
+                }
+            }
+            lo = (lo >> 4) | (hi << 60);
+            if (LONG) { hi = (hi >> 4) | (nx << 60); nx >>= 4; } else hi >>= 4;
+        }
+    }
+    if (!WRITE) {
+        const u32 tot = wave_sum_u32(own);
+        if (lane == 0) tile_cnt[t] = tot;
+        if (tot) lane_cnt[t * 64 + lane] = own;
+        if (lane < Q.n && mine) atomicAdd(&combo_cnt[lane], (unsigned long long)mine);
+    }
+}
+
+// ---- host side -----------------------------------------------------------------------------------------------------------------
+// letter -> 4-bit set; 0 = no pattern letter
+static u8 motif_code(char ch)
+{
+    static const char tab[] = "-TGKCYSBAWRDMHVN";
+    if (ch >= 'a' && ch <= 'z') ch = (char)(ch - 32);
+    if (ch == 'U') ch = 'T';
+    for (u32 k = 1; k < 16; k++) if (tab[k] == ch) return (u8)k;
+    return 0;
+}
+// 0, or 1 + the index of the letter that is none; -1: the length is not 1 .. 32
+static int motif_compile(const char *text, u8 fwd[32], u8 rev[32], size_t *len)
+{
+    const size_t m = strlen(text);
+    if (m < 1 || m > 32) return -1;
+    for (size_t j = 0; j < m; j++) { fwd[j] = motif_code(text[j]); if (!fwd[j]) return 1 + (int)j; }
+    for (size_t j = 0; j < m; j++) { const u8 p = fwd[m - 1 - j]; rev[j] = (u8)(((p & 1) << 3) | ((p & 2) << 1) | ((p & 4) >> 1) | (p >> 3)); }
+    for (size_t j = m; j < 32; j++) fwd[j] = rev[j] = 0;
+    *len = m;
+    return 0;
+}
+extern "C" int naf_gpu_compile_motif(const char *text, uint8_t fwd[32], uint8_t rev[32], size_t *len)
+{
+    if (!text || !fwd || !rev || !len) return NAF_GPU_EARG;
+    return motif_compile(text, fwd, rev, len) ? NAF_GPU_EARG : 0;
+}
+static LocCombo motif_masks(const u8 code[32], size_t m)
+{
+    LocCombo q = { 0, 0, 0, 0 };
+    for (size_t j = 0; j < m; j++) {
+        const u64 np = (u64)(~code[j] & 15) << (4 * (j & 15)), one = 1ull << (4 * (j & 15));
+        if (j < 16) { q.nl |= np; q.ol |= one; } else { q.nh |= np; q.oh |= one; }
+    }
+    return q;
+}
+
+// the arena as it is now, to be returned to once a piece is done (its kernels waited for)
+static std::vector<size_t> loc_arena_mark(naf_gpu_ctx *c) { std::vector<size_t> m; for (auto &ch : c->chunks) m.push_back(ch.used); return m; }
+static void loc_arena_release(naf_gpu_ctx *c, const std::vector<size_t> &m) { for (size_t k = 0; k < c->chunks.size(); k++) c->chunks[k].used = k < m.size() ? m[k] : 0; }
+
+struct LocPiece { u64 r_lo, r_hi, p_lo, p_hi; };
+
+// per_pattern: n_patterns x 2 counts (host), or nullptr.  write: the hits go to d_hits (hit_cap entries); too small a capacity is found
+// before anything is written.
+static int locate_run(naf_gpu_ctx *c, const u8 *d_naf, size_t naf_len, const char *h_patterns, size_t patterns_bytes, size_t n_patterns, int strands,
+                      u64 first, u64 count, u8 *d_hits, size_t hit_cap, u64 *n_hits, u64 *per_pattern, bool write)
+{
+    if (!c || !d_naf || !n_hits) return NAF_GPU_EARG;
+    *n_hits = 0;
+    if (n_patterns < 1 || n_patterns > LOC_MAX_PATTERNS) return ctx_fail(c, NAF_GPU_EARG, "locate: %zu patterns given, 1 to %d can be searched in one call", n_patterns, LOC_MAX_PATTERNS);
+    if (strands < 1 || strands > 3) return ctx_fail(c, NAF_GPU_EARG, "locate: strand mask %d is none of 1 (as stored), 2 (reverse), 3 (both)", strands);
+    if (!h_patterns) return ctx_fail(c, NAF_GPU_EARG, "locate: no patterns given (h_patterns is NULL)");
+    LocPats Q; memset(&Q, 0, sizeof Q);
+    bool any_long = false;
+    { size_t at = 0;
+      for (size_t k = 0; k < n_patterns; k++) {
+          const void *z = at < patterns_bytes ? memchr(h_patterns + at, 0, patterns_bytes - at) : nullptr;
+          if (!z) return ctx_fail(c, NAF_GPU_EARG, "locate: %zu patterns announced, %zu zero-terminated strings in %zu bytes", n_patterns, k, patterns_bytes);
+          const char *text = h_patterns + at;
+          u8 fwd[32], rev[32]; size_t m = 0;
+          const int bad = motif_compile(text, fwd, rev, &m);
+          if (bad < 0) return ctx_fail(c, NAF_GPU_EARG, "locate: pattern %zu has %zu letters, a pattern has 1 to 32", k, strlen(text));
+          if (bad > 0) {
+              const unsigned char ch = (unsigned char)text[bad - 1];
+              if (ch >= 33 && ch < 127) return ctx_fail(c, NAF_GPU_EARG, "locate: pattern %zu: letter '%c' (position %d) is no IUPAC nucleotide code", k, ch, bad);
+              return ctx_fail(c, NAF_GPU_EARG, "locate: pattern %zu: letter '\\x%02X' (position %d) is no IUPAC nucleotide code", k, ch, bad);
+          }
+          for (int s = 0; s < 2; s++) if (strands & (1 << s)) {
+              Q.c[Q.n] = motif_masks(s ? rev : fwd, m); Q.len[Q.n] = (u32)m; Q.pat[Q.n] = (u8)k; Q.strand[Q.n] = (u8)s; Q.n++;
+          }
+          any_long = any_long || m > 16;
+          at = (size_t)((const char *)z - h_patterns) + 1;
+      } }
+    if (per_pattern) for (size_t k = 0; k < 2 * n_patterns; k++) per_pattern[k] = 0;
+    arena_reset(c);
+    naf_gpu_unnaf_opts o = { NAF_OUT_SEQUENCES, 0, -1 };                          // the record tables of --sequences: lengths only, no ids, no mask
+    UnnafPlan pl;
+    int rc = unnaf_prepare(c, d_naf, naf_len, &o, pl); if (rc) return rc;
+    const naf_gpu_header &h = pl.h;
+    if (!pl.fourbit) return ctx_fail(c, NAF_GPU_EARG, "locate: nucleotide motifs cannot be searched in %s sequences", h.seq_type == NAF_SEQ_PROTEIN ? "protein" : "text");
+    const u64 N = h.n_sequences;
+    if (first > N) return ctx_fail(c, NAF_GPU_EARG, "locate: first record %llu, the archive has %llu", (unsigned long long)first, (unsigned long long)N);
+    if (count == NAF_GPU_WHOLE) count = N - first;
+    if (count > N - first) return ctx_fail(c, NAF_GPU_EARG, "locate: records %llu..%llu of %llu", (unsigned long long)first, (unsigned long long)(first + count), (unsigned long long)N);
+    if (N == 0) return 0;
+    if (!((h.flags >> 1) & 1)) return ctx_fail(c, NAF_GPU_EARG, "locate: the archive stores no sequence");
+    if (count == 0) return 0;
+    if ((rc = unnaf_sections(c, d_naf, pl))) return rc;
+    const EmitP &P = pl.P;
+
+    // the pieces: whole records, as many as stay within the piece size (a longer record is a piece of its own)
+    u64 piece = LOC_PIECE_DEFAULT;
+    { const char *e = ctx_opt(c, "LOCATE_PIECE"); if (e && e[0]) { const u64 v = strtoull(e, nullptr, 10); if (v) piece = v; } }
+    u64 ends[2] = { 0, 0 };
+    if ((rc = ctx_readback2(c, &ends[0], P.rec_base + first, 8, &ends[1], P.rec_base + first + count, 8))) return rc;
+    std::vector<LocPiece> pieces;
+    if (ends[1] - ends[0] <= piece) pieces.push_back({ first, first + count, ends[0], ends[1] });
+    else {
+        std::vector<u64> base(count + 1);
+        HIP_TRY(c, hipMemcpyAsync(base.data(), P.rec_base + first, (count + 1) * 8, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+        for (u64 a = 0; a < count; ) {
+            u64 b = (u64)(std::upper_bound(base.begin() + a, base.end(), base[a] + piece) - base.begin()) - 1;   // last record end within the piece
+            if (b <= a) b = a + 1;
+            pieces.push_back({ first + a, first + b, base[a], base[b] });
+            a = b;
+        }
+    }
+
+    u64 *combo_cnt = arena_new<u64>(c, LOC_MAX_COMBOS); if (!combo_cnt) return NAF_GPU_ENOMEM;
+    const u8 *whole_seq = nullptr;                                                // the whole stream, once a piece's range could not be had alone
+    u64 decoded = 0, total = 0;
+    std::vector<size_t> mark = loc_arena_mark(c);
+    auto sweep = [&](bool writing) -> int {
+        total = 0;
+        HIP_TRY(c, hipMemsetAsync(combo_cnt, 0, LOC_MAX_COMBOS * 8, c->stream));
+        for (const LocPiece &pc : pieces) {
+            if (pc.p_hi == pc.p_lo) continue;
+            const u8 *seq = whole_seq;
+            const u64 b_lo = pc.p_lo / 2, b_hi = (pc.p_hi + 1) / 2;
+            if (!seq) {
+                ZRange zs; memset(&zs, 0, sizeof zs);
+                zs.want_lo = b_lo; zs.want_hi = b_hi;
+                // (+ 64: the slack every caller of the decoder leaves behind its output, as select_run does; the search itself never reads
+                // past b_hi -- the lanes at a range's end load byte by byte -- and does not rely on it)
+                u64 need = (b_hi - b_lo) + 2 * 131072 + 64; if (need > pl.seq_bytes + 64) need = pl.seq_bytes + 64;
+                u8 *buf = (u8 *)arena_alloc(c, need); if (!buf) return NAF_GPU_ENOMEM;
+                size_t n = 0;
+                int r = zstd_decode_range(c, d_naf + h.payload_off[S_SEQ], h.comp_size[S_SEQ], 0, buf, need - 64, &n, &zs, pl.frame_head[S_SEQ]);
+                if (r == NAF_GPU_ECAP) {                                          // dependent blocks: the closure is the whole stream -- decoded once for the call
+                    buf = (u8 *)arena_alloc(c, pl.seq_bytes + 64); if (!buf) return NAF_GPU_ENOMEM;
+                    r = zstd_decode(c, d_naf + h.payload_off[S_SEQ], h.comp_size[S_SEQ], 0, buf, pl.seq_bytes, &n);
+                    if (r == NAF_GPU_ECAP || (r == 0 && n != pl.seq_bytes)) return ctx_fail(c, NAF_GPU_EFORMAT, "can't decompress sequence\n");
+                    if (r) return r;
+                    zs.ranged = false;
+                }
+                else if (r == 0 && n != pl.seq_bytes) return ctx_fail(c, NAF_GPU_EFORMAT, "can't decompress sequence\n");
+                else if (r) return r;
+                if (zs.ranged) { seq = (zs.own_buf ? zs.own_buf : buf) - zs.got_lo; decoded += zs.got_hi - zs.got_lo; }
+                else { seq = whole_seq = buf; decoded += pl.seq_bytes; mark = loc_arena_mark(c); }
+            }
+            const u64 t0 = pc.p_lo & ~1ull, ntiles = (pc.p_hi - t0 + LOC_TILE - 1) / LOC_TILE;
+            if (ntiles > 0x7FFFFFFFull) return ctx_fail(c, NAF_GPU_EARG, "locate: a piece of %llu bases is too long for one launch", (unsigned long long)(pc.p_hi - pc.p_lo));
+            u64 *tile_cnt = arena_new<u64>(c, ntiles + 2); u32 *lane_cnt = arena_new<u32>(c, ntiles * 64);
+            if (!tile_cnt || !lane_cnt) return NAF_GPU_ENOMEM;
+            HIP_TRY(c, hipMemsetAsync(tile_cnt + ntiles, 0, 8, c->stream));
+#define LOC_LAUNCH(W, name) do { \
+                if (any_long) LAUNCH(c, name, (k_locate<W, true>), (u32)ntiles, 64, 0, Q, seq, b_hi, P.rec_base, pc.r_lo, pc.r_hi, pc.p_lo, pc.p_hi, t0, tile_cnt, lane_cnt, (unsigned long long *)combo_cnt, (const u64 *)tile_cnt, total, d_hits, (u64)hit_cap); \
+                else LAUNCH(c, name, (k_locate<W, false>), (u32)ntiles, 64, 0, Q, seq, b_hi, P.rec_base, pc.r_lo, pc.r_hi, pc.p_lo, pc.p_hi, t0, tile_cnt, lane_cnt, (unsigned long long *)combo_cnt, (const u64 *)tile_cnt, total, d_hits, (u64)hit_cap); } while (0)
+            LOC_LAUNCH(false, "unnaf_locate_count");
+            int r = scan_exclusive_u64(c, tile_cnt, ntiles + 1, (u64 *)nullptr); if (r) return r;
+            u64 here = 0;
+            if ((r = ctx_readback(c, &here, tile_cnt + ntiles, 8))) return r;
+            if (writing && here) {
+                if (total + here > hit_cap) { *n_hits = total + here; return NAF_GPU_ECAP; }   // (one piece: nothing has been written; several: the counting sweep has ruled this out)
+                if (!d_hits) return NAF_GPU_EARG;
+                LOC_LAUNCH(true, "unnaf_locate_write");
+                HIP_TRY(c, hipGetLastError());
+                HIP_TRY(c, hipStreamSynchronize(c->stream));
+            }
+#undef LOC_LAUNCH
+            total += here;
+            loc_arena_release(c, mark);
+        }
+        return 0;
+    };
+    if (!write || pieces.size() > 1) { if ((rc = sweep(false))) return rc; }
+    *n_hits = total;
+    if (write && pieces.size() > 1 && total > hit_cap) return ctx_fail(c, NAF_GPU_ECAP, "locate: %llu hits, capacity %zu", (unsigned long long)total, hit_cap);
+    if (write) {
+        rc = sweep(true);
+        if (rc == NAF_GPU_ECAP && *n_hits > hit_cap) return ctx_fail(c, NAF_GPU_ECAP, "locate: %llu hits, capacity %zu", (unsigned long long)*n_hits, hit_cap);
+        if (rc) return rc;
+        *n_hits = total;
+    }
+    if (per_pattern) {
+        u64 cc[LOC_MAX_COMBOS];
+        if ((rc = ctx_readback(c, cc, combo_cnt, sizeof cc))) return rc;
+        for (u32 q = 0; q < Q.n; q++) per_pattern[2 * Q.pat[q] + Q.strand[q]] = cc[q];
+    }
+    if (ctx_tracing(c)) ctx_trace(c, "[locate] patterns %zu records %llu..%llu pieces %zu sequence bytes decoded %llu of %llu hits %llu\n", n_patterns,
+                                  (unsigned long long)first, (unsigned long long)(first + count), pieces.size(), (unsigned long long)decoded, (unsigned long long)pl.seq_bytes, (unsigned long long)total);
+    return 0;
+}
+
+extern "C" int naf_gpu_unnaf_locate_count(naf_gpu_ctx *c, const void *d_naf, size_t naf_len, const char *h_patterns, size_t patterns_bytes, size_t n_patterns, int strands,
+                                          uint64_t first, uint64_t count, uint64_t *n_hits, uint64_t *per_pattern)
+{
+    int rc = locate_run(c, (const u8 *)d_naf, naf_len, h_patterns, patterns_bytes, n_patterns, strands, first, count, nullptr, 0, n_hits, per_pattern, false);
+    if (c) arena_settle(c);
+    return rc;
+}
+extern "C" int naf_gpu_unnaf_locate(naf_gpu_ctx *c, const void *d_naf, size_t naf_len, const char *h_patterns, size_t patterns_bytes, size_t n_patterns, int strands,
+                                    uint64_t first, uint64_t count, naf_gpu_hit *d_hits, size_t hit_cap, uint64_t *n_hits)
+{
+    int rc = locate_run(c, (const u8 *)d_naf, naf_len, h_patterns, patterns_bytes, n_patterns, strands, first, count, (u8 *)d_hits, hit_cap, n_hits, nullptr, true);
+    if (c) arena_settle(c);
+    return rc;
+}

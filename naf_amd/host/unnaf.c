@@ -16,6 +16,10 @@ static FILE *OUT = NULL; static bool created_output_file = false, success = fals
 typedef struct { const char *region; unsigned long long first, last; bool rc; } selection;      /* region, or records first..last (1-based, inclusive); rc: its reverse complement */
 static selection *selections = NULL; static size_t n_selections = 0;
 static bool revcomp = false;                                      /* --revcomp: every selection of the call as its reverse complement */
+/* --locate PATTERN (up to 16) / --strand: where IUPAC motifs lie, as BED6 (this implementation only) */
+enum { MAX_LOCATE = 16 };
+static const char *locate_patterns[MAX_LOCATE]; static size_t n_locate = 0;
+static int locate_strands = 3; static bool strand_given = false;
 
 static void done(int status, void *arg)
 {
@@ -59,6 +63,20 @@ static void add_records(const char *spec)
     add_selection(NULL, a, b, false);
 }
 
+static void add_locate(const char *pattern)
+{
+    uint8_t fwd[32], rev[32]; size_t len;
+    if (naf_gpu_compile_motif(pattern, fwd, rev, &len)) die("can't parse the value of --locate parameter (1 to 32 IUPAC nucleotide letters)\n");
+    if (n_locate == MAX_LOCATE) die("at most %d --locate patterns can be searched at once\n", (int)MAX_LOCATE);
+    locate_patterns[n_locate++] = pattern;
+}
+static void set_strand(const char *v)
+{
+    if (!strcmp(v, "+")) locate_strands = 1; else if (!strcmp(v, "-")) locate_strands = 2; else if (!strcmp(v, "both")) locate_strands = 3;
+    else die("can't parse the value of --strand parameter (+, - or both)\n");
+    strand_given = true;
+}
+
 static void show_help(void)
 {
     msg("Usage: unnaf [OUTPUT-TYPE] [file.naf]\n"
@@ -77,7 +95,10 @@ static void show_help(void)
         "  --region ID[:A-B] - Sequence ID, or its bases A to B (1-based, inclusive; \"ID:A-\" = to its end)\n"
         "  --records A-B   - Sequences number A to B (1-based, inclusive)\n"
         "  --rc-region ID[:A-B] - The same region as its reverse complement (header \"ID:A-B/rc\"; DNA and RNA only)\n"
-        "  --revcomp       - Every selected sequence and region as its reverse complement\n");
+        "  --revcomp       - Every selected sequence and region as its reverse complement\n"
+        "Options for searching (output: BED6 lines \"ID begin end PATTERN 0 strand\", 0-based half-open; with at most one --records A-B or --region ID):\n"
+        "  --locate PATTERN - Every place where the IUPAC pattern (1 to 32 letters, e.g. NGG) matches; repeatable, up to 16 patterns\n"
+        "  --strand +|-|both - Search the sequences as stored, their reverse complement, or both (default)\n");
 }
 
 static void parse_command_line(int argc, char **argv)
@@ -90,12 +111,13 @@ static void parse_command_line(int argc, char **argv)
         {"--fasta", FASTA}, {"--fastq", FASTQ}, {"--dna", DNA}, {"--masked-dna", MASKED_DNA}, {"--unmasked-dna", UNMASKED_DNA},
         {"--masked-fasta", MASKED_FASTA}, {"--unmasked-fasta", UNMASKED_FASTA} };
     /* the other options (unnaf/src/unnaf.c:282-353), as a table: one that takes a value is only recognised with an argument behind it */
-    enum { OP_LINE_LENGTH, OP_OUT, OP_NO_MASK, OP_IGNORED, OP_HELP, OP_VERBOSE, OP_VERSION, OP_STDOUT, OP_REGION, OP_RECORDS, OP_RC_REGION, OP_REVCOMP };
+    enum { OP_LINE_LENGTH, OP_OUT, OP_NO_MASK, OP_IGNORED, OP_HELP, OP_VERBOSE, OP_VERSION, OP_STDOUT, OP_REGION, OP_RECORDS, OP_RC_REGION, OP_REVCOMP, OP_LOCATE, OP_STRAND };
     static const struct { const char *name; int op; bool value; } option_table[] = {
         { "--line-length", OP_LINE_LENGTH, true }, { "-o", OP_OUT, true }, { "--no-mask", OP_NO_MASK, false }, { "--binary-stdout", OP_IGNORED, false },
         { "--binary-stderr", OP_IGNORED, false }, { "--binary", OP_IGNORED, false }, { "--help", OP_HELP, false }, { "-h", OP_HELP, false },
         { "--verbose", OP_VERBOSE, false }, { "--version", OP_VERSION, false }, { "-V", OP_VERSION, false }, { "-c", OP_STDOUT, false },
-        { "--region", OP_REGION, true }, { "--records", OP_RECORDS, true }, { "--rc-region", OP_RC_REGION, true }, { "--revcomp", OP_REVCOMP, false } };
+        { "--region", OP_REGION, true }, { "--records", OP_RECORDS, true }, { "--rc-region", OP_RC_REGION, true }, { "--revcomp", OP_REVCOMP, false },
+        { "--locate", OP_LOCATE, true }, { "--strand", OP_STRAND, true } };
     for (int i = 1; i < argc; i++) {
         char *arg = argv[i];
         if (arg[0] != '-') {
@@ -124,6 +146,8 @@ static void parse_command_line(int argc, char **argv)
         case OP_RC_REGION: add_region(v, true); break;
         case OP_REVCOMP: revcomp = true; break;
         case OP_RECORDS: add_records(v); break;
+        case OP_LOCATE: add_locate(v); break;
+        case OP_STRAND: set_strand(v); break;
         }
     }
     if (print_version) {
@@ -132,6 +156,17 @@ static void parse_command_line(int argc, char **argv)
         exit(0);
     }
     if (force_stdout && out_file_path) die("-c and -o arguments can't be used together\n");
+    if (strand_given && !n_locate) die("--strand can be used only with --locate\n");
+    if (n_locate) {
+        if (out_type != UNDECIDED) die("--locate writes BED lines: no output type can be given with it\n");
+        if (revcomp) die("--locate searches both strands itself (--strand): --revcomp can't be used with it\n");
+        if (n_selections > 1) die("--locate can be restricted by one --records or one --region only\n");
+        if (n_selections && selections[0].rc) die("--locate searches both strands itself (--strand): --rc-region can't be used with it\n");
+        if (n_selections && selections[0].region) {
+            size_t l; uint64_t b, e; naf_gpu_parse_region(selections[0].region, &l, &b, &e);
+            if (!(b == 0 && e == NAF_GPU_WHOLE)) die("--locate can be restricted to a whole sequence only: --region ID, without a range\n");
+        }
+    }
     if ((n_selections || revcomp) && !(out_type == UNDECIDED || out_type == FASTA || out_type == FASTQ || out_type == SEQ || out_type == SEQUENCES))
         die("--region can be used only with sequence output\n");
     if (revcomp && !n_selections) die("--revcomp can be used only with --region or --records\n");
@@ -312,6 +347,60 @@ static void run_select(int mode, bool has_ids)
     free(ids); free(recs); free(segs); free(strand);
 }
 
+/* --locate: the table of hits is made on the device (naf_gpu_unnaf_locate: two passes over the packed stream); the BED lines are
+ * formatted here, on the host, from the downloaded table, a chunk at a time -- text for people and scripts, not a hot path. */
+static void run_locate(bool has_ids, bool has_names)
+{
+    upload();
+    const unsigned long long N = H.n_sequences;
+    uint64_t first = 0, count = NAF_GPU_WHOLE;
+    if (n_selections) {
+        const selection *s = &selections[0];
+        if (s->region) {
+            uint64_t rec = UINT64_MAX;
+            if (has_ids && N) GPU_TRY(naf_gpu_unnaf_find(gpu, d_naf, naf_len, s->region, strlen(s->region) + 1, 1, &rec));
+            if (rec == UINT64_MAX) die("sequence \"%s\" not found\n", s->region);
+            first = rec; count = 1;
+        } else {
+            if (s->last > N) die("--records: sequence %llu requested, the archive has %llu\n", s->last, N);
+            first = s->first - 1; count = s->last - s->first + 1;
+        }
+    }
+    size_t bytes = 0; for (size_t k = 0; k < n_locate; k++) bytes += strlen(locate_patterns[k]) + 1;
+    char *pats = (char *)malloc(bytes + 1); if (!pats) die("can't allocate memory\n");
+    size_t plen[MAX_LOCATE];
+    for (size_t k = 0, at = 0; k < n_locate; k++) { plen[k] = strlen(locate_patterns[k]); memcpy(pats + at, locate_patterns[k], plen[k] + 1); at += plen[k] + 1; }
+    uint64_t n = 0;
+    GPU_TRY(naf_gpu_unnaf_locate_count(gpu, d_naf, naf_len, pats, bytes, n_locate, locate_strands, first, count, &n, NULL));
+    phase("locate: count");
+    if (n) {
+        void *d_hits; GPU_TRY(naf_gpu_malloc(gpu, (size_t)n * sizeof(naf_gpu_hit), &d_hits));
+        uint64_t got = 0;
+        GPU_TRY(naf_gpu_unnaf_locate(gpu, d_naf, naf_len, pats, bytes, n_locate, locate_strands, first, count, (naf_gpu_hit *)d_hits, (size_t)n, &got));
+        if (got != n) die("can't decompress sequence\n");
+        phase("locate: hits");
+        /* the first column: ids, or the stored names of an archive without ids */
+        unsigned char *text = has_ids ? load_strings(0, "ids", N) : has_names ? load_strings(1, "names", N) : NULL;
+        const char **name = (const char **)malloc((size_t)(N + 1) * sizeof *name); if (!name) die("can't allocate memory\n");
+        { const char *p = (const char *)text; for (unsigned long long r = 0; r < N; r++) { name[r] = p ? p : ""; if (p) p += strlen(p) + 1; } }
+        const size_t chunk = 1 << 20;
+        naf_gpu_hit *hits = (naf_gpu_hit *)malloc((n < chunk ? (size_t)n : chunk) * sizeof *hits); if (!hits) die("can't allocate memory\n");
+        for (uint64_t a = 0; a < n; a += chunk) {
+            const size_t m = n - a < chunk ? (size_t)(n - a) : chunk;
+            GPU_TRY(naf_gpu_download(gpu, hits, (const naf_gpu_hit *)d_hits + a, m * sizeof *hits));
+            for (size_t k = 0; k < m; k++) {
+                const naf_gpu_hit *x = &hits[k];
+                if (x->record >= N || x->pattern >= n_locate) die("can't decompress sequence\n");
+                fprintf(OUT, "%s\t%llu\t%llu\t%s\t0\t%c\n", name[x->record], (unsigned long long)x->begin, (unsigned long long)(x->begin + plen[x->pattern]),
+                        locate_patterns[x->pattern], x->strand ? '-' : '+');
+            }
+        }
+        free(hits); free(name); free(text); naf_gpu_free(gpu, d_hits);
+        phase("locate: download + BED lines");
+    }
+    free(pats);
+}
+
 int main(int argc, char **argv)
 {
     prog_name = "unnaf";
@@ -353,11 +442,15 @@ int main(int argc, char **argv)
     bool large = out_type == IDS || out_type == NAMES || out_type == LENGTHS || out_type == MASK || out_type == FOUR_BIT || out_type == DNA ||
                  out_type == MASKED_DNA || out_type == UNMASKED_DNA || out_type == SEQ || out_type == FASTA || out_type == MASKED_FASTA ||
                  out_type == UNMASKED_FASTA || out_type == FASTQ;
-    if (large && !force_stdout && isatty(fileno(OUT)))
+    if (large && !n_locate && !force_stdout && isatty(fileno(OUT)))
         die("output file not specified - please either specify output file with '-o' or '>', or use '-c' option to force writing to console\n");
 
     unsigned long long N = H.n_sequences;
-    if (n_selections) {
+    if (n_locate) {
+        if (H.seq_type >= NAF_SEQ_PROTEIN) die("nucleotide motifs cannot be searched in %s sequences\n", tn[H.seq_type]);
+        run_locate(has_ids, has_names);
+    }
+    else if (n_selections) {
         if (out_type == FASTQ && !has_quality) die("FASTQ output requested, but input has no qualities\n");
         for (size_t k = 0; k < n_selections; k++) if (selections[k].rc && H.seq_type >= NAF_SEQ_PROTEIN) die("%s sequences have no reverse complement\n", tn[H.seq_type]);
         run_select(out_type == FASTA ? NAF_OUT_FASTA : out_type == FASTQ ? NAF_OUT_FASTQ : out_type == SEQ ? NAF_OUT_SEQ : NAF_OUT_SEQUENCES, has_ids);
