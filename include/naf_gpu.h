@@ -243,6 +243,44 @@ int  naf_gpu_unnaf_locate_count(naf_gpu_ctx *ctx, const void *d_naf, size_t naf_
 int  naf_gpu_unnaf_locate(naf_gpu_ctx *ctx, const void *d_naf, size_t naf_len, const char *h_patterns, size_t patterns_bytes, size_t n_patterns,
                           int strands, uint64_t first, uint64_t count, naf_gpu_hit *d_hits, size_t hit_cap, uint64_t *n_hits);
 
+/* ---- unnaf: base composition per record and per window, counted in the packed stream --------------------------
+ * What faCount, seqkit fx2tab -g -B and bedtools nuc answer from the text, counted from the 4-bit codes without expanding them.
+ *   Rows      window == 0: exactly one row per record, [0, len); an empty record gives a row of zeros.  window == W > 0: a record of len
+ *             bases gives ceil(len / W) rows [k W, min((k + 1) W, len)); an empty record gives none.  Any W >= 1 is legal, also one larger
+ *             than every record.
+ *   Order     ascending (record, begin); the same bytes on every run.  sum(n[0..15]) == end - begin in every row.
+ *   Records   [first, first + count), count = NAF_GPU_WHOLE: to the last record.  first > n_sequences, a range past the last record, a
+ *             protein or text archive and an archive that stores no sequence are NAF_GPU_EARG, as for naf_gpu_unnaf_locate; an archive
+ *             without records gives 0 rows.  FASTA and FASTQ archives alike, DNA and RNA.
+ *   Never     Bases behind the last record of a malformed archive and the padding nibble of an odd stream are in no row.
+ *   cpg       The C lies in the row; the G may lie in the next window of the same record, never in the next record, in the R7 tail or in
+ *             the padding nibble.
+ *   masked    With NAF_GPU_COMP_MASK and an archive that has a mask section: the bases g of the row with an odd number of mask toggles
+ *             <= g, g the base's index in the whole stream -- exactly the lower-case letters of the --sequences text.  Without the flag
+ *             or without a mask section it is 0 and the mask section is not decoded.  Any other bit in flags is NAF_GPU_EARG.
+ *   d_rows    DEVICE memory of any alignment; exactly 168 * n_rows bytes are written and nothing else.  With row_cap too small the call
+ *             returns NAF_GPU_ECAP, sets *n_rows to the whole count and writes nothing.
+ *   h_total   HOST, may be NULL: the sum of all rows; its record is the number of records covered, its begin 0, its end their bases.
+ * naf_gpu_unnaf_composition_rows needs the lengths section only and decodes no sequence.  More bases than NAF_GPU_COMPOSITION_PIECE
+ * (default 2^31) are decoded and counted in pieces of whole records; the result does not depend on the piece size.  Only the zstd blocks
+ * behind the records' bases are decoded when the frame allows it. */
+typedef struct {
+    uint64_t record, begin, end;   /* bases [begin, end) of record `record`, 0-based */
+    uint64_t n[16];                /* stored bases per 4-bit code; index = code in "-TGKCYSBAWRDMHVN" (n[1] is U in an RNA archive) */
+    uint64_t masked;               /* bases of the row that are lower case in the whole text with the mask applied; 0 without NAF_GPU_COMP_MASK */
+    uint64_t cpg;                  /* positions g in [begin, end) with stored base g == C (code 4) and base g + 1 == G (code 2), g + 1 in the SAME record */
+} naf_gpu_comp_row;                /* 168 bytes */
+enum { NAF_GPU_COMP_MASK = 1 };
+
+/* host only, no device: rows a record of n_bases gives under `window` */
+uint64_t naf_gpu_composition_rows_of(uint64_t n_bases, uint64_t window);
+
+int  naf_gpu_unnaf_composition_rows(naf_gpu_ctx *ctx, const void *d_naf, size_t naf_len, uint64_t window,
+                                    uint64_t first, uint64_t count, uint64_t *n_rows);
+int  naf_gpu_unnaf_composition(naf_gpu_ctx *ctx, const void *d_naf, size_t naf_len, uint64_t window, int flags,
+                               uint64_t first, uint64_t count, naf_gpu_comp_row *d_rows, size_t row_cap,
+                               uint64_t *n_rows, naf_gpu_comp_row *h_total);
+
 /* ---- ennaf ------------------------------------------------------------------------------------------ */
 typedef struct {
     int      format;            /* NAF_FMT_* (AUTO = sniff, process.c:547-583) */

@@ -30,6 +30,7 @@ EXPORTS = [
     "naf_gpu_unnaf_find", "naf_gpu_unnaf_record_table", "naf_gpu_unnaf_select_size", "naf_gpu_unnaf_select", "naf_gpu_parse_region",
     "naf_gpu_unnaf_select_stranded_size", "naf_gpu_unnaf_select_stranded",
     "naf_gpu_compile_motif", "naf_gpu_unnaf_locate_count", "naf_gpu_unnaf_locate",
+    "naf_gpu_composition_rows_of", "naf_gpu_unnaf_composition_rows", "naf_gpu_unnaf_composition",
 ]
 WHOLE = 2 ** 64 - 1                     # NAF_GPU_WHOLE: (record, 0, WHOLE) is the record as stored
 MAX_SHARDS = 64
@@ -94,6 +95,17 @@ class Hit(C.Structure):
 
 HIT_DTYPE = [("record", "<u8"), ("begin", "<u8"), ("pattern", "<u4"), ("strand", "<u4")]      # numpy's view of a table of hits
 STRAND_FORWARD, STRAND_REVERSE, STRAND_BOTH = 1, 2, 3
+
+
+class CompRow(C.Structure):
+    """naf_gpu_comp_row: the composition of bases [begin, end) of `record`: n[c] bases of 4-bit code c ("-TGKCYSBAWRDMHVN"), the
+    soft-masked ones, and the C's that a G of the same record follows."""
+    _fields_ = [("record", C.c_uint64), ("begin", C.c_uint64), ("end", C.c_uint64), ("n", C.c_uint64 * 16), ("masked", C.c_uint64), ("cpg", C.c_uint64)]
+
+
+COMP_DTYPE = [("record", "<u8"), ("begin", "<u8"), ("end", "<u8"), ("n", "<u8", (16,)), ("masked", "<u8"), ("cpg", "<u8")]      # numpy's view of a table of rows
+COMP_ROW_BYTES = 168
+COMP_MASK = 1
 
 
 class NafGpuError(RuntimeError):
@@ -185,6 +197,10 @@ def load():
         L.naf_gpu_compile_motif.argtypes = [C.c_char_p, u8p, u8p, C.POINTER(sz)]
         L.naf_gpu_unnaf_locate_count.argtypes = [vp, vp, sz, C.c_char_p, sz, sz, i, C.c_uint64, C.c_uint64, u64p, u64p]
         L.naf_gpu_unnaf_locate.argtypes = [vp, vp, sz, C.c_char_p, sz, sz, i, C.c_uint64, C.c_uint64, vp, sz, u64p]
+        L.naf_gpu_composition_rows_of.argtypes = [C.c_uint64, C.c_uint64]
+        L.naf_gpu_composition_rows_of.restype = C.c_uint64
+        L.naf_gpu_unnaf_composition_rows.argtypes = [vp, vp, sz, C.c_uint64, C.c_uint64, C.c_uint64, u64p]
+        L.naf_gpu_unnaf_composition.argtypes = [vp, vp, sz, C.c_uint64, i, C.c_uint64, C.c_uint64, vp, sz, u64p, C.POINTER(CompRow)]
         _lib = L
     return _lib
 
@@ -210,6 +226,11 @@ def compile_motif(text):
     if load().naf_gpu_compile_motif(b, fwd, rev, C.byref(n)):
         raise ValueError("not a pattern: %r" % (text,))
     return bytes(fwd[:n.value]), bytes(rev[:n.value])
+
+
+def composition_rows_of(n, window):
+    """Host-only: the rows a record of n bases gives under `window` (naf_gpu_composition_rows_of): 1 for window 0, else ceil(n / window)."""
+    return int(load().naf_gpu_composition_rows_of(int(n), int(window)))
 
 
 def hits_to_segments(hits, patterns, flank=0, lengths=None):
@@ -525,6 +546,34 @@ class Context:
         self._check(self.L.naf_gpu_unnaf_locate(self.h, _ptr(d_naf), d_naf.numel(), blob, len(blob), n, int(strands), int(first), cnt,
                                                 _ptr(buf), total.value, C.byref(total)))
         return np.frombuffer(buf[:24 * total.value].cpu().numpy().tobytes(), dtype=HIT_DTYPE), total.value
+
+    def unnaf_composition_rows(self, d_naf, window=0, first=0, count=None):
+        """The rows unnaf_composition gives for records [first, first + count) under `window` (naf_gpu_unnaf_composition_rows: the lengths
+        only, no sequence is decoded)."""
+        n = C.c_uint64()
+        self._check(self.L.naf_gpu_unnaf_composition_rows(self.h, _ptr(d_naf), d_naf.numel(), int(window), int(first), WHOLE if count is None else int(count), C.byref(n)))
+        return n.value
+
+    def unnaf_composition(self, d_naf, window=0, mask=True, first=0, count=None, out=None):
+        """(rows, total): the base composition of records [first, first + count) -- one row per record (window 0) or per window of
+        `window` bases -- as a structured numpy array (COMP_DTYPE: record, begin, end, n[16], masked, cpg), and their sum as a CompRow
+        (its record: the records covered, its end: their bases).  mask: count the soft-masked bases (NAF_GPU_COMP_MASK).  out: a uint8
+        device tensor to take the table (168 bytes a row); then `rows` is the torch view of its first 168 * n bytes and too small a
+        tensor raises NafGpuError(E_CAP).  Without it the rows are counted first (naf_gpu_unnaf_composition_rows)."""
+        import numpy as np
+        import torch
+        n, tot = C.c_uint64(), CompRow()
+        cnt = WHOLE if count is None else int(count)
+        flags = COMP_MASK if mask else 0
+        if out is not None:
+            self._check(self.L.naf_gpu_unnaf_composition(self.h, _ptr(d_naf), d_naf.numel(), int(window), flags, int(first), cnt,
+                                                         _ptr(out), out.numel() // COMP_ROW_BYTES, C.byref(n), C.byref(tot)))
+            return out[:COMP_ROW_BYTES * n.value], tot
+        self._check(self.L.naf_gpu_unnaf_composition_rows(self.h, _ptr(d_naf), d_naf.numel(), int(window), int(first), cnt, C.byref(n)))
+        buf = torch.empty(max(COMP_ROW_BYTES * n.value, 1), dtype=torch.uint8, device=self.device)
+        self._check(self.L.naf_gpu_unnaf_composition(self.h, _ptr(d_naf), d_naf.numel(), int(window), flags, int(first), cnt,
+                                                     _ptr(buf), n.value, C.byref(n), C.byref(tot)))
+        return np.frombuffer(buf[:COMP_ROW_BYTES * n.value].cpu().numpy().tobytes(), dtype=COMP_DTYPE), tot
 
     def histogram(self, d_buf):
         """Byte counts of a device buffer (unnaf --charcount)."""

@@ -20,6 +20,8 @@ static bool revcomp = false;                                      /* --revcomp: 
 enum { MAX_LOCATE = 16 };
 static const char *locate_patterns[MAX_LOCATE]; static size_t n_locate = 0;
 static int locate_strands = 3; static bool strand_given = false;
+/* --composition [--window N]: base composition per record or per window, as a tab-separated table (this implementation only) */
+static bool composition = false, window_given = false; static unsigned long long comp_window = 0;
 
 static void done(int status, void *arg)
 {
@@ -77,6 +79,18 @@ static void set_strand(const char *v)
     strand_given = true;
 }
 
+static void set_window(const char *v)
+{
+    unsigned long long a = 0; bool digit = false;
+    for (const char *p = v; *p; p++) {
+        if (*p == ',') continue;
+        if (*p < '0' || *p > '9' || a > (ULLONG_MAX - (unsigned)(*p - '0')) / 10) die("can't parse the value of --window parameter (a positive number of bases)\n");
+        a = a * 10 + (unsigned)(*p - '0'); digit = true;
+    }
+    if (!digit || a == 0) die("can't parse the value of --window parameter (a positive number of bases)\n");
+    comp_window = a; window_given = true;
+}
+
 static void show_help(void)
 {
     msg("Usage: unnaf [OUTPUT-TYPE] [file.naf]\n"
@@ -98,7 +112,10 @@ static void show_help(void)
         "  --revcomp       - Every selected sequence and region as its reverse complement\n"
         "Options for searching (output: BED6 lines \"ID begin end PATTERN 0 strand\", 0-based half-open; with at most one --records A-B or --region ID):\n"
         "  --locate PATTERN - Every place where the IUPAC pattern (1 to 32 letters, e.g. NGG) matches; repeatable, up to 16 patterns\n"
-        "  --strand +|-|both - Search the sequences as stored, their reverse complement, or both (default)\n");
+        "  --strand +|-|both - Search the sequences as stored, their reverse complement, or both (default)\n"
+        "Options for counting (output: a tab-separated table \"#seq start end A C G T N other gap masked CpG GC\"; with at most one --records A-B or --region ID):\n"
+        "  --composition   - Base composition of every sequence: bases per letter, soft-masked bases, CpG, GC fraction (--no-mask: masked = 0)\n"
+        "  --window N      - With --composition: one line per window of N bases instead of one per sequence\n");
 }
 
 static void parse_command_line(int argc, char **argv)
@@ -111,13 +128,13 @@ static void parse_command_line(int argc, char **argv)
         {"--fasta", FASTA}, {"--fastq", FASTQ}, {"--dna", DNA}, {"--masked-dna", MASKED_DNA}, {"--unmasked-dna", UNMASKED_DNA},
         {"--masked-fasta", MASKED_FASTA}, {"--unmasked-fasta", UNMASKED_FASTA} };
     /* the other options (unnaf/src/unnaf.c:282-353), as a table: one that takes a value is only recognised with an argument behind it */
-    enum { OP_LINE_LENGTH, OP_OUT, OP_NO_MASK, OP_IGNORED, OP_HELP, OP_VERBOSE, OP_VERSION, OP_STDOUT, OP_REGION, OP_RECORDS, OP_RC_REGION, OP_REVCOMP, OP_LOCATE, OP_STRAND };
+    enum { OP_LINE_LENGTH, OP_OUT, OP_NO_MASK, OP_IGNORED, OP_HELP, OP_VERBOSE, OP_VERSION, OP_STDOUT, OP_REGION, OP_RECORDS, OP_RC_REGION, OP_REVCOMP, OP_LOCATE, OP_STRAND, OP_COMPOSITION, OP_WINDOW };
     static const struct { const char *name; int op; bool value; } option_table[] = {
         { "--line-length", OP_LINE_LENGTH, true }, { "-o", OP_OUT, true }, { "--no-mask", OP_NO_MASK, false }, { "--binary-stdout", OP_IGNORED, false },
         { "--binary-stderr", OP_IGNORED, false }, { "--binary", OP_IGNORED, false }, { "--help", OP_HELP, false }, { "-h", OP_HELP, false },
         { "--verbose", OP_VERBOSE, false }, { "--version", OP_VERSION, false }, { "-V", OP_VERSION, false }, { "-c", OP_STDOUT, false },
         { "--region", OP_REGION, true }, { "--records", OP_RECORDS, true }, { "--rc-region", OP_RC_REGION, true }, { "--revcomp", OP_REVCOMP, false },
-        { "--locate", OP_LOCATE, true }, { "--strand", OP_STRAND, true } };
+        { "--locate", OP_LOCATE, true }, { "--strand", OP_STRAND, true }, { "--composition", OP_COMPOSITION, false }, { "--window", OP_WINDOW, true } };
     for (int i = 1; i < argc; i++) {
         char *arg = argv[i];
         if (arg[0] != '-') {
@@ -148,6 +165,8 @@ static void parse_command_line(int argc, char **argv)
         case OP_RECORDS: add_records(v); break;
         case OP_LOCATE: add_locate(v); break;
         case OP_STRAND: set_strand(v); break;
+        case OP_COMPOSITION: composition = true; break;
+        case OP_WINDOW: set_window(v); break;
         }
     }
     if (print_version) {
@@ -165,6 +184,18 @@ static void parse_command_line(int argc, char **argv)
         if (n_selections && selections[0].region) {
             size_t l; uint64_t b, e; naf_gpu_parse_region(selections[0].region, &l, &b, &e);
             if (!(b == 0 && e == NAF_GPU_WHOLE)) die("--locate can be restricted to a whole sequence only: --region ID, without a range\n");
+        }
+    }
+    if (window_given && !composition) die("--window can be used only with --composition\n");
+    if (composition) {
+        if (n_locate) die("--composition and --locate can't be used together\n");
+        if (out_type != UNDECIDED) die("--composition writes a table: no output type can be given with it\n");
+        if (revcomp) die("--composition counts the sequences as stored: --revcomp can't be used with it\n");
+        if (n_selections > 1) die("--composition can be restricted by one --records or one --region only\n");
+        if (n_selections && selections[0].rc) die("--composition counts the sequences as stored: --rc-region can't be used with it\n");
+        if (n_selections && selections[0].region) {
+            size_t l; uint64_t b, e; naf_gpu_parse_region(selections[0].region, &l, &b, &e);
+            if (!(b == 0 && e == NAF_GPU_WHOLE)) die("--composition can be restricted to a whole sequence only: --region ID, without a range\n");
         }
     }
     if ((n_selections || revcomp) && !(out_type == UNDECIDED || out_type == FASTA || out_type == FASTQ || out_type == SEQ || out_type == SEQUENCES))
@@ -401,6 +432,60 @@ static void run_locate(bool has_ids, bool has_names)
     free(pats);
 }
 
+/* --composition: the table of rows is made on the device (naf_gpu_unnaf_composition: one sweep over the packed stream); the lines are
+ * formatted here, on the host, from the downloaded rows, a chunk at a time -- text for people and scripts, not a hot path. */
+static void run_composition(bool has_ids, bool has_names)
+{
+    upload();
+    const unsigned long long N = H.n_sequences;
+    uint64_t first = 0, count = NAF_GPU_WHOLE;
+    if (n_selections) {
+        const selection *s = &selections[0];
+        if (s->region) {
+            uint64_t rec = UINT64_MAX;
+            if (has_ids && N) GPU_TRY(naf_gpu_unnaf_find(gpu, d_naf, naf_len, s->region, strlen(s->region) + 1, 1, &rec));
+            if (rec == UINT64_MAX) die("sequence \"%s\" not found\n", s->region);
+            first = rec; count = 1;
+        } else {
+            if (s->last > N) die("--records: sequence %llu requested, the archive has %llu\n", s->last, N);
+            first = s->first - 1; count = s->last - s->first + 1;
+        }
+    }
+    uint64_t n = 0;
+    GPU_TRY(naf_gpu_unnaf_composition_rows(gpu, d_naf, naf_len, comp_window, first, count, &n));
+    phase("composition: rows");
+    fprintf(OUT, "#seq\tstart\tend\tA\tC\tG\t%c\tN\tother\tgap\tmasked\tCpG\tGC\n", H.seq_type == NAF_SEQ_RNA ? 'U' : 'T');
+    if (n) {
+        void *d_rows; GPU_TRY(naf_gpu_malloc(gpu, (size_t)n * sizeof(naf_gpu_comp_row), &d_rows));
+        uint64_t got = 0;
+        GPU_TRY(naf_gpu_unnaf_composition(gpu, d_naf, naf_len, comp_window, use_mask ? NAF_GPU_COMP_MASK : 0, first, count, (naf_gpu_comp_row *)d_rows, (size_t)n, &got, NULL));
+        if (got != n) die("can't decompress sequence\n");
+        phase("composition: count");
+        /* the first column: ids, or the stored names of an archive without ids */
+        unsigned char *text = has_ids ? load_strings(0, "ids", N) : has_names ? load_strings(1, "names", N) : NULL;
+        const char **name = (const char **)malloc((size_t)(N + 1) * sizeof *name); if (!name) die("can't allocate memory\n");
+        { const char *p = (const char *)text; for (unsigned long long r = 0; r < N; r++) { name[r] = p ? p : ""; if (p) p += strlen(p) + 1; } }
+        const size_t chunk = 1 << 18;
+        naf_gpu_comp_row *rows = (naf_gpu_comp_row *)malloc((n < chunk ? (size_t)n : chunk) * sizeof *rows); if (!rows) die("can't allocate memory\n");
+        for (uint64_t a = 0; a < n; a += chunk) {
+            const size_t m = n - a < chunk ? (size_t)(n - a) : chunk;
+            GPU_TRY(naf_gpu_download(gpu, rows, (const naf_gpu_comp_row *)d_rows + a, m * sizeof *rows));
+            for (size_t k = 0; k < m; k++) {
+                const naf_gpu_comp_row *x = &rows[k];
+                if (x->record >= N) die("can't decompress sequence\n");
+                const unsigned long long A = x->n[8], Cc = x->n[4], G = x->n[2], T = x->n[1], Nn = x->n[15], gap = x->n[0];
+                unsigned long long other = 0; for (int q = 0; q < 16; q++) other += x->n[q];
+                other -= A + Cc + G + T + Nn + gap;
+                fprintf(OUT, "%s\t%llu\t%llu\t%llu\t%llu\t%llu\t%llu\t%llu\t%llu\t%llu\t%llu\t%llu\t", name[x->record], (unsigned long long)x->begin, (unsigned long long)x->end,
+                        A, Cc, G, T, Nn, other, gap, (unsigned long long)x->masked, (unsigned long long)x->cpg);
+                if (A + Cc + G + T) fprintf(OUT, "%.6f\n", (double)(Cc + G) / (double)(A + Cc + G + T)); else fprintf(OUT, "NA\n");
+            }
+        }
+        free(rows); free(name); free(text); naf_gpu_free(gpu, d_rows);
+        phase("composition: download + lines");
+    }
+}
+
 int main(int argc, char **argv)
 {
     prog_name = "unnaf";
@@ -442,13 +527,17 @@ int main(int argc, char **argv)
     bool large = out_type == IDS || out_type == NAMES || out_type == LENGTHS || out_type == MASK || out_type == FOUR_BIT || out_type == DNA ||
                  out_type == MASKED_DNA || out_type == UNMASKED_DNA || out_type == SEQ || out_type == FASTA || out_type == MASKED_FASTA ||
                  out_type == UNMASKED_FASTA || out_type == FASTQ;
-    if (large && !n_locate && !force_stdout && isatty(fileno(OUT)))
+    if (large && !n_locate && !composition && !force_stdout && isatty(fileno(OUT)))
         die("output file not specified - please either specify output file with '-o' or '>', or use '-c' option to force writing to console\n");
 
     unsigned long long N = H.n_sequences;
     if (n_locate) {
         if (H.seq_type >= NAF_SEQ_PROTEIN) die("nucleotide motifs cannot be searched in %s sequences\n", tn[H.seq_type]);
         run_locate(has_ids, has_names);
+    }
+    else if (composition) {
+        if (H.seq_type >= NAF_SEQ_PROTEIN) die("nucleotides cannot be counted in %s sequences\n", tn[H.seq_type]);
+        run_composition(has_ids, has_names);
     }
     else if (n_selections) {
         if (out_type == FASTQ && !has_quality) die("FASTQ output requested, but input has no qualities\n");
