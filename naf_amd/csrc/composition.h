@@ -1,7 +1,7 @@
 // composition.h -- base composition per record and per window, counted in the packed 4-bit stream (naf_gpu_composition_rows_of,
-// naf_gpu_unnaf_composition_rows, naf_gpu_unnaf_composition).  Part of emit.hip (included by it, behind locate.h): it uses that file's
-// side-section chain for the record tables and the mask toggles, the range decode of the selection path and the piece handling of the
-// motif search, and adds kernels of its own.
+// naf_gpu_unnaf_composition_rows, naf_gpu_unnaf_composition).  Part of emit.hip (included by it, behind locate.h): the front of the
+// call, the pieces and the decode of a piece's bytes are payload.h's (records_front, piece_plan, PieceSweep); this file holds the row
+// tables, the counting kernels and their launches.
 //
 // The contract (include/naf_gpu.h carries it too):
 //   rows      window 0: one row per record, [0, len), an empty record a row of zeros.  window W > 0: ceil(len / W) rows
@@ -249,20 +249,9 @@ static int composition_run(naf_gpu_ctx *c, const u8 *d_naf, size_t naf_len, u64 
     *n_rows = 0;
     if (h_total) memset(h_total, 0, sizeof *h_total);
     if (flags & ~(int)NAF_GPU_COMP_MASK) return ctx_fail(c, NAF_GPU_EARG, "composition: flags %d: only bit 0 (NAF_GPU_COMP_MASK) is defined", flags);
-    arena_reset(c);
-    naf_gpu_unnaf_opts o = { NAF_OUT_SEQUENCES, rows_only ? 0 : (flags & NAF_GPU_COMP_MASK), -1 };   // the record tables of --sequences; the mask only when asked for
     UnnafPlan pl;
-    int rc = unnaf_prepare(c, d_naf, naf_len, &o, pl); if (rc) return rc;
-    const naf_gpu_header &h = pl.h;
-    if (!pl.fourbit) return ctx_fail(c, NAF_GPU_EARG, "composition: nucleotides cannot be counted in %s sequences", h.seq_type == NAF_SEQ_PROTEIN ? "protein" : "text");
-    const u64 N = h.n_sequences;
-    if (first > N) return ctx_fail(c, NAF_GPU_EARG, "composition: first record %llu, the archive has %llu", (unsigned long long)first, (unsigned long long)N);
-    if (count == NAF_GPU_WHOLE) count = N - first;
-    if (count > N - first) return ctx_fail(c, NAF_GPU_EARG, "composition: records %llu..%llu of %llu", (unsigned long long)first, (unsigned long long)(first + count), (unsigned long long)N);
-    if (N == 0) return 0;
-    if (!((h.flags >> 1) & 1)) return ctx_fail(c, NAF_GPU_EARG, "composition: the archive stores no sequence");
-    if (count == 0) return 0;
-    if ((rc = unnaf_sections(c, d_naf, pl))) return rc;
+    int rc = records_front(c, d_naf, naf_len, rows_only ? 0 : (flags & NAF_GPU_COMP_MASK), "composition", "nucleotides cannot be counted", first, &count, pl);   // the mask only when asked for
+    if (rc || !count) return rc;
     const EmitP &P = pl.P;
 
     // every row's place: row_base[i] = first row of record first + i, row_base[count] = rows in all
@@ -275,32 +264,13 @@ static int composition_run(naf_gpu_ctx *c, const u8 *d_naf, size_t naf_len, u64 
     *n_rows = total;
     if (rows_only) return 0;
     if (total > row_cap) return ctx_fail(c, NAF_GPU_ECAP, "composition: %llu rows, capacity %zu", (unsigned long long)total, row_cap);
-    u64 ends[2] = { 0, 0 };
-    if ((rc = ctx_readback2(c, &ends[0], P.rec_base + first, 8, &ends[1], P.rec_base + first + count, 8))) return rc;
-    if (h_total) { h_total->record = count; h_total->end = ends[1] - ends[0]; }
+    // the pieces, and the first row of every piece (and the end of the last)
+    std::vector<RecPiece> pieces;
+    std::vector<u64> rows_at;
+    if ((rc = piece_plan(c, P, first, count, "COMPOSITION_PIECE", COMP_PIECE_DEFAULT, pieces, row_base, total, &rows_at))) return rc;
+    if (h_total) { h_total->record = count; h_total->end = pieces.back().p_hi - pieces.front().p_lo; }
     if (total == 0) return 0;
     if (!d_rows) return ctx_fail(c, NAF_GPU_EARG, "composition: no place for the rows (d_rows is NULL)");
-
-    // the pieces: whole records, as many as stay within the piece size (a longer record is a piece of its own)
-    u64 piece = COMP_PIECE_DEFAULT;
-    { const char *e = ctx_opt(c, "COMPOSITION_PIECE"); if (e && e[0]) { const u64 v = strtoull(e, nullptr, 10); if (v) piece = v; } }
-    std::vector<LocPiece> pieces;
-    std::vector<u64> rows_at;                                                     // first row of every piece, and the end of the last
-    if (ends[1] - ends[0] <= piece) { pieces.push_back({ first, first + count, ends[0], ends[1] }); rows_at = { 0, total }; }
-    else {
-        std::vector<u64> base(count + 1), rb(count + 1);
-        HIP_TRY(c, hipMemcpyAsync(base.data(), P.rec_base + first, (count + 1) * 8, hipMemcpyDeviceToHost, c->stream));
-        HIP_TRY(c, hipMemcpyAsync(rb.data(), row_base, (count + 1) * 8, hipMemcpyDeviceToHost, c->stream));
-        HIP_TRY(c, hipStreamSynchronize(c->stream));
-        for (u64 a = 0; a < count; ) {
-            u64 b = (u64)(std::upper_bound(base.begin() + a, base.end(), base[a] + piece) - base.begin()) - 1;   // last record end within the piece
-            if (b <= a) b = a + 1;
-            pieces.push_back({ first + a, first + b, base[a], base[b] });
-            rows_at.push_back(rb[a]);
-            a = b;
-        }
-        rows_at.push_back(total);
-    }
 
     // masked bases in front of every toggle
     const u64 *tog_ex = nullptr;
@@ -315,57 +285,32 @@ static int composition_run(naf_gpu_ctx *c, const u8 *d_naf, size_t naf_len, u64 
     HIP_TRY(c, hipMemsetAsync(d_sum, 0, 20 * 8, c->stream));
     const bool tracing = ctx_tracing(c), in_place = ((uintptr_t)d_rows & 7) == 0;
 
-    const u8 *whole_seq = nullptr;                                                // the whole stream, once a piece's range could not be had alone
-    u64 decoded = 0;
-    std::vector<size_t> mark = loc_arena_mark(c);
+    PieceSweep sw(c, d_naf, pl, "composition");
     for (size_t pi = 0; pi < pieces.size(); pi++) {
-        const LocPiece &pc = pieces[pi];
+        const RecPiece &pc = pieces[pi];
         const u64 R0 = rows_at[pi], nr = rows_at[pi + 1] - R0;
         if (!nr) continue;
         if (nr > 0x7FFFFFFFull * 256 / COMP_ROW_U64) return ctx_fail(c, NAF_GPU_EARG, "composition: a piece of %llu rows is too long for one launch", (unsigned long long)nr);
-        const u8 *seq = whole_seq;
-        const u64 b_lo = pc.p_lo / 2, b_hi = (pc.p_hi + 1) / 2;
-        if (!seq && pc.p_hi > pc.p_lo) {
-            ZRange zs; memset(&zs, 0, sizeof zs);
-            zs.want_lo = b_lo; zs.want_hi = b_hi;
-            // (+ 64: the slack every caller of the decoder leaves behind its output; the count itself never reads past b_hi)
-            u64 need = (b_hi - b_lo) + 2 * 131072 + 64; if (need > pl.seq_bytes + 64) need = pl.seq_bytes + 64;
-            u8 *buf = (u8 *)arena_alloc(c, need); if (!buf) return NAF_GPU_ENOMEM;
-            size_t n = 0;
-            int r = zstd_decode_range(c, d_naf + h.payload_off[S_SEQ], h.comp_size[S_SEQ], 0, buf, need - 64, &n, &zs, pl.frame_head[S_SEQ]);
-            if (r == NAF_GPU_ECAP) {                                              // dependent blocks: the closure is the whole stream -- decoded once for the call
-                buf = (u8 *)arena_alloc(c, pl.seq_bytes + 64); if (!buf) return NAF_GPU_ENOMEM;
-                r = zstd_decode(c, d_naf + h.payload_off[S_SEQ], h.comp_size[S_SEQ], 0, buf, pl.seq_bytes, &n);
-                if (r == NAF_GPU_ECAP || (r == 0 && n != pl.seq_bytes)) return ctx_fail(c, NAF_GPU_EFORMAT, "can't decompress sequence\n");
-                if (r) return r;
-                zs.ranged = false;
-            }
-            else if (r == 0 && n != pl.seq_bytes) return ctx_fail(c, NAF_GPU_EFORMAT, "can't decompress sequence\n");
-            else if (r) return r;
-            if (zs.ranged) { seq = (zs.own_buf ? zs.own_buf : buf) - zs.got_lo; decoded += zs.got_hi - zs.got_lo; }
-            else { seq = whole_seq = buf; decoded += pl.seq_bytes; mark = loc_arena_mark(c); }
-        }
+        const bool bases = pc.p_hi > pc.p_lo;                                     // (empty records at window 0: rows, and nothing to decode)
+        PieceSweep::Tiles tl = {};
+        if (bases && (rc = sw.seq_for(pc, COMP_TILE, &tl))) return rc;
         u64 *acc = in_place ? (u64 *)(d_rows + 168 * R0) : arena_new<u64>(c, nr * COMP_ROW_U64);
         if (!acc) return NAF_GPU_ENOMEM;
         LAUNCH(c, "unnaf_comp_rows", k_comp_rows, (u32)((nr + 255) / 256), 256, 0, P.rec_base, (const u64 *)row_base, first, pc.r_lo, pc.r_hi, R0, nr, W,
                P.toggles, tog_ex, P.n_toggles, acc);
-        if (pc.p_hi > pc.p_lo) {
-            const u64 t0 = pc.p_lo & ~1ull, ntiles = (pc.p_hi - t0 + COMP_TILE - 1) / COMP_TILE;
-            if (ntiles > 0x7FFFFFFFull) return ctx_fail(c, NAF_GPU_EARG, "composition: a piece of %llu bases is too long for one launch", (unsigned long long)(pc.p_hi - pc.p_lo));
-            LAUNCH(c, "unnaf_comp_count", k_comp_count, (u32)ntiles, 64, 0, seq, b_hi, P.rec_base, (const u64 *)row_base, first, pc.r_lo, pc.r_hi, pc.p_lo, pc.p_hi, t0, W, R0, acc,
-                   tracing ? (unsigned long long *)d_sum + 18 : (unsigned long long *)nullptr);
-        }
+        if (bases) LAUNCH(c, "unnaf_comp_count", k_comp_count, (u32)tl.ntiles, 64, 0, tl.seq, tl.b_hi, P.rec_base, (const u64 *)row_base, first, pc.r_lo, pc.r_hi, pc.p_lo, pc.p_hi, tl.t0, W, R0, acc,
+                          tracing ? (unsigned long long *)d_sum + 18 : (unsigned long long *)nullptr);
         if (h_total) { const u64 nb = (nr + 255) / 256; LAUNCH(c, "unnaf_comp_total", k_comp_total, (u32)(nb < 2048 ? nb : 2048), 256, 0, (const u64 *)acc, nr, (unsigned long long *)d_sum); }
         if (!in_place) LAUNCH(c, "unnaf_comp_copy", k_comp_copy, (u32)((nr * COMP_ROW_U64 + 255) / 256), 256, 0, (const u64 *)acc, d_rows + 168 * R0, nr * COMP_ROW_U64);
         HIP_TRY(c, hipGetLastError());
         HIP_TRY(c, hipStreamSynchronize(c->stream));
-        loc_arena_release(c, mark);
+        sw.release();
     }
     u64 sum[20];
     if (h_total || tracing) { if ((rc = ctx_readback(c, sum, d_sum, sizeof sum))) return rc; }
     if (h_total) { for (int k = 0; k < 16; k++) h_total->n[k] = sum[k]; h_total->masked = sum[16]; h_total->cpg = sum[17]; }
     if (tracing) ctx_trace(c, "[composition] rows %llu window %llu pieces %zu sequence bytes decoded %llu of %llu mask %llu tiles nucleotide %llu general %llu\n", (unsigned long long)total,
-                           (unsigned long long)W, pieces.size(), (unsigned long long)decoded, (unsigned long long)pl.seq_bytes, (unsigned long long)(tog_ex ? P.n_toggles : 0),
+                           (unsigned long long)W, pieces.size(), (unsigned long long)sw.decoded, (unsigned long long)pl.seq_bytes, (unsigned long long)(tog_ex ? P.n_toggles : 0),
                            (unsigned long long)sum[18], (unsigned long long)sum[19]);
     return 0;
 }

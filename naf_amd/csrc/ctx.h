@@ -93,6 +93,9 @@ void  arena_reset(naf_gpu_ctx *c);
 void *arena_alloc(naf_gpu_ctx *c, size_t bytes);
 void  arena_settle(naf_gpu_ctx *c);            // end of a whole call: arenas that grew become one allocation each (naf_gpu.hip)
 template <typename T> T *arena_new(naf_gpu_ctx *c, size_t n) { return (T *)arena_alloc(c, n * sizeof(T)); }
+// The arena as it is now, and back to it: what was allocated since is free again (its kernels have to be waited for first).
+static inline std::vector<size_t> arena_mark(const naf_gpu_ctx *c) { std::vector<size_t> m; for (auto &ch : c->chunks) m.push_back(ch.used); return m; }
+static inline void arena_release(naf_gpu_ctx *c, const std::vector<size_t> &m) { for (size_t k = 0; k < c->chunks.size(); k++) c->chunks[k].used = k < m.size() ? m[k] : 0; }
 
 // Small device->host readback through pinned staging (synchronises the stream).
 int ctx_readback(naf_gpu_ctx *c, void *h_dst, const void *d_src, size_t bytes);

@@ -1911,6 +1911,8 @@ static int unnaf_sections(naf_gpu_ctx *c, const u8 *d_naf, UnnafPlan &pl, naf_gp
     return 0;
 }
 
+#include "payload.h"
+
 static int unnaf_run(naf_gpu_ctx *c, const u8 *d_naf, size_t naf_len, const naf_gpu_unnaf_opts *o,
                      u64 out_begin, u64 out_end, bool whole, u8 *d_out, size_t out_cap, size_t *out_len, bool size_only)
 {
@@ -1921,44 +1923,20 @@ static int unnaf_run(naf_gpu_ctx *c, const u8 *d_naf, size_t naf_len, const naf_
     int rc = unnaf_prepare(c, d_naf, naf_len, o, pl); if (rc) return rc;
     if (pl.empty) { *out_len = 0; return 0; }
     const naf_gpu_header &h = pl.h;
-    ZRange rgs, rgq; ZRange *prs = nullptr, *prq = nullptr;
-    memset(&rgs, 0, sizeof rgs); memset(&rgq, 0, sizeof rgq);
-    u8 *seq = nullptr;
+    bool ranged = false; u64 s_lo = 0, s_hi = 0, q_lo = 0, q_hi = 0;               // a byte-range call: the bytes of the two streams it needs
     // sequence (and quality) payload: the dominant zstd streams
     auto payload_seq = [&]() -> int {
-        int r;
-        u64 seq_need = prs ? (rgs.want_hi - rgs.want_lo) + 2 * 131072 + 64 : pl.seq_bytes + 64;
-        if (seq_need > pl.seq_bytes + 64) seq_need = pl.seq_bytes + 64;
-        seq = (u8 *)arena_alloc(c, seq_need);
-        if (!seq) return NAF_GPU_ENOMEM;
-        size_t n = 0;
-        r = zstd_decode_range(c, d_naf + h.payload_off[S_SEQ], h.comp_size[S_SEQ], 0, seq, prs ? seq_need : pl.seq_bytes, &n, prs, pl.frame_head[S_SEQ]);
-        if (r == NAF_GPU_ECAP && prs) {                                              // dependent blocks: needs the whole stream
-            seq = (u8 *)arena_alloc(c, pl.seq_bytes + 64); if (!seq) return NAF_GPU_ENOMEM;
-            r = zstd_decode(c, d_naf + h.payload_off[S_SEQ], h.comp_size[S_SEQ], 0, seq, pl.seq_bytes, &n); prs = nullptr;
-        }
-        if (r == NAF_GPU_ECAP || (r == 0 && n != pl.seq_bytes)) return ctx_fail(c, NAF_GPU_EFORMAT, "can't decompress sequence\n");
-        if (r) return r;
-        pl.P.seq = (prs && prs->ranged) ? (prs->own_buf ? prs->own_buf : seq) - prs->got_lo : seq;
-        return 0;
+        PayloadSpan sp;
+        int r = payload_range(c, d_naf, pl, S_SEQ, s_lo, s_hi, ranged ? PAYLOAD_RANGE : PAYLOAD_WHOLE, &sp);
+        if (!r) pl.P.seq = sp.base;
+        return r;
     };
     // qc: the context the quality stream is decoded on (the archive's own, or the second side context beside the sequence stream)
     auto payload_qual = [&](naf_gpu_ctx *qc) -> int {
-        int r;
-        u64 qn = h.orig_size[S_QUAL];
-        u64 q_need = prq ? (rgq.want_hi - rgq.want_lo) + 2 * 131072 + 64 : qn + 64;
-        if (q_need > qn + 64) q_need = qn + 64;
-        u8 *q = (u8 *)arena_alloc(qc, q_need); if (!q) return NAF_GPU_ENOMEM;
-        size_t qgot = 0;
-        r = zstd_decode_range(qc, d_naf + h.payload_off[S_QUAL], h.comp_size[S_QUAL], 0, q, prq ? q_need : qn, &qgot, prq, pl.frame_head[S_QUAL]);
-        if (r == NAF_GPU_ECAP && prq) {
-            q = (u8 *)arena_alloc(qc, qn + 64); if (!q) return NAF_GPU_ENOMEM;
-            r = zstd_decode(qc, d_naf + h.payload_off[S_QUAL], h.comp_size[S_QUAL], 0, q, qn, &qgot); prq = nullptr;
-        }
-        if (r == NAF_GPU_ECAP || (r == 0 && qgot != qn)) return ctx_fail(qc, NAF_GPU_EFORMAT, "can't decompress quality\n");
-        if (r) return r;
-        pl.P.qual = (prq && prq->ranged) ? (prq->own_buf ? prq->own_buf : q) - prq->got_lo : q;
-        return 0;
+        PayloadSpan sp;
+        int r = payload_range(qc, d_naf, pl, S_QUAL, q_lo, q_hi, ranged ? PAYLOAD_RANGE : PAYLOAD_WHOLE, &sp);
+        if (!r) pl.P.qual = sp.base;
+        return r;
     };
     auto payload = [&]() -> int { int r = payload_seq(); if (r) return r; return pl.need_qual ? payload_qual(c) : 0; };
     const char *fuse = ctx_opt(c, "FUSE");
@@ -2035,9 +2013,9 @@ static int unnaf_run(naf_gpu_ctx *c, const u8 *d_naf, size_t naf_len, const naf_
         rec0 = g[2]; rec1 = g[3];
         if (g[1] < g[0]) g[1] = g[0];
         if (has_tail) g[1] = pl.P.T;
-        rgs.want_lo = pl.fourbit ? g[0] / 2 : g[0]; rgs.want_hi = pl.fourbit ? (g[1] + 1) / 2 : g[1];
-        rgq.want_lo = g[0]; rgq.want_hi = g[1];
-        prs = &rgs; prq = &rgq;
+        s_lo = pl.fourbit ? g[0] / 2 : g[0]; s_hi = pl.fourbit ? (g[1] + 1) / 2 : g[1];
+        q_lo = g[0]; q_hi = g[1];
+        ranged = true;
     }
     // Whole FASTA text of a 4-bit archive: decode and emit in one kernel when the frame is literal-only.
     // (Measured slower than decode + emit on MI355X for now: its per-lane 16-byte text stores are partial-line
@@ -2059,7 +2037,7 @@ static int unnaf_run(naf_gpu_ctx *c, const u8 *d_naf, size_t naf_len, const naf_
     }
     if (zflat.ready) { pl.P.fsrc = zflat.src; pl.P.fsi = zflat.si; pl.P.fslots = zflat.nslots; pl.P.fsym = zflat.sym; pl.P.ftail = zflat.tail; pl.P.ftail_q = zflat.tail_q; pl.P.ftail_n = zflat.tail_n; pl.P.fcls = zflat.cls; }
     if (pl.P.mode == -1) {                                                             // --4bit: the stream itself
-        HIP_TRY(c, hipMemcpyAsync(d_out, seq + out_begin, out_end - out_begin, hipMemcpyDeviceToDevice, c->stream));
+        HIP_TRY(c, hipMemcpyAsync(d_out, pl.P.seq + out_begin, out_end - out_begin, hipMemcpyDeviceToDevice, c->stream));
         return 0;
     }
     if (has_main) {

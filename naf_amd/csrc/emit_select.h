@@ -1,12 +1,12 @@
 // emit_select.h -- the selection path of unnaf: records and regions by number, id or range (naf_gpu_unnaf_find,
 // naf_gpu_unnaf_record_table, naf_gpu_unnaf_select, naf_gpu_unnaf_select_stranded).  Part of emit.hip (included by it, behind unnaf_run): it uses that file's
-// side-section chain (unnaf_prepare, unnaf_sections) and device helpers as they are, and adds kernels of its own.
+// side-section chain (unnaf_prepare, unnaf_sections), the payload decode of payload.h and device helpers as they are, and adds kernels of its own.
 //
 // A selection is a list of SEGMENTS -- bases [begin, end) of a record -- whose texts are laid end to end in the order given.  The
 // text of a segment is the text of a record that holds just those bases (header, wrapping restarted at its first base), so the
 // path builds, on the device, the same tables the whole text has per record, per segment instead (k_select_layout + two scans),
 // and a tile kernel composes 4 KiB of output per wavefront from them (k_emit_select).  The sequence stream is decoded only where
-// the segments lie: their base intervals are sorted and merged on the host and every merged interval is one zstd_decode_range;
+// the segments lie: their base intervals are sorted and merged on the host and every merged interval is one payload_range;
 // every segment carries the pointers of the range that holds its bases (k_select_bind).
 //
 // A segment may be asked for as its REVERSE COMPLEMENT (naf_gpu_unnaf_select_stranded): the same record text with the bases read from
@@ -485,49 +485,21 @@ static int select_run(naf_gpu_ctx *c, const u8 *d_naf, size_t naf_len, const naf
     std::vector<SelRange> hr(rgs.size());
     u64 decoded = 0;
     bool whole_stream = false;
-    const u64 qn = h.orig_size[S_QUAL];
+    PayloadSpan sp, qp;
     for (size_t k = 0; k < rgs.size() && !whole_stream; k++) {
-        ZRange zs; memset(&zs, 0, sizeof zs);
-        zs.want_lo = rgs[k].first / per_byte; zs.want_hi = (rgs[k].second + per_byte - 1) / per_byte;
-        u64 need = (zs.want_hi - zs.want_lo) + 2 * 131072 + 64; if (need > pl.seq_bytes + 64) need = pl.seq_bytes + 64;
-        u8 *buf = (u8 *)arena_alloc(c, need); if (!buf) return NAF_GPU_ENOMEM;
-        size_t n = 0;
-        rc = zstd_decode_range(c, d_naf + h.payload_off[S_SEQ], h.comp_size[S_SEQ], 0, buf, need - 64, &n, &zs, pl.frame_head[S_SEQ]);
+        const u64 g_lo = rgs[k].first, g_hi = rgs[k].second;
+        rc = payload_range(c, d_naf, pl, S_SEQ, g_lo / per_byte, (g_hi + per_byte - 1) / per_byte, PAYLOAD_RANGE_ONLY, &sp);
+        if (!rc && pl.need_qual) rc = payload_range(c, d_naf, pl, S_QUAL, g_lo, g_hi, PAYLOAD_RANGE_ONLY, &qp);
         if (rc == NAF_GPU_ECAP) { whole_stream = true; break; }                  // dependent blocks: the closure is the whole stream
-        if (rc == 0 && n != pl.seq_bytes) return ctx_fail(c, NAF_GPU_EFORMAT, "can't decompress sequence\n");
         if (rc) return rc;
-        hr[k].g_lo = rgs[k].first; hr[k].g_hi = rgs[k].second;
-        hr[k].seq = zs.ranged ? (zs.own_buf ? zs.own_buf : buf) - zs.got_lo : buf; hr[k].qual = nullptr;
-        decoded += zs.ranged ? zs.got_hi - zs.got_lo : pl.seq_bytes;
-        if (pl.need_qual) {
-            ZRange zq; memset(&zq, 0, sizeof zq);
-            zq.want_lo = rgs[k].first; zq.want_hi = rgs[k].second;
-            u64 qneed = (zq.want_hi - zq.want_lo) + 2 * 131072 + 64; if (qneed > qn + 64) qneed = qn + 64;
-            u8 *q = (u8 *)arena_alloc(c, qneed); if (!q) return NAF_GPU_ENOMEM;
-            size_t qgot = 0;
-            rc = zstd_decode_range(c, d_naf + h.payload_off[S_QUAL], h.comp_size[S_QUAL], 0, q, qneed - 64, &qgot, &zq, pl.frame_head[S_QUAL]);
-            if (rc == NAF_GPU_ECAP) { whole_stream = true; break; }
-            if (rc == 0 && qgot != qn) return ctx_fail(c, NAF_GPU_EFORMAT, "can't decompress quality\n");
-            if (rc) return rc;
-            hr[k].qual = zq.ranged ? (zq.own_buf ? zq.own_buf : q) - zq.got_lo : q;
-        }
+        hr[k] = SelRange{ g_lo, g_hi, sp.base, pl.need_qual ? qp.base : nullptr };
+        decoded += sp.got_hi - sp.got_lo;
     }
     if (whole_stream) {                                                          // one decode of everything for the call, as unnaf_run does
-        u8 *buf = (u8 *)arena_alloc(c, pl.seq_bytes + 64); if (!buf) return NAF_GPU_ENOMEM;
-        size_t n = 0;
-        rc = zstd_decode(c, d_naf + h.payload_off[S_SEQ], h.comp_size[S_SEQ], 0, buf, pl.seq_bytes, &n);
-        if (rc == NAF_GPU_ECAP || (rc == 0 && n != pl.seq_bytes)) return ctx_fail(c, NAF_GPU_EFORMAT, "can't decompress sequence\n");
-        if (rc) return rc;
-        hr.assign(1, SelRange{ 0, P.T, buf, nullptr });
+        if ((rc = payload_range(c, d_naf, pl, S_SEQ, 0, 0, PAYLOAD_WHOLE, &sp))) return rc;
+        if (pl.need_qual && (rc = payload_range(c, d_naf, pl, S_QUAL, 0, 0, PAYLOAD_WHOLE, &qp))) return rc;
+        hr.assign(1, SelRange{ 0, P.T, sp.base, pl.need_qual ? qp.base : nullptr });
         decoded = pl.seq_bytes;
-        if (pl.need_qual) {
-            u8 *q = (u8 *)arena_alloc(c, qn + 64); if (!q) return NAF_GPU_ENOMEM;
-            size_t qgot = 0;
-            rc = zstd_decode(c, d_naf + h.payload_off[S_QUAL], h.comp_size[S_QUAL], 0, q, qn, &qgot);
-            if (rc == NAF_GPU_ECAP || (rc == 0 && qgot != qn)) return ctx_fail(c, NAF_GPU_EFORMAT, "can't decompress quality\n");
-            if (rc) return rc;
-            hr[0].qual = q;
-        }
     }
     if (!hr.empty()) {
         SelRange *d_rg = arena_new<SelRange>(c, hr.size()); if (!d_rg) return NAF_GPU_ENOMEM;

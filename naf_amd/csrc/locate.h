@@ -1,6 +1,7 @@
 // locate.h -- IUPAC motifs on either strand, searched in the packed 4-bit stream (naf_gpu_compile_motif, naf_gpu_unnaf_locate_count,
-// naf_gpu_unnaf_locate).  Part of emit.hip (included by it, behind emit_select.h): it uses that file's side-section chain for the
-// record tables and the range decode of the selection path, and adds two kernels of its own.
+// naf_gpu_unnaf_locate).  Part of emit.hip (included by it, behind emit_select.h): the front of the call, the pieces and the decode of
+// a piece's bytes are payload.h's (records_front, piece_plan, PieceSweep); this file holds the motif compiler, the two kernels and their
+// launches.
 //
 // In the code table "-TGKCYSBAWRDMHVN" a base is a SET of nucleotides (A = 8, C = 4, G = 2, T/U = 1, N = 15, '-' = 0), so
 //   a stored base c matches a pattern letter p   <=>   c != 0 && (c & ~p) == 0
@@ -36,13 +37,6 @@
 struct LocCombo { u64 nl, nh, ol, oh; };     // ~p of letters 0..15 / 16..31 (0 behind the pattern); 1 in bit 0 of every nibble that holds a letter
 struct LocPats { LocCombo c[LOC_MAX_COMBOS]; u32 len[LOC_MAX_COMBOS]; u8 pat[LOC_MAX_COMBOS], strand[LOC_MAX_COMBOS]; u32 n; };
 
-__device__ __forceinline__ u32 wave_sum_u32(u32 v) { for (int d = 32; d; d >>= 1) v += (u32)__shfl_xor((int)v, d); return v; }
-__device__ __forceinline__ u32 wave_prefix_u32(u32 v, u32 lane)                 // exclusive
-{
-    u32 s = v;
-    for (int d = 1; d < 64; d <<= 1) { const u32 o = (u32)__shfl_up((int)s, d); if (lane >= (u32)d) s += o; }
-    return s - v;
-}
 // bit 4j set where nibble j of w is zero
 __device__ __forceinline__ u64 zero_nibbles(u64 w) { u64 t = w | (w >> 1); t |= t >> 2; return ~t & 0x1111111111111111ull; }
 
@@ -159,12 +153,6 @@ static LocCombo motif_masks(const u8 code[32], size_t m)
     return q;
 }
 
-// the arena as it is now, to be returned to once a piece is done (its kernels waited for)
-static std::vector<size_t> loc_arena_mark(naf_gpu_ctx *c) { std::vector<size_t> m; for (auto &ch : c->chunks) m.push_back(ch.used); return m; }
-static void loc_arena_release(naf_gpu_ctx *c, const std::vector<size_t> &m) { for (size_t k = 0; k < c->chunks.size(); k++) c->chunks[k].used = k < m.size() ? m[k] : 0; }
-
-struct LocPiece { u64 r_lo, r_hi, p_lo, p_hi; };
-
 // per_pattern: n_patterns x 2 counts (host), or nullptr.  write: the hits go to d_hits (hit_cap entries); too small a capacity is found
 // before anything is written.
 static int locate_run(naf_gpu_ctx *c, const u8 *d_naf, size_t naf_len, const char *h_patterns, size_t patterns_bytes, size_t n_patterns, int strands,
@@ -197,83 +185,32 @@ static int locate_run(naf_gpu_ctx *c, const u8 *d_naf, size_t naf_len, const cha
           at = (size_t)((const char *)z - h_patterns) + 1;
       } }
     if (per_pattern) for (size_t k = 0; k < 2 * n_patterns; k++) per_pattern[k] = 0;
-    arena_reset(c);
-    naf_gpu_unnaf_opts o = { NAF_OUT_SEQUENCES, 0, -1 };                          // the record tables of --sequences: lengths only, no ids, no mask
     UnnafPlan pl;
-    int rc = unnaf_prepare(c, d_naf, naf_len, &o, pl); if (rc) return rc;
-    const naf_gpu_header &h = pl.h;
-    if (!pl.fourbit) return ctx_fail(c, NAF_GPU_EARG, "locate: nucleotide motifs cannot be searched in %s sequences", h.seq_type == NAF_SEQ_PROTEIN ? "protein" : "text");
-    const u64 N = h.n_sequences;
-    if (first > N) return ctx_fail(c, NAF_GPU_EARG, "locate: first record %llu, the archive has %llu", (unsigned long long)first, (unsigned long long)N);
-    if (count == NAF_GPU_WHOLE) count = N - first;
-    if (count > N - first) return ctx_fail(c, NAF_GPU_EARG, "locate: records %llu..%llu of %llu", (unsigned long long)first, (unsigned long long)(first + count), (unsigned long long)N);
-    if (N == 0) return 0;
-    if (!((h.flags >> 1) & 1)) return ctx_fail(c, NAF_GPU_EARG, "locate: the archive stores no sequence");
-    if (count == 0) return 0;
-    if ((rc = unnaf_sections(c, d_naf, pl))) return rc;
+    int rc = records_front(c, d_naf, naf_len, 0, "locate", "nucleotide motifs cannot be searched", first, &count, pl);
+    if (rc || !count) return rc;
     const EmitP &P = pl.P;
-
-    // the pieces: whole records, as many as stay within the piece size (a longer record is a piece of its own)
-    u64 piece = LOC_PIECE_DEFAULT;
-    { const char *e = ctx_opt(c, "LOCATE_PIECE"); if (e && e[0]) { const u64 v = strtoull(e, nullptr, 10); if (v) piece = v; } }
-    u64 ends[2] = { 0, 0 };
-    if ((rc = ctx_readback2(c, &ends[0], P.rec_base + first, 8, &ends[1], P.rec_base + first + count, 8))) return rc;
-    std::vector<LocPiece> pieces;
-    if (ends[1] - ends[0] <= piece) pieces.push_back({ first, first + count, ends[0], ends[1] });
-    else {
-        std::vector<u64> base(count + 1);
-        HIP_TRY(c, hipMemcpyAsync(base.data(), P.rec_base + first, (count + 1) * 8, hipMemcpyDeviceToHost, c->stream));
-        HIP_TRY(c, hipStreamSynchronize(c->stream));
-        for (u64 a = 0; a < count; ) {
-            u64 b = (u64)(std::upper_bound(base.begin() + a, base.end(), base[a] + piece) - base.begin()) - 1;   // last record end within the piece
-            if (b <= a) b = a + 1;
-            pieces.push_back({ first + a, first + b, base[a], base[b] });
-            a = b;
-        }
-    }
+    std::vector<RecPiece> pieces;
+    if ((rc = piece_plan(c, P, first, count, "LOCATE_PIECE", LOC_PIECE_DEFAULT, pieces))) return rc;
 
     u64 *combo_cnt = arena_new<u64>(c, LOC_MAX_COMBOS); if (!combo_cnt) return NAF_GPU_ENOMEM;
-    const u8 *whole_seq = nullptr;                                                // the whole stream, once a piece's range could not be had alone
-    u64 decoded = 0, total = 0;
-    std::vector<size_t> mark = loc_arena_mark(c);
+    PieceSweep sw(c, d_naf, pl, "locate");
+    u64 total = 0;
     auto sweep = [&](bool writing) -> int {
         total = 0;
         HIP_TRY(c, hipMemsetAsync(combo_cnt, 0, LOC_MAX_COMBOS * 8, c->stream));
-        for (const LocPiece &pc : pieces) {
+        for (const RecPiece &pc : pieces) {
             if (pc.p_hi == pc.p_lo) continue;
-            const u8 *seq = whole_seq;
-            const u64 b_lo = pc.p_lo / 2, b_hi = (pc.p_hi + 1) / 2;
-            if (!seq) {
-                ZRange zs; memset(&zs, 0, sizeof zs);
-                zs.want_lo = b_lo; zs.want_hi = b_hi;
-                // (+ 64: the slack every caller of the decoder leaves behind its output, as select_run does; the search itself never reads
-                // past b_hi -- the lanes at a range's end load byte by byte -- and does not rely on it)
-                u64 need = (b_hi - b_lo) + 2 * 131072 + 64; if (need > pl.seq_bytes + 64) need = pl.seq_bytes + 64;
-                u8 *buf = (u8 *)arena_alloc(c, need); if (!buf) return NAF_GPU_ENOMEM;
-                size_t n = 0;
-                int r = zstd_decode_range(c, d_naf + h.payload_off[S_SEQ], h.comp_size[S_SEQ], 0, buf, need - 64, &n, &zs, pl.frame_head[S_SEQ]);
-                if (r == NAF_GPU_ECAP) {                                          // dependent blocks: the closure is the whole stream -- decoded once for the call
-                    buf = (u8 *)arena_alloc(c, pl.seq_bytes + 64); if (!buf) return NAF_GPU_ENOMEM;
-                    r = zstd_decode(c, d_naf + h.payload_off[S_SEQ], h.comp_size[S_SEQ], 0, buf, pl.seq_bytes, &n);
-                    if (r == NAF_GPU_ECAP || (r == 0 && n != pl.seq_bytes)) return ctx_fail(c, NAF_GPU_EFORMAT, "can't decompress sequence\n");
-                    if (r) return r;
-                    zs.ranged = false;
-                }
-                else if (r == 0 && n != pl.seq_bytes) return ctx_fail(c, NAF_GPU_EFORMAT, "can't decompress sequence\n");
-                else if (r) return r;
-                if (zs.ranged) { seq = (zs.own_buf ? zs.own_buf : buf) - zs.got_lo; decoded += zs.got_hi - zs.got_lo; }
-                else { seq = whole_seq = buf; decoded += pl.seq_bytes; mark = loc_arena_mark(c); }
-            }
-            const u64 t0 = pc.p_lo & ~1ull, ntiles = (pc.p_hi - t0 + LOC_TILE - 1) / LOC_TILE;
-            if (ntiles > 0x7FFFFFFFull) return ctx_fail(c, NAF_GPU_EARG, "locate: a piece of %llu bases is too long for one launch", (unsigned long long)(pc.p_hi - pc.p_lo));
+            PieceSweep::Tiles tl;
+            int r = sw.seq_for(pc, LOC_TILE, &tl); if (r) return r;
+            const u64 ntiles = tl.ntiles;
             u64 *tile_cnt = arena_new<u64>(c, ntiles + 2); u32 *lane_cnt = arena_new<u32>(c, ntiles * 64);
             if (!tile_cnt || !lane_cnt) return NAF_GPU_ENOMEM;
             HIP_TRY(c, hipMemsetAsync(tile_cnt + ntiles, 0, 8, c->stream));
 #define LOC_LAUNCH(W, name) do { \
-                if (any_long) LAUNCH(c, name, (k_locate<W, true>), (u32)ntiles, 64, 0, Q, seq, b_hi, P.rec_base, pc.r_lo, pc.r_hi, pc.p_lo, pc.p_hi, t0, tile_cnt, lane_cnt, (unsigned long long *)combo_cnt, (const u64 *)tile_cnt, total, d_hits, (u64)hit_cap); \
-                else LAUNCH(c, name, (k_locate<W, false>), (u32)ntiles, 64, 0, Q, seq, b_hi, P.rec_base, pc.r_lo, pc.r_hi, pc.p_lo, pc.p_hi, t0, tile_cnt, lane_cnt, (unsigned long long *)combo_cnt, (const u64 *)tile_cnt, total, d_hits, (u64)hit_cap); } while (0)
+                if (any_long) LAUNCH(c, name, (k_locate<W, true>), (u32)ntiles, 64, 0, Q, tl.seq, tl.b_hi, P.rec_base, pc.r_lo, pc.r_hi, pc.p_lo, pc.p_hi, tl.t0, tile_cnt, lane_cnt, (unsigned long long *)combo_cnt, (const u64 *)tile_cnt, total, d_hits, (u64)hit_cap); \
+                else LAUNCH(c, name, (k_locate<W, false>), (u32)ntiles, 64, 0, Q, tl.seq, tl.b_hi, P.rec_base, pc.r_lo, pc.r_hi, pc.p_lo, pc.p_hi, tl.t0, tile_cnt, lane_cnt, (unsigned long long *)combo_cnt, (const u64 *)tile_cnt, total, d_hits, (u64)hit_cap); } while (0)
             LOC_LAUNCH(false, "unnaf_locate_count");
-            int r = scan_exclusive_u64(c, tile_cnt, ntiles + 1, (u64 *)nullptr); if (r) return r;
+            if ((r = scan_exclusive_u64(c, tile_cnt, ntiles + 1, (u64 *)nullptr))) return r;
             u64 here = 0;
             if ((r = ctx_readback(c, &here, tile_cnt + ntiles, 8))) return r;
             if (writing && here) {
@@ -285,7 +222,7 @@ static int locate_run(naf_gpu_ctx *c, const u8 *d_naf, size_t naf_len, const cha
             }
 #undef LOC_LAUNCH
             total += here;
-            loc_arena_release(c, mark);
+            sw.release();
         }
         return 0;
     };
@@ -304,7 +241,7 @@ static int locate_run(naf_gpu_ctx *c, const u8 *d_naf, size_t naf_len, const cha
         for (u32 q = 0; q < Q.n; q++) per_pattern[2 * Q.pat[q] + Q.strand[q]] = cc[q];
     }
     if (ctx_tracing(c)) ctx_trace(c, "[locate] patterns %zu records %llu..%llu pieces %zu sequence bytes decoded %llu of %llu hits %llu\n", n_patterns,
-                                  (unsigned long long)first, (unsigned long long)(first + count), pieces.size(), (unsigned long long)decoded, (unsigned long long)pl.seq_bytes, (unsigned long long)total);
+                                  (unsigned long long)first, (unsigned long long)(first + count), pieces.size(), (unsigned long long)sw.decoded, (unsigned long long)pl.seq_bytes, (unsigned long long)total);
     return 0;
 }
 

@@ -89,3 +89,12 @@ __device__ __forceinline__ T wg_scan_inclusive(T v, T *total, T *lds /* 4 entrie
     *total = tot;
     return Op::template f<T>(pre, v);
 }
+
+// One u32 per lane of a wavefront of 64: the sum in every lane, and the exclusive prefix sum.
+__device__ __forceinline__ u32 wave_sum_u32(u32 v) { for (int d = 32; d; d >>= 1) v += (u32)__shfl_xor((int)v, d); return v; }
+__device__ __forceinline__ u32 wave_prefix_u32(u32 v, u32 lane)                 // exclusive
+{
+    u32 s = v;
+    for (int d = 1; d < 64; d <<= 1) { const u32 o = (u32)__shfl_up((int)s, d); if (lane >= (u32)d) s += o; }
+    return s - v;
+}

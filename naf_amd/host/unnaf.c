@@ -320,6 +320,38 @@ static void run_text(int mode, int masking_allowed)
     phase("download + write"); naf_gpu_free(gpu, d);
 }
 
+/* --records A-B against the archive's record count */
+static void check_records(const selection *s)
+{
+    if (s->last > H.n_sequences) die("--records: sequence %llu requested, the archive has %llu\n", s->last, (unsigned long long)H.n_sequences);
+}
+/* --locate / --composition: the one --records or --region they allow as (first, count); none = every record */
+static void one_record_range(bool has_ids, uint64_t *first, uint64_t *count)
+{
+    *first = 0; *count = NAF_GPU_WHOLE;
+    if (!n_selections) return;
+    const selection *s = &selections[0];
+    if (s->region) {
+        uint64_t rec = UINT64_MAX;
+        if (has_ids && H.n_sequences) GPU_TRY(naf_gpu_unnaf_find(gpu, d_naf, naf_len, s->region, strlen(s->region) + 1, 1, &rec));
+        if (rec == UINT64_MAX) die("sequence \"%s\" not found\n", s->region);
+        *first = rec; *count = 1;
+    } else {
+        check_records(s);
+        *first = s->first - 1; *count = s->last - s->first + 1;
+    }
+}
+/* the first column of their tables, per record: ids, or the stored names of an archive without ids (*text holds them; both are the caller's to free) */
+static const char **record_names(bool has_ids, bool has_names, unsigned char **text)
+{
+    const unsigned long long N = H.n_sequences;
+    *text = has_ids ? load_strings(0, "ids", N) : has_names ? load_strings(1, "names", N) : NULL;
+    const char **name = (const char **)malloc((size_t)(N + 1) * sizeof *name); if (!name) die("can't allocate memory\n");
+    const char *p = (const char *)*text;
+    for (unsigned long long r = 0; r < N; r++) { name[r] = p ? p : ""; if (p) p += strlen(p) + 1; }
+    return name;
+}
+
 /* --region / --records: ids to record numbers (naf_gpu_unnaf_find), then the segments' texts in command-line order
  * (naf_gpu_unnaf_select_stranded: --rc-region / --revcomp give a segment's reverse complement), on the first device.  Nothing is written before every id is found. */
 static void *sel_buf = NULL; static size_t sel_cap = 0;
@@ -344,7 +376,7 @@ static void run_select(int mode, bool has_ids)
         const selection *s = &selections[k];
         if (s->region) { size_t l; uint64_t b, e; naf_gpu_parse_region(s->region, &l, &b, &e); n_regions++; ids_bytes += l + 1; n_segs++; }
         else {
-            if (s->last > N) die("--records: sequence %llu requested, the archive has %llu\n", s->last, N);
+            check_records(s);
             n_segs += (size_t)(s->last - s->first + 1);
         }
     }
@@ -384,19 +416,8 @@ static void run_locate(bool has_ids, bool has_names)
 {
     upload();
     const unsigned long long N = H.n_sequences;
-    uint64_t first = 0, count = NAF_GPU_WHOLE;
-    if (n_selections) {
-        const selection *s = &selections[0];
-        if (s->region) {
-            uint64_t rec = UINT64_MAX;
-            if (has_ids && N) GPU_TRY(naf_gpu_unnaf_find(gpu, d_naf, naf_len, s->region, strlen(s->region) + 1, 1, &rec));
-            if (rec == UINT64_MAX) die("sequence \"%s\" not found\n", s->region);
-            first = rec; count = 1;
-        } else {
-            if (s->last > N) die("--records: sequence %llu requested, the archive has %llu\n", s->last, N);
-            first = s->first - 1; count = s->last - s->first + 1;
-        }
-    }
+    uint64_t first, count;
+    one_record_range(has_ids, &first, &count);
     size_t bytes = 0; for (size_t k = 0; k < n_locate; k++) bytes += strlen(locate_patterns[k]) + 1;
     char *pats = (char *)malloc(bytes + 1); if (!pats) die("can't allocate memory\n");
     size_t plen[MAX_LOCATE];
@@ -410,10 +431,7 @@ static void run_locate(bool has_ids, bool has_names)
         GPU_TRY(naf_gpu_unnaf_locate(gpu, d_naf, naf_len, pats, bytes, n_locate, locate_strands, first, count, (naf_gpu_hit *)d_hits, (size_t)n, &got));
         if (got != n) die("can't decompress sequence\n");
         phase("locate: hits");
-        /* the first column: ids, or the stored names of an archive without ids */
-        unsigned char *text = has_ids ? load_strings(0, "ids", N) : has_names ? load_strings(1, "names", N) : NULL;
-        const char **name = (const char **)malloc((size_t)(N + 1) * sizeof *name); if (!name) die("can't allocate memory\n");
-        { const char *p = (const char *)text; for (unsigned long long r = 0; r < N; r++) { name[r] = p ? p : ""; if (p) p += strlen(p) + 1; } }
+        unsigned char *text; const char **name = record_names(has_ids, has_names, &text);
         const size_t chunk = 1 << 20;
         naf_gpu_hit *hits = (naf_gpu_hit *)malloc((n < chunk ? (size_t)n : chunk) * sizeof *hits); if (!hits) die("can't allocate memory\n");
         for (uint64_t a = 0; a < n; a += chunk) {
@@ -438,19 +456,8 @@ static void run_composition(bool has_ids, bool has_names)
 {
     upload();
     const unsigned long long N = H.n_sequences;
-    uint64_t first = 0, count = NAF_GPU_WHOLE;
-    if (n_selections) {
-        const selection *s = &selections[0];
-        if (s->region) {
-            uint64_t rec = UINT64_MAX;
-            if (has_ids && N) GPU_TRY(naf_gpu_unnaf_find(gpu, d_naf, naf_len, s->region, strlen(s->region) + 1, 1, &rec));
-            if (rec == UINT64_MAX) die("sequence \"%s\" not found\n", s->region);
-            first = rec; count = 1;
-        } else {
-            if (s->last > N) die("--records: sequence %llu requested, the archive has %llu\n", s->last, N);
-            first = s->first - 1; count = s->last - s->first + 1;
-        }
-    }
+    uint64_t first, count;
+    one_record_range(has_ids, &first, &count);
     uint64_t n = 0;
     GPU_TRY(naf_gpu_unnaf_composition_rows(gpu, d_naf, naf_len, comp_window, first, count, &n));
     phase("composition: rows");
@@ -461,10 +468,7 @@ static void run_composition(bool has_ids, bool has_names)
         GPU_TRY(naf_gpu_unnaf_composition(gpu, d_naf, naf_len, comp_window, use_mask ? NAF_GPU_COMP_MASK : 0, first, count, (naf_gpu_comp_row *)d_rows, (size_t)n, &got, NULL));
         if (got != n) die("can't decompress sequence\n");
         phase("composition: count");
-        /* the first column: ids, or the stored names of an archive without ids */
-        unsigned char *text = has_ids ? load_strings(0, "ids", N) : has_names ? load_strings(1, "names", N) : NULL;
-        const char **name = (const char **)malloc((size_t)(N + 1) * sizeof *name); if (!name) die("can't allocate memory\n");
-        { const char *p = (const char *)text; for (unsigned long long r = 0; r < N; r++) { name[r] = p ? p : ""; if (p) p += strlen(p) + 1; } }
+        unsigned char *text; const char **name = record_names(has_ids, has_names, &text);
         const size_t chunk = 1 << 18;
         naf_gpu_comp_row *rows = (naf_gpu_comp_row *)malloc((n < chunk ? (size_t)n : chunk) * sizeof *rows); if (!rows) die("can't allocate memory\n");
         for (uint64_t a = 0; a < n; a += chunk) {

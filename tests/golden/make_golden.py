@@ -76,6 +76,14 @@ def mask_boundary_fasta():
 repeat_genome = synth.repeat_genome
 
 
+def repeat_fastq(read_len=30000):
+    """The bases of repeat_genome() as reads, every read with the same run of qualities: at -19 the blocks of its sequence stream
+    depend on each other, under a quality stream."""
+    seq = b"".join(ln for ln in repeat_genome().split(b"\n") if not ln.startswith(b">")).upper()
+    qual = bytes(33 + (i * 7) % 41 for i in range(read_len))
+    return b"".join(b"@r%d\n%s\n+\n%s\n" % (k, seq[a:a + read_len], qual[:len(seq[a:a + read_len])]) for k, a in enumerate(range(0, len(seq), read_len)))
+
+
 def naf_cases():
     os.makedirs(os.path.join(HERE, "naf"), exist_ok=True)
     tiny_many = b"".join(b">t%d\n%s\n" % (i, b"ACGTN"[: 1 + i % 5] * (1 + i % 6)) for i in range(3000))
@@ -132,6 +140,8 @@ def naf_cases():
         meta.append(entry)
         print(name, len(text), "->", len(naf), entry["frame_info"].get("seq"))
     json.dump(meta, open(os.path.join(HERE, "naf_cases.json"), "w"), indent=1)
+    # beside the cases (tests/test_gpu_select.py reads it by name)
+    open(os.path.join(HERE, "naf", "repeat_fastq_l19.naf"), "wb").write(O.ref_ennaf(repeat_fastq(), ["-19"]))
 
 
 def zstd_cases():

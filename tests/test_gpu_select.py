@@ -238,6 +238,21 @@ def test_a_range_of_reads_of_a_64_mb_read_set(gpu, oracle, monkeypatch, capfd):
     assert D <= stream + 4 * 131072 * K and D < T
 
 
+def test_reads_of_a_fastq_archive_whose_blocks_depend_on_each_other(gpu, oracle, monkeypatch, capfd):
+    """repeat_fastq_l19 (tests/golden/make_golden.py: 71 reads of 30 000 bases, the reference's -19): the last block of its sequence frame
+    reaches back to the first (offsets up to 1 032 831 in a stream of 1 052 885 bytes), so the range of a read at the end cannot be had
+    alone.  The call then gives up every range, the one of read 5 that could, and decodes sequence AND quality whole, once: one range,
+    D == T, and the bytes of the whole decode."""
+    naf = golden_bytes("naf", "repeat_fastq_l19.naf")
+    d_naf = gpu.to_device(naf)
+    R = Records(oracle, naf, FASTQ)
+    assert R.n == 71 and host(gpu.unnaf(d_naf, FASTQ)) == R.text
+    for segs in ([5, R.n - 1, R.n - 3], [R.n - 2]):
+        got, (K, ranges, D, T, side) = traced_select(gpu, d_naf, segs, FASTQ, monkeypatch, capfd)
+        assert got == R.expect(segs)
+        assert (K, ranges, side) == (len(segs), 1, 1) and D == T == (sum(len(b) for b in R.bases) + 1) // 2
+
+
 # ---- 5. find -------------------------------------------------------------------------------------------------------------------
 def ids_of(oracle, naf):
     h = oracle.parse_naf(naf)
