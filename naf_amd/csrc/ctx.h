@@ -29,11 +29,17 @@ struct FlatStream { u64 q0, A; };
 // decoded (at their natural offsets of the packed stream), so that every 4 KiB tile of text lies either over blocks that can be
 // read in place or over blocks that were decoded.  The slots of a block that cannot be read in place carry A = FLAT_DECODED.
 #define FLAT_DECODED (~0ull)
+// Filled in one place, flat_handoff (zstd_dec.hip), at every exit of zstd_decode_one that leaves the frame to be read in place; the caller zeroes it and sets `aux`.
 struct ZFlat { const u8 *src; const FlatStream *si; u64 nslots; const u8 *sym; void *status; bool ready;
+               // a final Raw block (the byte that holds the padding nibble of an odd stream, zstd_enc) -- its bytes lie in the frame as they are;
+               // packed index of its first byte; its length (bit 31: an RLE block, one stored byte)
                const u8 *tail; u64 tail_q; u32 tail_n;
-               const u8 *cls; u32 n_decoded; u32 n_walk;   // n_walk: decoded blocks whose literals need the Huffman walk (a latency-bound job beside the emit)
-                     // cls == nullptr: every block is flat (nothing was decoded)
-               struct naf_gpu_ctx *aux; hipEvent_t decoded_ev; void *later; };   // later: the decode of the blocks that are not flat, as a job to be run by the caller once its tile index is queued (zstd_flat_later)   // aux: a context whose stream is free for the decode of the blocks that are not flat (set by the caller; the emit of the flat tiles runs beside it); decoded_ev: set by the decoder when it used it -- to be waited for before the decoded bytes are read   // tail: a final Raw block (the byte that holds the padding nibble of an odd stream, zstd_enc) -- its bytes lie in the frame as they are; packed index of its first byte; its length
+               // cls == nullptr: every block is flat (nothing was decoded); n_walk: decoded blocks whose literals need the Huffman walk (a latency-bound job beside the emit)
+               const u8 *cls; u32 n_decoded; u32 n_walk;
+               // aux: a context whose stream is free for the decode of the blocks that are not flat (set by the caller; the emit of the flat tiles runs beside it)
+               // decoded_ev: set by the decoder when it used it -- to be waited for before the decoded bytes are read
+               // later: the decode of the blocks that are not flat, as a job the caller runs once its tile index is queued (zstd_flat_later) or drops (zstd_flat_drop)
+               struct naf_gpu_ctx *aux; hipEvent_t decoded_ev; void *later; };
 // The NAF_GPU_* switches (cross-check levers of the tests, development aids).  naf_gpu_init reads them from
 // the environment ONCE; afterwards only naf_gpu_set_option changes them -- no call looks at the environment.  Names are kept without
 // the NAF_GPU_ prefix.  Side contexts look at the options of the context they belong to (`root`).  TRACE=1: the verdicts of the paths a

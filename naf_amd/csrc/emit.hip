@@ -2047,11 +2047,12 @@ static int unnaf_run(naf_gpu_ctx *c, const u8 *d_naf, size_t naf_len, const naf_
         if (ek && !strcmp(ek, "short")) short_rec = pl.P.mode != EM_SEQ;
         if (ek && !strcmp(ek, "long")) short_rec = false;
         if (pl.P.force_slow) { short_rec = false; ek = "span"; }
+        const bool emit_wave = !ctx_opt_is(c, "EMIT_WAVE", '0');      // wavefront-sized workgroups ("0": the workgroups of 256 everywhere)
         if (whole && pl.P.mode == EM_FASTQ && !pl.P.force_slow && !(ek && ek[0])) {
             {
                 const u64 avg = pl.P.N ? (pl.P.out_end - pl.P.out_begin) / pl.P.N + 1 : 1;        // bytes of text per read
                 const u32 lanes = avg * 64 <= ER_STAGE * 7 / 8 ? 4u : avg * 32 <= ER_STAGE * 7 / 8 ? 8u : 16u;
-                const bool w1 = !(ctx_opt(c, "EMIT_WAVE") && ctx_opt(c, "EMIT_WAVE")[0] == '0');
+                const bool w1 = emit_wave;
                 const u32 wgt = w1 ? 64u : 256u, grid = (u32)cdiv(pl.P.N, wgt / lanes);
 #define ER_LAUNCH(FB, LN) do { if (w1) LAUNCH(c, "unnaf_emit_records", (k_emit_fastq_records<FB, LN, 64>), grid, 64, 0, pl.P, d_out); \
                                else LAUNCH(c, "unnaf_emit_records", (k_emit_fastq_records<FB, LN, 256>), grid, 256, 0, pl.P, d_out); } while (0)
@@ -2090,7 +2091,13 @@ static int unnaf_run(naf_gpu_ctx *c, const u8 *d_naf, size_t naf_len, const naf_
             // With a split decode (ZSplit) the index and the tiles behind the finished parts run on the second stream beside the
             // decode of the next part; this stream takes the tiles behind the last part, the boundary tiles, and waits for the other.
             naf_gpu_ctx *ic = split.done ? c->side2 : c;                                     // context the tile index is built on
-            const bool tile_wave = !(ctx_opt(c, "EMIT_WAVE") && ctx_opt(c, "EMIT_WAVE")[0] == '0');      // k_emit_tile_wave / k_emit_tile_flat_wave ("0": the workgroups of 256)
+            // tiles [t0, t1) of a decoded stream: k_emit_tile_wave, or k_emit_tile in workgroups of 256
+            auto emit_tiles = [&](naf_gpu_ctx *x, u64 t0, u64 t1) {
+                if (emit_wave && pl.fourbit) LAUNCH(x, "unnaf_emit", (k_emit_tile_wave<true, 2>), cdiv(t1 - t0, 2u), 64, 0, pl.P, (const TileIdx *)(ti + t0), d_out + t0 * 4096, (u64)(t1 - t0));
+                else if (emit_wave) LAUNCH(x, "unnaf_emit", (k_emit_tile_wave<false, 2>), cdiv(t1 - t0, 2u), 64, 0, pl.P, (const TileIdx *)(ti + t0), d_out + t0 * 4096, (u64)(t1 - t0));
+                else if (pl.fourbit) LAUNCH(x, "unnaf_emit", k_emit_tile<true>, (u32)(t1 - t0), 256, 0, pl.P, (const TileIdx *)(ti + t0), d_out + t0 * 4096);
+                else LAUNCH(x, "unnaf_emit", k_emit_tile<false>, (u32)(t1 - t0), 256, 0, pl.P, (const TileIdx *)(ti + t0), d_out + t0 * 4096);
+            };
             if (split.done) HIP_TRY(c, hipMemsetAsync(cnt, 0, 8, ic->stream));
             TileFlat *tsig = nullptr;
             if (zflat.ready) {
@@ -2117,10 +2124,7 @@ static int unnaf_run(naf_gpu_ctx *c, const u8 *d_naf, size_t naf_len, const naf_
                     if (t_hi > ntiles) t_hi = ntiles;
                     if (t_hi <= t_done) continue;
                     HIP_TRY(c, hipStreamWaitEvent(ic->stream, split.ev[k], 0));
-                    if (tile_wave && pl.fourbit) LAUNCH(ic, "unnaf_emit", (k_emit_tile_wave<true, 2>), cdiv(t_hi - t_done, 2u), 64, 0, pl.P, (const TileIdx *)(ti + t_done), d_out + t_done * 4096, (u64)(t_hi - t_done));
-                    else if (tile_wave) LAUNCH(ic, "unnaf_emit", (k_emit_tile_wave<false, 2>), cdiv(t_hi - t_done, 2u), 64, 0, pl.P, (const TileIdx *)(ti + t_done), d_out + t_done * 4096, (u64)(t_hi - t_done));
-                    else if (pl.fourbit) LAUNCH(ic, "unnaf_emit", k_emit_tile<true>, (u32)(t_hi - t_done), 256, 0, pl.P, (const TileIdx *)(ti + t_done), d_out + t_done * 4096);
-                    else LAUNCH(ic, "unnaf_emit", k_emit_tile<false>, (u32)(t_hi - t_done), 256, 0, pl.P, (const TileIdx *)(ti + t_done), d_out + t_done * 4096);
+                    emit_tiles(ic, t_done, t_hi);
                     t_done = t_hi;
                 }
                 HIP_TRY(c, hipEventRecord(c->split_ev[ZSPLIT_MAX + 1], ic->stream));
@@ -2135,9 +2139,8 @@ static int unnaf_run(naf_gpu_ctx *c, const u8 *d_naf, size_t naf_len, const naf_
                 // 1.9 instead of 1.1 ms (a realistic genome, 4 GB: 3.16 -> 3.41 ms); a job of flat literals and matches only (the reference's
                 // archive of random bases) is better off with it (4 GB: 2.45 -> 2.31 ms), its kernels in workgroups of 64 as well -- a
                 // workgroup of 256 waits for four wave slots of one CU to be free at once.  NAF_GPU_EMIT_WAVE=0: workgroups of 256 everywhere.
-                const char *ew = ctx_opt(c, "EMIT_WAVE");
                 const bool mixed = flat_job || (zflat.cls && zflat.n_decoded);
-                const bool wave = !(ew && ew[0] == '0') && (!mixed || zflat.n_walk == 0);
+                const bool wave = emit_wave && (!mixed || zflat.n_walk == 0);
                 // (many: about a toggle per tile or more -- a soft-masked genome, not the odd lower-case stretch)
                 if (wave && pl.P.masking && pl.P.n_toggles >= ntiles) { const u32 ch = ((u32)ntiles + 7) / 8; LAUNCH(c, "unnaf_emit_flat", k_emit_tile_flat_wave<1>, ch * 8, 64, 0, pl.P, (const TileIdx *)ti, (const TileFlat *)tsig, d_out, (u64)ntiles, ch); }
                 else if (wave) { const u32 ch = (cdiv(ntiles, 2u) + 7) / 8; LAUNCH(c, "unnaf_emit_flat", k_emit_tile_flat_wave<2>, ch * 8, 64, 0, pl.P, (const TileIdx *)ti, (const TileFlat *)tsig, d_out, (u64)ntiles, ch); }
@@ -2155,12 +2158,7 @@ static int unnaf_run(naf_gpu_ctx *c, const u8 *d_naf, size_t naf_len, const naf_
                     else LAUNCH(xc, "unnaf_emit", k_emit_tile_list<true>, lgrid, 256, 0, pl.P, (const TileIdx *)ti, (const u32 *)list2, (const u32 *)(cnt + 1), d_out);
                 }
             }
-            else if (t_done < ntiles) {
-                if (tile_wave && pl.fourbit) LAUNCH(c, "unnaf_emit", (k_emit_tile_wave<true, 2>), cdiv(ntiles - t_done, 2u), 64, 0, pl.P, (const TileIdx *)(ti + t_done), d_out + t_done * 4096, (u64)(ntiles - t_done));
-                else if (tile_wave) LAUNCH(c, "unnaf_emit", (k_emit_tile_wave<false, 2>), cdiv(ntiles - t_done, 2u), 64, 0, pl.P, (const TileIdx *)(ti + t_done), d_out + t_done * 4096, (u64)(ntiles - t_done));
-                else if (pl.fourbit) LAUNCH(c, "unnaf_emit", k_emit_tile<true>, (u32)(ntiles - t_done), 256, 0, pl.P, (const TileIdx *)(ti + t_done), d_out + t_done * 4096);
-                else LAUNCH(c, "unnaf_emit", k_emit_tile<false>, (u32)(ntiles - t_done), 256, 0, pl.P, (const TileIdx *)(ti + t_done), d_out + t_done * 4096);
-            }
+            else if (t_done < ntiles) emit_tiles(c, t_done, ntiles);
             // tiles holding a header or a record boundary (their number stays on the device)
             const u32 rest_grid = 4u * (u32)(ntiles < EMIT_REST_GRID ? ntiles : EMIT_REST_GRID);      // (quarter tiles: k_emit_rest)
             if (pl.fourbit) LAUNCH(xc, "unnaf_emit_rest", k_emit_rest<true>, rest_grid, 64, 0, pl.P, (const TileIdx *)ti, (const u64 *)tr, (const u32 *)list, (const u32 *)cnt, d_out);

@@ -15,6 +15,7 @@
 //   k_lz_prep/_deps/_exec   sequences executed as dataflow: literals and positions per block, per match the earlier matches its
 //                    source was written by, then units of 1024 sequences sweep over whatever has its sources done
 //                    (k_exec_seq_lds: blocks of at most 16 KiB assembled in LDS, in block order; k_exec_batch / k_exec_seq: cross-checks)
+#include <type_traits>
 #include "ctx.h"
 #include "wgscan.h"
 #include "zstd_dec_core.h"
@@ -3858,7 +3859,574 @@ static int zerr(naf_gpu_ctx *c, u32 e, const char *where)
     return ctx_fail(c, NAF_GPU_EZSTD, "zstd frame %s (%s)", m, where);
 }
 
-// Decode ONE frame whose header (after the magic) starts at d_src[0].  *consumed = bytes of the frame.
+// ---- the frame driver ------------------------------------------------------------------------------------------------
+// What the phases of zstd_decode_one share.  Plain data: the job a mostly-flat frame leaves for later keeps a copy of it (FlatJob).
+struct ZFrame {
+    naf_gpu_ctx *c; const u8 *src; size_t src_len; u8 *dst; size_t dst_cap; size_t *out_len, *consumed; ZRange *rg; const EmitP *fuse; u8 *text;
+    ZFrameHdr fh; u8 hb[18]; size_t hl;                           // the parsed header, and the frame's first bytes it was parsed from
+    u32 always_table, spec_min; bool uni_wanted;                  // options, read once
+    ZStat *st, hs; ZBlock *blk; u32 nblk, g;                      // the device's counters and their last read-back; block table; cdiv(nblk, 64)
+    i32 *own_huf, *own_ll, *own_of, *own_ml; u64 *seq_cnt, *sizes, *d_total_out; u32 n_seq_blk, n_huf_def, max_seq_regen;
+    u8 *huf_pool; u32 pool_cap; bool spec, lit_only_spec, tables_built, ranged_build, two_phase, have_ends;
+    u64 h4[5], hends[ZSPLIT_MAX];                                 // what the speculative continuation read back: block range, part ends
+    FseE *fse_pool; u32 *o_ll, *o_ml, *o_of, *seq_list; u64 *seq_rank;      // seq_list: the blocks that have sequences, in order; seq_rank: such blocks in front of block i
+    u32 b_first, b_count, huf_first, seq_t0, seq_t1; u64 bias; u32 *done; u8 *lit_scratch;      // the blocks to decode; among them seq_list[seq_t0 .. seq_t1)
+};
+static_assert(std::is_trivially_copyable<ZFrame>::value, "ZFrame is copied into the deferred job");
+#define Z_HANDED 1      // a phase's return: the frame was handed to the caller to be read in place, nothing more to do
+// The kernel templates the driver launches, named once: the compiler lays device code out in the order templates are first used, and this
+// keeps that layout -- the device code, byte for byte -- whatever the order of the host functions below.
+[[maybe_unused]] static const void *const driver_kernels[] = { (const void *)k_spec_walk<false>, (const void *)k_spec_walk<true>, (const void *)k_copy_fill<64>, (const void *)k_flat_literals<64>,
+    (const void *)k_huf_literals<false>, (const void *)k_huf_literals<true>, (const void *)k_copy_fill<256>, (const void *)k_flat_literals<256>, (const void *)k_huf_literals<false, true> };
+
+// ---- launches and hand-off shared by the phases
+// The literals of blocks [lo, hi): k_flat_literals for the blocks under a flat tree; for the others k_huf_par, or the workgroups with
+// ONE table in LDS and the plain kernel behind them for what they left (`redo`), or the plain kernel alone.
+struct LitPlan { u8 *dst, *lits; const u8 *cls; u8 *redo; bool wide, serial;     // wide: workgroups of 256 for the flat blocks (the deferred job: 64)
+                 u32 flat_on, plog, slot, ipitch, generic, pending; };           // generic: the HUF_GENERIC bit of the row pitch argument
+static int launch_literals(naf_gpu_ctx *c, const ZFrame &F, u32 lo, u32 hi, const LitPlan &p)
+{
+    if (hi <= lo) return 0;
+    const u32 n = hi - lo, huf_lds = p.slot * HUF_BLOCKS_PER_WG + 64 * p.ipitch + 64 * HUF_OROW + 512;
+    const ZBlock *blk = F.blk; const i32 *own_huf = F.own_huf; const u8 *pool = F.huf_pool;
+    EmitP ep; memset(&ep, 0, sizeof ep);
+    if (p.flat_on && !p.wide) LAUNCH(c, "zstd_flat_literals", k_flat_literals<64>, 4 * n, 64, 0, F.src, blk, hi, own_huf, pool, p.dst, p.lits, F.st, lo, p.cls);
+    else if (p.flat_on) LAUNCH(c, "zstd_flat_literals", k_flat_literals<256>, n, 256, 0, F.src, blk, hi, own_huf, pool, p.dst, p.lits, F.st, lo, p.cls);
+    if (p.serial && p.plog)        // (k_huf_par builds the tables it lacks itself, a workgroup at a time, in LDS: `pending`)
+        LAUNCH(c, "zstd_huf_literals", k_huf_par, cdiv((u64)n << (p.plog + 2), 64), 64, (p.plog >= 4 ? 1u : 16u >> p.plog) * p.slot,
+               F.src, blk, hi, own_huf, pool, p.slot, p.dst, p.lits, F.st, lo, p.plog, p.cls, p.flat_on, huf_par_margin_env(c), p.pending, (u64)F.src_len);
+    else if (p.serial) {
+        if (p.redo) LAUNCH(c, "zstd_huf_literals", (k_huf_literals<false, true>), cdiv(n, HUF_BLOCKS_PER_WG), 64, huf_lds - p.slot * (HUF_BLOCKS_PER_WG - 1u),
+               F.src, blk, hi, own_huf, pool, p.slot, p.dst, p.lits, F.st, lo, ep, (u8 *)nullptr, p.ipitch | p.generic, (u64)F.src_len, p.flat_on, p.cls, p.redo);
+        LAUNCH(c, "zstd_huf_literals", (k_huf_literals<false>), cdiv(n, HUF_BLOCKS_PER_WG), 64, huf_lds,
+               F.src, blk, hi, own_huf, pool, p.slot, p.dst, p.lits, F.st, lo, ep, (u8 *)nullptr, p.ipitch | p.generic, (u64)F.src_len, p.flat_on, p.redo ? (const u8 *)p.redo : p.cls);
+    }
+    return 0;
+}
+// The sequence executor over `nx` blocks of `list`: blocks that fit LDS there (NAF_GPU_EXEC_LDS=0: always the HBM executor, the cross-check).
+static int launch_exec(naf_gpu_ctx *c, const ZFrame &F, const u32 *list, u32 nx, const u8 *lits, u8 *dst, u32 *done)
+{
+    const u32 cap = (F.max_seq_regen + 1023u) & ~1023u;
+    if (F.max_seq_regen > EXEC_LDS || ctx_opt_is(c, "EXEC_LDS", '0'))
+        return launch_lz_exec(c, (const ZBlock *)F.blk, list, nx, (const u64 *)F.sizes, (const u64 *)F.seq_cnt, F.nblk, F.hs.total_seq, F.o_ll, F.o_ml, F.o_of, lits, dst, done, F.st);
+    LAUNCH(c, "zstd_exec_seq", k_exec_seq_lds, nx, 64, cap + 64u + 2u * EXEC_PJ_MAX, (const ZBlock *)F.blk, list, nx, (const u64 *)F.sizes, F.nblk,
+           (const u32 *)F.o_ll, (const u32 *)F.o_ml, (const u32 *)F.o_of, lits, dst, done, F.st, cap);
+    return 0;
+}
+// The tables the first phase of a two-phase build left out (spec_continuation), and the counters behind them.
+static int build_huf_rest(naf_gpu_ctx *c, const ZFrame &F, ZStat *hs)
+{
+    int rc = launch_build_huf(c, F.nblk, F.src, F.blk, F.nblk, F.huf_pool, F.pool_cap, F.st, 0u, (const u64 *)nullptr, 0u, (const i32 *)F.own_huf, 1u, 2u);
+    if (rc || (rc = ctx_readback(c, hs, F.st, sizeof *hs))) return rc;
+    return hs->err ? zerr(c, hs->err, "Huffman tables") : 0;
+}
+// First block of part k + 1 of a split decode of n blocks (ctx.h: ZSplit); the last part ends with the blocks.
+static u32 split_part_end(u32 n, int parts, int k) { return k + 1 == parts ? n : (u32)((u64)n * (k + 1) / parts) & ~(HUF_BLOCKS_PER_WG - 1u); }
+
+// Hands a frame that is read in place to the caller: the ONLY code that writes the ZFlat the caller left in c->zflat, and the end of such a call -- the
+// frame's length with its checksum, the output's length, the content size.  last_raw: the final Raw or (bit 31) RLE block's size where the frame has one
+// behind its flat blocks, else 0.  mixed: a mostly-flat frame's class table, counts and job; the other exits leave those as the caller zeroed them.
+struct FlatMixed { const u8 *cls; u32 n_decoded, n_walk; void *later; };
+static int flat_handoff(const ZFrame &F, const FlatStream *si, u64 nslots, const u8 *sym, u64 end_off, u64 total_out, u32 last_raw, const FlatMixed *mixed)
+{
+    naf_gpu_ctx *c = F.c; ZFlat *zf = c->zflat;
+    if (mixed) { zf->cls = mixed->cls; zf->n_decoded = mixed->n_decoded; zf->n_walk = mixed->n_walk; zf->decoded_ev = nullptr; zf->later = mixed->later; }      // (first: from here the job is the caller's to run or drop)
+    const size_t frame_end = end_off + (F.fh.checksum ? 4 : 0);
+    if (frame_end > F.src_len) return zerr(c, ZE_TRUNC, "checksum");
+    *F.consumed = frame_end;
+    const u32 tn = last_raw & 0x7FFFFFFFu; const bool rle = (last_raw >> 31) != 0;       // an RLE block stores one byte
+    zf->src = F.src; zf->si = si; zf->nslots = nslots; zf->sym = sym; zf->status = F.st; zf->ready = true;
+    zf->tail = last_raw ? F.src + (end_off - (rle ? 1u : tn)) : nullptr; zf->tail_q = total_out - (last_raw ? tn : 0u);
+    zf->tail_n = last_raw ? (rle ? tn | 0x80000000u : tn) : 0u;
+    if (F.rg) { F.rg->got_lo = 0; F.rg->got_hi = total_out; F.rg->ranged = false; }      // nothing was decoded: the emit kernel finds any byte of the stream itself
+    *F.out_len = total_out;
+    if (F.fh.has_fcs && F.fh.content_size != total_out) return zerr(c, ZE_CORRUPT, "content size mismatch");
+    return Z_HANDED;
+}
+
+// ---- block index: stride index (with the uniform and runs exits), speculative index, serial walk.  (The frame's first block header: where fh.hdr_size + 3 <= hl.)
+static u32 first_block_header(const ZFrame &F) { const u8 *p = F.hb + F.fh.hdr_size; return (u32)p[0] | ((u32)p[1] << 8) | ((u32)p[2] << 16); }
+struct SpecIdx { u32 chunk, win1, win2, nchunks; u64 *first, *land, *G, *start, *cnt; };
+// Frames of more than 4 MiB: 1 MiB chunks, candidates in the first 40 KiB / 128 KiB of each.  Smaller frames can still hold
+// thousands of tiny blocks (ids / names / lengths that compress 100:1 in 16 KiB blocks, a mask stream that is 1200 RLE blocks
+// of 4 bytes -- a serial walk of those costs milliseconds): small chunks with every byte tested as a candidate.  The chunk size changes nothing but how much of
+// the speculation is reused: the resolve pass re-walks from the true start wherever a chunk's candidate was wrong or missing.
+static void spec_geometry(const ZFrame &F, SpecIdx &X)
+{
+    X.chunk = SPEC_CHUNK; X.win1 = SPEC_WINDOW1; X.win2 = SPEC_WINDOW;
+    if (F.src_len <= 4ull * SPEC_CHUNK) {                        // about 128 chunks of 256 B .. 16 KiB, every byte a candidate
+        X.chunk = 256; while (X.chunk < SPEC_CHUNK_SMALL && (u64)X.chunk * 128 < F.src_len) X.chunk *= 2;
+        X.win1 = X.win2 = X.chunk;
+    } else if (F.src_len <= 256ull * SPEC_CHUNK && F.fh.hdr_size + 3 <= F.hl) {
+        // In between (a soft-masked genome's mask: 11 MB of 5 KB blocks): a chunk is walked by one lane, block after block, and 1 MiB
+        // of small blocks is a long walk for eleven lanes.  The frame's first block says what to expect: chunks of about sixteen
+        // such blocks (never wrong, only more or less of the speculation reused).
+        const u32 h0 = first_block_header(F);
+        const u32 b0 = ((h0 >> 1) & 3) == 1 ? 4u : (h0 >> 3) + 3;     // bytes of the first block (an RLE block stores one byte)
+        u32 want = SPEC_CHUNK_SMALL; while (want < SPEC_CHUNK && want < 16 * b0) want *= 2;
+        if (want < SPEC_CHUNK) { X.chunk = want; if (X.win1 > X.chunk) X.win1 = X.chunk; if (X.win2 > X.chunk) X.win2 = X.chunk; }
+    }
+    X.nchunks = (u32)((F.src_len + X.chunk - 1) / X.chunk);
+}
+// Runs of equal blocks (the sharded encoder's frames) behind a stride index that found more than one block size: Z_HANDED when the emit can read them in place.
+static int index_stride_runs(ZFrame &F, u32 S, u32 h0, u32 nmax, const u32 *sres)
+{
+    naf_gpu_ctx *c = F.c; int rc; const u8 *d_src = F.src;
+    UniRuns *R = arena_new<UniRuns>(c, 1); ZBlock *odd = arena_new<ZBlock>(c, STRIDE_TAIL + 1), *ublk0 = arena_new<ZBlock>(c, 1);
+    u32 *probe = arena_new<u32>(c, 2); UniInfo *U2 = arena_new<UniInfo>(c, 1);
+    FlatStream *usi2 = arena_new<FlatStream>(c, 4 * ((size_t)nmax + USEG_MAX) + 1); u8 *usym2 = (u8 *)arena_alloc(c, 16);
+    if (!R || !odd || !ublk0 || !probe || !U2 || !usi2 || !usym2) return NAF_GPU_ENOMEM;
+    for (u32 r = 0; r <= URUN_MAX; r++) {
+        LAUNCH(c, "zstd_index_stride", k_runs_next, 1, 64, 0, d_src, (u64)F.src_len, (u64)F.fh.hdr_size, S, h0, sres, R, odd, probe, r == 0 ? 1 : 0);
+        if (r < URUN_MAX) LAUNCH(c, "zstd_index_stride", k_runs_probe, cdiv(nmax, 256), 256, 0, d_src, (u64)F.src_len, S, h0, (const UniRuns *)R, probe);
+    }
+    LAUNCH(c, "zstd_flat_uniform", k_uni_head_runs, 1, 64, 0, d_src, (u64)F.fh.hdr_size, h0, R, odd, U2, ublk0, F.spec_min);
+    LAUNCH(c, "zstd_flat_uniform", k_uni_streams_runs, cdiv(4ull * ((u64)nmax + USEG_MAX) + 1, 256) + 1, 256, 0, d_src, S, (const UniRuns *)R, (const ZBlock *)odd, (const ZBlock *)ublk0, U2, usi2, usym2);
+    UniInfo hu2; memset(&hu2, 0, sizeof hu2);
+    if ((rc = ctx_readback(c, &hu2, U2, sizeof hu2))) return rc;
+    if (ctx_tracing(c)) ctx_trace(c, "[runs?] ok %u bad %u first run %u blocks %u huffman %u total %llu\n", hu2.ok, hu2.bad, hu2.np, hu2.nblk, hu2.nhb, (unsigned long long)hu2.total_out);
+    if (!(hu2.ok && !hu2.bad)) return 0;
+    return flat_handoff(F, usi2, 4ull * hu2.nhb, usym2, hu2.end_off, hu2.total_out, hu2.last_raw, nullptr);
+}
+// The stride index (frames of more than 4 MiB whose first block is a compressed one that is not the last): three launches and a read-back; a frame it cannot take costs
+// that read-back before the speculative index starts.  Leaves F.blk where every block repeats the first one's size; Z_HANDED for a uniform flat frame and for runs.
+static int index_stride(ZFrame &F, const SpecIdx &X)
+{
+    naf_gpu_ctx *c = F.c; int rc; const u8 *d_src = F.src; const size_t src_len = F.src_len; const ZFrameHdr &fh = F.fh; ZStat *st = F.st;
+    if (ctx_tracing(c)) ctx_trace(c, "[stride?] len %zu hdr %u hl %zu first %02x %02x %02x\n", src_len, fh.hdr_size, F.hl, F.hb[fh.hdr_size], F.hb[fh.hdr_size + 1], F.hb[fh.hdr_size + 2]);
+    if (!(src_len > 4ull * SPEC_CHUNK && fh.hdr_size + 3 <= F.hl) || ctx_opt_is(c, "STRIDE_INDEX", '0')) return 0;
+    const u32 h0 = first_block_header(F), S = 3 + (h0 >> 3);
+    const u64 nmax64 = (src_len - fh.hdr_size) / S;
+    if (!(((h0 >> 1) & 3) == BT_COMP && !(h0 & 1) && (h0 >> 3) <= ZBLOCK_MAX && S >= 256 && nmax64 >= 64 && nmax64 < 0x7FFFFF00ull)) return 0;
+    const u32 nmax = (u32)nmax64;
+    u32 *sres = (u32 *)(X.cnt + X.nchunks + 2); ZBlock *sblk = arena_new<ZBlock>(c, (size_t)nmax + STRIDE_TAIL);
+    if (!sblk) return NAF_GPU_ENOMEM;
+    HIP_TRY(c, hipMemsetAsync(sres, 0xFF, 8, c->stream));
+    LAUNCH(c, "zstd_index_stride", k_stride_probe, cdiv(nmax, 256), 256, 0, d_src, (u64)src_len, (u64)fh.hdr_size, S, h0, nmax, sres);
+    LAUNCH(c, "zstd_index_stride", k_stride_tail, 1, 64, 0, d_src, (u64)src_len, (u64)fh.hdr_size, S, nmax, sres, sblk, st);
+    // a uniform flat frame (k_uni_head) needs nothing of what follows: its stream table is made here, beside the verdict
+    UniInfo *U = nullptr; FlatStream *usi = nullptr; u8 *usym = nullptr;
+    if (F.uni_wanted) {
+        U = arena_new<UniInfo>(c, 1); ZBlock *ublk = arena_new<ZBlock>(c, STRIDE_TAIL + 1);
+        usi = arena_new<FlatStream>(c, 4 * ((size_t)nmax + STRIDE_TAIL) + 1); usym = (u8 *)arena_alloc(c, 16);
+        if (!U || !ublk || !usi || !usym) return NAF_GPU_ENOMEM;
+        LAUNCH(c, "zstd_flat_uniform", k_uni_head, 1, 64, 0, d_src, (u64)fh.hdr_size, S, h0, nmax, (const u32 *)sres, (const ZBlock *)sblk, (const ZStat *)st, U, ublk, F.spec_min);
+        LAUNCH(c, "zstd_flat_uniform", k_uni_streams, cdiv(4ull * ((u64)nmax + STRIDE_TAIL) + 1, 256) + 1, 256, 0, d_src, (u64)fh.hdr_size, S, (const ZBlock *)ublk, U, usi, usym);
+    }
+    LAUNCH(c, "zstd_index_stride", k_stride_write, cdiv(nmax, 256), 256, 0, (u64)fh.hdr_size, S, h0, (const u32 *)sres, sblk, (const u32 *)U);
+    u32 res2[2] = { 0, 0 }; UniInfo hu; memset(&hu, 0, sizeof hu); ZStat &hs = F.hs;
+    if (U) { void *hp[3] = { &hs, res2, &hu }; const void *dp[3] = { st, sres, U }; const size_t nb[3] = { sizeof hs, 8, sizeof hu }; rc = ctx_readbackv(c, 3, hp, dp, nb); }
+    else rc = ctx_readback2(c, &hs, st, sizeof hs, res2, sres, 8);
+    if (rc) return rc;
+    if (ctx_tracing(c)) ctx_trace(c, "[stride] len %zu S %u nmax %u prefix %u verdict %u err %u nblk %u\n", src_len, S, nmax, res2[0], res2[1], hs.err, hs.nblk);
+    if (ctx_tracing(c) && U) ctx_trace(c, "[uniform?] ok %u bad %u prefix %u blocks %u huffman %u regen %u total %llu\n", hu.ok, hu.bad, hu.np, hu.nblk, hu.nhb, hu.regen0, (unsigned long long)hu.total_out);
+    // every block repeats the first: the caller's emit kernel reads the streams in place (as an all-flat frame's, without the block table)
+    if (res2[1] == 1u && !hs.err && hs.nblk && hu.ok && !hu.bad) return flat_handoff(F, usi, 4ull * hu.nhb, usym, hs.end_off, hu.total_out, hu.last_raw, nullptr);
+    if (res2[1] == 1u && !hs.err && hs.nblk) F.blk = sblk;
+    // NAF_GPU_STRIDE_RUNS=0: the universal front, as before
+    if (res2[1] == 2u && !hs.err && F.uni_wanted && !ctx_opt_is(c, "STRIDE_RUNS", '0')) return index_stride_runs(F, S, h0, nmax, sres);
+    return 0;
+}
+// The speculative index: candidates for the first block start of every chunk, resolved into the true chain, counted, written (F.blk).
+static int index_speculative(ZFrame &F, const SpecIdx &X)
+{
+    naf_gpu_ctx *c = F.c; int rc; const u8 *d_src = F.src; const u64 len = (u64)F.src_len; ZStat *st = F.st;
+    const u32 nchunks = X.nchunks, chunk = X.chunk, win1 = X.win1, win2 = X.win2, gl = cdiv(nchunks, 64);
+    u64 *first = X.first, *land = X.land, *G = X.G, *start = X.start, *cnt = X.cnt; const u32 *skip = nullptr;
+    // the first block start of a chunk lies in its first 20 KiB whenever blocks compress to less than that (this build's 32 KiB
+    // blocks of packed bases: 16 KiB); the passes behind it only run for the chunks still without a candidate
+    const u32 win0 = chunk == SPEC_CHUNK ? SPEC_WINDOW0 : win1;
+    LAUNCH(c, "zstd_index_find", k_spec_find, cdiv(win0, 256 * 16) * (nchunks - 1), 256, 0, d_src, len, nchunks, first, 0u, win0, chunk, skip);
+    if (win1 > win0) LAUNCH(c, "zstd_index_find2", k_spec_find, cdiv(win1 - win0, 256 * 16) * (nchunks - 1), 256, 0, d_src, len, nchunks, first, win0, win1, chunk, skip);
+    if (win2 > win1) LAUNCH(c, "zstd_index_find2", k_spec_find, cdiv(win2 - win1, 256 * 16) * (nchunks - 1), 256, 0, d_src, len, nchunks, first, win1, win2, chunk, skip);
+    LAUNCH(c, "zstd_index_land", k_spec_land, gl, 64, 0, d_src, len, (const u64 *)first, nchunks, land, chunk, skip);
+    LAUNCH(c, "zstd_index_land2", k_spec_land2, gl, 64, 0, d_src, len, (const u64 *)first, (const u64 *)land, nchunks, G, chunk, skip);
+    LAUNCH(c, "zstd_index_resolve", k_spec_resolve, 1, 64, 0, d_src, len, (const u64 *)land, (const u64 *)G, nchunks, start, st, chunk, skip);
+    LAUNCH(c, "zstd_index_count", (k_spec_walk<false>), gl, 64, 0, d_src, len, (const u64 *)start, nchunks, cnt, (ZBlock *)nullptr, st, skip);
+    u64 *d_tot = cnt + nchunks + 1, tot = 0;
+    if ((rc = scan_exclusive_u64(c, cnt, nchunks, d_tot))) return rc;
+    if ((rc = ctx_readback2(c, &F.hs, st, sizeof F.hs, &tot, d_tot, 8))) return rc;
+    if (!F.hs.err && tot > 0 && tot < 0x7FFFFFFFull) {
+        if (!(F.blk = arena_new<ZBlock>(c, tot))) return NAF_GPU_ENOMEM;
+        LAUNCH(c, "zstd_index_write", (k_spec_walk<true>), gl, 64, 0, d_src, len, (const u64 *)start, nchunks, cnt, F.blk, st, (const u32 *)nullptr);
+        F.hs.nblk = (u32)tot;
+    } else HIP_TRY(c, hipMemsetAsync(st, 0, sizeof(ZStat), c->stream));     // not one well-formed frame for the parallel walk: serial walk decides
+    return 0;
+}
+// The parallel indexes: what both need, then the stride index and, for a frame that one does not take, the speculative index.
+static int index_parallel(ZFrame &F)
+{
+    naf_gpu_ctx *c = F.c; int rc; SpecIdx X; spec_geometry(F, X);
+    const u32 nchunks = X.nchunks;
+    X.first = arena_new<u64>(c, nchunks + 1); X.land = arena_new<u64>(c, nchunks + 2); X.G = arena_new<u64>(c, nchunks + 1);
+    X.start = arena_new<u64>(c, nchunks + 2); X.cnt = arena_new<u64>(c, (size_t)nchunks + 4);      // (+ the scan's total and the stride index's verdict behind it)
+    if (!X.first || !X.land || !X.G || !X.start || !X.cnt) return NAF_GPU_ENOMEM;
+    HIP_TRY(c, hipMemsetAsync(X.first, 0xFF, (size_t)nchunks * 8, c->stream));
+    u64 *h0 = (u64 *)c->h_stage; *h0 = F.fh.hdr_size;
+    HIP_TRY(c, hipMemcpyAsync(X.first, h0, 8, hipMemcpyHostToDevice, c->stream));
+    if ((rc = index_stride(F, X)) || F.blk) return rc;
+    return index_speculative(F, X);
+}
+// The serial walk of the block headers: frames too small for the parallel indexes, or not one well-formed chain.
+static int index_serial(ZFrame &F)
+{
+    naf_gpu_ctx *c = F.c; int rc;
+    u32 cap = (u32)(F.src_len / 16 + 1024);                       // one pass for anything but pathological runs of empty blocks
+    for (int attempt = 0; attempt < 2; attempt++) {
+        if (!(F.blk = arena_new<ZBlock>(c, cap))) return NAF_GPU_ENOMEM;
+        const u32 win = F.src_len < SCAN_WIN ? (u32)((F.src_len + 15) & ~15ull) + 16 : SCAN_WIN;
+        LAUNCH(c, "zstd_scan_blocks", k_scan_blocks, 1, 64, win + 16, F.src, (u64)F.src_len, (u64)F.fh.hdr_size, F.blk, cap, F.st, win);
+        if ((rc = ctx_readback(c, &F.hs, F.st, sizeof F.hs))) return rc;
+        if (F.hs.err) return zerr(c, F.hs.err, "block headers");
+        if (F.hs.nblk <= cap) break;
+        cap = F.hs.nblk;
+    }
+    return 0;
+}
+// ---- parse and ownership
+// Speculative continuation.  Most frames that are long enough to matter are literal-only (this build's own sequence, mask and
+// quality streams); for those nothing below needs the host: block sizes are final after the parse, so offsets, the block range
+// of a byte-range request, the Huffman tables and the part boundaries of a split decode are queued right away and the counters
+// come back in ONE read-back.  A frame that does have sequences then takes the long way from here (its tables are kept).
+static int spec_continuation(ZFrame &F)
+{
+    naf_gpu_ctx *c = F.c; int rc; const u8 *d_src = F.src; ZBlock *blk = F.blk; const u32 nblk = F.nblk; ZStat *st = F.st; ZRange *rg = F.rg;
+    u64 *r4 = nullptr; bool late_build = false;
+    if ((rc = scan_exclusive_u64(c, F.sizes, nblk, F.d_total_out))) return rc;
+    u64 *extra = arena_new<u64>(c, 8 + ZSPLIT_MAX); if (!extra) return NAF_GPU_ENOMEM;
+    if (rg && rg->want_hi > rg->want_lo) {
+        r4 = extra;
+        LAUNCH(c, "zstd_find_range", k_find_range, 1, 64, 0, (const u64 *)F.sizes, nblk, (const u64 *)F.d_total_out, rg->want_lo, rg->want_hi, (const i32 *)F.own_huf, r4);
+        F.ranged_build = true;
+    }
+    const u64 want_pool = (u64)nblk * HUF_TAB_MAX + 4096;
+    F.pool_cap = want_pool > 0xFFFFF000ull ? 0xFFFFF000u : (u32)want_pool;
+    if (!(F.huf_pool = (u8 *)arena_alloc(c, F.pool_cap))) return NAF_GPU_ENOMEM;
+    if (nblk <= 16384) {
+        // a stream of a few thousand blocks (a soft-masked genome's mask: a tree per block): a wavefront per block, all at once --
+        // one lane per tree (k_build_huf) is 0.35 ms of serial table building in front of the literals there
+        LAUNCH(c, "zstd_build_huf", k_build_huf_lds, nblk, 64, 0, d_src, blk, nblk, F.huf_pool, F.pool_cap, st, 0u, (const i32 *)F.own_huf);
+    } else {
+        LAUNCH(c, "zstd_build_huf", k_build_huf_few, 1024, 64, 0, d_src, blk, nblk, F.huf_pool, F.pool_cap, st, (const u64 *)r4, (const i32 *)F.own_huf);
+        // (a caller that can read flat blocks in place gets the flat trees recognised now and the other tables later: build_huf_rest)
+        F.two_phase = c->zflat && !rg && !F.always_table;
+        if (F.two_phase) LAUNCH(c, "zstd_build_huf", k_flat_find_main, FIND_MAIN_TREES, 64, 0, d_src, blk, nblk, F.huf_pool, F.pool_cap, st, (const i32 *)F.own_huf);
+        else late_build = true;
+        // (the group builder for frames of MANY distinct trees is queued once the counters say there are that many: its workgroups hold
+        // 64 KB of LDS each, and beside a Huffman walk of another stream -- which fills every CU's LDS -- even workgroups that find
+        // nothing to do waited a millisecond to start: a FASTQ's sequence frame, one tree, behind its quality frame's walk)
+    }
+    ZSplit *sp = c->zsplit;
+    if (sp && !rg && sp->parts >= 2) {
+        F.have_ends = true;
+        for (int k = 0; k + 1 < sp->parts; k++)
+            HIP_TRY(c, hipMemcpyAsync(extra + 8 + k, F.sizes + split_part_end(nblk, sp->parts, k), 8, hipMemcpyDeviceToDevice, c->stream));
+    }
+    u64 hx[8 + ZSPLIT_MAX];
+    if ((rc = ctx_readback2(c, &F.hs, st, sizeof F.hs, hx, extra, sizeof hx))) return rc;
+    memcpy(F.h4, hx, sizeof F.h4); memcpy(F.hends, hx + 8, sizeof F.hends);
+    if (late_build && !F.hs.err && F.hs.n_huf_distinct > HUF_FEW &&
+        ((rc = launch_build_huf(c, nblk, d_src, blk, nblk, F.huf_pool, F.pool_cap, st, 0u, (const u64 *)r4, F.always_table, (const i32 *)F.own_huf, 1u, 0u)) || (rc = ctx_readback(c, &F.hs, st, sizeof F.hs)))) return rc;
+    F.tables_built = true;
+    return 0;
+}
+static int parse_ownership(ZFrame &F)
+{
+    naf_gpu_ctx *c = F.c; int rc; const u32 nblk = F.nblk, g = F.g; ZStat *st = F.st;
+    i32 *own = arena_new<i32>(c, (size_t)nblk * 4);
+    F.seq_cnt = arena_new<u64>(c, (size_t)nblk + 1); F.sizes = arena_new<u64>(c, (size_t)nblk + 1);
+    if (!own || !F.seq_cnt || !F.sizes) return NAF_GPU_ENOMEM;
+    F.own_huf = own; F.own_ll = own + nblk; F.own_of = own + 2 * (size_t)nblk; F.own_ml = own + 3 * (size_t)nblk;
+    LAUNCH(c, "zstd_parse_blocks", k_parse_blocks, g, 64, 0, F.src, F.blk, nblk, F.own_huf, F.own_ll, F.own_of, F.own_ml, F.seq_cnt, F.sizes, st);
+    LAUNCH(c, "zstd_huf_dedup", k_huf_dedup, g, 64, 0, F.src, (const ZBlock *)F.blk, nblk, F.own_huf, st);
+    if ((rc = scan_inclusive_max_i32(c, F.own_huf, nblk))) return rc;
+    F.d_total_out = (u64 *)((u8 *)st + offsetof(ZStat, total_out));
+    F.spec = nblk > F.spec_min && !F.fuse;
+    if (F.spec) rc = spec_continuation(F);
+    else rc = ctx_readback(c, &F.hs, st, sizeof F.hs);
+    if (rc) return rc;
+    if (F.hs.err) return zerr(c, F.hs.err, "block parse");
+    F.n_seq_blk = F.hs.n_seq_blk; F.n_huf_def = F.hs.n_huf_def;
+    // fused decode+emit needs every block to be a literal-only Huffman block
+    if (F.fuse && !(F.n_seq_blk == 0 && F.hs.n_plain_huf == nblk && nblk > 0)) return ZSTD_NEED_TWO_PASS;
+    F.lit_only_spec = F.spec && F.n_seq_blk == 0;
+    if (F.spec && F.n_seq_blk && F.ranged_build) {
+        // the block range was worked out from sizes that sequences will change: forget those tables
+        F.tables_built = false;
+        for (size_t o : { offsetof(ZStat, huf_pool_used), offsetof(ZStat, max_huf_log), offsetof(ZStat, n_flat), offsetof(ZStat, n_huf_built) })
+            HIP_TRY(c, hipMemsetAsync((u8 *)st + o, 0, 4, c->stream));
+    }
+    return 0;
+}
+// ---- the in-place exits behind the parse
+// Every block a plain Huffman block of the same flat 4-bit tree: the caller's emit kernel reads the streams in place.
+// (A final Raw block is allowed: this build's encoder puts the byte with the padding nibble of an odd stream there, so that it does
+// not bring a seventeenth symbol into the last Huffman block.)
+static int exit_all_flat(ZFrame &F)
+{
+    naf_gpu_ctx *c = F.c; const ZStat &hs = F.hs; const u32 nblk = F.nblk;
+    const bool flat_tail = hs.last_raw != 0 && nblk >= 2 && hs.n_plain_huf == nblk - 1;
+    if (ctx_tracing(c) && c->zflat) ctx_trace(c, "[flat?] spec %d nblk %u seq_blk %u distinct %u built %u n_flat %u log %u plain %u last_raw %u always %u\n", (int)F.spec, nblk, F.n_seq_blk, hs.n_huf_distinct, hs.n_huf_built, hs.n_flat, hs.max_huf_log, hs.n_plain_huf, hs.last_raw, F.always_table);
+    if (!(c->zflat && F.lit_only_spec && nblk > 0 && hs.n_huf_distinct == 1 && hs.n_huf_built == 1 && hs.n_flat == 1 && hs.max_huf_log == 4 && (hs.n_plain_huf == nblk || flat_tail) && !F.always_table)) return 0;
+    const u32 nhb = flat_tail ? nblk - 1 : nblk;                  // the Huffman blocks
+    FlatStream *si = arena_new<FlatStream>(c, 4 * (size_t)nhb + 1); u8 *d_sym = (u8 *)arena_alloc(c, 16);
+    if (!si || !d_sym) return NAF_GPU_ENOMEM;
+    LAUNCH(c, "zstd_set_offsets", k_set_offsets, F.g, 64, 0, F.blk, nblk, (const u64 *)F.sizes, (u32 *)nullptr, (u32 *)nullptr, (u32 *)nullptr);
+    LAUNCH(c, "zstd_flat_streams", k_flat_streams, cdiv(4ull * nhb, 256), 256, 0, F.src, (const ZBlock *)F.blk, nhb, (const i32 *)F.own_huf, (const u8 *)F.huf_pool, si, d_sym, F.st, (const u64 *)F.d_total_out, flat_tail ? (u64)(hs.last_raw & 0x7FFFFFFFu) : 0ull);
+    return flat_handoff(F, si, 4ull * nhb, d_sym, hs.end_off, hs.total_out, flat_tail ? hs.last_raw : 0u, nullptr);
+}
+// The classification of a mostly-flat frame (ctx.h: ZFlat, `cls`): which blocks are read in place, which are decoded -- the blocks
+// that are not flat and their neighbours, and with_sequences the blocks with matches and the blocks those copy from (k_seq_sources).
+struct FlatClass { FlatStream *si; u8 *sym, *cls, *lits; u32 *done2; u32 n_dec, n_walk; };
+static int flat_classify(ZFrame &F, bool with_sequences, FlatClass &K)
+{
+    naf_gpu_ctx *c = F.c; int rc; const u32 nblk = F.nblk, g = F.g, main = 0xFFFFFFFFu - F.hs.flat_main_inv;
+    K.si = arena_new<FlatStream>(c, 4 * (size_t)nblk + 1); K.sym = (u8 *)arena_alloc(c, 16);
+    u8 *cls0 = (u8 *)arena_alloc(c, nblk); K.cls = (u8 *)arena_alloc(c, nblk); u32 *d_nx = arena_new<u32>(c, 2);
+    K.done2 = with_sequences ? arena_new<u32>(c, nblk) : nullptr; K.lits = with_sequences ? (u8 *)arena_alloc(c, F.hs.total_out + 16) : nullptr;
+    if (!K.si || !K.sym || !cls0 || !K.cls || !d_nx || (with_sequences && (!K.done2 || !K.lits))) return NAF_GPU_ENOMEM;
+    HIP_TRY(c, hipMemsetAsync(d_nx, 0, 8, c->stream));
+    LAUNCH(c, "zstd_set_offsets", k_set_offsets, g, 64, 0, F.blk, nblk, (const u64 *)F.sizes, K.done2, (u32 *)nullptr, (u32 *)nullptr);
+    // (with sequences every table has been built by now, whatever the first phase left out)
+    LAUNCH(c, "zstd_flat_class", k_flat_mark_owner, g, 64, 0, F.src, F.blk, nblk, (const i32 *)F.own_huf, main, !with_sequences && F.two_phase ? 1u : 0u);
+    LAUNCH(c, "zstd_flat_class", k_flat_sym, 1, 256, 0, F.src, (const ZBlock *)F.blk, main, (const u8 *)F.huf_pool, K.sym);
+    LAUNCH(c, "zstd_flat_class", k_flat_class, g, 64, 0, (const ZBlock *)F.blk, nblk, (const i32 *)F.own_huf, cls0, d_nx + 1);
+    if (with_sequences) LAUNCH(c, "zstd_flat_class", k_seq_sources, cdiv(F.n_seq_blk, 64), 64, 0, (const ZBlock *)F.blk, (const u32 *)F.seq_list, F.n_seq_blk, (const u64 *)F.sizes, (const u32 *)F.o_ll, (const u32 *)F.o_ml, (const u32 *)F.o_of, cls0);
+    LAUNCH(c, "zstd_flat_class", k_flat_class2, g, 64, 0, (const u8 *)cls0, nblk, K.cls, d_nx);
+    u32 nx2[2] = { 0, 0 };
+    if ((rc = ctx_readback(c, nx2, d_nx, 8))) return rc;
+    K.n_dec = nx2[0]; K.n_walk = nx2[1];
+    if (ctx_tracing(c) && with_sequences) ctx_trace(c, "[flat mixed] nblk %u decoded %u main %u (blocks with sequences %u)\n", nblk, K.n_dec, main, F.n_seq_blk);
+    else if (ctx_tracing(c)) ctx_trace(c, "[flat mixed] nblk %u decoded %u main %u\n", nblk, K.n_dec, main);
+    return 0;
+}
+// The decode of a mostly-flat frame's other blocks -- with the tables still to be built for them (`pending`) -- handed back to the
+// caller as a job: it runs once the caller has queued its tile index, on the caller's spare stream when there is one, beside the emit
+// of the flat tiles, which needs none of it (zstd_flat_later).
+struct FlatJob { ZFrame F; const u8 *cls; u8 *lits; u32 *done2; u32 n_walk; bool pending; };      // (F.out_len, consumed, rg, fuse, text: the finished call's, dead in this copy)
+static int flat_job_steps(naf_gpu_ctx *c, const FlatJob &J)
+{
+    const ZFrame &F = J.F; const ZStat &hs0 = F.hs; const u32 nblk = F.nblk; const bool with_sequences = F.n_seq_blk != 0; int rc;
+    if (c != F.c) HIP_TRY(c, hipStreamWaitEvent(c->stream, F.c->split_ev[0], 0));      // recorded by the caller behind its tile index
+    const u32 plog = J.n_walk ? huf_par_plog(c, hs0.max_lit_regen, J.n_walk) : 0u;
+    u32 max_log = hs0.max_huf_log;
+    if (J.pending && J.n_walk && !plog) {
+        // the one-lane-per-stream kernel takes its tables from the pool: the trees left out so far, now
+        ZStat h2; if ((rc = build_huf_rest(c, F, &h2))) return rc;
+        max_log = h2.max_huf_log;
+    }
+    if (with_sequences || hs0.n_plain_huf != nblk) LAUNCH(c, "zstd_copy_fill", k_copy_fill<64>, 4 * nblk, 64, 0, F.src, (const ZBlock *)F.blk, nblk, F.dst, J.lits, 0u, J.cls);
+    LitPlan p; memset(&p, 0, sizeof p);
+    p.dst = F.dst; p.lits = J.lits; p.cls = J.cls; p.serial = J.n_walk != 0; p.flat_on = 1u; p.plog = plog; p.pending = J.pending ? 1u : 0u;
+    p.slot = plog && J.pending ? (u32)HUF_TAB_MAX : huf_slot_bytes(max_log); p.ipitch = max_log > 7 ? HUF_IROW_BIG : HUF_IROW;
+    if ((rc = launch_literals(c, F, 0u, nblk, p))) return rc;
+    return with_sequences ? launch_exec(c, F, (const u32 *)F.seq_list, F.n_seq_blk, (const u8 *)J.lits, F.dst, J.done2) : 0;
+}
+// Whichever step fails, on whichever context: the text goes where the caller looks.
+int zstd_flat_later(naf_gpu_ctx *, ZFlat *zf)
+{
+    if (!zf || !zf->later) return 0;
+    FlatJob *j = (FlatJob *)zf->later; zf->later = nullptr;
+    naf_gpu_ctx *mc = j->F.c, *c = zf->aux ? zf->aux : mc;
+    const int rc = flat_job_steps(c, *j); delete j;
+    if (rc && c != mc) memcpy(mc->err, c->err, sizeof mc->err);
+    return rc;
+}
+void zstd_flat_drop(ZFlat *zf) { if (zf && zf->later) { delete (FlatJob *)zf->later; zf->later = nullptr; } }
+// Most blocks flat, some not: the blocks that are not, and their neighbours, are decoded into F.dst at their natural offsets; the
+// caller's emit reads the rest in place.  Whole-stream calls only; a frame whose blocks mostly need decoding takes the ordinary path
+// (NAF_GPU_FLAT_MIXED=0: always).
+static bool mostly_flat_wanted(const ZFrame &F)
+{
+    return F.c->zflat && F.spec && !F.always_table && !F.rg && F.hs.flat_main_inv && F.dst && F.hs.total_out <= F.dst_cap && !ctx_opt_is(F.c, "FLAT_MIXED", '0');
+}
+static int exit_mostly_flat(ZFrame &F, bool with_sequences)
+{
+    naf_gpu_ctx *c = F.c; int rc; const u32 nblk = F.nblk; FlatClass K;
+    if ((rc = flat_classify(F, with_sequences, K))) return rc;
+    if ((u64)K.n_dec * 2 > nblk) return 0;
+    LAUNCH(c, "zstd_flat_streams", k_flat_streams_mixed, cdiv(4ull * nblk, 256), 256, 0, F.src, (const ZBlock *)F.blk, nblk, (const u8 *)K.cls, K.si, F.st, (const u64 *)F.d_total_out);
+    FlatMixed M = { K.cls, K.n_dec, K.n_walk, nullptr };
+    if (with_sequences || K.n_dec) M.later = new FlatJob{ F, K.cls, K.lits, K.done2, K.n_walk, !with_sequences && F.two_phase && F.hs.n_huf_distinct > HUF_FEW };
+    return flat_handoff(F, K.si, 4ull * nblk, K.sym, F.hs.end_off, F.hs.total_out, 0u, &M);
+}
+
+// ---- sequences: their tables and the list of their blocks, then the walk that turns them into (literal length, match length, offset) arrays and final block sizes
+static int seq_tables(ZFrame &F)
+{
+    naf_gpu_ctx *c = F.c; int rc; const u32 nblk = F.nblk, g = F.g; ZStat *st = F.st;
+    for (i32 *own : { F.own_ll, F.own_of, F.own_ml }) if ((rc = scan_inclusive_max_i32(c, own, nblk))) return rc;
+    if ((rc = scan_exclusive_u64(c, F.seq_cnt, nblk, (u64 *)((u8 *)st + offsetof(ZStat, total_seq))))) return rc;
+    u32 fse_cap = F.n_seq_blk * (512 + 256 + 512);
+    if (!(F.fse_pool = arena_new<FseE>(c, fse_cap))) return NAF_GPU_ENOMEM;
+    LAUNCH(c, "zstd_build_fse", k_build_fse, cdiv(3 * (u64)nblk, 64), 64, 0, F.src, F.blk, nblk, F.fse_pool, fse_cap, st);
+    if ((rc = ctx_readback(c, &F.hs, st, sizeof F.hs))) return rc;
+    if (F.hs.err) return zerr(c, F.hs.err, "table build");
+    size_t ns = F.hs.total_seq ? F.hs.total_seq : 1;
+    F.o_ll = arena_new<u32>(c, ns); F.o_ml = arena_new<u32>(c, ns); F.o_of = arena_new<u32>(c, ns);
+    if (!F.o_ll || !F.o_ml || !F.o_of) return NAF_GPU_ENOMEM;
+    F.seq_list = arena_new<u32>(c, F.n_seq_blk);
+    u64 *flag = arena_new<u64>(c, (size_t)nblk + 1); F.seq_rank = flag;
+    if (!F.seq_list || !flag) return NAF_GPU_ENOMEM;
+    LAUNCH(c, "zstd_seq_flag", k_seq_flag, g, 64, 0, (const ZBlock *)F.blk, nblk, flag);
+    if ((rc = scan_exclusive_u64(c, flag, nblk, (u64 *)nullptr))) return rc;
+    LAUNCH(c, "zstd_seq_list", k_seq_list, g, 64, 0, (const ZBlock *)F.blk, nblk, (const u64 *)flag, F.seq_list);
+    return 0;
+}
+static int sequences(ZFrame &F)
+{
+    naf_gpu_ctx *c = F.c; int rc; const u8 *d_src = F.src; ZBlock *blk = F.blk; const u32 nblk = F.nblk, n_seq_blk = F.n_seq_blk; ZStat *st = F.st;
+    if (n_seq_blk && (rc = seq_tables(F))) return rc;
+    if (F.lit_only_spec) return 0;
+    // (a lane per block, every lane on a chain of its own: a frame of a few thousand blocks spreads over more wavefronts, 16 lanes each)
+    const u32 dsl = nblk < 32768 ? 16u : 64u;
+    // blocks under tables of their own (libzstd's) by a wavefront each with the tables in LDS, the others a lane per block
+    const u32 all_wave = ctx_opt_is(c, "SEQ_WAVE", 'a') ? 1u : 0u;
+    const u32 own_tabs = (n_seq_blk && !ctx_opt_is(c, "SEQ_WAVE", '0')) ? 1u + all_wave : 0u;
+    u32 *wave_list = own_tabs ? arena_new<u32>(c, n_seq_blk) : nullptr;
+    if (own_tabs && !wave_list) return NAF_GPU_ENOMEM;
+    LAUNCH(c, "zstd_decode_seq", k_decode_seq, cdiv(nblk, dsl), dsl, 0, d_src, blk, nblk, (const i32 *)F.own_ll, (const i32 *)F.own_of, (const i32 *)F.own_ml,
+           (const u64 *)F.seq_cnt, (const FseE *)F.fse_pool, (const FseE *)c->d_predef, F.o_ll, F.o_ml, F.o_of, F.sizes, st, own_tabs, wave_list);
+    const u32 wgrid = n_seq_blk < 8192u ? n_seq_blk : 8192u;
+    if (own_tabs && ctx_opt_is(c, "SEQ_WAVE", 'l'))       // (kept as a cross-check: one lane walking the block with the general routine's shape)
+        LAUNCH(c, "zstd_decode_seq", k_decode_seq_wave, wgrid, 64, 0, d_src, blk, (const u32 *)wave_list, (const i32 *)F.own_ll, (const i32 *)F.own_of, (const i32 *)F.own_ml,
+               (const u64 *)F.seq_cnt, (const FseE *)F.fse_pool, (const FseE *)c->d_predef, F.o_ll, F.o_ml, F.o_of, F.sizes, st);
+    else if (own_tabs)
+        LAUNCH(c, "zstd_decode_seq", k_decode_seq_wave2, wgrid, 64, 0, d_src, blk, (const u32 *)wave_list, (const i32 *)F.own_ll, (const i32 *)F.own_of, (const i32 *)F.own_ml,
+               (const u64 *)F.seq_cnt, (const FseE *)F.fse_pool, (const FseE *)c->d_predef, F.o_ll, F.o_ml, F.o_of, F.sizes, st, all_wave | (ctx_opt_is(c, "SEQ_REP", 'w') ? 2u : 0u));
+    if (n_seq_blk) LAUNCH(c, "zstd_rep_fast", k_rep_fast, cdiv(n_seq_blk, 256), 256, 0, blk, (const u32 *)F.seq_list, n_seq_blk, st);
+    if ((rc = scan_exclusive_u64(c, F.sizes, nblk, F.d_total_out))) return rc;
+    if ((rc = ctx_readback(c, &F.hs, st, sizeof F.hs))) return rc;
+    return F.hs.err ? zerr(c, F.hs.err, "sequences") : 0;
+}
+// ---- range and closure
+// Range request (multi-GPU sharding): decode only the blocks that feed [want_lo, want_hi).  Needs blocks that
+// do not reference earlier output, i.e. a frame without sequences (this build's own frames; reference-made
+// random-ACGT frames); a frame with matches takes the range's dependency closure (NAF_GPU_RANGE_CLOSURE=0: the whole frame).
+static int range_select(ZFrame &F)
+{
+    naf_gpu_ctx *c = F.c; int rc; const u32 nblk = F.nblk, n_seq_blk = F.n_seq_blk; ZRange *rg = F.rg; const ZStat &hs = F.hs; u64 *h4 = F.h4;
+    F.b_count = nblk; F.seq_t1 = n_seq_blk;                      // (b_first, huf_first, bias, seq_t0: 0)
+    if (F.fuse) { F.dst = nullptr; F.dst_cap = ~(size_t)0; }
+    if (rg) { rg->got_lo = 0; rg->got_hi = hs.total_out; rg->ranged = false; rg->own_buf = nullptr; }
+    if (rg && n_seq_blk == 0 && nblk > 0 && rg->want_hi > rg->want_lo) {
+        if (!F.lit_only_spec) {
+            u64 *r4b = arena_new<u64>(c, 5); if (!r4b) return NAF_GPU_ENOMEM;
+            LAUNCH(c, "zstd_find_range", k_find_range, 1, 64, 0, (const u64 *)F.sizes, nblk, (const u64 *)F.d_total_out, rg->want_lo, rg->want_hi, (const i32 *)F.own_huf, r4b);
+            if ((rc = ctx_readback(c, h4, r4b, 40))) return rc;
+        }
+        F.huf_first = (u32)h4[4];
+        F.b_first = (u32)h4[0]; F.b_count = (u32)(h4[1] - h4[0]); F.bias = h4[2];
+        rg->got_lo = h4[2]; rg->got_hi = h4[3]; rg->ranged = true;
+        if (h4[3] - h4[2] > F.dst_cap) return ctx_fail(c, NAF_GPU_ECAP, "zstd range output needs %llu bytes, capacity %zu", (unsigned long long)(h4[3] - h4[2]), F.dst_cap);
+        F.dst -= F.bias;                                     // block b lands at d_dst_orig + (out_off[b] - got_lo)
+    } else if (rg && n_seq_blk && nblk > 0 && rg->want_hi > rg->want_lo && !ctx_opt_is(c, "RANGE_CLOSURE", '0')) {
+        // blocks with matches: the range's dependency closure (kernels above).  On archives that are mostly literals -- what the
+        // reference makes of a genome at its default level -- that is the range's own blocks and a few in front of them.
+        u32 *f = arena_new<u32>(c, nblk); u64 *r4b = arena_new<u64>(c, 5 + 8); if (!f || !r4b) return NAF_GPU_ENOMEM;
+        LAUNCH(c, "zstd_find_range", k_find_range, 1, 64, 0, (const u64 *)F.sizes, nblk, (const u64 *)F.d_total_out, rg->want_lo, rg->want_hi, (const i32 *)F.own_huf, r4b);
+        LAUNCH(c, "zstd_range_closure", k_iota_u32, F.g, 64, 0, f, nblk);
+        LAUNCH(c, "zstd_range_closure", k_seq_reach, cdiv(n_seq_blk, 64), 64, 0, (const ZBlock *)F.blk, (const u32 *)F.seq_list, n_seq_blk, (const u64 *)F.sizes, (const u32 *)F.o_ll, (const u32 *)F.o_ml, (const u32 *)F.o_of, f);
+        LAUNCH(c, "zstd_range_closure", k_range_closure, 1, 64, 0, (const u32 *)f, (const u64 *)F.sizes, nblk, (const u64 *)F.d_total_out, (const u64 *)r4b, (const i32 *)F.own_huf, (const u64 *)F.seq_rank, n_seq_blk, r4b + 5);
+        u64 h7[7]; if ((rc = ctx_readback(c, h7, r4b + 5, sizeof h7))) return rc;
+        const u64 need = h7[3] - h7[2];
+        if (ctx_tracing(c)) ctx_trace(c, "[range] want %llu..%llu -> blocks %llu..%llu (bytes %llu..%llu of %llu), tables from %llu, seq blocks %llu..%llu of %u\n", (unsigned long long)rg->want_lo, (unsigned long long)rg->want_hi,
+                    (unsigned long long)h7[0], (unsigned long long)h7[1], (unsigned long long)h7[2], (unsigned long long)h7[3], (unsigned long long)hs.total_out, (unsigned long long)h7[4], (unsigned long long)h7[5], (unsigned long long)h7[6], n_seq_blk);
+        if (need < hs.total_out) {
+            if (need > F.dst_cap) {
+                // the caller sized its buffer for the range alone: take the closure's from the arena and say so (ZRange.own_buf)
+                F.dst = (u8 *)arena_alloc(c, need + 64); if (!F.dst) return NAF_GPU_ENOMEM;
+                F.dst_cap = need; rg->own_buf = F.dst;
+            }
+            F.huf_first = (u32)h7[4];
+            F.b_first = (u32)h7[0]; F.b_count = (u32)(h7[1] - h7[0]); F.bias = h7[2];
+            F.seq_t0 = (u32)h7[5]; F.seq_t1 = (u32)h7[6];
+            rg->got_lo = h7[2]; rg->got_hi = h7[3]; rg->ranged = true;
+            F.dst -= F.bias;
+        } else if (hs.total_out > F.dst_cap) return ctx_fail(c, NAF_GPU_ECAP, "zstd output needs %llu bytes, capacity %zu", (unsigned long long)hs.total_out, F.dst_cap);
+    } else if (hs.total_out > F.dst_cap) return ctx_fail(c, NAF_GPU_ECAP, "zstd output needs %llu bytes, capacity %zu", (unsigned long long)hs.total_out, F.dst_cap);
+    return 0;
+}
+// ---- literals
+// Literal-only frame of a whole-text call: block ranges in order, an event behind each (ctx.h: ZSplit); the raw / RLE blocks first, so that a finished part is complete.
+static int literals_split(ZFrame &F, const LitPlan &p)
+{
+    naf_gpu_ctx *c = F.c; int rc; ZSplit *sp = c->zsplit; const u32 nblk = F.nblk;
+    if (F.hs.n_plain_huf != nblk) LAUNCH(c, "zstd_copy_fill", k_copy_fill<256>, nblk, 256, 0, F.src, (const ZBlock *)F.blk, nblk, F.dst, F.lit_scratch, 0u, (const u8 *)nullptr);
+    // output offsets of the part ends: they came with the counters when the frame took the speculative route
+    if (F.have_ends) for (int k = 0; k + 1 < sp->parts; k++) sp->out_end[k] = F.hends[k];
+    else {
+        u64 *e2 = arena_new<u64>(c, ZSPLIT_MAX); if (!e2) return NAF_GPU_ENOMEM;
+        for (int k = 0; k + 1 < sp->parts; k++) HIP_TRY(c, hipMemcpyAsync(e2 + k, F.sizes + split_part_end(nblk, sp->parts, k), 8, hipMemcpyDeviceToDevice, c->stream));
+        if ((rc = ctx_readback(c, sp->out_end, e2, 8 * (size_t)(sp->parts - 1)))) return rc;
+    }
+    sp->out_end[sp->parts - 1] = F.hs.total_out;
+    u32 lo_b = 0;
+    for (int k = 0; k < sp->parts; k++) {
+        const u32 hi_b = split_part_end(nblk, sp->parts, k);
+        if ((rc = launch_literals(c, F, lo_b, hi_b, p))) return rc;
+        HIP_TRY(c, hipEventRecord(sp->ev[k], c->stream));
+        lo_b = hi_b;
+    }
+    sp->done = 1;
+    return 0;
+}
+static int literals(ZFrame &F)
+{
+    naf_gpu_ctx *c = F.c; int rc; const u32 nblk = F.nblk, b_first = F.b_first, b_count = F.b_count, b_end = b_first + b_count; const EmitP *fuse = F.fuse;
+    if (F.n_seq_blk) {
+        F.done = arena_new<u32>(c, nblk);
+        const u64 span = F.rg && F.rg->ranged ? F.rg->got_hi - F.rg->got_lo : F.hs.total_out;
+        F.lit_scratch = (u8 *)arena_alloc(c, span + 16);
+        if (!F.done || !F.lit_scratch) return NAF_GPU_ENOMEM;
+        F.lit_scratch -= F.bias;                                     // indexed by a block's place in the whole output, like F.dst
+    }
+    LAUNCH(c, "zstd_set_offsets", k_set_offsets, F.g, 64, 0, F.blk, nblk, (const u64 *)F.sizes, F.done, (u32 *)nullptr, (u32 *)nullptr);
+    bool copy_fill_done = false;
+    if (F.n_huf_def) {
+        if (!F.tables_built) {
+            // tables of the blocks that will be decoded (and of the earlier blocks that own a table in force there)
+            const u32 hb_n = b_end - F.huf_first;
+            F.pool_cap = (hb_n < F.n_huf_def ? hb_n : F.n_huf_def) * (u32)HUF_TAB_MAX + 4096u;   // largest table of either form
+            if (!(F.huf_pool = (u8 *)arena_alloc(c, F.pool_cap))) return NAF_GPU_ENOMEM;
+            if (hb_n && hb_n <= 512) LAUNCH(c, "zstd_build_huf", k_build_huf_lds, hb_n, 64, 0, F.src, F.blk, b_end, F.huf_pool, F.pool_cap, F.st, F.huf_first, (const i32 *)F.own_huf);
+            else if (hb_n && (rc = launch_build_huf(c, hb_n, F.src, F.blk, b_end, F.huf_pool, F.pool_cap, F.st, F.huf_first, (const u64 *)nullptr, (F.always_table || fuse) ? 1u : 0u, (const i32 *)F.own_huf, 0u, 0u))) return rc;
+            if ((rc = ctx_readback(c, &F.hs, F.st, sizeof F.hs))) return rc;
+            if (F.hs.err) return zerr(c, F.hs.err, "Huffman tables");
+        }
+        const ZStat &hs = F.hs;
+        if (fuse && hs.max_huf_log > 7) return ZSTD_NEED_TWO_PASS;
+        LitPlan p; memset(&p, 0, sizeof p);
+        p.dst = F.dst; p.lits = F.lit_scratch; p.wide = true; p.slot = huf_slot_bytes(hs.max_huf_log);
+        p.ipitch = hs.max_huf_log > 7 ? HUF_IROW_BIG : HUF_IROW; p.generic = ctx_opt_is(c, "HUF_GENERIC", '1') ? 0x8000u : 0u;
+        if (b_count && fuse) LAUNCH(c, "zstd_huf_fused_emit", (k_huf_literals<true>), cdiv(b_count, HUF_BLOCKS_PER_WG), 64, p.slot * HUF_BLOCKS_PER_WG + 64 * p.ipitch + 512,
+               F.src, (const ZBlock *)F.blk, b_end, (const i32 *)F.own_huf, (const u8 *)F.huf_pool, p.slot, F.dst, F.lit_scratch, F.st, b_first, *fuse, F.text, p.ipitch | p.generic, (u64)F.src_len, 0u, (const u8 *)nullptr);
+        else if (b_count) {
+            // blocks whose tree is flat go to k_flat_literals; the serial kernel is not launched when that is all of them
+            p.flat_on = (hs.n_flat && !F.always_table) ? 1u : 0u;
+            p.serial = !p.flat_on || hs.n_flat < hs.n_huf_built;
+            p.plog = huf_par_plog(c, hs.max_lit_regen, b_count);
+            // a frame of few trees (this build's frame tree, libzstd's runs of treeless blocks): workgroups with ONE table in LDS, the
+            // workgroups whose blocks are under several trees through a second launch of the plain kernel (NAF_GPU_HUF_SHARED=0: never)
+            if (p.serial && !p.plog && (u64)hs.n_huf_distinct * 64 <= b_count && !ctx_opt_is(c, "HUF_SHARED", '0')) {
+                p.redo = (u8 *)arena_alloc(c, (size_t)nblk + 16); if (!p.redo) return NAF_GPU_ENOMEM;
+                HIP_TRY(c, hipMemsetAsync(p.redo, 0, nblk, c->stream));
+            }
+            ZSplit *sp = c->zsplit;
+            const char *smin = ctx_opt(c, "SPLIT_MIN");                      // blocks per part below which a split is not worth its launches (tests lower it)
+            const u32 split_min = smin ? (u32)atoi(smin) : 4096u;
+            if (sp && !F.rg && F.n_seq_blk == 0 && b_first == 0 && b_count == nblk && b_count >= split_min * (u32)sp->parts && b_count >= 16u * HUF_BLOCKS_PER_WG * (u32)sp->parts) {
+                if ((rc = literals_split(F, p))) return rc;
+                copy_fill_done = true;
+            } else if ((rc = launch_literals(c, F, b_first, b_end, p))) return rc;
+        }
+    }
+    if (b_count && !fuse && !copy_fill_done && F.hs.n_plain_huf != nblk) LAUNCH(c, "zstd_copy_fill", k_copy_fill<256>, b_count, 256, 0, F.src, (const ZBlock *)F.blk, b_end, F.dst, F.lit_scratch, b_first, (const u8 *)nullptr);
+    return 0;
+}
+
+// Decode ONE frame whose header (after the magic) starts at d_src[0].  *consumed = bytes of the frame.  Seven ways out beside the decoded frame and an error: the small
+// frame; a frame handed to the caller to be read in place (Z_HANDED: uniform, runs, all flat, mostly flat, mostly flat with sequences); a split decode, whose status the caller reads.
 static int zstd_decode_one(naf_gpu_ctx *c, const u8 *d_src, size_t src_len, u8 *d_dst, size_t dst_cap,
                            size_t *out_len, size_t *consumed, ZRange *rg, const EmitP *fuse, u8 *text, const u8 *head = nullptr)
 {
@@ -3869,637 +4437,63 @@ static int zstd_decode_one(naf_gpu_ctx *c, const u8 *d_src, size_t src_len, u8 *
         if (!d_res) return NAF_GPU_ENOMEM;
         LAUNCH(c, "zstd_small_frame", k_small_frame, 1, 64, 0, d_src, (u32)src_len, d_dst, (u32)dst_cap, (const FseE *)c->d_predef, d_res);
         u32 res[3]; if ((rc = ctx_readback(c, res, d_res, 12))) return rc;
-        if (res[0] == 0) { *out_len = res[1]; *consumed = res[2]; return 0; }
+        if (res[0] == 0) { *out_len = res[1]; *consumed = res[2]; return 0; }                        // exit 1
         if (res[0] != SMALL_TOO_BIG) return zerr(c, res[0], "small frame");
     }
-    u8 hb[18]; size_t hl = src_len < 18 ? src_len : 18;
-    if (head) memcpy(hb, head, hl);
-    else { rc = ctx_readback(c, hb, d_src, hl); if (rc) return rc; }
-    ZFrameHdr fh = zstd_parse_frame_header(hb, hl);
-    if (fh.err) return zerr(c, (u32)fh.err, "frame header");
-
-    ZStat *st = arena_new<ZStat>(c, 1);
-    if (!st) return NAF_GPU_ENOMEM;
-    HIP_TRY(c, hipMemsetAsync(st, 0, sizeof(ZStat), c->stream));
+    ZFrame F; memset(&F, 0, sizeof F);
+    F.c = c; F.src = d_src; F.src_len = src_len; F.dst = d_dst; F.dst_cap = dst_cap; F.out_len = out_len; F.consumed = consumed; F.rg = rg; F.fuse = fuse; F.text = text;
+    F.hl = src_len < 18 ? src_len : 18;
+    if (head) memcpy(F.hb, head, F.hl);
+    else if ((rc = ctx_readback(c, F.hb, d_src, F.hl))) return rc;
+    F.fh = zstd_parse_frame_header(F.hb, F.hl);
+    if (F.fh.err) return zerr(c, (u32)F.fh.err, "frame header");
+    if (!(F.st = arena_new<ZStat>(c, 1))) return NAF_GPU_ENOMEM;
+    HIP_TRY(c, hipMemsetAsync(F.st, 0, sizeof(ZStat), c->stream));
+    F.always_table = ctx_opt_is(c, "FLAT", '0') ? 1u : 0u;                     // "0": every block through the serial kernel (cross-check)
+    const char *smin = ctx_opt(c, "SPEC_MIN");                                 // tests: frames of a few dozen blocks through the paths of the big ones
+    F.spec_min = smin ? (u32)atoi(smin) : 512u;
+    F.uni_wanted = c->zflat && !fuse && !F.always_table && !ctx_opt_is(c, "UNIFORM", '0');      // "0": a uniform flat frame takes the general front too
     // ---- block index
-    ZBlock *blk = nullptr; ZStat hs; bool indexed = false;
-    const char *nospec = ctx_opt(c, "SERIAL_INDEX");
-    const char *fl_env = ctx_opt(c, "FLAT");                                 // "0": every block through the serial kernel (cross-check)
-    const u32 always_table = (fl_env && fl_env[0] == '0') ? 1u : 0u;
-    const char *smin = ctx_opt(c, "SPEC_MIN");                      // tests: frames of a few dozen blocks through the paths of the big ones
-    const u32 spec_min = smin ? (u32)atoi(smin) : 512u;
-    const char *un_env = ctx_opt(c, "UNIFORM");                              // "0": a uniform flat frame takes the general front too
-    const bool uni_wanted = c->zflat && !fuse && !always_table && !(un_env && un_env[0] == '0');
-    // Frames of more than 4 MiB: 1 MiB chunks, candidates in the first 40 KiB / 128 KiB of each.  Smaller frames can still hold
-    // thousands of tiny blocks (ids / names / lengths that compress 100:1 in 16 KiB blocks, a mask stream that is 1200 RLE blocks
-    // of 4 bytes -- a serial walk of those costs milliseconds): small chunks with every byte tested as a candidate.  The chunk size changes nothing but how much of
-    // the speculation is reused: the resolve pass re-walks from the true start wherever a chunk's candidate was wrong or missing.
-    u32 chunk = SPEC_CHUNK, win1 = SPEC_WINDOW1, win2 = SPEC_WINDOW;
-    if (src_len <= 4ull * SPEC_CHUNK) {                          // about 128 chunks of 256 B .. 16 KiB, every byte a candidate
-        chunk = 256; while (chunk < SPEC_CHUNK_SMALL && (u64)chunk * 128 < src_len) chunk *= 2;
-        win1 = win2 = chunk;
-    } else if (src_len <= 256ull * SPEC_CHUNK && fh.hdr_size + 3 <= hl) {
-        // In between (a soft-masked genome's mask: 11 MB of 5 KB blocks): a chunk is walked by one lane, block after block, and 1 MiB
-        // of small blocks is a long walk for eleven lanes.  The frame's first block says what to expect: chunks of about sixteen
-        // such blocks (never wrong, only more or less of the speculation reused).
-        const u32 h0 = (u32)hb[fh.hdr_size] | ((u32)hb[fh.hdr_size + 1] << 8) | ((u32)hb[fh.hdr_size + 2] << 16);
-        const u32 b0 = ((h0 >> 1) & 3) == 1 ? 4u : (h0 >> 3) + 3;     // bytes of the first block (an RLE block stores one byte)
-        u32 want = SPEC_CHUNK_SMALL; while (want < SPEC_CHUNK && want < 16 * b0) want *= 2;
-        if (want < SPEC_CHUNK) { chunk = want; if (win1 > chunk) win1 = chunk; if (win2 > chunk) win2 = chunk; }
-    }
-    if (src_len >= 2048 && !(nospec && nospec[0] == '1')) {
-        u32 nchunks = (u32)((src_len + chunk - 1) / chunk);
-        u64 *first = arena_new<u64>(c, nchunks + 1), *land = arena_new<u64>(c, nchunks + 2), *G = arena_new<u64>(c, nchunks + 1);
-        u64 *start = arena_new<u64>(c, nchunks + 2), *cnt = arena_new<u64>(c, (size_t)nchunks + 4);      // (+ the scan's total and the stride index's verdict behind it)
-        if (!first || !land || !G || !start || !cnt) return NAF_GPU_ENOMEM;
-        HIP_TRY(c, hipMemsetAsync(first, 0xFF, (size_t)nchunks * 8, c->stream));
-        u64 *h0 = (u64 *)c->h_stage; *h0 = fh.hdr_size;
-        HIP_TRY(c, hipMemcpyAsync(first, h0, 8, hipMemcpyHostToDevice, c->stream));
-        u32 gl = cdiv(nchunks, 64);
-        // the stride index first (frames of more than 4 MiB whose first block is a compressed one that is not the last): three launches and
-        // a read-back; a frame it cannot take costs that read-back before the speculative index starts
-        {
-            const char *se = ctx_opt(c, "STRIDE_INDEX");
-            if (ctx_tracing(c)) ctx_trace(c, "[stride?] len %zu hdr %u hl %zu first %02x %02x %02x\n", src_len, fh.hdr_size, hl, hb[fh.hdr_size], hb[fh.hdr_size + 1], hb[fh.hdr_size + 2]);
-            if (src_len > 4ull * SPEC_CHUNK && fh.hdr_size + 3 <= hl && !(se && se[0] == '0')) {
-                const u32 h0 = (u32)hb[fh.hdr_size] | ((u32)hb[fh.hdr_size + 1] << 8) | ((u32)hb[fh.hdr_size + 2] << 16);
-                const u32 S = 3 + (h0 >> 3);
-                const u64 nmax64 = (src_len - fh.hdr_size) / S;
-                if (((h0 >> 1) & 3) == BT_COMP && !(h0 & 1) && (h0 >> 3) <= ZBLOCK_MAX && S >= 256 && nmax64 >= 64 && nmax64 < 0x7FFFFF00ull) {
-                    const u32 nmax = (u32)nmax64;
-                    u32 *sres = (u32 *)(cnt + nchunks + 2); ZBlock *sblk = arena_new<ZBlock>(c, (size_t)nmax + STRIDE_TAIL);
-                    if (!sblk) return NAF_GPU_ENOMEM;
-                    HIP_TRY(c, hipMemsetAsync(sres, 0xFF, 8, c->stream));
-                    LAUNCH(c, "zstd_index_stride", k_stride_probe, cdiv(nmax, 256), 256, 0, d_src, (u64)src_len, (u64)fh.hdr_size, S, h0, nmax, sres);
-                    LAUNCH(c, "zstd_index_stride", k_stride_tail, 1, 64, 0, d_src, (u64)src_len, (u64)fh.hdr_size, S, nmax, sres, sblk, st);
-                    // a uniform flat frame (k_uni_head) needs nothing of what follows: its stream table is made here, beside the verdict
-                    UniInfo *U = nullptr; FlatStream *usi = nullptr; u8 *usym = nullptr;
-                    if (uni_wanted) {
-                        U = arena_new<UniInfo>(c, 1); ZBlock *ublk = arena_new<ZBlock>(c, STRIDE_TAIL + 1);
-                        usi = arena_new<FlatStream>(c, 4 * ((size_t)nmax + STRIDE_TAIL) + 1); usym = (u8 *)arena_alloc(c, 16);
-                        if (!U || !ublk || !usi || !usym) return NAF_GPU_ENOMEM;
-                        LAUNCH(c, "zstd_flat_uniform", k_uni_head, 1, 64, 0, d_src, (u64)fh.hdr_size, S, h0, nmax, (const u32 *)sres, (const ZBlock *)sblk, (const ZStat *)st, U, ublk, spec_min);
-                        LAUNCH(c, "zstd_flat_uniform", k_uni_streams, cdiv(4ull * ((u64)nmax + STRIDE_TAIL) + 1, 256) + 1, 256, 0, d_src, (u64)fh.hdr_size, S, (const ZBlock *)ublk, U, usi, usym);
-                    }
-                    LAUNCH(c, "zstd_index_stride", k_stride_write, cdiv(nmax, 256), 256, 0, (u64)fh.hdr_size, S, h0, (const u32 *)sres, sblk, (const u32 *)U);
-                    u32 res2[2] = { 0, 0 }; UniInfo hu; memset(&hu, 0, sizeof hu);
-                    if (U) { void *hp[3] = { &hs, res2, &hu }; const void *dp[3] = { st, sres, U }; const size_t nb[3] = { sizeof hs, 8, sizeof hu }; rc = ctx_readbackv(c, 3, hp, dp, nb); }
-                    else rc = ctx_readback2(c, &hs, st, sizeof hs, res2, sres, 8);
-                    if (rc) return rc;
-                    if (ctx_tracing(c)) ctx_trace(c, "[stride] len %zu S %u nmax %u prefix %u verdict %u err %u nblk %u\n", src_len, S, nmax, res2[0], res2[1], hs.err, hs.nblk);
-                    if (ctx_tracing(c) && U) ctx_trace(c, "[uniform?] ok %u bad %u prefix %u blocks %u huffman %u regen %u total %llu\n", hu.ok, hu.bad, hu.np, hu.nblk, hu.nhb, hu.regen0, (unsigned long long)hu.total_out);
-                    if (res2[1] == 1u && !hs.err && hs.nblk && hu.ok && !hu.bad) {
-                        // every block repeats the first: the caller's emit kernel reads the streams in place (as below, without the block table)
-                        ZFlat *zf = c->zflat;
-                        const size_t frame_end = hs.end_off + (fh.checksum ? 4 : 0);
-                        if (frame_end > src_len) return zerr(c, ZE_TRUNC, "checksum");
-                        *consumed = frame_end;
-                        const bool flat_tail = hu.last_raw != 0;
-                        zf->src = d_src; zf->si = usi; zf->nslots = 4ull * hu.nhb; zf->sym = usym; zf->status = st; zf->ready = true;
-                        const u32 tn = hu.last_raw & 0x7FFFFFFFu; const bool rle = (hu.last_raw >> 31) != 0;       // an RLE block stores one byte
-                        zf->tail = flat_tail ? d_src + (hs.end_off - (rle ? 1u : tn)) : nullptr; zf->tail_q = hu.total_out - (flat_tail ? tn : 0u);
-                        zf->tail_n = flat_tail ? (rle ? tn | 0x80000000u : tn) : 0u;
-                        if (rg) { rg->got_lo = 0; rg->got_hi = hu.total_out; rg->ranged = false; }
-                        *out_len = hu.total_out;
-                        if (fh.has_fcs && fh.content_size != hu.total_out) return zerr(c, ZE_CORRUPT, "content size mismatch");
-                        return 0;
-                    }
-                    if (res2[1] == 1u && !hs.err && hs.nblk) { blk = sblk; indexed = true; }
-                    // runs of equal blocks (the sharded encoder's frames): NAF_GPU_STRIDE_RUNS=0: the universal front, as before
-                    if (res2[1] == 2u && !hs.err && uni_wanted && !ctx_opt_is(c, "STRIDE_RUNS", '0')) {
-                        UniRuns *R = arena_new<UniRuns>(c, 1); ZBlock *odd = arena_new<ZBlock>(c, STRIDE_TAIL + 1), *ublk0 = arena_new<ZBlock>(c, 1);
-                        u32 *probe = arena_new<u32>(c, 2); UniInfo *U2 = arena_new<UniInfo>(c, 1);
-                        FlatStream *usi2 = arena_new<FlatStream>(c, 4 * ((size_t)nmax + USEG_MAX) + 1); u8 *usym2 = (u8 *)arena_alloc(c, 16);
-                        if (!R || !odd || !ublk0 || !probe || !U2 || !usi2 || !usym2) return NAF_GPU_ENOMEM;
-                        for (u32 r = 0; r <= URUN_MAX; r++) {
-                            LAUNCH(c, "zstd_index_stride", k_runs_next, 1, 64, 0, d_src, (u64)src_len, (u64)fh.hdr_size, S, h0, (const u32 *)sres, R, odd, probe, r == 0 ? 1 : 0);
-                            if (r < URUN_MAX) LAUNCH(c, "zstd_index_stride", k_runs_probe, cdiv(nmax, 256), 256, 0, d_src, (u64)src_len, S, h0, (const UniRuns *)R, probe);
-                        }
-                        LAUNCH(c, "zstd_flat_uniform", k_uni_head_runs, 1, 64, 0, d_src, (u64)fh.hdr_size, h0, R, odd, U2, ublk0, spec_min);
-                        LAUNCH(c, "zstd_flat_uniform", k_uni_streams_runs, cdiv(4ull * ((u64)nmax + USEG_MAX) + 1, 256) + 1, 256, 0, d_src, S, (const UniRuns *)R, (const ZBlock *)odd, (const ZBlock *)ublk0, U2, usi2, usym2);
-                        UniInfo hu2; memset(&hu2, 0, sizeof hu2);
-                        if ((rc = ctx_readback(c, &hu2, U2, sizeof hu2))) return rc;
-                        if (ctx_tracing(c)) ctx_trace(c, "[runs?] ok %u bad %u first run %u blocks %u huffman %u total %llu\n", hu2.ok, hu2.bad, hu2.np, hu2.nblk, hu2.nhb, (unsigned long long)hu2.total_out);
-                        if (hu2.ok && !hu2.bad) {
-                            ZFlat *zf = c->zflat;
-                            const size_t frame_end = hu2.end_off + (fh.checksum ? 4 : 0);
-                            if (frame_end > src_len) return zerr(c, ZE_TRUNC, "checksum");
-                            *consumed = frame_end;
-                            const bool flat_tail = hu2.last_raw != 0;
-                            zf->src = d_src; zf->si = usi2; zf->nslots = 4ull * hu2.nhb; zf->sym = usym2; zf->status = st; zf->ready = true;
-                            const u32 tn = hu2.last_raw & 0x7FFFFFFFu; const bool rle = (hu2.last_raw >> 31) != 0;
-                            zf->tail = flat_tail ? d_src + (hu2.end_off - (rle ? 1u : tn)) : nullptr; zf->tail_q = hu2.total_out - (flat_tail ? tn : 0u);
-                            zf->tail_n = flat_tail ? (rle ? tn | 0x80000000u : tn) : 0u;
-                            if (rg) { rg->got_lo = 0; rg->got_hi = hu2.total_out; rg->ranged = false; }
-                            *out_len = hu2.total_out;
-                            if (fh.has_fcs && fh.content_size != hu2.total_out) return zerr(c, ZE_CORRUPT, "content size mismatch");
-                            return 0;
-                        }
-                    }
-                }
-            }
-        }
-        const u32 *skip = nullptr;
-        if (!indexed) {
-        // the first block start of a chunk lies in its first 20 KiB whenever blocks compress to less than that (this build's 32 KiB
-        // blocks of packed bases: 16 KiB); the passes behind it only run for the chunks still without a candidate
-        const u32 win0 = chunk == SPEC_CHUNK ? SPEC_WINDOW0 : win1;
-        LAUNCH(c, "zstd_index_find", k_spec_find, cdiv(win0, 256 * 16) * (nchunks - 1), 256, 0, d_src, (u64)src_len, nchunks, first, 0u, win0, chunk, skip);
-        if (win1 > win0) LAUNCH(c, "zstd_index_find2", k_spec_find, cdiv(win1 - win0, 256 * 16) * (nchunks - 1), 256, 0, d_src, (u64)src_len, nchunks, first, win0, win1, chunk, skip);
-        if (win2 > win1) LAUNCH(c, "zstd_index_find2", k_spec_find, cdiv(win2 - win1, 256 * 16) * (nchunks - 1), 256, 0, d_src, (u64)src_len, nchunks, first, win1, win2, chunk, skip);
-        LAUNCH(c, "zstd_index_land", k_spec_land, gl, 64, 0, d_src, (u64)src_len, (const u64 *)first, nchunks, land, chunk, skip);
-        LAUNCH(c, "zstd_index_land2", k_spec_land2, gl, 64, 0, d_src, (u64)src_len, (const u64 *)first, (const u64 *)land, nchunks, G, chunk, skip);
-        LAUNCH(c, "zstd_index_resolve", k_spec_resolve, 1, 64, 0, d_src, (u64)src_len, (const u64 *)land, (const u64 *)G, nchunks, start, st, chunk, skip);
-        LAUNCH(c, "zstd_index_count", (k_spec_walk<false>), gl, 64, 0, d_src, (u64)src_len, (const u64 *)start, nchunks, cnt, (ZBlock *)nullptr, st, skip);
-        u64 *d_tot = cnt + nchunks + 1;
-        if ((rc = scan_exclusive_u64(c, cnt, nchunks, d_tot))) return rc;
-        u64 tot = 0;
-        rc = ctx_readback2(c, &hs, st, sizeof hs, &tot, d_tot, 8); if (rc) return rc;
-        if (!hs.err && tot > 0 && tot < 0x7FFFFFFFull) {
-            blk = arena_new<ZBlock>(c, tot);
-            if (!blk) return NAF_GPU_ENOMEM;
-            LAUNCH(c, "zstd_index_write", (k_spec_walk<true>), gl, 64, 0, d_src, (u64)src_len, (const u64 *)start, nchunks, cnt, blk, st, (const u32 *)nullptr);
-            hs.nblk = (u32)tot; indexed = true;
-        } else {
-            HIP_TRY(c, hipMemsetAsync(st, 0, sizeof(ZStat), c->stream));     // not one well-formed frame for the parallel walk: serial walk decides
-        }
-        }
-    }
-    if (!indexed) {
-        u32 cap = (u32)(src_len / 16 + 1024);                         // one pass for anything but pathological runs of empty blocks
-        for (int attempt = 0; attempt < 2; attempt++) {
-            blk = arena_new<ZBlock>(c, cap);
-            if (!blk) return NAF_GPU_ENOMEM;
-            const u32 win = src_len < SCAN_WIN ? (u32)((src_len + 15) & ~15ull) + 16 : SCAN_WIN;
-            LAUNCH(c, "zstd_scan_blocks", k_scan_blocks, 1, 64, win + 16, d_src, (u64)src_len, (u64)fh.hdr_size, blk, cap, st, win);
-            rc = ctx_readback(c, &hs, st, sizeof hs); if (rc) return rc;
-            if (hs.err) return zerr(c, hs.err, "block headers");
-            if (hs.nblk <= cap) break;
-            cap = hs.nblk;
-        }
-    }
-    u32 nblk = hs.nblk;
-    size_t frame_end = hs.end_off + (fh.checksum ? 4 : 0);
+    if (src_len >= 2048 && !ctx_opt_is(c, "SERIAL_INDEX", '1') && (rc = index_parallel(F))) return rc == Z_HANDED ? 0 : rc;      // exits 2, 3: uniform, runs
+    if (!F.blk && (rc = index_serial(F))) return rc;
+    F.nblk = F.hs.nblk; F.g = cdiv(F.nblk, 64);
+    const size_t frame_end = F.hs.end_off + (F.fh.checksum ? 4 : 0);
     if (frame_end > src_len) return zerr(c, ZE_TRUNC, "checksum");
     *consumed = frame_end;
-
-    // ---- parse + ownership
-    i32 *own = arena_new<i32>(c, (size_t)nblk * 4);
-    u64 *seq_cnt = arena_new<u64>(c, (size_t)nblk + 1), *sizes = arena_new<u64>(c, (size_t)nblk + 1);
-    if (!own || !seq_cnt || !sizes) return NAF_GPU_ENOMEM;
-    i32 *own_huf = own, *own_ll = own + nblk, *own_of = own + 2 * (size_t)nblk, *own_ml = own + 3 * (size_t)nblk;
-    u32 g = cdiv(nblk, 64);
-    LAUNCH(c, "zstd_parse_blocks", k_parse_blocks, g, 64, 0, d_src, blk, nblk, own_huf, own_ll, own_of, own_ml, seq_cnt, sizes, st);
-    LAUNCH(c, "zstd_huf_dedup", k_huf_dedup, g, 64, 0, d_src, (const ZBlock *)blk, nblk, own_huf, st);
-    if ((rc = scan_inclusive_max_i32(c, own_huf, nblk))) return rc;
-    u64 *d_total_out = (u64 *)((u8 *)st + offsetof(ZStat, total_out));
-    // Speculative continuation.  Most frames that are long enough to matter are literal-only (this build's own sequence, mask and
-    // quality streams); for those nothing below needs the host: block sizes are final after the parse, so offsets, the block range
-    // of a byte-range request, the Huffman tables and the part boundaries of a split decode are queued right away and the counters
-    // come back in ONE read-back.  A frame that does have sequences then takes the long way from here (its tables are kept).
-    const bool spec = nblk > spec_min && !fuse;
-    u64 *r4 = nullptr, *ends = nullptr; u8 *huf_pool = nullptr; u32 pool_cap = 0; bool tables_built = false; bool ranged_build = false; bool two_phase = false;
-    u64 h4[5] = { 0, 0, 0, 0, 0 }, hends[ZSPLIT_MAX] = { 0 };
-    bool late_build = false;
-    if (spec) {
-        if ((rc = scan_exclusive_u64(c, sizes, nblk, d_total_out))) return rc;
-        u64 *extra = arena_new<u64>(c, 8 + ZSPLIT_MAX); if (!extra) return NAF_GPU_ENOMEM;
-        if (rg && rg->want_hi > rg->want_lo) {
-            r4 = extra;
-            LAUNCH(c, "zstd_find_range", k_find_range, 1, 64, 0, (const u64 *)sizes, nblk, (const u64 *)d_total_out, rg->want_lo, rg->want_hi, (const i32 *)own_huf, r4);
-            ranged_build = true;
-        }
-        const u64 want_pool = (u64)nblk * HUF_TAB_MAX + 4096;
-        pool_cap = want_pool > 0xFFFFF000ull ? 0xFFFFF000u : (u32)want_pool;
-        huf_pool = (u8 *)arena_alloc(c, pool_cap);
-        if (!huf_pool) return NAF_GPU_ENOMEM;
-        if (nblk <= 16384) {
-            // a stream of a few thousand blocks (a soft-masked genome's mask: a tree per block): a wavefront per block, all at once --
-            // one lane per tree (k_build_huf) is 0.35 ms of serial table building in front of the literals there
-            LAUNCH(c, "zstd_build_huf", k_build_huf_lds, nblk, 64, 0, d_src, blk, nblk, huf_pool, pool_cap, st, 0u, (const i32 *)own_huf);
-        } else {
-            LAUNCH(c, "zstd_build_huf", k_build_huf_few, 1024, 64, 0, d_src, blk, nblk, huf_pool, pool_cap, st, (const u64 *)r4, (const i32 *)own_huf);
-            // (a caller that can read flat blocks in place gets the flat trees recognised now and the other tables later: see phase 2 below)
-            two_phase = c->zflat && !rg && !always_table;
-            if (two_phase) LAUNCH(c, "zstd_build_huf", k_flat_find_main, FIND_MAIN_TREES, 64, 0, d_src, blk, nblk, huf_pool, pool_cap, st, (const i32 *)own_huf);
-            else late_build = true;
-            // (the group builder for frames of MANY distinct trees is queued once the counters say there are that many: its workgroups hold
-            // 64 KB of LDS each, and beside a Huffman walk of another stream -- which fills every CU's LDS -- even workgroups that find
-            // nothing to do waited a millisecond to start: a FASTQ's sequence frame, one tree, behind its quality frame's walk)
-        }
-        ZSplit *sp = c->zsplit;
-        if (sp && !rg && sp->parts >= 2) {
-            ends = extra + 8;
-            for (int k = 0; k + 1 < sp->parts; k++) {
-                u32 hi_b = (u32)((u64)nblk * (k + 1) / sp->parts) & ~(HUF_BLOCKS_PER_WG - 1u);
-                HIP_TRY(c, hipMemcpyAsync(ends + k, sizes + hi_b, 8, hipMemcpyDeviceToDevice, c->stream));
-            }
-        }
-        u64 hx[8 + ZSPLIT_MAX];
-        rc = ctx_readback2(c, &hs, st, sizeof hs, hx, extra, sizeof hx); if (rc) return rc;
-        memcpy(h4, hx, sizeof h4); memcpy(hends, hx + 8, sizeof hends);
-        if (late_build && !hs.err && hs.n_huf_distinct > HUF_FEW) {
-            if ((rc = launch_build_huf(c, nblk, d_src, blk, nblk, huf_pool, pool_cap, st, 0u, (const u64 *)r4, always_table, (const i32 *)own_huf, 1u, 0u))) return rc;
-            rc = ctx_readback(c, &hs, st, sizeof hs); if (rc) return rc;
-        }
-        tables_built = true;
-    } else {
-        rc = ctx_readback(c, &hs, st, sizeof hs); if (rc) return rc;
-    }
-    if (hs.err) return zerr(c, hs.err, "block parse");
-    u32 n_seq_blk = hs.n_seq_blk, n_huf_def = hs.n_huf_def;
-    // fused decode+emit needs every block to be a literal-only Huffman block
-    if (fuse && !(n_seq_blk == 0 && hs.n_plain_huf == nblk && nblk > 0)) return ZSTD_NEED_TWO_PASS;
-    const bool lit_only_spec = spec && n_seq_blk == 0;
-    if (spec && n_seq_blk && ranged_build) {
-        // the block range was worked out from sizes that sequences will change: forget those tables
-        tables_built = false;
-        HIP_TRY(c, hipMemsetAsync((u8 *)st + offsetof(ZStat, huf_pool_used), 0, 4, c->stream));
-        HIP_TRY(c, hipMemsetAsync((u8 *)st + offsetof(ZStat, max_huf_log), 0, 4, c->stream));
-        HIP_TRY(c, hipMemsetAsync((u8 *)st + offsetof(ZStat, n_flat), 0, 4, c->stream));
-        HIP_TRY(c, hipMemsetAsync((u8 *)st + offsetof(ZStat, n_huf_built), 0, 4, c->stream));
-    }
-    // (a final Raw block is allowed: this build's encoder puts the byte with the padding nibble of an odd stream there, so that it does
-    // not bring a seventeenth symbol into the last Huffman block)
-    const bool flat_tail = hs.last_raw != 0 && nblk >= 2 && hs.n_plain_huf == nblk - 1;
-    if (ctx_tracing(c) && c->zflat) ctx_trace(c, "[flat?] spec %d nblk %u seq_blk %u distinct %u built %u n_flat %u log %u plain %u last_raw %u always %u\n", (int)spec, nblk, n_seq_blk, hs.n_huf_distinct, hs.n_huf_built, hs.n_flat, hs.max_huf_log, hs.n_plain_huf, hs.last_raw, always_table);
-    if (c->zflat && lit_only_spec && nblk > 0 && hs.n_huf_distinct == 1 && hs.n_huf_built == 1 && hs.n_flat == 1 && hs.max_huf_log == 4 && (hs.n_plain_huf == nblk || flat_tail) && !always_table) {
-        // every block a plain Huffman block of the same flat 4-bit tree: the caller's emit kernel reads the streams in place
-        ZFlat *zf = c->zflat;
-        const u32 nhb = flat_tail ? nblk - 1 : nblk;                  // the Huffman blocks
-        FlatStream *si = arena_new<FlatStream>(c, 4 * (size_t)nhb + 1); u8 *d_sym = (u8 *)arena_alloc(c, 16);
-        if (!si || !d_sym) return NAF_GPU_ENOMEM;
-        LAUNCH(c, "zstd_set_offsets", k_set_offsets, g, 64, 0, blk, nblk, (const u64 *)sizes, (u32 *)nullptr, (u32 *)nullptr, (u32 *)nullptr);
-        LAUNCH(c, "zstd_flat_streams", k_flat_streams, cdiv(4ull * nhb, 256), 256, 0, d_src, (const ZBlock *)blk, nhb, (const i32 *)own_huf, (const u8 *)huf_pool, si, d_sym, st, (const u64 *)d_total_out, flat_tail ? (u64)(hs.last_raw & 0x7FFFFFFFu) : 0ull);
-        zf->src = d_src; zf->si = si; zf->nslots = 4ull * nhb; zf->sym = d_sym; zf->status = st; zf->ready = true;
-        {
-            const u32 tn = hs.last_raw & 0x7FFFFFFFu; const bool rle = (hs.last_raw >> 31) != 0;       // an RLE block stores one byte
-            zf->tail = flat_tail ? d_src + (hs.end_off - (rle ? 1u : tn)) : nullptr; zf->tail_q = hs.total_out - (flat_tail ? tn : 0u);
-            zf->tail_n = flat_tail ? (rle ? tn | 0x80000000u : tn) : 0u;
-        }
-        if (rg) { rg->got_lo = 0; rg->got_hi = hs.total_out; rg->ranged = false; }      // nothing was decoded: the emit kernel finds any byte of the stream itself
-        *out_len = hs.total_out;
-        if (fh.has_fcs && fh.content_size != hs.total_out) return zerr(c, ZE_CORRUPT, "content size mismatch");
-        return 0;
-    }
-    // Most blocks flat, some not (ctx.h: ZFlat, `cls`): the blocks that are not, and their neighbours, are decoded into d_dst at their
-    // natural offsets; the caller's emit reads the rest in place.  Whole-stream calls only; a frame whose blocks mostly need
-    // decoding takes the ordinary path below (NAF_GPU_FLAT_MIXED=0: always).
-    {
-        const char *fm = ctx_opt(c, "FLAT_MIXED");
-        if (c->zflat && lit_only_spec && nblk > 0 && !always_table && !rg && hs.flat_main_inv && d_dst && hs.total_out <= dst_cap && !(fm && fm[0] == '0')) {
-            const u32 main = 0xFFFFFFFFu - hs.flat_main_inv;
-            ZFlat *zf = c->zflat;
-            FlatStream *si = arena_new<FlatStream>(c, 4 * (size_t)nblk + 1); u8 *d_sym = (u8 *)arena_alloc(c, 16);
-            u8 *cls0 = (u8 *)arena_alloc(c, nblk), *cls = (u8 *)arena_alloc(c, nblk); u32 *d_nx = arena_new<u32>(c, 2);
-            if (!si || !d_sym || !cls0 || !cls || !d_nx) return NAF_GPU_ENOMEM;
-            HIP_TRY(c, hipMemsetAsync(d_nx, 0, 8, c->stream));
-            LAUNCH(c, "zstd_set_offsets", k_set_offsets, g, 64, 0, blk, nblk, (const u64 *)sizes, (u32 *)nullptr, (u32 *)nullptr, (u32 *)nullptr);
-            LAUNCH(c, "zstd_flat_class", k_flat_mark_owner, g, 64, 0, d_src, blk, nblk, (const i32 *)own_huf, main, two_phase ? 1u : 0u);
-            LAUNCH(c, "zstd_flat_class", k_flat_sym, 1, 256, 0, d_src, (const ZBlock *)blk, main, (const u8 *)huf_pool, d_sym);
-            LAUNCH(c, "zstd_flat_class", k_flat_class, g, 64, 0, (const ZBlock *)blk, nblk, (const i32 *)own_huf, cls0, d_nx + 1);
-            LAUNCH(c, "zstd_flat_class", k_flat_class2, g, 64, 0, (const u8 *)cls0, nblk, cls, d_nx);
-            u32 nx2[2] = { 0, 0 };
-            if ((rc = ctx_readback(c, nx2, d_nx, 8))) return rc;
-            const u32 n_dec = nx2[0], n_walk = nx2[1];
-            if (ctx_tracing(c)) ctx_trace(c, "[flat mixed] nblk %u decoded %u main %u\n", nblk, n_dec, main);
-            if ((u64)n_dec * 2 <= nblk) {
-                LAUNCH(c, "zstd_flat_streams", k_flat_streams_mixed, cdiv(4ull * nblk, 256), 256, 0, d_src, (const ZBlock *)blk, nblk, (const u8 *)cls, si, st, (const u64 *)d_total_out);
-                zf->decoded_ev = nullptr; zf->later = nullptr;
-                if (n_dec) {
-                    // The decode of those blocks -- with the tables still to be built for them -- is handed back to the caller as a job: it
-                    // runs once the caller has queued its tile index, on the caller's spare stream when there is one, beside the emit of
-                    // the flat tiles, which needs none of it (zstd_flat_later).
-                    const bool pending = two_phase && hs.n_huf_distinct > HUF_FEW;
-                    const ZStat hs0 = hs; naf_gpu_ctx *mc = c; naf_gpu_ctx *aux = zf->aux;
-                    const u64 src_len64 = (u64)src_len;
-                    zf->later = new std::function<int()>([=]() -> int {
-                        naf_gpu_ctx *c = aux ? aux : mc;
-                        if (c != mc) HIP_TRY(mc, hipStreamWaitEvent(c->stream, mc->split_ev[0], 0));      // recorded by the caller behind its tile index
-                        const u32 plog = n_walk ? huf_par_plog(c, hs0.max_lit_regen, n_walk) : 0u;
-                        u32 max_log = hs0.max_huf_log;
-                        if (pending && n_walk && !plog) {
-                            // the one-lane-per-stream kernel takes its tables from the pool: the trees left out so far, now
-                            { int r3 = launch_build_huf(c, nblk, d_src, blk, nblk, huf_pool, pool_cap, st, 0u, (const u64 *)nullptr, 0u, (const i32 *)own_huf, 1u, 2u); if (r3) { if (c != mc) memcpy(mc->err, c->err, sizeof mc->err); return r3; } }
-                            ZStat h2; int r2 = ctx_readback(c, &h2, st, sizeof h2);
-                            if (r2) { if (c != mc) memcpy(mc->err, c->err, sizeof mc->err); return r2; }
-                            if (h2.err) return zerr(mc, h2.err, "Huffman tables");
-                            max_log = h2.max_huf_log;
-                        }
-                        if (hs0.n_plain_huf != nblk) LAUNCH(c, "zstd_copy_fill", k_copy_fill<64>, 4 * nblk, 64, 0, d_src, (const ZBlock *)blk, nblk, d_dst, (u8 *)nullptr, 0u, (const u8 *)cls);
-                        LAUNCH(c, "zstd_flat_literals", k_flat_literals<64>, 4 * nblk, 64, 0, d_src, (const ZBlock *)blk, nblk, (const i32 *)own_huf, (const u8 *)huf_pool, d_dst, (u8 *)nullptr, st, 0u, (const u8 *)cls);
-                        if (n_walk && plog) {
-                            // (k_huf_par builds the tables it lacks itself, a workgroup at a time, in LDS)
-                            const u32 slot = pending ? (u32)HUF_TAB_MAX : huf_slot_bytes(max_log);
-                            LAUNCH(c, "zstd_huf_literals", k_huf_par, cdiv((u64)nblk << (plog + 2), 64), 64, (plog >= 4 ? 1u : 16u >> plog) * slot,
-                                   d_src, (const ZBlock *)blk, nblk, (const i32 *)own_huf, (const u8 *)huf_pool, slot, d_dst, (u8 *)nullptr, st, 0u, plog, (const u8 *)cls, 1u, huf_par_margin_env(c), pending ? 1u : 0u, src_len64);
-                        } else if (n_walk) {
-                            const u32 slot = huf_slot_bytes(max_log), ipitch = max_log > 7 ? HUF_IROW_BIG : HUF_IROW;
-                            EmitP ep; memset(&ep, 0, sizeof ep);
-                            LAUNCH(c, "zstd_huf_literals", (k_huf_literals<false>), cdiv(nblk, HUF_BLOCKS_PER_WG), 64, slot * HUF_BLOCKS_PER_WG + 64 * ipitch + 64 * HUF_OROW + 512,
-                                   d_src, (const ZBlock *)blk, nblk, (const i32 *)own_huf, (const u8 *)huf_pool, slot, d_dst, (u8 *)nullptr, st, 0u, ep, (u8 *)nullptr, ipitch, src_len64, 1u, (const u8 *)cls);
-                        }
-                        return 0;
-                    });
-                }
-                zf->src = d_src; zf->si = si; zf->nslots = 4ull * nblk; zf->sym = d_sym; zf->status = st; zf->ready = true;
-                zf->tail = nullptr; zf->tail_q = hs.total_out; zf->tail_n = 0; zf->cls = cls; zf->n_decoded = n_dec; zf->n_walk = n_walk;
-                *out_len = hs.total_out;
-                if (fh.has_fcs && fh.content_size != hs.total_out) return zerr(c, ZE_CORRUPT, "content size mismatch");
-                return 0;
-            }
-        }
-    }
-    if (two_phase && hs.n_huf_distinct > HUF_FEW) {
-        // not a frame for the in-place emit after all: the tables phase 1 left out, now
-        if ((rc = launch_build_huf(c, nblk, d_src, blk, nblk, huf_pool, pool_cap, st, 0u, (const u64 *)nullptr, 0u, (const i32 *)own_huf, 1u, 2u))) return rc;
-        rc = ctx_readback(c, &hs, st, sizeof hs); if (rc) return rc;
-        if (hs.err) return zerr(c, hs.err, "Huffman tables");
-    }
-    u64 *d_total_seq = (u64 *)((u8 *)st + offsetof(ZStat, total_seq));
-    FseE *fse_pool = nullptr; u32 *o_ll = nullptr, *o_ml = nullptr, *o_of = nullptr;
-    if (n_seq_blk) {
-        if ((rc = scan_inclusive_max_i32(c, own_ll, nblk))) return rc;
-        if ((rc = scan_inclusive_max_i32(c, own_of, nblk))) return rc;
-        if ((rc = scan_inclusive_max_i32(c, own_ml, nblk))) return rc;
-        if ((rc = scan_exclusive_u64(c, seq_cnt, nblk, d_total_seq))) return rc;
-        u32 fse_cap = n_seq_blk * (512 + 256 + 512);
-        fse_pool = arena_new<FseE>(c, fse_cap);
-        if (!fse_pool) return NAF_GPU_ENOMEM;
-        LAUNCH(c, "zstd_build_fse", k_build_fse, cdiv(3 * (u64)nblk, 64), 64, 0, d_src, blk, nblk, fse_pool, fse_cap, st);
-        rc = ctx_readback(c, &hs, st, sizeof hs); if (rc) return rc;
-        if (hs.err) return zerr(c, hs.err, "table build");
-        size_t ns = hs.total_seq ? hs.total_seq : 1;
-        o_ll = arena_new<u32>(c, ns); o_ml = arena_new<u32>(c, ns); o_of = arena_new<u32>(c, ns);
-        if (!o_ll || !o_ml || !o_of) return NAF_GPU_ENOMEM;
-    }
-    u32 *seq_list = nullptr;                                 // indices of the blocks that have sequences, in order
-    u64 *seq_rank = nullptr;                                 // blocks with sequences in front of block i
-    if (n_seq_blk) {
-        seq_list = arena_new<u32>(c, n_seq_blk);
-        u64 *flag = arena_new<u64>(c, (size_t)nblk + 1); seq_rank = flag;
-        if (!seq_list || !flag) return NAF_GPU_ENOMEM;
-        LAUNCH(c, "zstd_seq_flag", k_seq_flag, g, 64, 0, (const ZBlock *)blk, nblk, flag);
-        if ((rc = scan_exclusive_u64(c, flag, nblk, (u64 *)nullptr))) return rc;
-        LAUNCH(c, "zstd_seq_list", k_seq_list, g, 64, 0, (const ZBlock *)blk, nblk, (const u64 *)flag, seq_list);
-    }
-    if (!lit_only_spec) {
-        // (a lane per block, every lane on a chain of its own: a frame of a few thousand blocks spreads over more wavefronts, 16 lanes each)
-        const u32 dsl = nblk < 32768 ? 16u : 64u;
-        // blocks under tables of their own (libzstd's) by a wavefront each with the tables in LDS, the others a lane per block
-        const u32 all_wave = ctx_opt_is(c, "SEQ_WAVE", 'a') ? 1u : 0u;
-        const u32 own_tabs = (n_seq_blk && !ctx_opt_is(c, "SEQ_WAVE", '0')) ? 1u + all_wave : 0u;
-        u32 *wave_list = own_tabs ? arena_new<u32>(c, n_seq_blk) : nullptr;
-        if (own_tabs && !wave_list) return NAF_GPU_ENOMEM;
-        LAUNCH(c, "zstd_decode_seq", k_decode_seq, cdiv(nblk, dsl), dsl, 0, d_src, blk, nblk, (const i32 *)own_ll, (const i32 *)own_of, (const i32 *)own_ml,
-               (const u64 *)seq_cnt, (const FseE *)fse_pool, (const FseE *)c->d_predef, o_ll, o_ml, o_of, sizes, st, own_tabs, wave_list);
-        const u32 wgrid = n_seq_blk < 8192u ? n_seq_blk : 8192u;
-        if (own_tabs && ctx_opt_is(c, "SEQ_WAVE", 'l'))       // (kept as a cross-check: one lane walking the block with the general routine's shape)
-            LAUNCH(c, "zstd_decode_seq", k_decode_seq_wave, wgrid, 64, 0, d_src, blk, (const u32 *)wave_list, (const i32 *)own_ll, (const i32 *)own_of, (const i32 *)own_ml,
-                   (const u64 *)seq_cnt, (const FseE *)fse_pool, (const FseE *)c->d_predef, o_ll, o_ml, o_of, sizes, st);
-        else if (own_tabs)
-            LAUNCH(c, "zstd_decode_seq", k_decode_seq_wave2, wgrid, 64, 0, d_src, blk, (const u32 *)wave_list, (const i32 *)own_ll, (const i32 *)own_of, (const i32 *)own_ml,
-                   (const u64 *)seq_cnt, (const FseE *)fse_pool, (const FseE *)c->d_predef, o_ll, o_ml, o_of, sizes, st, all_wave | (ctx_opt_is(c, "SEQ_REP", 'w') ? 2u : 0u));
-        if (n_seq_blk) LAUNCH(c, "zstd_rep_fast", k_rep_fast, cdiv(n_seq_blk, 256), 256, 0, blk, (const u32 *)seq_list, n_seq_blk, st);
-        if ((rc = scan_exclusive_u64(c, sizes, nblk, d_total_out))) return rc;
-        rc = ctx_readback(c, &hs, st, sizeof hs); if (rc) return rc;
-        if (hs.err) return zerr(c, hs.err, "sequences");
-    }
-    const u32 max_seq_regen = hs.max_seq_regen;
-    if (ctx_tracing(c) && n_seq_blk) ctx_trace(c, "[seq] blocks %u with sequences %u sequences %llu out %llu\n", nblk, n_seq_blk, (unsigned long long)hs.total_seq, (unsigned long long)hs.total_out);
+    // ---- parse + ownership, the exits of a literal-only frame that is read in place
+    if ((rc = parse_ownership(F))) return rc;
+    if ((rc = exit_all_flat(F))) return rc == Z_HANDED ? 0 : rc;                                                                  // exit 4
+    if (F.lit_only_spec && mostly_flat_wanted(F) && (rc = exit_mostly_flat(F, false))) return rc == Z_HANDED ? 0 : rc;            // exit 5
+    // not a frame for the in-place emit after all: the tables phase 1 left out, now
+    if (F.two_phase && F.hs.n_huf_distinct > HUF_FEW && (rc = build_huf_rest(c, F, &F.hs))) return rc;
+    // ---- sequences
+    if ((rc = sequences(F))) return rc;
+    F.max_seq_regen = F.hs.max_seq_regen;
+    if (ctx_tracing(c) && F.n_seq_blk) ctx_trace(c, "[seq] blocks %u with sequences %u sequences %llu out %llu\n", F.nblk, F.n_seq_blk, (unsigned long long)F.hs.total_seq, (unsigned long long)F.hs.total_out);
     // entry states matter only when some sequence of the frame uses a repeat code (this build's own LZ blocks never do)
-    if (n_seq_blk && (hs.rep_slow & 1)) LAUNCH(c, "zstd_rep_chain", k_rep_chain, 1, 64, 0, blk, nblk);
-    *out_len = hs.total_out;
-    if (fh.has_fcs && fh.content_size != hs.total_out) return zerr(c, ZE_CORRUPT, "content size mismatch");
+    if (F.n_seq_blk && (F.hs.rep_slow & 1)) LAUNCH(c, "zstd_rep_chain", k_rep_chain, 1, 64, 0, F.blk, F.nblk);
+    *out_len = F.hs.total_out;
+    if (F.fh.has_fcs && F.fh.content_size != F.hs.total_out) return zerr(c, ZE_CORRUPT, "content size mismatch");
     // A frame that is mostly flat AND has a few blocks with matches -- what libzstd makes of packed random bases: one 4-bit tree,
     // treeless blocks behind it, a chance match every few dozen blocks -- takes the mostly-flat way too: the blocks with sequences, the
     // blocks their matches copy from (k_seq_sources) and the neighbours of both are decoded into d_dst (literals, then the executor,
     // as below), everything else is read in place by the caller's emit.  Whole-stream calls (NAF_GPU_FLAT_SEQ=0: never).
-    {
-        const char *fm = ctx_opt(c, "FLAT_MIXED"), *fsq = ctx_opt(c, "FLAT_SEQ");
-        if (c->zflat && spec && n_seq_blk && tables_built && !fuse && !always_table && !rg && hs.flat_main_inv && d_dst && hs.total_out <= dst_cap &&
-            (u64)n_seq_blk * 8 <= nblk && !(fm && fm[0] == '0') && !(fsq && fsq[0] == '0')) {
-            const u32 main = 0xFFFFFFFFu - hs.flat_main_inv;
-            ZFlat *zf = c->zflat;
-            FlatStream *si = arena_new<FlatStream>(c, 4 * (size_t)nblk + 1); u8 *d_sym = (u8 *)arena_alloc(c, 16);
-            u8 *cls0 = (u8 *)arena_alloc(c, nblk), *cls = (u8 *)arena_alloc(c, nblk); u32 *d_nx = arena_new<u32>(c, 2);
-            u32 *done2 = arena_new<u32>(c, nblk); u8 *lits = (u8 *)arena_alloc(c, hs.total_out + 16);
-            if (!si || !d_sym || !cls0 || !cls || !d_nx || !done2 || !lits) return NAF_GPU_ENOMEM;
-            HIP_TRY(c, hipMemsetAsync(d_nx, 0, 8, c->stream));
-            LAUNCH(c, "zstd_set_offsets", k_set_offsets, g, 64, 0, blk, nblk, (const u64 *)sizes, done2, (u32 *)nullptr, (u32 *)nullptr);
-            LAUNCH(c, "zstd_flat_class", k_flat_mark_owner, g, 64, 0, d_src, blk, nblk, (const i32 *)own_huf, main, 0u);
-            LAUNCH(c, "zstd_flat_class", k_flat_sym, 1, 256, 0, d_src, (const ZBlock *)blk, main, (const u8 *)huf_pool, d_sym);
-            LAUNCH(c, "zstd_flat_class", k_flat_class, g, 64, 0, (const ZBlock *)blk, nblk, (const i32 *)own_huf, cls0, d_nx + 1);
-            LAUNCH(c, "zstd_flat_class", k_seq_sources, cdiv(n_seq_blk, 64), 64, 0, (const ZBlock *)blk, (const u32 *)seq_list, n_seq_blk, (const u64 *)sizes, (const u32 *)o_ll, (const u32 *)o_ml, (const u32 *)o_of, cls0);
-            LAUNCH(c, "zstd_flat_class", k_flat_class2, g, 64, 0, (const u8 *)cls0, nblk, cls, d_nx);
-            u32 nx2[2] = { 0, 0 };
-            if ((rc = ctx_readback(c, nx2, d_nx, 8))) return rc;
-            const u32 n_dec = nx2[0], n_walk = nx2[1];
-            if (ctx_tracing(c)) ctx_trace(c, "[flat mixed] nblk %u decoded %u main %u (blocks with sequences %u)\n", nblk, n_dec, main, n_seq_blk);
-            if ((u64)n_dec * 2 <= nblk) {
-                LAUNCH(c, "zstd_flat_streams", k_flat_streams_mixed, cdiv(4ull * nblk, 256), 256, 0, d_src, (const ZBlock *)blk, nblk, (const u8 *)cls, si, st, (const u64 *)d_total_out);
-                zf->decoded_ev = nullptr;
-                const ZStat hs0 = hs; naf_gpu_ctx *mc = c; naf_gpu_ctx *aux = zf->aux; const u64 ns_all = hs.total_seq;
-                const u64 src_len64 = (u64)src_len;
-                zf->later = new std::function<int()>([=]() -> int {
-                    naf_gpu_ctx *c = aux ? aux : mc;
-                    if (c != mc) HIP_TRY(mc, hipStreamWaitEvent(c->stream, mc->split_ev[0], 0));      // recorded by the caller behind its tile index
-                    const u32 plog = n_walk ? huf_par_plog(c, hs0.max_lit_regen, n_walk) : 0u;
-                    LAUNCH(c, "zstd_copy_fill", k_copy_fill<64>, 4 * nblk, 64, 0, d_src, (const ZBlock *)blk, nblk, d_dst, lits, 0u, (const u8 *)cls);
-                    LAUNCH(c, "zstd_flat_literals", k_flat_literals<64>, 4 * nblk, 64, 0, d_src, (const ZBlock *)blk, nblk, (const i32 *)own_huf, (const u8 *)huf_pool, d_dst, lits, st, 0u, (const u8 *)cls);
-                    if (n_walk && plog) {
-                        const u32 slot = huf_slot_bytes(hs0.max_huf_log);
-                        LAUNCH(c, "zstd_huf_literals", k_huf_par, cdiv((u64)nblk << (plog + 2), 64), 64, (plog >= 4 ? 1u : 16u >> plog) * slot,
-                               d_src, (const ZBlock *)blk, nblk, (const i32 *)own_huf, (const u8 *)huf_pool, slot, d_dst, lits, st, 0u, plog, (const u8 *)cls, 1u, huf_par_margin_env(c), 0u, src_len64);
-                    } else if (n_walk) {
-                        const u32 slot = huf_slot_bytes(hs0.max_huf_log), ipitch = hs0.max_huf_log > 7 ? HUF_IROW_BIG : HUF_IROW;
-                        EmitP ep; memset(&ep, 0, sizeof ep);
-                        LAUNCH(c, "zstd_huf_literals", (k_huf_literals<false>), cdiv(nblk, HUF_BLOCKS_PER_WG), 64, slot * HUF_BLOCKS_PER_WG + 64 * ipitch + 64 * HUF_OROW + 512,
-                               d_src, (const ZBlock *)blk, nblk, (const i32 *)own_huf, (const u8 *)huf_pool, slot, d_dst, lits, st, 0u, ep, (u8 *)nullptr, ipitch, src_len64, 1u, (const u8 *)cls);
-                    }
-                    const char *el = ctx_opt(c, "EXEC_LDS");
-                    if (hs0.max_seq_regen <= EXEC_LDS && !(el && el[0] == '0'))
-                         LAUNCH(c, "zstd_exec_seq", k_exec_seq_lds, n_seq_blk, 64, ((hs0.max_seq_regen + 1023u) & ~1023u) + 64u + 2u * EXEC_PJ_MAX, (const ZBlock *)blk, (const u32 *)seq_list, n_seq_blk, (const u64 *)sizes, nblk,
-                               (const u32 *)o_ll, (const u32 *)o_ml, (const u32 *)o_of, (const u8 *)lits, d_dst, done2, st, (hs0.max_seq_regen + 1023u) & ~1023u);
-                    else { const int rcx = launch_lz_exec(c, (const ZBlock *)blk, (const u32 *)seq_list, n_seq_blk, (const u64 *)sizes, (const u64 *)seq_cnt, nblk, ns_all, o_ll, o_ml, o_of, (const u8 *)lits, d_dst, done2, st); if (rcx) return rcx; }
-                    return 0;
-                });
-                zf->src = d_src; zf->si = si; zf->nslots = 4ull * nblk; zf->sym = d_sym; zf->status = st; zf->ready = true;
-                zf->tail = nullptr; zf->tail_q = hs.total_out; zf->tail_n = 0; zf->cls = cls; zf->n_decoded = n_dec; zf->n_walk = n_walk;
-                return 0;
-            }
-        }
-    }
-    // Range request (multi-GPU sharding): decode only the blocks that feed [want_lo, want_hi).  Needs blocks that
-    // do not reference earlier output, i.e. a frame without sequences (this build's own frames; reference-made
-    // random-ACGT frames); otherwise the whole frame is decoded.
-    u32 b_first = 0, b_count = nblk, huf_first = 0; u64 bias = 0;
-    u32 seq_t0 = 0, seq_t1 = n_seq_blk;                          // the blocks with sequences among the decoded ones: seq_list[seq_t0 .. seq_t1)
-    if (fuse) { d_dst = nullptr; dst_cap = ~(size_t)0; }
-    if (rg) { rg->got_lo = 0; rg->got_hi = hs.total_out; rg->ranged = false; rg->own_buf = nullptr; }
-    if (rg && n_seq_blk == 0 && nblk > 0 && rg->want_hi > rg->want_lo) {
-        if (!lit_only_spec) {
-            u64 *r4b = arena_new<u64>(c, 5); if (!r4b) return NAF_GPU_ENOMEM;
-            LAUNCH(c, "zstd_find_range", k_find_range, 1, 64, 0, (const u64 *)sizes, nblk, (const u64 *)d_total_out, rg->want_lo, rg->want_hi, (const i32 *)own_huf, r4b);
-            rc = ctx_readback(c, h4, r4b, 40); if (rc) return rc;
-        }
-        huf_first = (u32)h4[4];
-        b_first = (u32)h4[0]; b_count = (u32)(h4[1] - h4[0]); bias = h4[2];
-        rg->got_lo = h4[2]; rg->got_hi = h4[3]; rg->ranged = true;
-        if (h4[3] - h4[2] > dst_cap) return ctx_fail(c, NAF_GPU_ECAP, "zstd range output needs %llu bytes, capacity %zu", (unsigned long long)(h4[3] - h4[2]), dst_cap);
-        d_dst -= bias;                                       // block b lands at d_dst_orig + (out_off[b] - got_lo)
-    } else if (rg && n_seq_blk && nblk > 0 && rg->want_hi > rg->want_lo && !(ctx_opt(c, "RANGE_CLOSURE") && ctx_opt(c, "RANGE_CLOSURE")[0] == '0')) {
-        // blocks with matches: the range's dependency closure (kernels above).  On archives that are mostly literals -- what the
-        // reference makes of a genome at its default level -- that is the range's own blocks and a few in front of them.
-        u32 *f = arena_new<u32>(c, nblk); u64 *r4b = arena_new<u64>(c, 5 + 8); if (!f || !r4b) return NAF_GPU_ENOMEM;
-        LAUNCH(c, "zstd_find_range", k_find_range, 1, 64, 0, (const u64 *)sizes, nblk, (const u64 *)d_total_out, rg->want_lo, rg->want_hi, (const i32 *)own_huf, r4b);
-        LAUNCH(c, "zstd_range_closure", k_iota_u32, g, 64, 0, f, nblk);
-        LAUNCH(c, "zstd_range_closure", k_seq_reach, cdiv(n_seq_blk, 64), 64, 0, (const ZBlock *)blk, (const u32 *)seq_list, n_seq_blk, (const u64 *)sizes, (const u32 *)o_ll, (const u32 *)o_ml, (const u32 *)o_of, f);
-        LAUNCH(c, "zstd_range_closure", k_range_closure, 1, 64, 0, (const u32 *)f, (const u64 *)sizes, nblk, (const u64 *)d_total_out, (const u64 *)r4b, (const i32 *)own_huf, (const u64 *)seq_rank, n_seq_blk, r4b + 5);
-        u64 h7[7]; rc = ctx_readback(c, h7, r4b + 5, sizeof h7); if (rc) return rc;
-        const u64 need = h7[3] - h7[2];
-        if (ctx_tracing(c)) ctx_trace(c, "[range] want %llu..%llu -> blocks %llu..%llu (bytes %llu..%llu of %llu), tables from %llu, seq blocks %llu..%llu of %u\n", (unsigned long long)rg->want_lo, (unsigned long long)rg->want_hi,
-                    (unsigned long long)h7[0], (unsigned long long)h7[1], (unsigned long long)h7[2], (unsigned long long)h7[3], (unsigned long long)hs.total_out, (unsigned long long)h7[4], (unsigned long long)h7[5], (unsigned long long)h7[6], n_seq_blk);
-        if (need < hs.total_out) {
-            if (need > dst_cap) {
-                // the caller sized its buffer for the range alone: take the closure's from the arena and say so (ZRange.own_buf)
-                d_dst = (u8 *)arena_alloc(c, need + 64); if (!d_dst) return NAF_GPU_ENOMEM;
-                dst_cap = need; rg->own_buf = d_dst;
-            }
-            huf_first = (u32)h7[4];
-            b_first = (u32)h7[0]; b_count = (u32)(h7[1] - h7[0]); bias = h7[2];
-            seq_t0 = (u32)h7[5]; seq_t1 = (u32)h7[6];
-            rg->got_lo = h7[2]; rg->got_hi = h7[3]; rg->ranged = true;
-            d_dst -= bias;
-        } else if (hs.total_out > dst_cap) return ctx_fail(c, NAF_GPU_ECAP, "zstd output needs %llu bytes, capacity %zu", (unsigned long long)hs.total_out, dst_cap);
-    } else if (hs.total_out > dst_cap) return ctx_fail(c, NAF_GPU_ECAP, "zstd output needs %llu bytes, capacity %zu", (unsigned long long)hs.total_out, dst_cap);
-
-    u32 *done = nullptr; u8 *lit_scratch = nullptr;
-    if (n_seq_blk) {
-        done = arena_new<u32>(c, nblk);
-        const u64 span = rg && rg->ranged ? rg->got_hi - rg->got_lo : hs.total_out;
-        lit_scratch = (u8 *)arena_alloc(c, span + 16);
-        if (!done || !lit_scratch) return NAF_GPU_ENOMEM;
-        lit_scratch -= bias;                                     // indexed by a block's place in the whole output, like d_dst
-    }
-    LAUNCH(c, "zstd_set_offsets", k_set_offsets, g, 64, 0, blk, nblk, (const u64 *)sizes, done, (u32 *)nullptr, (u32 *)nullptr);
-    bool copy_fill_done = false;
-    if (n_huf_def) {
-        // tables of the blocks that will be decoded (and of the earlier blocks that own a table in force there)
-        u32 hb_end = b_first + b_count, hb_n = hb_end - huf_first;
-        if (!tables_built) {
-            pool_cap = (hb_n < n_huf_def ? hb_n : n_huf_def) * (u32)HUF_TAB_MAX + 4096u;   // largest table of either form
-            huf_pool = (u8 *)arena_alloc(c, pool_cap);
-            if (!huf_pool) return NAF_GPU_ENOMEM;
-            if (hb_n && hb_n <= 512) LAUNCH(c, "zstd_build_huf", k_build_huf_lds, hb_n, 64, 0, d_src, blk, hb_end, huf_pool, pool_cap, st, huf_first, (const i32 *)own_huf);
-            else if (hb_n) { if ((rc = launch_build_huf(c, hb_n, d_src, blk, hb_end, huf_pool, pool_cap, st, huf_first, (const u64 *)nullptr, (always_table || fuse) ? 1u : 0u, (const i32 *)own_huf, 0u, 0u))) return rc; }
-            rc = ctx_readback(c, &hs, st, sizeof hs); if (rc) return rc;
-            if (hs.err) return zerr(c, hs.err, "Huffman tables");
-        }
-        u32 slot = huf_slot_bytes(hs.max_huf_log);
-        u32 b_end = b_first + b_count;
-        if (fuse && hs.max_huf_log > 7) return ZSTD_NEED_TWO_PASS;
-        EmitP ep; memset(&ep, 0, sizeof ep); if (fuse) ep = *fuse;
-        u32 ipitch = hs.max_huf_log > 7 ? HUF_IROW_BIG : HUF_IROW;
-        u32 ipitch_arg = ipitch | ((ctx_opt(c, "HUF_GENERIC") && ctx_opt(c, "HUF_GENERIC")[0] == '1') ? 0x8000u : 0u);
-        if (b_count && fuse) LAUNCH(c, "zstd_huf_fused_emit", (k_huf_literals<true>), cdiv(b_count, HUF_BLOCKS_PER_WG), 64, slot * HUF_BLOCKS_PER_WG + 64 * ipitch + 512,
-               d_src, (const ZBlock *)blk, b_end, (const i32 *)own_huf, (const u8 *)huf_pool, slot, d_dst, lit_scratch, st, b_first, ep, text, ipitch_arg, (u64)src_len, 0u, (const u8 *)nullptr);
-        else if (b_count) {
-            const u32 huf_lds = slot * HUF_BLOCKS_PER_WG + 64 * ipitch + 64 * HUF_OROW + 512;
-            // blocks whose tree is flat go to k_flat_literals; the serial kernel is not launched when that is all of them
-            const u32 flat_on = (hs.n_flat && !always_table) ? 1u : 0u;
-            const bool serial_needed = !flat_on || hs.n_flat < hs.n_huf_built;
-            const u32 plog = huf_par_plog(c, hs.max_lit_regen, b_count), par_lds = (plog >= 4 ? 1u : 16u >> plog) * slot;
-            // a frame of few trees (this build's frame tree, libzstd's runs of treeless blocks): workgroups with ONE table in LDS, the
-            // workgroups whose blocks are under several trees through a second launch of the plain kernel (NAF_GPU_HUF_SHARED=0: never)
-            u8 *redo = nullptr;
-            { const char *hsx = ctx_opt(c, "HUF_SHARED");
-              if (serial_needed && !plog && (u64)hs.n_huf_distinct * 64 <= b_count && !(hsx && hsx[0] == '0')) {
-                redo = (u8 *)arena_alloc(c, (size_t)nblk + 16); if (!redo) return NAF_GPU_ENOMEM;
-                HIP_TRY(c, hipMemsetAsync(redo, 0, nblk, c->stream));
-              } }
-            const u32 huf_lds_shared = huf_lds - slot * (HUF_BLOCKS_PER_WG - 1u);
-            ZSplit *sp = c->zsplit;
-            const char *smin = ctx_opt(c, "SPLIT_MIN");                      // blocks per part below which a split is not worth its launches (tests lower it)
-            const u32 split_min = smin ? (u32)atoi(smin) : 4096u;
-            if (sp && !rg && n_seq_blk == 0 && b_first == 0 && b_count == nblk && b_count >= split_min * (u32)sp->parts && b_count >= 16u * HUF_BLOCKS_PER_WG * (u32)sp->parts) {
-                // literal-only frame of a whole-text call: block ranges in order, an event behind each (see ZSplit); the raw / RLE
-                // blocks first, so that a finished part is complete
-                if (hs.n_plain_huf != nblk) LAUNCH(c, "zstd_copy_fill", k_copy_fill<256>, b_count, 256, 0, d_src, (const ZBlock *)blk, b_first + b_count, d_dst, lit_scratch, b_first, (const u8 *)nullptr);
-                copy_fill_done = true;
-                // output offsets of the part ends: they came with the counters when the frame took the speculative route
-                if (ends) for (int k = 0; k + 1 < sp->parts; k++) sp->out_end[k] = hends[k];
-                else {
-                    u64 *e2 = arena_new<u64>(c, ZSPLIT_MAX); if (!e2) return NAF_GPU_ENOMEM;
-                    for (int k = 0; k + 1 < sp->parts; k++) {
-                        u32 hi_b = (u32)((u64)b_count * (k + 1) / sp->parts) & ~(HUF_BLOCKS_PER_WG - 1u);
-                        HIP_TRY(c, hipMemcpyAsync(e2 + k, sizes + hi_b, 8, hipMemcpyDeviceToDevice, c->stream));
-                    }
-                    rc = ctx_readback(c, sp->out_end, e2, 8 * (size_t)(sp->parts - 1)); if (rc) return rc;
-                }
-                sp->out_end[sp->parts - 1] = hs.total_out;
-                u32 lo_b = 0;
-                for (int k = 0; k < sp->parts; k++) {
-                    u32 hi_b = k + 1 == sp->parts ? b_count : (u32)((u64)b_count * (k + 1) / sp->parts) & ~(HUF_BLOCKS_PER_WG - 1u);
-                    if (hi_b > lo_b && flat_on) LAUNCH(c, "zstd_flat_literals", k_flat_literals<256>, hi_b - lo_b, 256, 0, d_src, (const ZBlock *)blk, hi_b, (const i32 *)own_huf, (const u8 *)huf_pool, d_dst, lit_scratch, st, lo_b, (const u8 *)nullptr);
-                    if (hi_b > lo_b && serial_needed && plog) LAUNCH(c, "zstd_huf_literals", k_huf_par, cdiv((u64)(hi_b - lo_b) << (plog + 2), 64), 64, par_lds,
-                           d_src, (const ZBlock *)blk, hi_b, (const i32 *)own_huf, (const u8 *)huf_pool, slot, d_dst, lit_scratch, st, lo_b, plog, (const u8 *)nullptr, flat_on, huf_par_margin_env(c), 0u, (u64)src_len);
-                    else if (hi_b > lo_b && serial_needed && redo) {
-                        LAUNCH(c, "zstd_huf_literals", (k_huf_literals<false, true>), cdiv(hi_b - lo_b, HUF_BLOCKS_PER_WG), 64, huf_lds_shared,
-                               d_src, (const ZBlock *)blk, hi_b, (const i32 *)own_huf, (const u8 *)huf_pool, slot, d_dst, lit_scratch, st, lo_b, ep, text, ipitch_arg, (u64)src_len, flat_on, (const u8 *)nullptr, redo);
-                        LAUNCH(c, "zstd_huf_literals", (k_huf_literals<false>), cdiv(hi_b - lo_b, HUF_BLOCKS_PER_WG), 64, huf_lds,
-                               d_src, (const ZBlock *)blk, hi_b, (const i32 *)own_huf, (const u8 *)huf_pool, slot, d_dst, lit_scratch, st, lo_b, ep, text, ipitch_arg, (u64)src_len, flat_on, (const u8 *)redo);
-                    }
-                    else if (hi_b > lo_b && serial_needed) LAUNCH(c, "zstd_huf_literals", (k_huf_literals<false>), cdiv(hi_b - lo_b, HUF_BLOCKS_PER_WG), 64, huf_lds,
-                           d_src, (const ZBlock *)blk, hi_b, (const i32 *)own_huf, (const u8 *)huf_pool, slot, d_dst, lit_scratch, st, lo_b, ep, text, ipitch_arg, (u64)src_len, flat_on, (const u8 *)nullptr);
-                    HIP_TRY(c, hipEventRecord(sp->ev[k], c->stream));
-                    lo_b = hi_b;
-                }
-                sp->done = 1;
-            } else {
-                if (flat_on) LAUNCH(c, "zstd_flat_literals", k_flat_literals<256>, b_count, 256, 0, d_src, (const ZBlock *)blk, b_end, (const i32 *)own_huf, (const u8 *)huf_pool, d_dst, lit_scratch, st, b_first, (const u8 *)nullptr);
-                if (serial_needed && plog) LAUNCH(c, "zstd_huf_literals", k_huf_par, cdiv((u64)b_count << (plog + 2), 64), 64, par_lds,
-                   d_src, (const ZBlock *)blk, b_end, (const i32 *)own_huf, (const u8 *)huf_pool, slot, d_dst, lit_scratch, st, b_first, plog, (const u8 *)nullptr, flat_on, huf_par_margin_env(c), 0u, (u64)src_len);
-                else if (serial_needed && redo) {
-                    LAUNCH(c, "zstd_huf_literals", (k_huf_literals<false, true>), cdiv(b_count, HUF_BLOCKS_PER_WG), 64, huf_lds_shared,
-                       d_src, (const ZBlock *)blk, b_end, (const i32 *)own_huf, (const u8 *)huf_pool, slot, d_dst, lit_scratch, st, b_first, ep, text, ipitch_arg, (u64)src_len, flat_on, (const u8 *)nullptr, redo);
-                    LAUNCH(c, "zstd_huf_literals", (k_huf_literals<false>), cdiv(b_count, HUF_BLOCKS_PER_WG), 64, huf_lds,
-                       d_src, (const ZBlock *)blk, b_end, (const i32 *)own_huf, (const u8 *)huf_pool, slot, d_dst, lit_scratch, st, b_first, ep, text, ipitch_arg, (u64)src_len, flat_on, (const u8 *)redo);
-                }
-                else if (serial_needed) LAUNCH(c, "zstd_huf_literals", (k_huf_literals<false>), cdiv(b_count, HUF_BLOCKS_PER_WG), 64, huf_lds,
-                   d_src, (const ZBlock *)blk, b_end, (const i32 *)own_huf, (const u8 *)huf_pool, slot, d_dst, lit_scratch, st, b_first, ep, text, ipitch_arg, (u64)src_len, flat_on, (const u8 *)nullptr);
-            }
-        }
-    }
-    if (b_count && !fuse && !copy_fill_done && hs.n_plain_huf != nblk) LAUNCH(c, "zstd_copy_fill", k_copy_fill<256>, b_count, 256, 0, d_src, (const ZBlock *)blk, b_first + b_count, d_dst, lit_scratch, b_first, (const u8 *)nullptr);
-    if (seq_t1 > seq_t0) {
-        const char *el = ctx_opt(c, "EXEC_LDS");                      // "0": always the HBM executor (cross-check)
-        const u32 nx = seq_t1 - seq_t0;
-        if (max_seq_regen <= EXEC_LDS && !(el && el[0] == '0'))
-             LAUNCH(c, "zstd_exec_seq", k_exec_seq_lds, nx, 64, ((max_seq_regen + 1023u) & ~1023u) + 64u + 2u * EXEC_PJ_MAX, (const ZBlock *)blk, (const u32 *)(seq_list + seq_t0), nx, (const u64 *)sizes, nblk,
-                   (const u32 *)o_ll, (const u32 *)o_ml, (const u32 *)o_of, (const u8 *)lit_scratch, d_dst, done, st, (max_seq_regen + 1023u) & ~1023u);
-        else if ((rc = launch_lz_exec(c, (const ZBlock *)blk, (const u32 *)(seq_list + seq_t0), nx, (const u64 *)sizes, (const u64 *)seq_cnt, nblk, hs.total_seq, o_ll, o_ml, o_of, (const u8 *)lit_scratch, d_dst, done, st))) return rc;
-    }
-    if (c->zsplit && c->zsplit->done) { c->zsplit->status = st; return 0; }      // the caller checks the status once the emit is queued (zstd_split_status)
-    rc = ctx_readback(c, &hs, st, sizeof hs); if (rc) return rc;
+    if (F.n_seq_blk && F.tables_built && (u64)F.n_seq_blk * 8 <= F.nblk && !ctx_opt_is(c, "FLAT_SEQ", '0') && mostly_flat_wanted(F) &&
+        (rc = exit_mostly_flat(F, true))) return rc == Z_HANDED ? 0 : rc;                                                         // exit 6
+    // ---- range, literals, executor
+    if ((rc = range_select(F))) return rc;
+    if ((rc = literals(F))) return rc;
+    if (F.seq_t1 > F.seq_t0 && (rc = launch_exec(c, F, (const u32 *)(F.seq_list + F.seq_t0), F.seq_t1 - F.seq_t0, (const u8 *)F.lit_scratch, F.dst, F.done))) return rc;
+    // ---- final status
+    if (c->zsplit && c->zsplit->done) { c->zsplit->status = F.st; return 0; }      // exit 7: the caller checks the status once the emit is queued (zstd_split_status)
+    if ((rc = ctx_readback(c, &F.hs, F.st, sizeof F.hs))) return rc;
 #ifdef NAF_EXEC_PROF
-    if (hs.prof[6]) fprintf(stderr, "[exec prof] blocks %llu seqs %llu | cycles per block: load+scan %llu literals %llu hops %llu final copies %llu serial %llu | serial matches per block %.1f\n", hs.prof[6], hs.prof[7],
+    const ZStat &hs = F.hs; if (hs.prof[6]) fprintf(stderr, "[exec prof] blocks %llu seqs %llu | cycles per block: load+scan %llu literals %llu hops %llu final copies %llu serial %llu | serial matches per block %.1f\n", hs.prof[6], hs.prof[7],
                             hs.prof[0] / hs.prof[6], hs.prof[1] / hs.prof[6], hs.prof[2] / hs.prof[6], hs.prof[3] / hs.prof[6], hs.prof[4] / hs.prof[6], (double)hs.prof[5] / (double)hs.prof[6]);
 #endif
-    if (hs.err) return zerr(c, hs.err, "block decode");
+    if (F.hs.err) return zerr(c, F.hs.err, "block decode");
     return 0;
 }
-
-// the job a mostly-flat frame's decoder left for after the caller's tile index (ctx.h: ZFlat.later); aux_used: the job went to the spare stream
-int zstd_flat_later(naf_gpu_ctx *c, ZFlat *zf)
-{
-    if (!zf || !zf->later) return 0;
-    std::function<int()> *f = (std::function<int()> *)zf->later; zf->later = nullptr;
-    const int rc = (*f)();
-    delete f;
-    return rc;
-}
-void zstd_flat_drop(ZFlat *zf) { if (zf && zf->later) { delete (std::function<int()> *)zf->later; zf->later = nullptr; } }
 
 // status of a split decode whose final read-back was left to the caller
 int zstd_split_status(naf_gpu_ctx *c, const ZSplit *sp)
