@@ -281,6 +281,55 @@ int  naf_gpu_unnaf_composition(naf_gpu_ctx *ctx, const void *d_naf, size_t naf_l
                                uint64_t first, uint64_t count, naf_gpu_comp_row *d_rows, size_t row_cap,
                                uint64_t *n_rows, naf_gpu_comp_row *h_total);
 
+/* ---- unnaf: quality statistics per read and per cycle, counted in the quality stream -----------------------------
+ * What seqkit fx2tab -q, seqkit stats -a and FastQC's per-base quality answer from the FASTQ text, counted from the stored quality codes
+ * without composing that text.  Two tables of the same row, a histogram of the byte values and a total; all arithmetic is integer
+ * arithmetic, and the rows are the same bytes on every run and for every piece size.
+ *   Error table   naf_gpu_quality_error_table: tab[b] = 2^32 for b < 33, round_half_up(2^32 * 10^(-(b - 33) / 10)) for b >= 33 (0 from
+ *                 b = 133 on): the error probability of Phred+33 code b times 2^32.  Integer literals in the library, not pow at run
+ *                 time: tab[33] = 4294967296, tab[43] = 429496730, tab[53] = 42949673, tab[73] = 429497, tab[126] = 2; entries 33..126
+ *                 sum to 20882629606.  Sums of it (ee) are taken mod 2^64; no row of fewer than 2^32 codes can wrap.
+ *   Records       [first, first + count), count = NAF_GPU_WHOLE: to the last record.  first > n_sequences and a range past the last
+ *                 record are NAF_GPU_EARG, as for naf_gpu_unnaf_composition; an archive without a quality section is NAF_GPU_EARG
+ *                 ("no quality" in last_error).  Any sequence type is accepted, protein and text included: the lengths and the quality
+ *                 section are all that is decoded, never the sequence or the mask (an archive with qualities whose sequence section was
+ *                 cut out is NAF_GPU_EARG: its lengths have nothing to be held against).  An archive without records gives 0 rows.
+ *   Record table  exactly one row per record, ascending: key = the record's number, n = its length.  An empty read gives n = 0, sum = 0,
+ *                 ee = 0, min = 255, max = 0.  d_rec_rows == NULL: the table is not wanted; rec_cap is ignored, *n_records is still set.
+ *   Cycle table   cycle_bin = W >= 1: ceil(maxlen / W) rows, maxlen the longest SELECTED record (0 rows when all of them are empty);
+ *                 row k holds every quality code of every selected record whose 0-based position in its read lies in [k W, (k + 1) W).
+ *                 cycle_bin = 0: no cycle table, *n_cycle_rows = 0.  d_cycle_rows == NULL with W > 0: the table is not wanted
+ *                 (*n_cycle_rows is still set).  Both tables NULL is legal: h_hist and h_total are then all that is made.
+ *   h_hist        HOST, may be NULL: the count per byte value over the selected records.
+ *   h_total       HOST, may be NULL: the sum over the selected records; its key is the number of records covered, its min and max are
+ *                 taken over all their codes.
+ *   Capacity      the d_* pointers are DEVICE memory of any alignment; exactly 56 * rows bytes of each wanted table are written and
+ *                 nothing else.  If either wanted table's capacity is too small the call returns NAF_GPU_ECAP, sets both counts to the
+ *                 whole sizes and writes nothing to either table.
+ *   Malformed     a quality stream shorter than the bases of the records is NAF_GPU_EFORMAT ("corrupted quality").  Bytes behind the
+ *                 last record's last code are in no row and not in h_hist.
+ *   Pieces        more quality bytes than NAF_GPU_QUALITY_PIECE (default 2^31) are decoded and counted in pieces of whole records; the
+ *                 result does not depend on the piece size.  Only the zstd blocks behind the selected records are decoded when the
+ *                 frame allows it; a frame of dependent blocks is decoded whole once.
+ * naf_gpu_unnaf_quality_rows needs the lengths section only; no quality byte is decoded.  All 256 byte values are legal codes.
+ * TRACE=1: "[quality] records R cycle rows C pieces P quality bytes decoded X of Y lds bins K global bins G" per counting call. */
+typedef struct {
+    uint64_t key;            /* record table: the record's number.  cycle table: the bin's number k; the bin holds read positions [k W, (k+1) W) */
+    uint64_t n;              /* quality codes counted in the row */
+    uint64_t sum;            /* sum of their byte values (raw bytes, no offset taken off) */
+    uint64_t ee;             /* sum of naf_gpu_quality_error_table()[byte]: expected errors times 2^32 */
+    uint64_t n_q20, n_q30;   /* codes with byte >= 33 + 20, byte >= 33 + 30 */
+    uint32_t min, max;       /* smallest / largest byte of the row; a row with n == 0 has min = 255, max = 0 */
+} naf_gpu_qual_row;          /* 56 bytes */
+
+/* host only, no device */
+int  naf_gpu_quality_error_table(uint64_t tab[256]);
+int  naf_gpu_unnaf_quality_rows(naf_gpu_ctx *ctx, const void *d_naf, size_t naf_len, uint64_t cycle_bin, uint64_t first, uint64_t count,
+                                uint64_t *n_records, uint64_t *n_cycle_rows);
+int  naf_gpu_unnaf_quality(naf_gpu_ctx *ctx, const void *d_naf, size_t naf_len, uint64_t cycle_bin, uint64_t first, uint64_t count,
+                           naf_gpu_qual_row *d_rec_rows, size_t rec_cap, naf_gpu_qual_row *d_cycle_rows, size_t cycle_cap,
+                           uint64_t *n_records, uint64_t *n_cycle_rows, uint64_t h_hist[256], naf_gpu_qual_row *h_total);
+
 /* ---- ennaf ------------------------------------------------------------------------------------------ */
 typedef struct {
     int      format;            /* NAF_FMT_* (AUTO = sniff, process.c:547-583) */

@@ -31,6 +31,7 @@ EXPORTS = [
     "naf_gpu_unnaf_select_stranded_size", "naf_gpu_unnaf_select_stranded",
     "naf_gpu_compile_motif", "naf_gpu_unnaf_locate_count", "naf_gpu_unnaf_locate",
     "naf_gpu_composition_rows_of", "naf_gpu_unnaf_composition_rows", "naf_gpu_unnaf_composition",
+    "naf_gpu_quality_error_table", "naf_gpu_unnaf_quality_rows", "naf_gpu_unnaf_quality",
 ]
 WHOLE = 2 ** 64 - 1                     # NAF_GPU_WHOLE: (record, 0, WHOLE) is the record as stored
 MAX_SHARDS = 64
@@ -106,6 +107,18 @@ class CompRow(C.Structure):
 COMP_DTYPE = [("record", "<u8"), ("begin", "<u8"), ("end", "<u8"), ("n", "<u8", (16,)), ("masked", "<u8"), ("cpg", "<u8")]      # numpy's view of a table of rows
 COMP_ROW_BYTES = 168
 COMP_MASK = 1
+
+
+class QualRow(C.Structure):
+    """naf_gpu_qual_row: the quality codes of one read (key: its number) or of one bin of read positions (key: the bin's number): how
+    many, the sum of their bytes, the sum of their error-table entries (expected errors times 2^32), those at or above Q20 and Q30
+    (Phred+33), and the smallest and largest byte (255 and 0 in a row without codes)."""
+    _fields_ = [("key", C.c_uint64), ("n", C.c_uint64), ("sum", C.c_uint64), ("ee", C.c_uint64), ("n_q20", C.c_uint64), ("n_q30", C.c_uint64),
+                ("min", C.c_uint32), ("max", C.c_uint32)]
+
+
+QUAL_DTYPE = [("key", "<u8"), ("n", "<u8"), ("sum", "<u8"), ("ee", "<u8"), ("n_q20", "<u8"), ("n_q30", "<u8"), ("min", "<u4"), ("max", "<u4")]      # numpy's view of a table of rows
+QUAL_ROW_BYTES = 56
 
 
 class NafGpuError(RuntimeError):
@@ -201,6 +214,9 @@ def load():
         L.naf_gpu_composition_rows_of.restype = C.c_uint64
         L.naf_gpu_unnaf_composition_rows.argtypes = [vp, vp, sz, C.c_uint64, C.c_uint64, C.c_uint64, u64p]
         L.naf_gpu_unnaf_composition.argtypes = [vp, vp, sz, C.c_uint64, i, C.c_uint64, C.c_uint64, vp, sz, u64p, C.POINTER(CompRow)]
+        L.naf_gpu_quality_error_table.argtypes = [u64p]
+        L.naf_gpu_unnaf_quality_rows.argtypes = [vp, vp, sz, C.c_uint64, C.c_uint64, C.c_uint64, u64p, u64p]
+        L.naf_gpu_unnaf_quality.argtypes = [vp, vp, sz, C.c_uint64, C.c_uint64, C.c_uint64, vp, sz, vp, sz, u64p, u64p, u64p, C.POINTER(QualRow)]
         _lib = L
     return _lib
 
@@ -231,6 +247,16 @@ def compile_motif(text):
 def composition_rows_of(n, window):
     """Host-only: the rows a record of n bases gives under `window` (naf_gpu_composition_rows_of): 1 for window 0, else ceil(n / window)."""
     return int(load().naf_gpu_composition_rows_of(int(n), int(window)))
+
+
+def quality_error_table():
+    """Host-only: the 256 entries of naf_gpu_quality_error_table -- the error probability of Phred+33 byte b times 2^32, rounded half up
+    (2^32 below 33) -- as a list of ints."""
+    tab = (C.c_uint64 * 256)()
+    rc = load().naf_gpu_quality_error_table(tab)
+    if rc:
+        raise NafGpuError(rc, load().naf_gpu_strerror(rc).decode())
+    return [int(v) for v in tab]
 
 
 def hits_to_segments(hits, patterns, flank=0, lengths=None):
@@ -574,6 +600,48 @@ class Context:
         self._check(self.L.naf_gpu_unnaf_composition(self.h, _ptr(d_naf), d_naf.numel(), int(window), flags, int(first), cnt,
                                                      _ptr(buf), n.value, C.byref(n), C.byref(tot)))
         return np.frombuffer(buf[:COMP_ROW_BYTES * n.value].cpu().numpy().tobytes(), dtype=COMP_DTYPE), tot
+
+    def unnaf_quality_rows(self, d_naf, cycle_bin=0, first=0, count=None):
+        """(record rows, cycle rows) that unnaf_quality gives for records [first, first + count) under `cycle_bin`
+        (naf_gpu_unnaf_quality_rows: the lengths only, no quality byte is decoded)."""
+        nr, nc = C.c_uint64(), C.c_uint64()
+        self._check(self.L.naf_gpu_unnaf_quality_rows(self.h, _ptr(d_naf), d_naf.numel(), int(cycle_bin), int(first), WHOLE if count is None else int(count),
+                                                      C.byref(nr), C.byref(nc)))
+        return nr.value, nc.value
+
+    def unnaf_quality(self, d_naf, cycle_bin=0, first=0, count=None, records=True, cycles=None, out_records=None, out_cycles=None):
+        """(rec_rows, cycle_rows, hist, total): the quality statistics of records [first, first + count) -- one row per read, and one per
+        bin of `cycle_bin` read positions -- as structured numpy arrays (QUAL_DTYPE: key, n, sum, ee, n_q20, n_q30, min, max), the count
+        per byte value as a list of 256 ints and the sum over all as a QualRow (its key: the records covered).  records / cycles: whether
+        the table is wanted (cycles=None: when cycle_bin > 0); a table that is not wanted comes back as None.  out_records / out_cycles:
+        uint8 device tensors to take the tables (56 bytes a row); that table is then the torch view of the bytes written, and too small
+        a tensor raises NafGpuError(E_CAP).  Without them the rows are counted first (naf_gpu_unnaf_quality_rows)."""
+        import numpy as np
+        import torch
+        cnt = WHOLE if count is None else int(count)
+        W = int(cycle_bin)
+        cycles = (W > 0) if cycles is None else (bool(cycles) and W > 0)
+        nr, nc, tot, hist = C.c_uint64(), C.c_uint64(), QualRow(), (C.c_uint64 * 256)()
+        if (records and out_records is None) or (cycles and out_cycles is None):
+            self._check(self.L.naf_gpu_unnaf_quality_rows(self.h, _ptr(d_naf), d_naf.numel(), W, int(first), cnt, C.byref(nr), C.byref(nc)))
+        bufs = []
+        for want, out, n in ((records, out_records, nr.value), (cycles, out_cycles, nc.value)):
+            if want and out is None:
+                bufs.append((torch.empty(max(QUAL_ROW_BYTES * n, 1), dtype=torch.uint8, device=self.device), n, True))
+            elif want:
+                bufs.append((out, out.numel() // QUAL_ROW_BYTES, False))
+            else:
+                bufs.append((None, 0, False))
+        (rb, rcap, rown), (cb, ccap, cown) = bufs
+        self._check(self.L.naf_gpu_unnaf_quality(self.h, _ptr(d_naf), d_naf.numel(), W, int(first), cnt, _ptr(rb) if rb is not None else None, rcap,
+                                                 _ptr(cb) if cb is not None else None, ccap, C.byref(nr), C.byref(nc), hist, C.byref(tot)))
+
+        def table(buf, own, n):
+            if buf is None:
+                return None
+            view = buf[:QUAL_ROW_BYTES * n]
+            return np.frombuffer(view.cpu().numpy().tobytes(), dtype=QUAL_DTYPE) if own else view
+        return table(rb, rown, nr.value), table(cb, cown, nc.value), [int(v) for v in hist], tot
 
     def histogram(self, d_buf):
         """Byte counts of a device buffer (unnaf --charcount)."""

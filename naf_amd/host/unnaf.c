@@ -22,6 +22,8 @@ static const char *locate_patterns[MAX_LOCATE]; static size_t n_locate = 0;
 static int locate_strands = 3; static bool strand_given = false;
 /* --composition [--window N]: base composition per record or per window, as a tab-separated table (this implementation only) */
 static bool composition = false, window_given = false; static unsigned long long comp_window = 0;
+/* --quality [--cycles N]: quality statistics per read or per bin of N read positions, as a tab-separated table (this implementation only) */
+static bool quality = false, cycles_given = false; static unsigned long long qual_cycles = 0;
 
 static void done(int status, void *arg)
 {
@@ -91,6 +93,18 @@ static void set_window(const char *v)
     comp_window = a; window_given = true;
 }
 
+static void set_cycles(const char *v)
+{
+    unsigned long long a = 0; bool digit = false;
+    for (const char *p = v; *p; p++) {
+        if (*p == ',') continue;
+        if (*p < '0' || *p > '9' || a > (ULLONG_MAX - (unsigned)(*p - '0')) / 10) die("can't parse the value of --cycles parameter (a positive number of read positions)\n");
+        a = a * 10 + (unsigned)(*p - '0'); digit = true;
+    }
+    if (!digit || a == 0) die("can't parse the value of --cycles parameter (a positive number of read positions)\n");
+    qual_cycles = a; cycles_given = true;
+}
+
 static void show_help(void)
 {
     msg("Usage: unnaf [OUTPUT-TYPE] [file.naf]\n"
@@ -115,7 +129,9 @@ static void show_help(void)
         "  --strand +|-|both - Search the sequences as stored, their reverse complement, or both (default)\n"
         "Options for counting (output: a tab-separated table \"#seq start end A C G T N other gap masked CpG GC\"; with at most one --records A-B or --region ID):\n"
         "  --composition   - Base composition of every sequence: bases per letter, soft-masked bases, CpG, GC fraction (--no-mask: masked = 0)\n"
-        "  --window N      - With --composition: one line per window of N bases instead of one per sequence\n");
+        "  --window N      - With --composition: one line per window of N bases instead of one per sequence\n"
+        "  --quality       - Quality of every read, from the stored quality codes: \"#seq length mean min max q20 q30 ee\" (Phred+33; ee: expected errors)\n"
+        "  --cycles N      - With --quality: one line per N read positions instead, over all reads: \"#cycle_begin cycle_end n mean min max q20 q30 ee\"\n");
 }
 
 static void parse_command_line(int argc, char **argv)
@@ -128,13 +144,14 @@ static void parse_command_line(int argc, char **argv)
         {"--fasta", FASTA}, {"--fastq", FASTQ}, {"--dna", DNA}, {"--masked-dna", MASKED_DNA}, {"--unmasked-dna", UNMASKED_DNA},
         {"--masked-fasta", MASKED_FASTA}, {"--unmasked-fasta", UNMASKED_FASTA} };
     /* the other options (unnaf/src/unnaf.c:282-353), as a table: one that takes a value is only recognised with an argument behind it */
-    enum { OP_LINE_LENGTH, OP_OUT, OP_NO_MASK, OP_IGNORED, OP_HELP, OP_VERBOSE, OP_VERSION, OP_STDOUT, OP_REGION, OP_RECORDS, OP_RC_REGION, OP_REVCOMP, OP_LOCATE, OP_STRAND, OP_COMPOSITION, OP_WINDOW };
+    enum { OP_LINE_LENGTH, OP_OUT, OP_NO_MASK, OP_IGNORED, OP_HELP, OP_VERBOSE, OP_VERSION, OP_STDOUT, OP_REGION, OP_RECORDS, OP_RC_REGION, OP_REVCOMP, OP_LOCATE, OP_STRAND, OP_COMPOSITION, OP_WINDOW, OP_QUALITY, OP_CYCLES };
     static const struct { const char *name; int op; bool value; } option_table[] = {
         { "--line-length", OP_LINE_LENGTH, true }, { "-o", OP_OUT, true }, { "--no-mask", OP_NO_MASK, false }, { "--binary-stdout", OP_IGNORED, false },
         { "--binary-stderr", OP_IGNORED, false }, { "--binary", OP_IGNORED, false }, { "--help", OP_HELP, false }, { "-h", OP_HELP, false },
         { "--verbose", OP_VERBOSE, false }, { "--version", OP_VERSION, false }, { "-V", OP_VERSION, false }, { "-c", OP_STDOUT, false },
         { "--region", OP_REGION, true }, { "--records", OP_RECORDS, true }, { "--rc-region", OP_RC_REGION, true }, { "--revcomp", OP_REVCOMP, false },
-        { "--locate", OP_LOCATE, true }, { "--strand", OP_STRAND, true }, { "--composition", OP_COMPOSITION, false }, { "--window", OP_WINDOW, true } };
+        { "--locate", OP_LOCATE, true }, { "--strand", OP_STRAND, true }, { "--composition", OP_COMPOSITION, false }, { "--window", OP_WINDOW, true },
+        { "--quality", OP_QUALITY, false }, { "--cycles", OP_CYCLES, true } };
     for (int i = 1; i < argc; i++) {
         char *arg = argv[i];
         if (arg[0] != '-') {
@@ -167,6 +184,8 @@ static void parse_command_line(int argc, char **argv)
         case OP_STRAND: set_strand(v); break;
         case OP_COMPOSITION: composition = true; break;
         case OP_WINDOW: set_window(v); break;
+        case OP_QUALITY: quality = true; break;
+        case OP_CYCLES: set_cycles(v); break;
         }
     }
     if (print_version) {
@@ -196,6 +215,19 @@ static void parse_command_line(int argc, char **argv)
         if (n_selections && selections[0].region) {
             size_t l; uint64_t b, e; naf_gpu_parse_region(selections[0].region, &l, &b, &e);
             if (!(b == 0 && e == NAF_GPU_WHOLE)) die("--composition can be restricted to a whole sequence only: --region ID, without a range\n");
+        }
+    }
+    if (cycles_given && !quality) die("--cycles can be used only with --quality\n");
+    if (quality) {
+        if (n_locate) die("--quality and --locate can't be used together\n");
+        if (composition) die("--quality and --composition can't be used together\n");
+        if (out_type != UNDECIDED) die("--quality writes a table: no output type can be given with it\n");
+        if (revcomp) die("--quality reads the qualities as stored: --revcomp can't be used with it\n");
+        if (n_selections > 1) die("--quality can be restricted by one --records or one --region only\n");
+        if (n_selections && selections[0].rc) die("--quality reads the qualities as stored: --rc-region can't be used with it\n");
+        if (n_selections && selections[0].region) {
+            size_t l; uint64_t b, e; naf_gpu_parse_region(selections[0].region, &l, &b, &e);
+            if (!(b == 0 && e == NAF_GPU_WHOLE)) die("--quality can be restricted to a whole sequence only: --region ID, without a range\n");
         }
     }
     if ((n_selections || revcomp) && !(out_type == UNDECIDED || out_type == FASTA || out_type == FASTQ || out_type == SEQ || out_type == SEQUENCES))
@@ -490,6 +522,54 @@ static void run_composition(bool has_ids, bool has_names)
     }
 }
 
+/* --quality [--cycles N]: the rows are made on the device (naf_gpu_unnaf_quality: one sweep over the quality stream); the lines are
+ * formatted here, on the host, from the downloaded rows, a chunk at a time. */
+static void quality_stats(FILE *f, const naf_gpu_qual_row *x)
+{
+    if (x->n) fprintf(f, "%.4f\t%d\t%d", (double)x->sum / (double)x->n - 33.0, (int)x->min - 33, (int)x->max - 33); else fprintf(f, "NA\tNA\tNA");
+    fprintf(f, "\t%llu\t%llu\t%.6f\n", (unsigned long long)x->n_q20, (unsigned long long)x->n_q30, (double)x->ee / 4294967296.0);
+}
+static void run_quality(bool has_ids, bool has_names)
+{
+    upload();
+    const unsigned long long N = H.n_sequences;
+    uint64_t first, count;
+    one_record_range(has_ids, &first, &count);
+    uint64_t n_rec = 0, far = 0;                                   /* (one row per read position: the longest selected read) */
+    GPU_TRY(naf_gpu_unnaf_quality_rows(gpu, d_naf, naf_len, 1, first, count, &n_rec, &far));
+    const uint64_t W = qual_cycles, n = cycles_given ? far / W + (far % W != 0) : n_rec;
+    phase("quality: rows");
+    fprintf(OUT, cycles_given ? "#cycle_begin\tcycle_end\tn\tmean\tmin\tmax\tq20\tq30\tee\n" : "#seq\tlength\tmean\tmin\tmax\tq20\tq30\tee\n");
+    if (!n) return;
+    void *d_rows; GPU_TRY(naf_gpu_malloc(gpu, (size_t)n * sizeof(naf_gpu_qual_row), &d_rows));
+    uint64_t got_rec = 0, got_cyc = 0;
+    if (cycles_given) GPU_TRY(naf_gpu_unnaf_quality(gpu, d_naf, naf_len, W, first, count, NULL, 0, (naf_gpu_qual_row *)d_rows, (size_t)n, &got_rec, &got_cyc, NULL, NULL));
+    else GPU_TRY(naf_gpu_unnaf_quality(gpu, d_naf, naf_len, 0, first, count, (naf_gpu_qual_row *)d_rows, (size_t)n, NULL, 0, &got_rec, &got_cyc, NULL, NULL));
+    if ((cycles_given ? got_cyc : got_rec) != n) die("can't decompress quality\n");
+    phase("quality: count");
+    unsigned char *text = NULL; const char **name = cycles_given ? NULL : record_names(has_ids, has_names, &text);
+    const size_t chunk = 1 << 18;
+    naf_gpu_qual_row *rows = (naf_gpu_qual_row *)malloc((n < chunk ? (size_t)n : chunk) * sizeof *rows); if (!rows) die("can't allocate memory\n");
+    for (uint64_t a = 0; a < n; a += chunk) {
+        const size_t m = n - a < chunk ? (size_t)(n - a) : chunk;
+        GPU_TRY(naf_gpu_download(gpu, rows, (const naf_gpu_qual_row *)d_rows + a, m * sizeof *rows));
+        for (size_t k = 0; k < m; k++) {
+            const naf_gpu_qual_row *x = &rows[k];
+            if (cycles_given) {
+                if (x->key != a + k) die("can't decompress quality\n");
+                const unsigned long long b = x->key * W + 1, e = far - x->key * W > W ? (x->key + 1) * W : far;
+                fprintf(OUT, "%llu\t%llu\t%llu\t", b, e, (unsigned long long)x->n);
+            } else {
+                if (x->key >= N) die("can't decompress quality\n");
+                fprintf(OUT, "%s\t%llu\t", name[x->key], (unsigned long long)x->n);
+            }
+            quality_stats(OUT, x);
+        }
+    }
+    free(rows); free(name); free(text); naf_gpu_free(gpu, d_rows);
+    phase("quality: download + lines");
+}
+
 int main(int argc, char **argv)
 {
     prog_name = "unnaf";
@@ -531,7 +611,7 @@ int main(int argc, char **argv)
     bool large = out_type == IDS || out_type == NAMES || out_type == LENGTHS || out_type == MASK || out_type == FOUR_BIT || out_type == DNA ||
                  out_type == MASKED_DNA || out_type == UNMASKED_DNA || out_type == SEQ || out_type == FASTA || out_type == MASKED_FASTA ||
                  out_type == UNMASKED_FASTA || out_type == FASTQ;
-    if (large && !n_locate && !composition && !force_stdout && isatty(fileno(OUT)))
+    if (large && !n_locate && !composition && !quality && !force_stdout && isatty(fileno(OUT)))
         die("output file not specified - please either specify output file with '-o' or '>', or use '-c' option to force writing to console\n");
 
     unsigned long long N = H.n_sequences;
@@ -543,6 +623,7 @@ int main(int argc, char **argv)
         if (H.seq_type >= NAF_SEQ_PROTEIN) die("nucleotides cannot be counted in %s sequences\n", tn[H.seq_type]);
         run_composition(has_ids, has_names);
     }
+    else if (quality) run_quality(has_ids, has_names);
     else if (n_selections) {
         if (out_type == FASTQ && !has_quality) die("FASTQ output requested, but input has no qualities\n");
         for (size_t k = 0; k < n_selections; k++) if (selections[k].rc && H.seq_type >= NAF_SEQ_PROTEIN) die("%s sequences have no reverse complement\n", tn[H.seq_type]);
