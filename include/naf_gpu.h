@@ -330,6 +330,49 @@ int  naf_gpu_unnaf_quality(naf_gpu_ctx *ctx, const void *d_naf, size_t naf_len, 
                            naf_gpu_qual_row *d_rec_rows, size_t rec_cap, naf_gpu_qual_row *d_cycle_rows, size_t cycle_cap,
                            uint64_t *n_records, uint64_t *n_cycle_rows, uint64_t h_hist[256], naf_gpu_qual_row *h_total);
 
+/* ---- unnaf: runs of a base class and soft-masked intervals per record, listed from the packed stream ------------------
+ * What seqtk cutN -g, twoBitInfo -nBed and seqtk hrun answer from the text -- where the assembly gaps, the contigs inside the scaffolds,
+ * the homopolymers and the soft-masked intervals lie -- as a table of intervals of unknown length, made without expanding the codes.
+ *   Class     `set` has bit c set for 4-bit code c of "-TGKCYSBAWRDMHVN".  Membership is LITERAL: a stored N is in {N} and a stored R is
+ *             not -- unlike the containment rule of naf_gpu_unnaf_locate, where a pattern N matches every stored base.
+ *             naf_gpu_parse_base_class takes letters of ACGTU RYSWKM BDHV N and '-', either case, U = T; a leading '^' complements the
+ *             set within the sixteen codes.  The empty string, a bare "^" and any other character are NAF_GPU_EARG.
+ *   Run       a maximal stretch of consecutive bases of ONE record whose codes are all in `set`, with end - begin >= min_len.  A record's
+ *             end always ends a run: a run that reaches the last base of record r and one that starts at base 0 of the next non-empty
+ *             record are two rows, however many empty records lie between them.  code = the code of the run's first base.
+ *   EACH      NAF_GPU_RUNS_EACH: every code of `set` is a class of its own; a run is then a maximal stretch of one and the same code (a
+ *             homopolymer for set = ACGT) and code is that code.
+ *   MASKED    NAF_GPU_RUNS_MASKED: runs of bases g that have an odd number of mask toggles <= g, g the base's index in the whole stream
+ *             -- exactly the lower-case letters of the --sequences text --, split at record ends in the same way; code = 0.  `set` must
+ *             be 0 and EACH absent (NAF_GPU_EARG otherwise).  An archive without a mask section gives 0 runs.  Neither the sequence nor
+ *             the quality section is decoded.  Everything is defined by parity, so equal toggles of a foreign archive cancel.
+ *   Never     Bases behind the last record of a malformed archive and the padding nibble of an odd stream are in no run,
+ *             also for a `set` that holds '-' (code 0).
+ *   Errors    NAF_GPU_EARG, last_error saying which: set == 0 without MASKED; min_len == 0; unknown flag bits; first > n_sequences or a
+ *             range past the last record, as for naf_gpu_unnaf_composition; protein and text archives; an archive that stores no
+ *             sequence (for MASKED too: its lengths have nothing to be held against).  An archive without records gives 0 runs.
+ *   Order     ascending (record, begin); the same bytes on every run and for every piece size.
+ *   Outputs   *n_runs is always the whole count; *n_bases (may be NULL) the sum of end - begin.  d_runs is DEVICE memory of any
+ *             alignment; exactly 32 * n_runs bytes are written and nothing else.  With run_cap too small the call returns NAF_GPU_ECAP,
+ *             sets *n_runs and writes nothing.
+ *   Pieces    more bases than NAF_GPU_RUNS_PIECE (default 2^31) are decoded and swept in pieces of whole records, so no run crosses a
+ *             piece; the result does not depend on the piece size.  Only the zstd blocks behind the records are decoded when the frame
+ *             allows it.  The tables of run starts and ends of a piece live in the context's scratch arena (at the worst one of each per
+ *             two bases; per base with EACH at min_len 1): when it cannot hold them the call returns NAF_GPU_ENOMEM and last_error
+ *             names NAF_GPU_RUNS_PIECE.
+ * A run is exactly the (record, begin, end) that naf_gpu_unnaf_select takes: the runs of ^N, selected, are a scaffold's contigs.
+ * TRACE=1: "[runs] runs R candidates K pieces P sequence bytes decoded X of Y mask toggles T" per call that reaches the records. */
+typedef struct { uint64_t record, begin, end; uint32_t code, reserved; } naf_gpu_run;   /* 32 bytes; reserved = 0 */
+enum { NAF_GPU_RUNS_EACH = 1, NAF_GPU_RUNS_MASKED = 2 };
+
+/* host only, no device */
+int  naf_gpu_parse_base_class(const char *text, uint16_t *set);
+
+int  naf_gpu_unnaf_runs_count(naf_gpu_ctx *ctx, const void *d_naf, size_t naf_len, uint16_t set, int flags, uint64_t min_len,
+                              uint64_t first, uint64_t count, uint64_t *n_runs, uint64_t *n_bases);
+int  naf_gpu_unnaf_runs(naf_gpu_ctx *ctx, const void *d_naf, size_t naf_len, uint16_t set, int flags, uint64_t min_len,
+                        uint64_t first, uint64_t count, naf_gpu_run *d_runs, size_t run_cap, uint64_t *n_runs, uint64_t *n_bases);
+
 /* ---- ennaf ------------------------------------------------------------------------------------------ */
 typedef struct {
     int      format;            /* NAF_FMT_* (AUTO = sniff, process.c:547-583) */

@@ -32,6 +32,7 @@ EXPORTS = [
     "naf_gpu_compile_motif", "naf_gpu_unnaf_locate_count", "naf_gpu_unnaf_locate",
     "naf_gpu_composition_rows_of", "naf_gpu_unnaf_composition_rows", "naf_gpu_unnaf_composition",
     "naf_gpu_quality_error_table", "naf_gpu_unnaf_quality_rows", "naf_gpu_unnaf_quality",
+    "naf_gpu_parse_base_class", "naf_gpu_unnaf_runs_count", "naf_gpu_unnaf_runs",
 ]
 WHOLE = 2 ** 64 - 1                     # NAF_GPU_WHOLE: (record, 0, WHOLE) is the record as stored
 MAX_SHARDS = 64
@@ -119,6 +120,17 @@ class QualRow(C.Structure):
 
 QUAL_DTYPE = [("key", "<u8"), ("n", "<u8"), ("sum", "<u8"), ("ee", "<u8"), ("n_q20", "<u8"), ("n_q30", "<u8"), ("min", "<u4"), ("max", "<u4")]      # numpy's view of a table of rows
 QUAL_ROW_BYTES = 56
+
+
+class Run(C.Structure):
+    """naf_gpu_run: bases [begin, end) of `record` are a run -- of a base class (code: the 4-bit code of its first base; with RUNS_EACH
+    the code of all of them) or of soft-masked bases (code 0)."""
+    _fields_ = [("record", C.c_uint64), ("begin", C.c_uint64), ("end", C.c_uint64), ("code", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+RUN_DTYPE = [("record", "<u8"), ("begin", "<u8"), ("end", "<u8"), ("code", "<u4"), ("reserved", "<u4")]      # numpy's view of a table of runs
+RUN_BYTES = 32
+RUNS_EACH, RUNS_MASKED = 1, 2
 
 
 class NafGpuError(RuntimeError):
@@ -217,6 +229,9 @@ def load():
         L.naf_gpu_quality_error_table.argtypes = [u64p]
         L.naf_gpu_unnaf_quality_rows.argtypes = [vp, vp, sz, C.c_uint64, C.c_uint64, C.c_uint64, u64p, u64p]
         L.naf_gpu_unnaf_quality.argtypes = [vp, vp, sz, C.c_uint64, C.c_uint64, C.c_uint64, vp, sz, vp, sz, u64p, u64p, u64p, C.POINTER(QualRow)]
+        L.naf_gpu_parse_base_class.argtypes = [C.c_char_p, C.POINTER(C.c_uint16)]
+        L.naf_gpu_unnaf_runs_count.argtypes = [vp, vp, sz, C.c_uint16, i, C.c_uint64, C.c_uint64, C.c_uint64, u64p, u64p]
+        L.naf_gpu_unnaf_runs.argtypes = [vp, vp, sz, C.c_uint16, i, C.c_uint64, C.c_uint64, C.c_uint64, vp, sz, u64p, u64p]
         _lib = L
     return _lib
 
@@ -257,6 +272,31 @@ def quality_error_table():
     if rc:
         raise NafGpuError(rc, load().naf_gpu_strerror(rc).decode())
     return [int(v) for v in tab]
+
+
+def parse_base_class(text):
+    """Host-only: the 16-bit set of a base class (naf_gpu_parse_base_class) -- bit c for 4-bit code c of "-TGKCYSBAWRDMHVN"; letters of
+    ACGTU RYSWKM BDHV N and '-' in either case, a leading '^' complements.  ValueError for what is no class."""
+    b = text.encode("latin1") if isinstance(text, str) else bytes(text)
+    if b"\0" in b:
+        raise ValueError("not a base class: %r" % (text,))
+    s = C.c_uint16()
+    if load().naf_gpu_parse_base_class(b, C.byref(s)):
+        raise ValueError("not a base class: %r" % (text,))
+    return s.value
+
+
+def runs_to_segments(runs, flank=0, lengths=None):
+    """The (record, begin, end) tuples unnaf_select takes, one per run (rows of the table unnaf_runs returns).  flank: that many bases
+    more on either side, clamped to the record -- to its start always, to its end when `lengths` (the n_bases of unnaf_record_table,
+    indexed by record number) is given; unnaf_select clamps an end beyond the record itself."""
+    out = []
+    for x in runs:
+        r, b, e = int(x["record"]), max(0, int(x["begin"]) - flank), int(x["end"]) + flank
+        if lengths is not None:
+            e = min(e, int(lengths[r]))
+        out.append((r, b, e))
+    return out
 
 
 def hits_to_segments(hits, patterns, flank=0, lengths=None):
@@ -642,6 +682,51 @@ class Context:
             view = buf[:QUAL_ROW_BYTES * n]
             return np.frombuffer(view.cpu().numpy().tobytes(), dtype=QUAL_DTYPE) if own else view
         return table(rb, rown, nr.value), table(cb, cown, nc.value), [int(v) for v in hist], tot
+
+    @staticmethod
+    def _run_class(cls, each, masked):
+        """(set, flags) of a runs call; cls: a class as text (parse_base_class) or as the 16-bit set; None with masked."""
+        flags = (RUNS_EACH if each else 0) | (RUNS_MASKED if masked else 0)
+        s = 0 if cls is None else parse_base_class(cls) if isinstance(cls, (str, bytes)) else int(cls)
+        if not 0 <= s <= 0xFFFF:
+            raise ValueError("not a base class: %r" % (cls,))
+        return s, flags
+
+    def unnaf_runs_count(self, d_naf, cls, each=False, masked=False, min_len=1, first=0, count=None):
+        """(n_runs, n_bases) of the runs unnaf_runs lists (naf_gpu_unnaf_runs_count)."""
+        s, flags = self._run_class(cls, each, masked)
+        n, nb = C.c_uint64(), C.c_uint64()
+        self._check(self.L.naf_gpu_unnaf_runs_count(self.h, _ptr(d_naf), d_naf.numel(), s, flags, int(min_len), int(first), WHOLE if count is None else int(count),
+                                                    C.byref(n), C.byref(nb)))
+        return n.value, nb.value
+
+    def unnaf_runs(self, d_naf, cls, each=False, masked=False, min_len=1, first=0, count=None, out=None):
+        """(rows, n_bases): the runs of at least min_len bases of base class `cls` -- text as parse_base_class takes it, or the 16-bit set;
+        each: every code of it a class of its own -- or, with masked (cls None or 0), the soft-masked intervals, in records
+        [first, first + count), as a structured numpy array (RUN_DTYPE: record, begin, end, code, reserved) in ascending (record, begin),
+        and the sum of their lengths.  out: a uint8 device tensor to take the table (32 bytes a run); then `rows` is the torch view of
+        its first 32 * n bytes and too small a tensor raises NafGpuError(E_CAP).  Without it a table sized by a guess is tried first and
+        one of the whole count when that was too small (the call reports it with E_CAP)."""
+        import numpy as np
+        import torch
+        s, flags = self._run_class(cls, each, masked)
+        n, nb = C.c_uint64(), C.c_uint64()
+        cnt = WHOLE if count is None else int(count)
+
+        def call(buf, cap):
+            return self.L.naf_gpu_unnaf_runs(self.h, _ptr(d_naf), d_naf.numel(), s, flags, int(min_len), int(first), cnt, _ptr(buf), cap, C.byref(n), C.byref(nb))
+        if out is not None:
+            self._check(call(out, out.numel() // RUN_BYTES))
+            return out[:RUN_BYTES * n.value], nb.value
+        cap = 4096
+        buf = torch.empty(RUN_BYTES * cap, dtype=torch.uint8, device=self.device)
+        rc = call(buf, cap)
+        if rc == E_CAP:
+            cap = n.value
+            buf = torch.empty(RUN_BYTES * cap, dtype=torch.uint8, device=self.device)
+            rc = call(buf, cap)
+        self._check(rc)
+        return np.frombuffer(buf[:RUN_BYTES * n.value].cpu().numpy().tobytes(), dtype=RUN_DTYPE), nb.value
 
     def histogram(self, d_buf):
         """Byte counts of a device buffer (unnaf --charcount)."""

@@ -24,6 +24,9 @@ static int locate_strands = 3; static bool strand_given = false;
 static bool composition = false, window_given = false; static unsigned long long comp_window = 0;
 /* --quality [--cycles N]: quality statistics per read or per bin of N read positions, as a tab-separated table (this implementation only) */
 static bool quality = false, cycles_given = false; static unsigned long long qual_cycles = 0;
+/* --runs CLASS / --masked-runs [--min-run N] [--each]: runs of a base class or soft-masked intervals, as BED4 (this implementation only) */
+static const char *runs_class = NULL; static uint16_t runs_set = 0; static bool masked_runs = false, runs_each = false, min_run_given = false;
+static unsigned long long min_run = 1;
 
 static void done(int status, void *arg)
 {
@@ -105,6 +108,24 @@ static void set_cycles(const char *v)
     qual_cycles = a; cycles_given = true;
 }
 
+static void set_runs(const char *v)
+{
+    if (runs_class) die("only one --runs class can be listed at a time\n");
+    if (naf_gpu_parse_base_class(v, &runs_set) || !runs_set) die("can't parse the value of --runs parameter (letters of ACGTU RYSWKM BDHV N and -, ^ in front for all the others)\n");
+    runs_class = v;
+}
+static void set_min_run(const char *v)
+{
+    unsigned long long a = 0; bool digit = false;
+    for (const char *p = v; *p; p++) {
+        if (*p == ',') continue;
+        if (*p < '0' || *p > '9' || a > (ULLONG_MAX - (unsigned)(*p - '0')) / 10) die("can't parse the value of --min-run parameter (a positive number of bases)\n");
+        a = a * 10 + (unsigned)(*p - '0'); digit = true;
+    }
+    if (!digit || a == 0) die("can't parse the value of --min-run parameter (a positive number of bases)\n");
+    min_run = a; min_run_given = true;
+}
+
 static void show_help(void)
 {
     msg("Usage: unnaf [OUTPUT-TYPE] [file.naf]\n"
@@ -131,7 +152,12 @@ static void show_help(void)
         "  --composition   - Base composition of every sequence: bases per letter, soft-masked bases, CpG, GC fraction (--no-mask: masked = 0)\n"
         "  --window N      - With --composition: one line per window of N bases instead of one per sequence\n"
         "  --quality       - Quality of every read, from the stored quality codes: \"#seq length mean min max q20 q30 ee\" (Phred+33; ee: expected errors)\n"
-        "  --cycles N      - With --quality: one line per N read positions instead, over all reads: \"#cycle_begin cycle_end n mean min max q20 q30 ee\"\n");
+        "  --cycles N      - With --quality: one line per N read positions instead, over all reads: \"#cycle_begin cycle_end n mean min max q20 q30 ee\"\n"
+        "Options for listing runs (output: BED4 lines \"ID begin end NAME\", 0-based half-open; with at most one --records A-B or --region ID):\n"
+        "  --runs CLASS    - Every maximal run of bases of CLASS: letters of ACGTU RYSWKM BDHV N and -, taken literally (N is the stored N only); ^CLASS = all other codes\n"
+        "  --masked-runs   - Every soft-masked interval (NAME is \"mask\")\n"
+        "  --min-run N     - With --runs or --masked-runs: only runs of at least N bases (default 1)\n"
+        "  --each          - With --runs: every letter of CLASS on its own, e.g. homopolymers for ACGT (NAME is the run's letter)\n");
 }
 
 static void parse_command_line(int argc, char **argv)
@@ -144,14 +170,15 @@ static void parse_command_line(int argc, char **argv)
         {"--fasta", FASTA}, {"--fastq", FASTQ}, {"--dna", DNA}, {"--masked-dna", MASKED_DNA}, {"--unmasked-dna", UNMASKED_DNA},
         {"--masked-fasta", MASKED_FASTA}, {"--unmasked-fasta", UNMASKED_FASTA} };
     /* the other options (unnaf/src/unnaf.c:282-353), as a table: one that takes a value is only recognised with an argument behind it */
-    enum { OP_LINE_LENGTH, OP_OUT, OP_NO_MASK, OP_IGNORED, OP_HELP, OP_VERBOSE, OP_VERSION, OP_STDOUT, OP_REGION, OP_RECORDS, OP_RC_REGION, OP_REVCOMP, OP_LOCATE, OP_STRAND, OP_COMPOSITION, OP_WINDOW, OP_QUALITY, OP_CYCLES };
+    enum { OP_LINE_LENGTH, OP_OUT, OP_NO_MASK, OP_IGNORED, OP_HELP, OP_VERBOSE, OP_VERSION, OP_STDOUT, OP_REGION, OP_RECORDS, OP_RC_REGION, OP_REVCOMP, OP_LOCATE, OP_STRAND, OP_COMPOSITION, OP_WINDOW, OP_QUALITY, OP_CYCLES, OP_RUNS, OP_MASKED_RUNS, OP_MIN_RUN, OP_EACH };
     static const struct { const char *name; int op; bool value; } option_table[] = {
         { "--line-length", OP_LINE_LENGTH, true }, { "-o", OP_OUT, true }, { "--no-mask", OP_NO_MASK, false }, { "--binary-stdout", OP_IGNORED, false },
         { "--binary-stderr", OP_IGNORED, false }, { "--binary", OP_IGNORED, false }, { "--help", OP_HELP, false }, { "-h", OP_HELP, false },
         { "--verbose", OP_VERBOSE, false }, { "--version", OP_VERSION, false }, { "-V", OP_VERSION, false }, { "-c", OP_STDOUT, false },
         { "--region", OP_REGION, true }, { "--records", OP_RECORDS, true }, { "--rc-region", OP_RC_REGION, true }, { "--revcomp", OP_REVCOMP, false },
         { "--locate", OP_LOCATE, true }, { "--strand", OP_STRAND, true }, { "--composition", OP_COMPOSITION, false }, { "--window", OP_WINDOW, true },
-        { "--quality", OP_QUALITY, false }, { "--cycles", OP_CYCLES, true } };
+        { "--quality", OP_QUALITY, false }, { "--cycles", OP_CYCLES, true },
+        { "--runs", OP_RUNS, true }, { "--masked-runs", OP_MASKED_RUNS, false }, { "--min-run", OP_MIN_RUN, true }, { "--each", OP_EACH, false } };
     for (int i = 1; i < argc; i++) {
         char *arg = argv[i];
         if (arg[0] != '-') {
@@ -186,6 +213,10 @@ static void parse_command_line(int argc, char **argv)
         case OP_WINDOW: set_window(v); break;
         case OP_QUALITY: quality = true; break;
         case OP_CYCLES: set_cycles(v); break;
+        case OP_RUNS: set_runs(v); break;
+        case OP_MASKED_RUNS: masked_runs = true; break;
+        case OP_MIN_RUN: set_min_run(v); break;
+        case OP_EACH: runs_each = true; break;
         }
     }
     if (print_version) {
@@ -228,6 +259,23 @@ static void parse_command_line(int argc, char **argv)
         if (n_selections && selections[0].region) {
             size_t l; uint64_t b, e; naf_gpu_parse_region(selections[0].region, &l, &b, &e);
             if (!(b == 0 && e == NAF_GPU_WHOLE)) die("--quality can be restricted to a whole sequence only: --region ID, without a range\n");
+        }
+    }
+    if (min_run_given && !runs_class && !masked_runs) die("--min-run can be used only with --runs or --masked-runs\n");
+    if (runs_each && !runs_class) die("--each can be used only with --runs\n");
+    if (runs_class || masked_runs) {
+        const char *me = runs_class ? "--runs" : "--masked-runs";
+        if (runs_class && masked_runs) die("--runs and --masked-runs can't be used together\n");
+        if (n_locate) die("%s and --locate can't be used together\n", me);
+        if (composition) die("%s and --composition can't be used together\n", me);
+        if (quality) die("%s and --quality can't be used together\n", me);
+        if (out_type != UNDECIDED) die("%s writes BED lines: no output type can be given with it\n", me);
+        if (revcomp) die("%s lists the sequences as stored: --revcomp can't be used with it\n", me);
+        if (n_selections > 1) die("%s can be restricted by one --records or one --region only\n", me);
+        if (n_selections && selections[0].rc) die("%s lists the sequences as stored: --rc-region can't be used with it\n", me);
+        if (n_selections && selections[0].region) {
+            size_t l; uint64_t b, e; naf_gpu_parse_region(selections[0].region, &l, &b, &e);
+            if (!(b == 0 && e == NAF_GPU_WHOLE)) die("%s can be restricted to a whole sequence only: --region ID, without a range\n", me);
         }
     }
     if ((n_selections || revcomp) && !(out_type == UNDECIDED || out_type == FASTA || out_type == FASTQ || out_type == SEQ || out_type == SEQUENCES))
@@ -570,6 +618,44 @@ static void run_quality(bool has_ids, bool has_names)
     phase("quality: download + lines");
 }
 
+/* --runs / --masked-runs: the table of runs is made on the device (naf_gpu_unnaf_runs: the packed stream's run starts and ends, paired by
+ * rank; the mask's toggle list); the BED lines are formatted here, on the host, from the downloaded table, a chunk at a time. */
+static void run_runs(bool has_ids, bool has_names)
+{
+    upload();
+    const unsigned long long N = H.n_sequences;
+    uint64_t first, count;
+    one_record_range(has_ids, &first, &count);
+    const int flags = masked_runs ? NAF_GPU_RUNS_MASKED : runs_each ? NAF_GPU_RUNS_EACH : 0;
+    const uint16_t set = masked_runs ? 0 : runs_set;
+    uint64_t n = 0;
+    GPU_TRY(naf_gpu_unnaf_runs_count(gpu, d_naf, naf_len, set, flags, min_run, first, count, &n, NULL));
+    phase("runs: count");
+    if (n) {
+        void *d_runs; GPU_TRY(naf_gpu_malloc(gpu, (size_t)n * sizeof(naf_gpu_run), &d_runs));
+        uint64_t got = 0;
+        GPU_TRY(naf_gpu_unnaf_runs(gpu, d_naf, naf_len, set, flags, min_run, first, count, (naf_gpu_run *)d_runs, (size_t)n, &got, NULL));
+        if (got != n) die("can't decompress sequence\n");
+        phase("runs: rows");
+        unsigned char *text; const char **name = record_names(has_ids, has_names, &text);
+        const size_t chunk = 1 << 20;
+        naf_gpu_run *rows = (naf_gpu_run *)malloc((n < chunk ? (size_t)n : chunk) * sizeof *rows); if (!rows) die("can't allocate memory\n");
+        const char *letters = H.seq_type == NAF_SEQ_RNA ? "-UGKCYSBAWRDMHVN" : "-TGKCYSBAWRDMHVN";
+        for (uint64_t a = 0; a < n; a += chunk) {
+            const size_t m = n - a < chunk ? (size_t)(n - a) : chunk;
+            GPU_TRY(naf_gpu_download(gpu, rows, (const naf_gpu_run *)d_runs + a, m * sizeof *rows));
+            for (size_t k = 0; k < m; k++) {
+                const naf_gpu_run *x = &rows[k];
+                if (x->record >= N || x->code > 15) die("can't decompress sequence\n");
+                fprintf(OUT, "%s\t%llu\t%llu\t", name[x->record], (unsigned long long)x->begin, (unsigned long long)x->end);
+                if (masked_runs) fprintf(OUT, "mask\n"); else if (runs_each) fprintf(OUT, "%c\n", letters[x->code]); else fprintf(OUT, "%s\n", runs_class);
+            }
+        }
+        free(rows); free(name); free(text); naf_gpu_free(gpu, d_runs);
+        phase("runs: download + BED lines");
+    }
+}
+
 int main(int argc, char **argv)
 {
     prog_name = "unnaf";
@@ -611,7 +697,7 @@ int main(int argc, char **argv)
     bool large = out_type == IDS || out_type == NAMES || out_type == LENGTHS || out_type == MASK || out_type == FOUR_BIT || out_type == DNA ||
                  out_type == MASKED_DNA || out_type == UNMASKED_DNA || out_type == SEQ || out_type == FASTA || out_type == MASKED_FASTA ||
                  out_type == UNMASKED_FASTA || out_type == FASTQ;
-    if (large && !n_locate && !composition && !quality && !force_stdout && isatty(fileno(OUT)))
+    if (large && !n_locate && !composition && !quality && !runs_class && !masked_runs && !force_stdout && isatty(fileno(OUT)))
         die("output file not specified - please either specify output file with '-o' or '>', or use '-c' option to force writing to console\n");
 
     unsigned long long N = H.n_sequences;
@@ -624,6 +710,10 @@ int main(int argc, char **argv)
         run_composition(has_ids, has_names);
     }
     else if (quality) run_quality(has_ids, has_names);
+    else if (runs_class || masked_runs) {
+        if (H.seq_type >= NAF_SEQ_PROTEIN) die("runs of bases cannot be listed in %s sequences\n", tn[H.seq_type]);
+        run_runs(has_ids, has_names);
+    }
     else if (n_selections) {
         if (out_type == FASTQ && !has_quality) die("FASTQ output requested, but input has no qualities\n");
         for (size_t k = 0; k < n_selections; k++) if (selections[k].rc && H.seq_type >= NAF_SEQ_PROTEIN) die("%s sequences have no reverse complement\n", tn[H.seq_type]);
