@@ -20,8 +20,7 @@ FASTA, FASTQ, SEQ, SEQUENCES = 0, 1, 2, 3
 E_ARG = -8
 SUB_CASES = ["mixed_60", "mask_bounds", "acgt_odd", "acgt_1m2", "rna_small", "ll_override", "tiny_many", "repeat_l19", "repeat_long27"]   # test_gpu_select.SUB_CASES that hold nucleotides
 
-COMP_DNA = bytes.maketrans(b"ACGTMRWSYKVHDBN-acgtmrwsykvhdbn-", b"TGCAKYWSRMBDHVN-tgcakywsrmbdhvn-")
-COMP_RNA = bytes.maketrans(b"ACGUMRWSYKVHDBN-acgumrwsykvhdbn-", b"UGCAKYWSRMBDHVN-ugcakywsrmbdhvn-")
+from select_plan import COMP_DNA, COMP_RNA, Records          # the expectation, from the oracle's whole text (shared with the planned tests)
 
 
 @pytest.fixture(scope="module")
@@ -36,81 +35,6 @@ def gpu():
 
 def host(t):
     return t.cpu().numpy().tobytes()
-
-
-# ---- the expectation, from the oracle's whole text ----------------------------------------------------------------------------
-class Records:
-    """The records of a DNA / RNA archive as the oracle prints them under (mode, use_mask, line_length), and from them the text of
-    a segment on either strand."""
-
-    def __init__(self, oracle, naf, mode, use_mask=True, line_length=-1):
-        h = oracle.parse_naf(naf)
-        assert h.seq_type in (0, 1)
-        self.mode, self.comp, self.has_ids = mode, COMP_RNA if h.seq_type == 1 else COMP_DNA, bool(h.flags & 0x20)
-        self.L = line_length if line_length >= 0 else h.line_length
-        self.ids = oracle.zstd_decompress(h.frame(naf, 0)).split(b"\0")[:-1] if self.has_ids else [b""] * h.n_sequences
-        self.text = oracle.unnaf(naf, FASTQ if mode == FASTQ else FASTA if mode == FASTA else SEQUENCES, use_mask, line_length)
-        self.whole, self.bases, self.head, self.plus, self.qual = [], [], [], [], []
-        t = self.text
-        if mode == FASTQ:
-            lines = t.split(b"\n")[:-1]
-            assert len(lines) == 4 * h.n_sequences
-            for k in range(0, len(lines), 4):
-                self.whole.append(b"\n".join(lines[k:k + 4]) + b"\n")
-                self.head.append(lines[k]); self.bases.append(lines[k + 1]); self.plus.append(lines[k + 2]); self.qual.append(lines[k + 3])
-        elif mode == FASTA:
-            lens = [len(x) for x in oracle.unnaf(naf, SEQUENCES, use_mask, line_length).split(b"\n")[:-1]]
-            assert len(lens) == h.n_sequences
-            a = 0
-            for ln in lens:
-                assert t[a:a + 1] == b">"
-                body = t.index(b"\n", a) + 1
-                b = body + (0 if ln == 0 else ln + ((ln + self.L - 1) // self.L if self.L else 1))
-                self.whole.append(t[a:b]); self.head.append(t[a:body - 1]); self.bases.append(t[body:b].replace(b"\n", b"")); a = b
-                assert len(self.bases[-1]) == ln
-            assert a == len(t)
-        else:
-            lines = t.split(b"\n")[:-1]
-            assert len(lines) == h.n_sequences
-            for ln in lines:
-                self.bases.append(ln); self.whole.append(ln + (b"\n" if mode == SEQUENCES else b""))
-        self.n = len(self.whole)
-
-    def wrap(self, s):
-        if not s:
-            return b""
-        if self.L == 0:
-            return s + b"\n"
-        return b"".join(s[i:i + self.L] + b"\n" for i in range(0, len(s), self.L))
-
-    def segment(self, rec, begin=0, end=None, reverse=0):
-        whole = begin == 0 and end is None
-        if whole and not reverse:
-            return self.whole[rec]
-        s = self.bases[rec] if whole else self.bases[rec][begin:min(end, len(self.bases[rec]))]
-        assert whole or s, "the test asks for an empty sub-range"
-        if reverse:
-            s = s.translate(self.comp)[::-1]
-        if self.mode == SEQ:
-            return s
-        if self.mode == SEQUENCES:
-            return s + b"\n"
-        mark = b"/rc" if reverse else b""
-        if whole:                                            # (reverse) '>' id "/rc", then what the stored line has behind the id; without ids the stored line, then "/rc"
-            hd = self.head[rec]
-            if self.has_ids:
-                assert hd[1:1 + len(self.ids[rec])] == self.ids[rec]
-                hd = hd[:1 + len(self.ids[rec])] + mark + hd[1 + len(self.ids[rec]):]
-            else:
-                hd = hd + mark
-            if self.mode == FASTQ:
-                return hd + b"\n" + s + b"\n" + self.plus[rec] + b"\n" + self.qual[rec][::-1] + b"\n"
-            return hd + b"\n" + self.wrap(s)
-        assert self.mode == FASTA
-        return b">" + self.ids[rec] + b":%d-%d" % (begin + 1, begin + len(s)) + mark + b"\n" + self.wrap(s)
-
-    def expect(self, segs):
-        return b"".join(self.segment(*s) for s in segs)
 
 
 def norm(s, reverse):
