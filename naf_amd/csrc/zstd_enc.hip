@@ -919,7 +919,8 @@ __device__ __forceinline__ bool ldm_key(u64 a, u64 b, u32 tlog, u32 &idx)
 {
     const u64 ha = ldm_mix(a);
     if (ha >> 61) return false;
-    idx = (u32)((ha ^ (ldm_mix(b ^ 0x5555555555555555ull) >> 7)) >> (64 - tlog));
+    // (an anchor's three top bits are zero: they are shifted out, or the index would reach an eighth of the table only)
+    idx = (u32)(((ha << 3) ^ ldm_mix(b ^ 0x5555555555555555ull)) >> (64 - tlog));
     return true;
 }
 __global__ __launch_bounds__(256) void k_ldm_insert(const u8 *src, u64 n, LdmTab L)

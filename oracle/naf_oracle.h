@@ -46,6 +46,19 @@ typedef struct {
 /* Decode the first frame and report its shape (test-side classification of golden frames). */
 long long nafo_zstd_frame_info_get(const uint8_t *src, size_t src_len, nafo_zstd_frame_info *info);
 
+/* The blocks and sequences of the first frame as the decoder meets them (tests that plant matches and look for them). */
+typedef struct { uint32_t type, size; } nafo_zstd_block;          /* Block_Type 0 Raw, 1 RLE, 2 Compressed; decoded size */
+typedef struct {
+    uint32_t block;                 /* number of the block that holds the sequence */
+    uint32_t offset_value;          /* Offset_Value as coded: 1..3 are repeat codes, else distance + 3 */
+    uint64_t pos;                   /* position of the match's first byte in the frame's output */
+    uint64_t ll, ml, distance;      /* Literals_Length, Match_Length, the resolved distance */
+} nafo_zstd_seq;
+typedef struct { nafo_zstd_block *blocks; size_t n_blocks, cap_blocks; nafo_zstd_seq *seqs; size_t n_seqs, cap_seqs; } nafo_zstd_seqlist;
+/* Decode the first frame and list it; returns the decoded size or <0 (the list is then empty).  Free with nafo_zstd_seqlist_free. */
+long long nafo_zstd_sequences(const uint8_t *src, size_t src_len, nafo_zstd_seqlist *list);
+void nafo_zstd_seqlist_free(nafo_zstd_seqlist *list);
+
 /* ---- NAF transforms : naf_oracle.c -------------------------------------------------------- */
 enum { NAFO_DNA = 0, NAFO_RNA = 1, NAFO_PROTEIN = 2, NAFO_TEXT = 3 };
 enum { NAFO_FMT_UNKNOWN = 0, NAFO_FMT_FASTA = 1, NAFO_FMT_FASTQ = 2 };

@@ -56,6 +56,35 @@ class FrameInfo(C.Structure):
                 ("has_fcs", C.c_uint32), ("max_offset", C.c_uint64)]
 
 
+class _ZBlock(C.Structure):
+    _fields_ = [("type", C.c_uint32), ("size", C.c_uint32)]
+
+
+class _ZSeq(C.Structure):
+    _fields_ = [("block", C.c_uint32), ("offset_value", C.c_uint32), ("pos", C.c_uint64), ("ll", C.c_uint64), ("ml", C.c_uint64),
+                ("distance", C.c_uint64)]
+
+
+class _ZSeqList(C.Structure):
+    _fields_ = [("blocks", C.POINTER(_ZBlock)), ("n_blocks", C.c_size_t), ("cap_blocks", C.c_size_t),
+                ("seqs", C.POINTER(_ZSeq)), ("n_seqs", C.c_size_t), ("cap_seqs", C.c_size_t)]
+
+
+class FrameSequences:
+    """What zstd_sequences lists: per block `block_type` (0 Raw, 1 RLE, 2 Compressed) and `block_size` (decoded bytes); per sequence the
+    numpy columns `block`, `pos` (the match's first byte in the output), `ll`, `ml`, `distance` and `offset_value` (as coded: 1..3 are
+    the repeat codes, else distance + 3)."""
+
+    def __init__(self, size, blocks, seqs):
+        self.size = size
+        self.block_type, self.block_size = blocks["type"].astype("i8"), blocks["size"].astype("i8")
+        for k in ("block", "pos", "ll", "ml", "distance", "offset_value"):
+            setattr(self, k, seqs[k].astype("i8"))
+
+    def __len__(self):
+        return len(self.pos)
+
+
 _lib = None
 
 
@@ -73,6 +102,9 @@ def lib():
         L.nafo_zstd_store_raw.argtypes = [C.c_char_p, C.c_size_t, C.c_void_p, C.c_size_t]
         L.nafo_zstd_frame_info_get.restype = C.c_longlong
         L.nafo_zstd_frame_info_get.argtypes = [C.c_char_p, C.c_size_t, C.POINTER(FrameInfo)]
+        L.nafo_zstd_sequences.restype = C.c_longlong
+        L.nafo_zstd_sequences.argtypes = [C.c_char_p, C.c_size_t, C.POINTER(_ZSeqList)]
+        L.nafo_zstd_seqlist_free.argtypes = [C.POINTER(_ZSeqList)]
         L.nafo_split_text.restype = C.c_int
         L.nafo_split_text.argtypes = [C.c_char_p, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(_Split)]
         L.nafo_split_free.argtypes = [C.POINTER(_Split)]
@@ -125,6 +157,23 @@ def zstd_frame_info(frame: bytes) -> FrameInfo:
     if n < 0:
         raise ValueError("oracle zstd: error %d" % n)
     return fi
+
+
+def zstd_sequences(frame: bytes) -> FrameSequences:
+    """Blocks and sequences of the (first) frame, listed by the decoder as it decodes them."""
+    import numpy as np
+    l = _ZSeqList()
+    n = lib().nafo_zstd_sequences(frame, len(frame), C.byref(l))
+    if n < 0:
+        raise ValueError("oracle zstd: error %d" % n)
+    try:
+        bt = np.dtype([("type", "<u4"), ("size", "<u4")])
+        st = np.dtype([("block", "<u4"), ("offset_value", "<u4"), ("pos", "<u8"), ("ll", "<u8"), ("ml", "<u8"), ("distance", "<u8")])
+        blocks = np.frombuffer(C.string_at(l.blocks, l.n_blocks * bt.itemsize), dtype=bt) if l.n_blocks else np.zeros(0, bt)
+        seqs = np.frombuffer(C.string_at(l.seqs, l.n_seqs * st.itemsize), dtype=st) if l.n_seqs else np.zeros(0, st)
+    finally:
+        lib().nafo_zstd_seqlist_free(C.byref(l))
+    return FrameSequences(int(n), blocks, seqs)
 
 
 # ---- ennaf side ------------------------------------------------------------------------------------

@@ -36,7 +36,34 @@ typedef struct {
     fse_table ll, of, ml; int ll_valid, of_valid, ml_valid;
     uint64_t rep[3];
     nafo_zstd_frame_info *info;
+    nafo_zstd_seqlist *list;        /* nafo_zstd_sequences: every block and sequence as decoded */
+    uint32_t block_no;
 } frame_ctx;
+
+/* append to the lists of nafo_zstd_sequences; 0, or ERR_DST when memory runs out */
+static int list_block(nafo_zstd_seqlist *l, uint32_t type, uint32_t size)
+{
+    if (l->n_blocks == l->cap_blocks) {
+        size_t cap = l->cap_blocks ? l->cap_blocks * 2 : 64;
+        nafo_zstd_block *nb = (nafo_zstd_block *)realloc(l->blocks, cap * sizeof *nb);
+        if (!nb) return ERR_DST;
+        l->blocks = nb; l->cap_blocks = cap;
+    }
+    l->blocks[l->n_blocks].type = type; l->blocks[l->n_blocks].size = size; l->n_blocks++;
+    return 0;
+}
+static int list_seq(nafo_zstd_seqlist *l, uint32_t block, uint64_t pos, uint64_t ll, uint64_t ml, uint64_t off, uint64_t ofv)
+{
+    if (l->n_seqs == l->cap_seqs) {
+        size_t cap = l->cap_seqs ? l->cap_seqs * 2 : 1024;
+        nafo_zstd_seq *ns = (nafo_zstd_seq *)realloc(l->seqs, cap * sizeof *ns);
+        if (!ns) return ERR_DST;
+        l->seqs = ns; l->cap_seqs = cap;
+    }
+    nafo_zstd_seq *q = &l->seqs[l->n_seqs++];
+    q->block = block; q->offset_value = (uint32_t)ofv; q->pos = pos; q->ll = ll; q->ml = ml; q->distance = off;
+    return 0;
+}
 
 /* ---- forward bit reader (FSE table descriptions) ---------------------------------------- */
 typedef struct { const uint8_t *p; size_t len; size_t bitpos; } fwd_bits;
@@ -346,6 +373,7 @@ static long long decode_compressed_block(frame_ctx *c, const uint8_t *src, size_
         if (op + ll + ml > MAX_BLOCK) return ERR_CORR;
         memcpy(out + op, lits + lp, ll); op += ll; lp += ll;
         if (seq_dump) fprintf(seq_dump, "%llu %llu %llu %llu\n", (unsigned long long)(dst_pos + op), (unsigned long long)ll, (unsigned long long)ml, (unsigned long long)off);
+        if (c->list && list_seq(c->list, c->block_no, dst_pos + op - frame_start, ll, ml, off, ofv) < 0) return ERR_DST;
         if (off > dst_pos + op - frame_start) return ERR_CORR;
         if (c->info && off > c->info->max_offset) c->info->max_offset = off;
         for (uint64_t k = 0; k < ml; k++) { out[op] = out[op - off]; op++; }
@@ -358,8 +386,15 @@ static long long decode_compressed_block(frame_ctx *c, const uint8_t *src, size_
     return (long long)op;
 }
 
+static long long decode_frame_x(const uint8_t *src, size_t len, uint8_t *dst, size_t dst_pos, size_t dst_cap,
+                                size_t *consumed, nafo_zstd_frame_info *info, nafo_zstd_seqlist *list);
 static long long decode_frame(const uint8_t *src, size_t len, uint8_t *dst, size_t dst_pos, size_t dst_cap,
                               size_t *consumed, nafo_zstd_frame_info *info)
+{
+    return decode_frame_x(src, len, dst, dst_pos, dst_cap, consumed, info, NULL);
+}
+static long long decode_frame_x(const uint8_t *src, size_t len, uint8_t *dst, size_t dst_pos, size_t dst_cap,
+                                size_t *consumed, nafo_zstd_frame_info *info, nafo_zstd_seqlist *list)
 {
     seq_dump_open();
     if (len < 4) return ERR_SRC;
@@ -397,13 +432,14 @@ static long long decode_frame(const uint8_t *src, size_t len, uint8_t *dst, size
 
     frame_ctx *c = (frame_ctx *)calloc(1, sizeof *c);
     if (!c) return ERR_DST;
-    c->rep[0] = 1; c->rep[1] = 4; c->rep[2] = 8; c->info = info;
+    c->rep[0] = 1; c->rep[1] = 4; c->rep[2] = 8; c->info = info; c->list = list;
     size_t start = dst_pos; long long rc = 0;
     for (;;) {
         if (end - p < 3) { rc = ERR_SRC; break; }
         uint32_t bh = p[0] | (p[1] << 8) | ((uint32_t)p[2] << 16); p += 3;
         int last = bh & 1, type = (bh >> 1) & 3; size_t bsize = bh >> 3;
         if (info) info->n_blocks++;
+        const size_t block_start = dst_pos;
         if (type == 0) {
             if (bsize > MAX_BLOCK) { rc = ERR_CORR; break; }
             if ((size_t)(end - p) < bsize) { rc = ERR_SRC; break; }
@@ -421,6 +457,8 @@ static long long decode_frame(const uint8_t *src, size_t len, uint8_t *dst, size
             if (n < 0) { rc = n; break; }
             dst_pos += (size_t)n; p += bsize; if (info) info->n_compressed++;
         } else { rc = ERR_CORR; break; }
+        if (list && list_block(list, (uint32_t)type, (uint32_t)(dst_pos - block_start)) < 0) { rc = ERR_DST; break; }
+        c->block_no++;
         if (last) break;
     }
     free(c);
@@ -471,6 +509,29 @@ long long nafo_zstd_frame_info_get(const uint8_t *src, size_t src_len, nafo_zstd
         if (!tmp) return ERR_DST;
         long long n = decode_frame(src, src_len, tmp, 0, cap, NULL, info);
         free(tmp);
+        if (n != ERR_DST) return n;
+        cap *= 4;
+        if (cap > ((size_t)1 << 40)) return ERR_DST;
+    }
+}
+
+void nafo_zstd_seqlist_free(nafo_zstd_seqlist *list)
+{
+    free(list->blocks); free(list->seqs);
+    memset(list, 0, sizeof *list);
+}
+
+long long nafo_zstd_sequences(const uint8_t *src, size_t src_len, nafo_zstd_seqlist *list)
+{
+    size_t cap = src_len * 4 + (1u << 20);
+    for (;;) {
+        uint8_t *tmp = (uint8_t *)malloc(cap);
+        if (!tmp) return ERR_DST;
+        memset(list, 0, sizeof *list);
+        long long n = decode_frame_x(src, src_len, tmp, 0, cap, NULL, NULL, list);
+        free(tmp);
+        if (n >= 0) return n;
+        nafo_zstd_seqlist_free(list);
         if (n != ERR_DST) return n;
         cap *= 4;
         if (cap > ((size_t)1 << 40)) return ERR_DST;

@@ -173,7 +173,7 @@ extern "C" long long emul_zstd_compress_lzx(const u8 *src, size_t n, u32 block, 
     auto key_of = [&](u64 pos, u32 &idx) -> bool {
         u64 a, b; memcpy(&a, s0 + pos, 8); memcpy(&b, s0 + pos + 8, 8);
         if ((ldm_mix(a) >> 61) != 0) return false;
-        idx = (u32)((ldm_mix(a) ^ (ldm_mix(b ^ 0x5555555555555555ull) >> 7)) >> (64 - tlog));
+        idx = (u32)(((ldm_mix(a) << 3) ^ ldm_mix(b ^ 0x5555555555555555ull)) >> (64 - tlog));
         return true;
     };
     for (u64 pos = 0; pos + 16 <= n; pos++) { u32 idx; if (key_of(pos, idx)) { u32 &t = tab[((pos >> elog) << tlog) + idx]; u32 rel = (u32)(pos & (E - 1)); if (rel < t) t = rel; } }
