@@ -1,7 +1,7 @@
 // composition.h -- base composition per record and per window, counted in the packed 4-bit stream (naf_gpu_composition_rows_of,
 // naf_gpu_unnaf_composition_rows, naf_gpu_unnaf_composition).  Part of emit.hip (included by it, behind locate.h): the front of the
-// call, the pieces and the decode of a piece's bytes are payload.h's (records_front, piece_plan, PieceSweep); this file holds the row
-// tables, the counting kernels and their launches.
+// call, the pieces and the decode of a piece's bytes are payload.h's (records_front, piece_plan, PieceSweep); the lane's 64 bases, the base
+// behind them, the bit planes and the row copy are packed.h's; this file holds the row tables, the counting kernels and their launches.
 //
 // The contract (include/naf_gpu.h carries it too):
 //   rows      window 0: one row per record, [0, len), an empty record a row of zeros.  window W > 0: ceil(len / W) rows
@@ -30,17 +30,14 @@
 #define COMP_TILE 4096u
 #define COMP_ROW_U64 21u
 #define COMP_PIECE_DEFAULT (1ull << 31)      // bases counted per decode (NAF_GPU_COMPOSITION_PIECE)
-#define COMP_L 0x11111111u
 
 __host__ __device__ __forceinline__ u64 comp_rows_of(u64 n, u64 W) { return W == 0 ? 1 : n / W + (n % W != 0); }
-
-typedef u32 comp_u32x4 __attribute__((ext_vector_type(4)));
 
 // bit 0 of every nibble of dword i (bases 8 i .. 8 i + 7 of a lane) whose base number is < k, k in 0 .. 64
 __device__ __forceinline__ u32 comp_below(u32 k, int i)
 {
     const int kk = (int)k - 8 * i;
-    return kk <= 0 ? 0u : kk >= 8 ? COMP_L : (COMP_L & ((1u << (4 * kk)) - 1u));
+    return kk <= 0 ? 0u : kk >= 8 ? NIB_L : (NIB_L & ((1u << (4 * kk)) - 1u));
 }
 
 // Counts of a lane's bases [a, b) into cnt[0..15], and into cnt[16] the C's of [a, bc) (bc <= b) whose next base is a G.  x: the lane's 64
@@ -51,20 +48,20 @@ __device__ __forceinline__ void comp_span(const u32 (&x)[8], u32 gnext, u32 a, u
 {
     u32 g2[9];
 #pragma unroll
-    for (int i = 0; i < 8; i++) { const u32 y = x[i]; g2[i] = FAST ? (y >> 1) & COMP_L : ~y & (y >> 1) & ~(y >> 2) & ~(y >> 3) & COMP_L; }
+    for (int i = 0; i < 8; i++) { const u32 y = x[i]; g2[i] = FAST ? (y >> 1) & NIB_L : ~y & (y >> 1) & ~(y >> 2) & ~(y >> 3) & NIB_L; }
     g2[8] = gnext;
 #pragma unroll
     for (int i = 0; i < 8; i++) {
-        const u32 y = x[i];
-        const u32 p0 = y & COMP_L, p1 = (y >> 1) & COMP_L, p2 = (y >> 2) & COMP_L, p3 = (y >> 3) & COMP_L;
-        const u32 m = FULL ? COMP_L : comp_below(b, i) & ~comp_below(a, i), mc = FULL ? COMP_L : comp_below(bc, i) & ~comp_below(a, i);
+        const u32 m = FULL ? NIB_L : comp_below(b, i) & ~comp_below(a, i), mc = FULL ? NIB_L : comp_below(bc, i) & ~comp_below(a, i);
         const u32 gn = (g2[i] >> 4) | (g2[i + 1] << 28);
         if (FAST) {
-            cnt[1] += __popc(p0 & m); cnt[2] += __popc(p1 & m); cnt[4] += __popc(p2 & m); cnt[8] += __popc(p3 & m);
+            const u32 y = x[i], p2 = (y >> 2) & NIB_L;
+            cnt[1] += __popc(y & NIB_L & m); cnt[2] += __popc((y >> 1) & NIB_L & m); cnt[4] += __popc(p2 & m); cnt[8] += __popc((y >> 3) & NIB_L & m);
             cnt[16] += __popc(p2 & gn & mc);
         } else {
-            const u32 q0 = p0 ^ COMP_L, q1 = p1 ^ COMP_L, q2 = p2 ^ COMP_L, q3 = p3 ^ COMP_L;
-            const u32 lo[4] = { q0 & q1 & m, p0 & q1 & m, q0 & p1 & m, p0 & p1 & m }, hi[4] = { q2 & q3, p2 & q3, q2 & p3, p2 & p3 };
+            u32 lo[4], hi[4]; nib_products(x[i], lo, hi);
+#pragma unroll
+            for (int l = 0; l < 4; l++) lo[l] &= m;
 #pragma unroll
             for (int h = 0; h < 4; h++)
 #pragma unroll
@@ -91,32 +88,17 @@ __global__ __launch_bounds__(64) void k_comp_count(const u8 *seq, u64 b_end, con
     const u64 g = t0 + t * COMP_TILE + lane * 64;                                 // the lane's first base
     const u64 lo = g > p_lo ? g : p_lo, hi = g + 64 < p_hi ? g + 64 : p_hi;       // the bases of it that are counted
     const bool active = g < p_hi && lo < hi;
-    u32 x[8] = { 0, 0, 0, 0, 0, 0, 0, 0 }, nx = 0;
-    if (active) {
-        const u64 b0 = g >> 1;
-        if (b0 + 32 <= b_end) {
-            comp_u32x4 v0, v1; memcpy(&v0, seq + b0, 16); memcpy(&v1, seq + b0 + 16, 16);
-            x[0] = v0.x; x[1] = v0.y; x[2] = v0.z; x[3] = v0.w; x[4] = v1.x; x[5] = v1.y; x[6] = v1.z; x[7] = v1.w;
-        } else {
-#pragma unroll
-            for (u32 k = 0; k < 8; k++) {
-                u32 v = 0;
-                for (u32 i = 0; i < 4; i++) if (b0 + 4 * k + i < b_end) v |= (u32)seq[b0 + 4 * k + i] << (8 * i);
-                x[k] = v;
-            }
-        }
-        if (lane == 63 && b0 + 32 < b_end) nx = seq[b0 + 32];                     // the base behind the tile's last
-    }
-    { const u32 o = (u32)__shfl_down((int)x[0], 1); if (lane != 63) nx = o; }
-    const u32 gnext = (nx & 15u) == 2u ? 1u : 0u;
+    u32 x[8] = { 0, 0, 0, 0, 0, 0, 0, 0 };
+    if (active) packed_load64(seq, b_end, g, x);
+    const u32 gnext = packed_behind(seq, b_end, g, active, lane, x) == 2u ? 1u : 0u;
 
     // single nucleotides only?  the sum of the planes is the number of letters in a base's set
     const u32 a0 = active ? (u32)(lo - g) : 0u, b0n = active ? (u32)(hi - g) : 0u;
     u32 bad = 0;
 #pragma unroll
     for (int i = 0; i < 8; i++) {
-        const u32 y = x[i], s = (y & COMP_L) + ((y >> 1) & COMP_L) + ((y >> 2) & COMP_L) + ((y >> 3) & COMP_L);
-        bad |= (s ^ COMP_L) & ((comp_below(b0n, i) & ~comp_below(a0, i)) * 15u);
+        const u32 y = x[i], s = (y & NIB_L) + ((y >> 1) & NIB_L) + ((y >> 2) & NIB_L) + ((y >> 3) & NIB_L);
+        bad |= (s ^ NIB_L) & ((comp_below(b0n, i) & ~comp_below(a0, i)) * 15u);
     }
     const bool fast = __ballot(bad != 0) == 0;
     if (paths && lane == 0) atomicAdd(&paths[fast ? 0 : 1], 1ull);
@@ -232,13 +214,6 @@ __global__ __launch_bounds__(256) void k_comp_total(const u64 *acc, u64 nrows, u
         if ((threadIdx.x & 63) == 0 && v) atomicAdd(&total[q], (unsigned long long)v);
     }
 }
-// the rows of a piece from the arena to a d_rows of any alignment
-__global__ __launch_bounds__(256) void k_comp_copy(const u64 *src, u8 *dst, u64 n)
-{
-    const u64 i = (u64)blockIdx.x * 256 + threadIdx.x;
-    if (i < n) st64(dst + 8 * i, src[i]);
-}
-
 // ---- host side -----------------------------------------------------------------------------------------------------------------
 extern "C" uint64_t naf_gpu_composition_rows_of(uint64_t n_bases, uint64_t window) { return comp_rows_of(n_bases, window); }
 
@@ -250,12 +225,12 @@ static int composition_run(naf_gpu_ctx *c, const u8 *d_naf, size_t naf_len, u64 
     if (h_total) memset(h_total, 0, sizeof *h_total);
     if (flags & ~(int)NAF_GPU_COMP_MASK) return ctx_fail(c, NAF_GPU_EARG, "composition: flags %d: only bit 0 (NAF_GPU_COMP_MASK) is defined", flags);
     UnnafPlan pl;
-    int rc = records_front(c, d_naf, naf_len, rows_only ? 0 : (flags & NAF_GPU_COMP_MASK), "composition", "nucleotides cannot be counted", first, &count, pl);   // the mask only when asked for
+    int rc = records_front(c, d_naf, naf_len, FRONT_4BIT | (!rows_only && (flags & NAF_GPU_COMP_MASK) ? FRONT_MASK : 0), "composition", "nucleotides cannot be counted", first, &count, pl);   // the mask only when asked for
     if (rc || !count) return rc;
     const EmitP &P = pl.P;
 
     // every row's place: row_base[i] = first row of record first + i, row_base[count] = rows in all
-    if (count + 1 > 0x7FFFFFFFull * 256) return ctx_fail(c, NAF_GPU_EARG, "composition: %llu records are too many for one launch", (unsigned long long)count);
+    LAUNCH_LIMIT(c, count + 1, 1, "composition: %llu records are too many for one launch", (unsigned long long)count);
     u64 *row_base = arena_new<u64>(c, count + 2); if (!row_base) return NAF_GPU_ENOMEM;
     LAUNCH(c, "unnaf_comp_rowcount", k_comp_rowcount, (u32)((count + 256) / 256), 256, 0, P.rec_len + first, count, W, row_base);
     if ((rc = scan_exclusive_u64(c, row_base, count + 1, (u64 *)nullptr))) return rc;
@@ -275,7 +250,7 @@ static int composition_run(naf_gpu_ctx *c, const u8 *d_naf, size_t naf_len, u64 
     // masked bases in front of every toggle
     const u64 *tog_ex = nullptr;
     if (P.masking && P.n_toggles) {
-        if (P.n_toggles + 1 > 0x7FFFFFFFull * 256) return ctx_fail(c, NAF_GPU_EARG, "composition: %llu mask toggles are too many for one launch", (unsigned long long)P.n_toggles);
+        LAUNCH_LIMIT(c, P.n_toggles + 1, 1, "composition: %llu mask toggles are too many for one launch", (unsigned long long)P.n_toggles);
         u64 *ex = arena_new<u64>(c, P.n_toggles + 2); if (!ex) return NAF_GPU_ENOMEM;
         LAUNCH(c, "unnaf_comp_mask", k_comp_togval, (u32)((P.n_toggles + 256) / 256), 256, 0, P.toggles, P.n_toggles, ex);
         if ((rc = scan_exclusive_u64(c, ex, P.n_toggles + 1, (u64 *)nullptr))) return rc;
@@ -290,7 +265,7 @@ static int composition_run(naf_gpu_ctx *c, const u8 *d_naf, size_t naf_len, u64 
         const RecPiece &pc = pieces[pi];
         const u64 R0 = rows_at[pi], nr = rows_at[pi + 1] - R0;
         if (!nr) continue;
-        if (nr > 0x7FFFFFFFull * 256 / COMP_ROW_U64) return ctx_fail(c, NAF_GPU_EARG, "composition: a piece of %llu rows is too long for one launch", (unsigned long long)nr);
+        LAUNCH_LIMIT(c, nr, COMP_ROW_U64, "composition: a piece of %llu rows is too long for one launch", (unsigned long long)nr);
         const bool bases = pc.p_hi > pc.p_lo;                                     // (empty records at window 0: rows, and nothing to decode)
         PieceSweep::Tiles tl = {};
         if (bases && (rc = sw.seq_for(pc, COMP_TILE, &tl))) return rc;
@@ -301,7 +276,7 @@ static int composition_run(naf_gpu_ctx *c, const u8 *d_naf, size_t naf_len, u64 
         if (bases) LAUNCH(c, "unnaf_comp_count", k_comp_count, (u32)tl.ntiles, 64, 0, tl.seq, tl.b_hi, P.rec_base, (const u64 *)row_base, first, pc.r_lo, pc.r_hi, pc.p_lo, pc.p_hi, tl.t0, W, R0, acc,
                           tracing ? (unsigned long long *)d_sum + 18 : (unsigned long long *)nullptr);
         if (h_total) { const u64 nb = (nr + 255) / 256; LAUNCH(c, "unnaf_comp_total", k_comp_total, (u32)(nb < 2048 ? nb : 2048), 256, 0, (const u64 *)acc, nr, (unsigned long long *)d_sum); }
-        if (!in_place) LAUNCH(c, "unnaf_comp_copy", k_comp_copy, (u32)((nr * COMP_ROW_U64 + 255) / 256), 256, 0, (const u64 *)acc, d_rows + 168 * R0, nr * COMP_ROW_U64);
+        if (!in_place) LAUNCH(c, "unnaf_row_copy", k_row_copy, (u32)((nr * COMP_ROW_U64 + 255) / 256), 256, 0, (const u64 *)acc, d_rows + 168 * R0, nr * COMP_ROW_U64);
         HIP_TRY(c, hipGetLastError());
         HIP_TRY(c, hipStreamSynchronize(c->stream));
         sw.release();

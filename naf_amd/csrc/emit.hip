@@ -15,6 +15,7 @@
 #include "ctx.h"
 #include "wgscan.h"
 #include "emit_core.h"
+#include "packed.h"
 #include <thread>
 
 // 16 bytes of output text that nothing on the device reads again: the nontemporal hint keeps them from displacing the compressed stream
@@ -22,9 +23,8 @@
 __device__ __forceinline__ void st_text16(u8 *p, const uint4 &v, int nt)
 {
     if (nt) {
-        typedef unsigned int u32x4_t __attribute__((ext_vector_type(4)));
-        u32x4_t nv; nv.x = v.x; nv.y = v.y; nv.z = v.z; nv.w = v.w;
-        __builtin_nontemporal_store(nv, (u32x4_t *)p);
+        u32x4 nv; nv.x = v.x; nv.y = v.y; nv.z = v.z; nv.w = v.w;
+        __builtin_nontemporal_store(nv, (u32x4 *)p);
     } else *(uint4 *)p = v;
 }
 

@@ -1,7 +1,7 @@
 // locate.h -- IUPAC motifs on either strand, searched in the packed 4-bit stream (naf_gpu_compile_motif, naf_gpu_unnaf_locate_count,
 // naf_gpu_unnaf_locate).  Part of emit.hip (included by it, behind emit_select.h): the front of the call, the pieces and the decode of
 // a piece's bytes are payload.h's (records_front, piece_plan, PieceSweep); this file holds the motif compiler, the two kernels and their
-// launches.
+// launches; the byte-wise load in front of the stream's end is packed.h's (packed_tail), the letter table payload.h's (base_code).
 //
 // In the code table "-TGKCYSBAWRDMHVN" a base is a SET of nucleotides (A = 8, C = 4, G = 2, T/U = 1, N = 15, '-' = 0), so
 //   a stored base c matches a pattern letter p   <=>   c != 0 && (c & ~p) == 0
@@ -69,14 +69,7 @@ __global__ __launch_bounds__(64) void k_locate(LocPats Q, const u8 *seq, u64 b_e
         if (b0 + nb <= b_end) {
 #pragma unroll
             for (u32 k = 0; k < nb / 8; k++) w[k] = ld64(seq + b0 + 8 * k);
-        } else {
-#pragma unroll
-            for (u32 k = 0; k < nb / 8; k++) {
-                u64 v = 0;
-                for (u32 i = 0; i < 8; i++) if (b0 + 8 * k + i < b_end) v |= (u64)seq[b0 + 8 * k + i] << (8 * i);
-                w[k] = v;
-            }
-        }
+        } else packed_tail<(LONG ? 6 : 5)>(seq, b_end, b0, w);
         const u64 x0 = g > p_lo ? g : p_lo;
         r = upper_bound_u64(rec_base, r_lo, r_hi + 1, x0) - 1;                    // rec_base[r_lo] <= x0 < rec_base[r_hi]: r_lo <= r < r_hi
         rbase = rec_base[r]; rend = rec_base[r + 1];
@@ -118,15 +111,8 @@ __global__ __launch_bounds__(64) void k_locate(LocPats Q, const u8 *seq, u64 b_e
 }
 
 // ---- host side -----------------------------------------------------------------------------------------------------------------
-// letter -> 4-bit set; 0 = no pattern letter
-static u8 motif_code(char ch)
-{
-    static const char tab[] = "-TGKCYSBAWRDMHVN";
-    if (ch >= 'a' && ch <= 'z') ch = (char)(ch - 32);
-    if (ch == 'U') ch = 'T';
-    for (u32 k = 1; k < 16; k++) if (tab[k] == ch) return (u8)k;
-    return 0;
-}
+// letter -> 4-bit set; 0 = no pattern letter (a gap is none)
+static u8 motif_code(char ch) { const int k = base_code(ch); return k > 0 ? (u8)k : 0; }
 // 0, or 1 + the index of the letter that is none; -1: the length is not 1 .. 32
 static int motif_compile(const char *text, u8 fwd[32], u8 rev[32], size_t *len)
 {
@@ -186,7 +172,7 @@ static int locate_run(naf_gpu_ctx *c, const u8 *d_naf, size_t naf_len, const cha
       } }
     if (per_pattern) for (size_t k = 0; k < 2 * n_patterns; k++) per_pattern[k] = 0;
     UnnafPlan pl;
-    int rc = records_front(c, d_naf, naf_len, 0, "locate", "nucleotide motifs cannot be searched", first, &count, pl);
+    int rc = records_front(c, d_naf, naf_len, FRONT_4BIT, "locate", "nucleotide motifs cannot be searched", first, &count, pl);
     if (rc || !count) return rc;
     const EmitP &P = pl.P;
     std::vector<RecPiece> pieces;
@@ -194,54 +180,35 @@ static int locate_run(naf_gpu_ctx *c, const u8 *d_naf, size_t naf_len, const cha
 
     u64 *combo_cnt = arena_new<u64>(c, LOC_MAX_COMBOS); if (!combo_cnt) return NAF_GPU_ENOMEM;
     PieceSweep sw(c, d_naf, pl, "locate");
-    u64 total = 0;
-    auto sweep = [&](bool writing) -> int {
-        total = 0;
-        HIP_TRY(c, hipMemsetAsync(combo_cnt, 0, LOC_MAX_COMBOS * 8, c->stream));
-        for (const RecPiece &pc : pieces) {
-            if (pc.p_hi == pc.p_lo) continue;
-            PieceSweep::Tiles tl;
-            int r = sw.seq_for(pc, LOC_TILE, &tl); if (r) return r;
-            const u64 ntiles = tl.ntiles;
-            u64 *tile_cnt = arena_new<u64>(c, ntiles + 2); u32 *lane_cnt = arena_new<u32>(c, ntiles * 64);
-            if (!tile_cnt || !lane_cnt) return NAF_GPU_ENOMEM;
-            HIP_TRY(c, hipMemsetAsync(tile_cnt + ntiles, 0, 8, c->stream));
+    rc = count_then_write(sw, pieces, LOC_TILE, { "hits", write, hit_cap, combo_cnt, LOC_MAX_COMBOS * 8 }, n_hits,
+                          [&](const RecPiece &pc, const PieceSweep::Tiles &tl, bool writing, u64 before, u64 *here) -> int {
+        const u64 ntiles = tl.ntiles;
+        u64 *tile_cnt = arena_new<u64>(c, ntiles + 2); u32 *lane_cnt = arena_new<u32>(c, ntiles * 64);
+        if (!tile_cnt || !lane_cnt) return NAF_GPU_ENOMEM;
+        HIP_TRY(c, hipMemsetAsync(tile_cnt + ntiles, 0, 8, c->stream));
 #define LOC_LAUNCH(W, name) do { \
-                if (any_long) LAUNCH(c, name, (k_locate<W, true>), (u32)ntiles, 64, 0, Q, tl.seq, tl.b_hi, P.rec_base, pc.r_lo, pc.r_hi, pc.p_lo, pc.p_hi, tl.t0, tile_cnt, lane_cnt, (unsigned long long *)combo_cnt, (const u64 *)tile_cnt, total, d_hits, (u64)hit_cap); \
-                else LAUNCH(c, name, (k_locate<W, false>), (u32)ntiles, 64, 0, Q, tl.seq, tl.b_hi, P.rec_base, pc.r_lo, pc.r_hi, pc.p_lo, pc.p_hi, tl.t0, tile_cnt, lane_cnt, (unsigned long long *)combo_cnt, (const u64 *)tile_cnt, total, d_hits, (u64)hit_cap); } while (0)
-            LOC_LAUNCH(false, "unnaf_locate_count");
-            if ((r = scan_exclusive_u64(c, tile_cnt, ntiles + 1, (u64 *)nullptr))) return r;
-            u64 here = 0;
-            if ((r = ctx_readback(c, &here, tile_cnt + ntiles, 8))) return r;
-            if (writing && here) {
-                if (total + here > hit_cap) { *n_hits = total + here; return NAF_GPU_ECAP; }   // (one piece: nothing has been written; several: the counting sweep has ruled this out)
-                if (!d_hits) return NAF_GPU_EARG;
-                LOC_LAUNCH(true, "unnaf_locate_write");
-                HIP_TRY(c, hipGetLastError());
-                HIP_TRY(c, hipStreamSynchronize(c->stream));
-            }
-#undef LOC_LAUNCH
-            total += here;
-            sw.release();
+            if (any_long) LAUNCH(c, name, (k_locate<W, true>), (u32)ntiles, 64, 0, Q, tl.seq, tl.b_hi, P.rec_base, pc.r_lo, pc.r_hi, pc.p_lo, pc.p_hi, tl.t0, tile_cnt, lane_cnt, (unsigned long long *)combo_cnt, (const u64 *)tile_cnt, before, d_hits, (u64)hit_cap); \
+            else LAUNCH(c, name, (k_locate<W, false>), (u32)ntiles, 64, 0, Q, tl.seq, tl.b_hi, P.rec_base, pc.r_lo, pc.r_hi, pc.p_lo, pc.p_hi, tl.t0, tile_cnt, lane_cnt, (unsigned long long *)combo_cnt, (const u64 *)tile_cnt, before, d_hits, (u64)hit_cap); } while (0)
+        LOC_LAUNCH(false, "unnaf_locate_count");
+        int r = tile_totals(c, ntiles, tile_cnt, here); if (r) return r;
+        if (writing && *here) {
+            if (before + *here > hit_cap) return NAF_GPU_ECAP;
+            if (!d_hits) return NAF_GPU_EARG;
+            LOC_LAUNCH(true, "unnaf_locate_write");
+            HIP_TRY(c, hipGetLastError());
+            HIP_TRY(c, hipStreamSynchronize(c->stream));
         }
+#undef LOC_LAUNCH
         return 0;
-    };
-    if (!write || pieces.size() > 1) { if ((rc = sweep(false))) return rc; }
-    *n_hits = total;
-    if (write && pieces.size() > 1 && total > hit_cap) return ctx_fail(c, NAF_GPU_ECAP, "locate: %llu hits, capacity %zu", (unsigned long long)total, hit_cap);
-    if (write) {
-        rc = sweep(true);
-        if (rc == NAF_GPU_ECAP && *n_hits > hit_cap) return ctx_fail(c, NAF_GPU_ECAP, "locate: %llu hits, capacity %zu", (unsigned long long)*n_hits, hit_cap);
-        if (rc) return rc;
-        *n_hits = total;
-    }
+    });
+    if (rc) return rc;
     if (per_pattern) {
         u64 cc[LOC_MAX_COMBOS];
         if ((rc = ctx_readback(c, cc, combo_cnt, sizeof cc))) return rc;
         for (u32 q = 0; q < Q.n; q++) per_pattern[2 * Q.pat[q] + Q.strand[q]] = cc[q];
     }
     if (ctx_tracing(c)) ctx_trace(c, "[locate] patterns %zu records %llu..%llu pieces %zu sequence bytes decoded %llu of %llu hits %llu\n", n_patterns,
-                                  (unsigned long long)first, (unsigned long long)(first + count), pieces.size(), (unsigned long long)sw.decoded, (unsigned long long)pl.seq_bytes, (unsigned long long)total);
+                                  (unsigned long long)first, (unsigned long long)(first + count), pieces.size(), (unsigned long long)sw.decoded, (unsigned long long)pl.seq_bytes, (unsigned long long)*n_hits);
     return 0;
 }
 

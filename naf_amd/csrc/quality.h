@@ -1,7 +1,7 @@
 // quality.h -- quality statistics per read and per cycle, counted in the quality stream (naf_gpu_quality_error_table,
-// naf_gpu_unnaf_quality_rows, naf_gpu_unnaf_quality).  Part of emit.hip (included by it, behind composition.h): the pieces and the decode
-// of a byte range are payload.h's (piece_plan, payload_range); this file holds the front of the call (lengths only, any sequence type),
-// the row tables, the counting kernel and its launches.  The contract is include/naf_gpu.h's.
+// naf_gpu_unnaf_quality_rows, naf_gpu_unnaf_quality).  Part of emit.hip (included by it, behind composition.h): the front of the call,
+// the pieces and the decode of a piece's bytes are payload.h's (records_front -- lengths only, any sequence type --, piece_plan, PieceSweep),
+// the row copy is packed.h's; this file holds the row tables, the counting kernel and its launches.  The contract is include/naf_gpu.h's.
 //
 // In a .naf the quality byte g belongs to base g, so rec_base / rec_len of the sequence are the record tables of the quality stream.  A row
 // is 7 u64: key, n, sum, ee, n_q20, n_q30 and the u32 pair (min, max).  Record rows are initialised with key, n = rec_len and min = 255
@@ -58,7 +58,6 @@ struct QBin { unsigned long long ns, qq, ee; u32 mn, mx; };        // LDS: n << 
 struct QStat { u32 n, sum, q20, q30, mn, mx; u64 ee; };
 __device__ __forceinline__ void qual_zero(QStat &S) { S.n = S.sum = S.q20 = S.q30 = 0; S.mn = 255; S.mx = 0; S.ee = 0; }
 
-typedef u32 qual_u32x4 __attribute__((ext_vector_type(4)));
 typedef unsigned short qual_u16x2 __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ u32 qual_pk_min(u32 a, u32 b)
 {
@@ -203,7 +202,7 @@ __global__ __launch_bounds__(256) void k_qual_count(QualP P)
             if (active) {
                 if (g >= P.b_lo && g + 64 <= P.b_hi) {
 #pragma unroll
-                    for (int i = 0; i < 4; i++) { qual_u32x4 v; memcpy(&v, P.q + g + 16 * i, 16); x[4 * i] = v.x; x[4 * i + 1] = v.y; x[4 * i + 2] = v.z; x[4 * i + 3] = v.w; }
+                    for (int i = 0; i < 4; i++) { u32x4 v; memcpy(&v, P.q + g + 16 * i, 16); x[4 * i] = v.x; x[4 * i + 1] = v.y; x[4 * i + 2] = v.z; x[4 * i + 3] = v.w; }
                 } else {                                                          // the head or the tail of what was decoded
 #pragma unroll
                     for (int j = 0; j < 64; j++) if (g + j >= lo && g + j < hi) x[j >> 2] |= (u32)P.q[g + j] << (8 * (j & 3));
@@ -320,13 +319,6 @@ __global__ __launch_bounds__(256) void k_qual_maxlen(const u64 *len, u64 n, unsi
     for (int d = 32; d; d >>= 1) { const u64 o = shfl_u64(m, (int)((threadIdx.x & 63) ^ d)); m = o > m ? o : m; }
     if ((threadIdx.x & 63) == 0 && m) atomicMax(out, (unsigned long long)m);
 }
-// rows from the arena to a table of any alignment
-__global__ __launch_bounds__(256) void k_qual_copy(const u64 *src, u8 *dst, u64 n)
-{
-    const u64 i = (u64)blockIdx.x * 256 + threadIdx.x;
-    if (i < n) st64(dst + 8 * i, src[i]);
-}
-
 // ---- host side -----------------------------------------------------------------------------------------------------------------
 extern "C" int naf_gpu_quality_error_table(uint64_t tab[256])
 {
@@ -335,26 +327,15 @@ extern "C" int naf_gpu_quality_error_table(uint64_t tab[256])
     return 0;
 }
 
-// arena_reset, the checks of first / count (worded as records_front words them), the archive's quality section and the record tables
-// from the lengths alone -- any sequence type; neither sequence nor mask nor ids are decoded.  *count comes back resolved; 0 = nothing
-// to do, and the tables were then not made.
+// records_front for a call on the quality stream -- the record tables from the lengths alone, any sequence type; neither sequence nor
+// mask nor ids are decoded -- and the check that every base has its quality code.
 static int quality_front(naf_gpu_ctx *c, const u8 *d_naf, size_t naf_len, u64 first, u64 *count, UnnafPlan &pl)
 {
-    arena_reset(c);
-    naf_gpu_unnaf_opts o = { NAF_OUT_SEQUENCES, 0, -1 };
-    int rc = unnaf_prepare(c, d_naf, naf_len, &o, pl); if (rc) return rc;
+    int rc = records_front(c, d_naf, naf_len, FRONT_QUALITY, "quality", nullptr, first, count, pl);
+    if (rc || !*count) return rc;
     const naf_gpu_header &h = pl.h;
-    const u64 N = h.n_sequences;
-    if (first > N) return ctx_fail(c, NAF_GPU_EARG, "quality: first record %llu, the archive has %llu", (unsigned long long)first, (unsigned long long)N);
-    if (*count == NAF_GPU_WHOLE) *count = N - first;
-    if (*count > N - first) return ctx_fail(c, NAF_GPU_EARG, "quality: records %llu..%llu of %llu", (unsigned long long)first, (unsigned long long)(first + *count), (unsigned long long)N);
-    if (N == 0) { *count = 0; return 0; }
-    if (!(h.flags & 1)) return ctx_fail(c, NAF_GPU_EARG, "quality: the archive has no quality section");
-    if (pl.empty) return ctx_fail(c, NAF_GPU_EARG, "quality: the archive stores no sequence to hold its lengths against");
-    if (*count == 0) return 0;
-    if ((rc = unnaf_sections(c, d_naf, pl))) return rc;
     u64 bases = 0;
-    if ((rc = ctx_readback(c, &bases, pl.P.rec_base + N, 8))) return rc;
+    if ((rc = ctx_readback(c, &bases, pl.P.rec_base + h.n_sequences, 8))) return rc;
     if (h.orig_size[S_QUAL] < bases)
         return ctx_fail(c, NAF_GPU_EFORMAT, "corrupted quality: %llu quality codes stored for %llu bases\n", (unsigned long long)h.orig_size[S_QUAL], (unsigned long long)bases);
     return 0;
@@ -374,7 +355,7 @@ static int quality_run(naf_gpu_ctx *c, const u8 *d_naf, size_t naf_len, u64 W, u
     *n_records = count;
 
     // the longest selected record: the cycle table's rows
-    if (count > 0x7FFFFFFFull * 256) return ctx_fail(c, NAF_GPU_EARG, "quality: %llu records are too many for one launch", (unsigned long long)count);
+    LAUNCH_LIMIT(c, count, 1, "quality: %llu records are too many for one launch", (unsigned long long)count);
     u64 *d_sum = arena_new<u64>(c, 8 + 256); if (!d_sum) return NAF_GPU_ENOMEM;   // [0] longest, [1..7] the total row, [8..263] the histogram
     HIP_TRY(c, hipMemsetAsync(d_sum, 0, (8 + 256) * 8, c->stream));
     u64 maxlen = 0;
@@ -397,7 +378,7 @@ static int quality_run(naf_gpu_ctx *c, const u8 *d_naf, size_t naf_len, u64 W, u
     u64 *d_total = d_sum + 1, *d_cyc_acc = nullptr;
     LAUNCH(c, "unnaf_qual_rows", k_qual_rows, 1, 256, 0, d_total, (u64)1, count, (const u64 *)nullptr);
     if (want_cyc && C) {
-        if (C > 0x7FFFFFFFull * 256 / QUAL_ROW_U64) return ctx_fail(c, NAF_GPU_EARG, "quality: %llu cycle rows are too many for one launch", (unsigned long long)C);
+        LAUNCH_LIMIT(c, C, QUAL_ROW_U64, "quality: %llu cycle rows are too many for one launch", (unsigned long long)C);
         d_cyc_acc = arena_new<u64>(c, C * QUAL_ROW_U64); if (!d_cyc_acc) return NAF_GPU_ENOMEM;
         LAUNCH(c, "unnaf_qual_rows", k_qual_rows, (u32)((C + 255) / 256), 256, 0, d_cyc_acc, C, (u64)0, (const u64 *)nullptr);
     }
@@ -410,25 +391,16 @@ static int quality_run(naf_gpu_ctx *c, const u8 *d_naf, size_t naf_len, u64 W, u
     { const char *e = ctx_opt(c, "QUALITY_FLUSH"); if (e && e[0]) { const u64 v = strtoull(e, nullptr, 10); if (v && v < flush_iters) flush_iters = (u32)v; } }
     const u64 q_bytes = pl.h.orig_size[S_QUAL];
 
-    // piece by piece: a piece's bytes are decoded alone where the frame allows it and given back with its rows; a frame of dependent
-    // blocks is decoded whole once and stays
-    std::vector<size_t> mark = arena_mark(c);
-    const u8 *whole = nullptr;
-    u64 decoded = 0;
+    PieceSweep sw(c, d_naf, pl, "quality", S_QUAL);
     for (size_t pi = 0; pi < pieces.size(); pi++) {
         const RecPiece &pc = pieces[pi];
         const u64 nr = pc.r_hi - pc.r_lo;
-        if (nr > 0x7FFFFFFFull * 256 / QUAL_ROW_U64) return ctx_fail(c, NAF_GPU_EARG, "quality: a piece of %llu records is too long for one launch", (unsigned long long)nr);
+        LAUNCH_LIMIT(c, nr, QUAL_ROW_U64, "quality: a piece of %llu records is too long for one launch", (unsigned long long)nr);
         QualP Q; memset(&Q, 0, sizeof Q);
         if (pc.p_hi > pc.p_lo) {
-            if (!whole) {
-                PayloadSpan sp;
-                if ((rc = payload_range(c, d_naf, pl, S_QUAL, pc.p_lo, pc.p_hi, PAYLOAD_RANGE, &sp))) return rc;
-                decoded += sp.got_hi - sp.got_lo;
-                if (sp.ranged) { Q.q = sp.base; Q.b_lo = sp.got_lo; Q.b_hi = sp.got_hi; }
-                else { whole = sp.base; mark = arena_mark(c); }
-            }
-            if (whole) { Q.q = whole; Q.b_lo = 0; Q.b_hi = q_bytes; }
+            PayloadSpan sp;
+            if ((rc = sw.bytes_for(pc.p_lo, pc.p_hi, &sp))) return rc;
+            Q.q = sp.base; Q.b_lo = sp.got_lo; Q.b_hi = sp.got_hi;
             if (Q.b_lo > pc.p_lo || Q.b_hi < pc.p_hi) return ctx_fail(c, NAF_GPU_EFORMAT, "can't decompress quality\n");
         }
         u64 *acc = nullptr;
@@ -446,19 +418,19 @@ static int quality_run(naf_gpu_ctx *c, const u8 *d_naf, size_t naf_len, u64 W, u
             const u64 wgs = (Q.ntiles + 3) / 4;
             LAUNCH(c, "unnaf_qual_count", k_qual_count, (u32)(wgs < max_grid ? wgs : max_grid), 256, 0, Q);
         }
-        if (want_rec) LAUNCH(c, "unnaf_qual_copy", k_qual_copy, (u32)((nr * QUAL_ROW_U64 + 255) / 256), 256, 0, (const u64 *)acc, d_rec + 56 * (pc.r_lo - first), nr * QUAL_ROW_U64);
+        if (want_rec) LAUNCH(c, "unnaf_row_copy", k_row_copy, (u32)((nr * QUAL_ROW_U64 + 255) / 256), 256, 0, (const u64 *)acc, d_rec + 56 * (pc.r_lo - first), nr * QUAL_ROW_U64);
         HIP_TRY(c, hipGetLastError());
         HIP_TRY(c, hipStreamSynchronize(c->stream));
-        arena_release(c, mark);
+        sw.release();
     }
-    if (d_cyc_acc) LAUNCH(c, "unnaf_qual_copy", k_qual_copy, (u32)((C * QUAL_ROW_U64 + 255) / 256), 256, 0, (const u64 *)d_cyc_acc, d_cyc, C * QUAL_ROW_U64);
+    if (d_cyc_acc) LAUNCH(c, "unnaf_row_copy", k_row_copy, (u32)((C * QUAL_ROW_U64 + 255) / 256), 256, 0, (const u64 *)d_cyc_acc, d_cyc, C * QUAL_ROW_U64);
     HIP_TRY(c, hipGetLastError());
     u64 sum[8 + 256];
     if ((rc = ctx_readback(c, sum, d_sum, sizeof sum))) return rc;                // (waits for the copy too)
     if (h_hist) memcpy(h_hist, sum + 8, 256 * 8);
     if (h_total) { h_total->n = sum[2]; h_total->sum = sum[3]; h_total->ee = sum[4]; h_total->n_q20 = sum[5]; h_total->n_q30 = sum[6]; h_total->min = (u32)sum[7]; h_total->max = (u32)(sum[7] >> 32); }
     if (ctx_tracing(c)) ctx_trace(c, "[quality] records %llu cycle rows %llu pieces %zu quality bytes decoded %llu of %llu lds bins %u global bins %llu\n", (unsigned long long)count,
-                                  (unsigned long long)C, pieces.size(), (unsigned long long)decoded, (unsigned long long)q_bytes, K, (unsigned long long)(d_cyc_acc ? C - K : 0));
+                                  (unsigned long long)C, pieces.size(), (unsigned long long)sw.decoded, (unsigned long long)q_bytes, K, (unsigned long long)(d_cyc_acc ? C - K : 0));
     return 0;
 }
 

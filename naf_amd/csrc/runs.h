@@ -1,7 +1,8 @@
 // runs.h -- runs of a base class and soft-masked intervals per record, listed from the packed 4-bit stream and from the mask's toggle
 // list (naf_gpu_parse_base_class, naf_gpu_unnaf_runs_count, naf_gpu_unnaf_runs).  Part of emit.hip (included by it, behind quality.h):
-// the front of the call, the pieces and the decode of a piece's bytes are payload.h's (records_front, piece_plan, PieceSweep); this file
-// holds the class parser, the kernels and their launches.
+// the front of the call, the pieces and the decode of a piece's bytes are payload.h's (records_front, piece_plan, PieceSweep); the lane's
+// 64 bases, the bases in front of and behind them and the bit planes are packed.h's; this file holds the class parser, the kernels and
+// their launches.
 //
 // The contract (include/naf_gpu.h carries it too):
 //   class     bit c of `set` = 4-bit code c of "-TGKCYSBAWRDMHVN".  Membership is LITERAL: a stored N is in {N}, a stored R is not --
@@ -33,23 +34,18 @@
 
 #define RUNS_TILE 4096u
 #define RUNS_PIECE_DEFAULT (1ull << 31)      // bases swept per decode (NAF_GPU_RUNS_PIECE)
-#define RUNS_L 0x11111111u
 #define RUNS_FLAGS (NAF_GPU_RUNS_EACH | NAF_GPU_RUNS_MASKED)
-
-typedef u32 runs_u32x4 __attribute__((ext_vector_type(4)));
 
 // bit 0 of each of a dword's eight nibbles -> eight adjacent bits
 __device__ __forceinline__ u32 runs_pack8(u32 y)
 {
-    y &= RUNS_L; y = (y | (y >> 3)) & 0x03030303u; y = (y | (y >> 6)) & 0x000F000Fu;
+    y &= NIB_L; y = (y | (y >> 3)) & 0x03030303u; y = (y | (y >> 6)) & 0x000F000Fu;
     return (y | (y >> 12)) & 0xFFu;
 }
 // bit 0 of every nibble of y whose code is in `set` (the same in every lane: the ANDs are picked by scalar branches)
 __device__ __forceinline__ u32 runs_member(u32 y, u32 set)
 {
-    const u32 p0 = y & RUNS_L, p1 = (y >> 1) & RUNS_L, p2 = (y >> 2) & RUNS_L, p3 = (y >> 3) & RUNS_L;
-    const u32 q0 = p0 ^ RUNS_L, q1 = p1 ^ RUNS_L, q2 = p2 ^ RUNS_L, q3 = p3 ^ RUNS_L;
-    const u32 lo[4] = { q0 & q1, p0 & q1, q0 & p1, p0 & p1 }, hi[4] = { q2 & q3, p2 & q3, q2 & p3, p2 & p3 };
+    u32 lo[4], hi[4]; nib_products(y, lo, hi);
     u32 m = 0;
 #pragma unroll
     for (int h = 0; h < 4; h++) {
@@ -80,24 +76,9 @@ __global__ __launch_bounds__(64) void k_runs_mark(const u8 *seq, u64 b_end, cons
     const u64 g = t0 + t * RUNS_TILE + lane * 64;                                 // the lane's first base
     const u64 lo = g > p_lo ? g : p_lo, hi = g + 64 < p_hi ? g + 64 : p_hi;       // the bases of it that are swept
     const bool active = g < p_hi && lo < hi;
-    u32 x[8] = { 0, 0, 0, 0, 0, 0, 0, 0 }, pc = 0, nc = 0;
-    if (active) {
-        const u64 b0 = g >> 1;
-        if (b0 + 32 <= b_end) {
-            runs_u32x4 v0, v1; memcpy(&v0, seq + b0, 16); memcpy(&v1, seq + b0 + 16, 16);
-            x[0] = v0.x; x[1] = v0.y; x[2] = v0.z; x[3] = v0.w; x[4] = v1.x; x[5] = v1.y; x[6] = v1.z; x[7] = v1.w;
-        } else {
-#pragma unroll
-            for (u32 k = 0; k < 8; k++) {
-                u32 v = 0;
-                for (u32 i = 0; i < 4; i++) if (b0 + 4 * k + i < b_end) v |= (u32)seq[b0 + 4 * k + i] << (8 * i);
-                x[k] = v;
-            }
-        }
-        if (lane == 0 && g > p_lo) pc = (u32)seq[b0 - 1] >> 4;                    // the base in front of the tile's first (g - 1 >= p_lo: a decoded byte)
-        if (lane == 63 && b0 + 32 < b_end) nc = (u32)seq[b0 + 32] & 15u;          // the base behind the tile's last
-    }
-    { const u32 up = (u32)__shfl_up((int)x[7], 1) >> 28, dn = (u32)__shfl_down((int)x[0], 1) & 15u; if (lane != 0) pc = up; if (lane != 63) nc = dn; }
+    u32 x[8] = { 0, 0, 0, 0, 0, 0, 0, 0 };
+    if (active) packed_load64(seq, b_end, g, x);
+    const u32 pc = packed_front(seq, p_lo, g, active, lane, x), nc = packed_behind(seq, b_end, g, active, lane, x);
 
     u64 S = 0, E = 0;
     if (active) {
@@ -234,43 +215,38 @@ __global__ __launch_bounds__(256) void k_runs_mask_cand(const u64 *rec_base, u64
 // 0, or NAF_GPU_EARG for what is no class
 extern "C" int naf_gpu_parse_base_class(const char *text, uint16_t *set)
 {
-    static const char tab[] = "-TGKCYSBAWRDMHVN";
     if (!text || !set) return NAF_GPU_EARG;
     const bool inv = text[0] == '^';
     const char *p = text + (inv ? 1 : 0);
     if (!*p) return NAF_GPU_EARG;
     u32 s = 0;
     for (; *p; p++) {
-        char ch = *p;
-        if (ch >= 'a' && ch <= 'z') ch = (char)(ch - 32);
-        if (ch == 'U') ch = 'T';
-        const char *q = (const char *)memchr(tab, ch, 16);
-        if (!q) return NAF_GPU_EARG;
-        s |= 1u << (u32)(q - tab);
+        const int k = base_code(*p);
+        if (k < 0) return NAF_GPU_EARG;
+        s |= 1u << k;
     }
     *set = (uint16_t)(inv ? ~s & 0xFFFFu : s);
     return 0;
 }
 
-// what both kinds of call do with a table of candidates: the min_len flags, their scan and -- when writing -- the rows
+// what both kinds of call do with a table of candidates: the min_len flags, their scan (*here = the kept ones) and -- when writing -- the rows
+// behind the `before` of earlier tables.  A bare NAF_GPU_ECAP when before + *here > run_cap: nothing of this table has then been written.
 static int runs_finish(naf_gpu_ctx *c, const u64 *starts, const u64 *ends, u64 n, u64 min_len, const u64 *rec_base, u64 r_lo, u64 r_hi, const u8 *seq,
-                       unsigned long long *d_sum, bool writing, u8 *d_runs, u64 run_cap, u64 *total, u64 *n_runs)
+                       unsigned long long *d_sum, bool writing, u8 *d_runs, u64 run_cap, u64 before, u64 *here)
 {
-    if (n + 1 > 0x7FFFFFFFull * 256) return ctx_fail(c, NAF_GPU_EARG, "runs: %llu candidates are too many for one launch: set NAF_GPU_RUNS_PIECE to fewer bases", (unsigned long long)n);
+    LAUNCH_LIMIT(c, n + 1, 1, "runs: %llu candidates are too many for one launch: set NAF_GPU_RUNS_PIECE to fewer bases", (unsigned long long)n);
     u64 *flag = arena_new<u64>(c, n + 2);
     if (!flag) return ctx_fail(c, NAF_GPU_ENOMEM, "runs: no room for the flags of %llu candidates: set NAF_GPU_RUNS_PIECE to fewer bases", (unsigned long long)n);
     LAUNCH(c, "unnaf_runs_pair", k_runs_pair, (u32)((n + 256) / 256), 256, 0, starts, ends, n, min_len, flag, d_sum);
     int rc = scan_exclusive_u64(c, flag, n + 1, (u64 *)nullptr); if (rc) return rc;
-    u64 here = 0;
-    if ((rc = ctx_readback(c, &here, flag + n, 8))) return rc;
-    if (writing && here) {
-        if (*total + here > run_cap) { *n_runs = *total + here; return NAF_GPU_ECAP; }      // (one piece: nothing has been written; several: the counting sweep has ruled this out)
+    if ((rc = ctx_readback(c, here, flag + n, 8))) return rc;
+    if (writing && *here) {
+        if (before + *here > run_cap) return NAF_GPU_ECAP;
         if (!d_runs) return ctx_fail(c, NAF_GPU_EARG, "runs: no place for the rows (d_runs is NULL)");
-        LAUNCH(c, "unnaf_runs_rows", k_runs_rows, (u32)((n + 255) / 256), 256, 0, starts, ends, (const u64 *)flag, n, rec_base, r_lo, r_hi, seq, *total, d_runs);
+        LAUNCH(c, "unnaf_runs_rows", k_runs_rows, (u32)((n + 255) / 256), 256, 0, starts, ends, (const u64 *)flag, n, rec_base, r_lo, r_hi, seq, before, d_runs);
         HIP_TRY(c, hipGetLastError());
         HIP_TRY(c, hipStreamSynchronize(c->stream));
     }
-    *total += here;
     return 0;
 }
 
@@ -287,7 +263,7 @@ static int runs_run(naf_gpu_ctx *c, const u8 *d_naf, size_t naf_len, u32 set, in
     if (!masked && !set) return ctx_fail(c, NAF_GPU_EARG, "runs: the class is empty (set 0)");
     if (!min_len) return ctx_fail(c, NAF_GPU_EARG, "runs: min_len 0: a run has at least one base");
     UnnafPlan pl;
-    int rc = records_front(c, d_naf, naf_len, masked ? 1 : 0, "runs", "runs of bases cannot be listed", first, &count, pl);   // the mask only when asked for
+    int rc = records_front(c, d_naf, naf_len, FRONT_4BIT | (masked ? FRONT_MASK : 0), "runs", "runs of bases cannot be listed", first, &count, pl);   // the mask only when asked for
     if (rc || !count) return rc;
     const EmitP &P = pl.P;
     const bool tracing = ctx_tracing(c);
@@ -299,7 +275,7 @@ static int runs_run(naf_gpu_ctx *c, const u8 *d_naf, size_t naf_len, u32 set, in
         HIP_TRY(c, hipMemsetAsync(d_sum, 0, 16, c->stream));
         const u64 nt = P.masking ? P.n_toggles : 0;
         if (nt) {
-            if (nt + 1 > 0x7FFFFFFFull * 256 || count + 1 > 0x7FFFFFFFull * 256) return ctx_fail(c, NAF_GPU_EARG, "runs: %llu mask toggles, %llu records: too many for one launch", (unsigned long long)nt, (unsigned long long)count);
+            LAUNCH_LIMIT(c, std::max(nt, count) + 1, 1, "runs: %llu mask toggles, %llu records: too many for one launch", (unsigned long long)nt, (unsigned long long)count);
             // the toggles that change the parity
             u64 *keep = arena_new<u64>(c, nt + 2); if (!keep) return NAF_GPU_ENOMEM;
             LAUNCH(c, "unnaf_runs_mask_keep", k_runs_tog_keep, (u32)((nt + 256) / 256), 256, 0, P.toggles, nt, keep);
@@ -313,12 +289,12 @@ static int runs_run(naf_gpu_ctx *c, const u8 *d_naf, size_t naf_len, u32 set, in
             if ((rc = scan_exclusive_u64(c, cnt, count + 1, (u64 *)nullptr))) return rc;
             if ((rc = ctx_readback(c, &cands, cnt + count, 8))) return rc;
             if (cands) {
-                if (cands > 0x7FFFFFFFull * 256) return ctx_fail(c, NAF_GPU_EARG, "runs: %llu masked intervals are too many for one launch", (unsigned long long)cands);
+                LAUNCH_LIMIT(c, cands, 1, "runs: %llu masked intervals are too many for one launch", (unsigned long long)cands);
                 u64 *starts = arena_new<u64>(c, cands), *ends = arena_new<u64>(c, cands);
                 if (!starts || !ends) return ctx_fail(c, NAF_GPU_ENOMEM, "runs: no room for %llu masked intervals", (unsigned long long)cands);
                 LAUNCH(c, "unnaf_runs_mask_cand", k_runs_mask_cand, (u32)((cands + 255) / 256), 256, 0, P.rec_base, first, count, (const u64 *)cnt, (const u64 *)tc, nc, cands, starts, ends);
-                rc = runs_finish(c, starts, ends, cands, min_len, P.rec_base, first, first + count, nullptr, d_sum, write, d_runs, run_cap, &total, n_runs);
-                if (rc == NAF_GPU_ECAP) return ctx_fail(c, NAF_GPU_ECAP, "runs: %llu runs, capacity %zu", (unsigned long long)*n_runs, run_cap);
+                rc = runs_finish(c, starts, ends, cands, min_len, P.rec_base, first, first + count, nullptr, d_sum, write, d_runs, run_cap, 0, &total);
+                if (rc == NAF_GPU_ECAP) { *n_runs = total; return cap_fail(c, "runs", "runs", total, run_cap); }
                 if (rc) return rc;
             }
         }
@@ -327,49 +303,33 @@ static int runs_run(naf_gpu_ctx *c, const u8 *d_naf, size_t naf_len, u32 set, in
         if ((rc = piece_plan(c, P, first, count, "RUNS_PIECE", RUNS_PIECE_DEFAULT, pieces))) return rc;
         n_pieces = pieces.size();
         PieceSweep sw(c, d_naf, pl, "runs");
-        auto sweep = [&](bool writing) -> int {
-            total = 0; cands = 0;
-            HIP_TRY(c, hipMemsetAsync(d_sum, 0, 16, c->stream));
-            for (const RecPiece &pc : pieces) {
-                if (pc.p_hi == pc.p_lo) continue;
-                PieceSweep::Tiles tl;
-                int r = sw.seq_for(pc, RUNS_TILE, &tl); if (r) return r;
-                const u64 ntiles = tl.ntiles;
-                u64 *cnt_s = arena_new<u64>(c, ntiles + 2), *cnt_e = arena_new<u64>(c, ntiles + 2);
-                if (!cnt_s || !cnt_e) return ctx_fail(c, NAF_GPU_ENOMEM, "runs: no room for the counts of %llu tiles: set NAF_GPU_RUNS_PIECE to fewer bases", (unsigned long long)ntiles);
-                HIP_TRY(c, hipMemsetAsync(cnt_s + ntiles, 0, 8, c->stream));
-                HIP_TRY(c, hipMemsetAsync(cnt_e + ntiles, 0, 8, c->stream));
+        u64 cands_of[2] = { 0, 0 };                                                 // of the counting and of the writing sweep
+        rc = count_then_write(sw, pieces, RUNS_TILE, { "runs", write, run_cap, d_sum, 16 }, &total,
+                              [&](const RecPiece &pc, const PieceSweep::Tiles &tl, bool writing, u64 before, u64 *here) -> int {
+            const u64 ntiles = tl.ntiles;
+            u64 *cnt_s = arena_new<u64>(c, ntiles + 2), *cnt_e = arena_new<u64>(c, ntiles + 2);
+            if (!cnt_s || !cnt_e) return ctx_fail(c, NAF_GPU_ENOMEM, "runs: no room for the counts of %llu tiles: set NAF_GPU_RUNS_PIECE to fewer bases", (unsigned long long)ntiles);
+            HIP_TRY(c, hipMemsetAsync(cnt_s + ntiles, 0, 8, c->stream));
+            HIP_TRY(c, hipMemsetAsync(cnt_e + ntiles, 0, 8, c->stream));
 #define RUNS_LAUNCH(W, name, st, en, cap) LAUNCH(c, name, k_runs_mark<W>, (u32)ntiles, 64, 0, tl.seq, tl.b_hi, P.rec_base, pc.r_lo, pc.r_hi, pc.p_lo, pc.p_hi, tl.t0, set, each ? 1u : 0u, min_len, \
-                                                  cnt_s, cnt_e, (const u64 *)cnt_s, (const u64 *)cnt_e, st, en, cap)
-                RUNS_LAUNCH(false, "unnaf_runs_count", (u64 *)nullptr, (u64 *)nullptr, (u64)0);
-                if ((r = scan_exclusive_u64(c, cnt_s, ntiles + 1, (u64 *)nullptr))) return r;
-                if ((r = scan_exclusive_u64(c, cnt_e, ntiles + 1, (u64 *)nullptr))) return r;
-                u64 ns = 0, ne = 0;
-                if ((r = ctx_readback2(c, &ns, cnt_s + ntiles, 8, &ne, cnt_e + ntiles, 8))) return r;
-                if (ns != ne) return ctx_fail(c, NAF_GPU_EFORMAT, "runs: %llu run starts and %llu run ends in one piece", (unsigned long long)ns, (unsigned long long)ne);
-                if (ns) {
-                    // (in the worst case one start and one end per two bases of the piece -- per base with NAF_GPU_RUNS_EACH at min_len 1)
-                    u64 *starts = arena_new<u64>(c, ns), *ends = arena_new<u64>(c, ns);
-                    if (!starts || !ends) return ctx_fail(c, NAF_GPU_ENOMEM, "runs: no room for %llu run starts and ends of a piece of %llu bases: set NAF_GPU_RUNS_PIECE to fewer bases",
-                                                          (unsigned long long)ns, (unsigned long long)(pc.p_hi - pc.p_lo));
-                    RUNS_LAUNCH(true, "unnaf_runs_write", starts, ends, ns);
-                    r = runs_finish(c, starts, ends, ns, min_len, P.rec_base, pc.r_lo, pc.r_hi, tl.seq, d_sum, writing, d_runs, run_cap, &total, n_runs);
-                    if (r) return r;
-                    cands += ns;
-                }
+                                              cnt_s, cnt_e, (const u64 *)cnt_s, (const u64 *)cnt_e, st, en, cap)
+            RUNS_LAUNCH(false, "unnaf_runs_count", (u64 *)nullptr, (u64 *)nullptr, (u64)0);
+            u64 ns = 0, ne = 0;
+            int r = tile_totals(c, ntiles, cnt_s, &ns, cnt_e, &ne); if (r) return r;
+            if (ns != ne) return ctx_fail(c, NAF_GPU_EFORMAT, "runs: %llu run starts and %llu run ends in one piece", (unsigned long long)ns, (unsigned long long)ne);
+            if (!ns) return 0;
+            // (in the worst case one start and one end per two bases of the piece -- per base with NAF_GPU_RUNS_EACH at min_len 1)
+            u64 *starts = arena_new<u64>(c, ns), *ends = arena_new<u64>(c, ns);
+            if (!starts || !ends) return ctx_fail(c, NAF_GPU_ENOMEM, "runs: no room for %llu run starts and ends of a piece of %llu bases: set NAF_GPU_RUNS_PIECE to fewer bases",
+                                                  (unsigned long long)ns, (unsigned long long)(pc.p_hi - pc.p_lo));
+            RUNS_LAUNCH(true, "unnaf_runs_write", starts, ends, ns);
 #undef RUNS_LAUNCH
-                sw.release();
-            }
-            return 0;
-        };
-        if (!write || pieces.size() > 1) { if ((rc = sweep(false))) return rc; }
+            cands_of[writing] += ns;
+            return runs_finish(c, starts, ends, ns, min_len, P.rec_base, pc.r_lo, pc.r_hi, tl.seq, d_sum, writing, d_runs, run_cap, before, here);
+        });
         *n_runs = total;
-        if (write && pieces.size() > 1 && total > run_cap) return ctx_fail(c, NAF_GPU_ECAP, "runs: %llu runs, capacity %zu", (unsigned long long)total, run_cap);
-        if (write) {
-            rc = sweep(true);
-            if (rc == NAF_GPU_ECAP) return ctx_fail(c, NAF_GPU_ECAP, "runs: %llu runs, capacity %zu", (unsigned long long)*n_runs, run_cap);
-            if (rc) return rc;
-        }
+        if (rc) return rc;
+        cands = cands_of[write];
         decoded = sw.decoded;
     }
     *n_runs = total;
