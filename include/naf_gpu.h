@@ -373,6 +373,52 @@ int  naf_gpu_unnaf_runs_count(naf_gpu_ctx *ctx, const void *d_naf, size_t naf_le
 int  naf_gpu_unnaf_runs(naf_gpu_ctx *ctx, const void *d_naf, size_t naf_len, uint16_t set, int flags, uint64_t min_len,
                         uint64_t first, uint64_t count, naf_gpu_run *d_runs, size_t run_cap, uint64_t *n_runs, uint64_t *n_bases);
 
+/* ---- unnaf: k-mer spectrum per record or per selection, counted in the packed stream -------------------------------
+ * What jellyfish count -m K, tetranucleotide frequencies per contig, codon and hexamer usage answer from the text: exact dense counts of
+ * all 4^K k-mers, K = 1 .. 12, made without composing that text.  All arithmetic is integer adds.
+ *   Index       A = 0, C = 1, G = 2, T/U = 3, two bits a base; the FIRST base is the most significant, so ascending index is the
+ *               lexicographic order of the k-mer strings.  A table has 4^K uint64_t counters.  naf_gpu_kmer_index takes 1 .. 12 letters of
+ *               ACGTU in either case (anything else: NAF_GPU_EARG) and gives K and the index -- with canonical != 0 the smaller of the
+ *               index and that of the reverse complement; naf_gpu_kmer_text writes the K letters (T, never U) and a 0 byte, and is
+ *               NAF_GPU_EARG for K outside 1 .. 12 or index >= 4^K.
+ *   Counted     Position g of record r is counted if and only if bases g .. g + K - 1 all lie in record r and each is stored as exactly
+ *               A, C, G or T/U (codes 8, 4, 2, 1 of "-TGKCYSBAWRDMHVN").  Any other stored code -- N, an ambiguity code, the gap --
+ *               invalidates every k-mer that covers it.  Case (the soft mask) plays no part and the mask section is never decoded.  A
+ *               record shorter than K gives nothing.  Every start position counts: AAA in ten A gives eight.
+ *   Never       Bases behind the last record of a malformed archive and the padding nibble of an odd stream are in no k-mer.
+ *   CANONICAL   NAF_GPU_KMER_CANONICAL: each counted k-mer adds to min(index, index of its reverse complement); every other bin stays 0.
+ *               A k-mer equal to its own reverse complement (even K only) counts once per occurrence, not twice.
+ *   PER_RECORD  NAF_GPU_KMER_PER_RECORD: one table per record of [first, first + count), laid end to end in record order: table i is at
+ *               d_counts + i * 4^K; an empty or too-short record gives a table of zeros.  d_rows (may be NULL when not wanted) gets one
+ *               naf_gpu_kmer_row per record, at any alignment: begin = 0, end = the length, positions = max(len - K + 1, 0), counted =
+ *               the sum of the record's table.  Without the flag there is one table for all selected records (an empty selection: one
+ *               table of zeros), *n_rows = 1, d_rows is ignored; k-mers never span two records either way.
+ *   h_total     HOST, may be NULL: record = the records covered, begin = 0, end = their bases, positions and counted summed.
+ *   Records     [first, first + count), count = NAF_GPU_WHOLE: to the last record.  Errors and archive kinds are those of
+ *               naf_gpu_unnaf_composition: first > n_sequences, a range past the last record, protein archives, text archives and
+ *               archives that store no sequence are NAF_GPU_EARG; an archive without records gives zero tables (*n_rows = 0).
+ *   Arguments   NAF_GPU_EARG, last_error saying which: K outside 1 .. 12; unknown flag bits; a d_counts that is not 8-byte aligned.
+ *   Capacity    count_cap is in counters, row_cap in rows.  If either wanted table does not fit the call returns NAF_GPU_ECAP, sets
+ *               *n_rows and *n_counters to the whole sizes and writes nothing.  Otherwise exactly 8 * n_rows * 4^K bytes and (with
+ *               PER_RECORD and a d_rows) 40 * n_rows bytes are written and nothing else; the call zeroes the tables itself.
+ *   Pieces      the bytes are the same on every run and for every piece size.  More bases than NAF_GPU_KMERS_PIECE (default 2^31) are
+ *               decoded and swept in pieces of whole records; only the zstd blocks behind the records are decoded when the frame allows
+ *               it.  NAF_GPU_KMERS_LDS_K (0 .. 7, default 7): the largest K counted in LDS bins; the result does not depend on it.
+ * naf_gpu_unnaf_kmers_rows needs the lengths section only and decodes no sequence.
+ * TRACE=1: "[kmers] k K rows R pieces P sequence bytes decoded X of Y lds tiles A global tiles B" per counting call that reaches the records. */
+typedef struct { uint64_t record, begin, end, positions, counted; } naf_gpu_kmer_row;   /* 40 bytes */
+enum { NAF_GPU_KMER_CANONICAL = 1, NAF_GPU_KMER_PER_RECORD = 2 };
+
+/* host only, no device */
+int  naf_gpu_kmer_index(const char *kmer, int canonical, unsigned *k, uint64_t *index);
+int  naf_gpu_kmer_text(unsigned k, uint64_t index, char out[13]);
+
+int  naf_gpu_unnaf_kmers_rows(naf_gpu_ctx *ctx, const void *d_naf, size_t naf_len, unsigned k, int flags, uint64_t first, uint64_t count,
+                              uint64_t *n_rows, uint64_t *n_counters);
+int  naf_gpu_unnaf_kmers(naf_gpu_ctx *ctx, const void *d_naf, size_t naf_len, unsigned k, int flags, uint64_t first, uint64_t count,
+                         uint64_t *d_counts, size_t count_cap, naf_gpu_kmer_row *d_rows, size_t row_cap,
+                         uint64_t *n_rows, uint64_t *n_counters, naf_gpu_kmer_row *h_total);
+
 /* ---- ennaf ------------------------------------------------------------------------------------------ */
 typedef struct {
     int      format;            /* NAF_FMT_* (AUTO = sniff, process.c:547-583) */

@@ -33,6 +33,7 @@ EXPORTS = [
     "naf_gpu_composition_rows_of", "naf_gpu_unnaf_composition_rows", "naf_gpu_unnaf_composition",
     "naf_gpu_quality_error_table", "naf_gpu_unnaf_quality_rows", "naf_gpu_unnaf_quality",
     "naf_gpu_parse_base_class", "naf_gpu_unnaf_runs_count", "naf_gpu_unnaf_runs",
+    "naf_gpu_kmer_index", "naf_gpu_kmer_text", "naf_gpu_unnaf_kmers_rows", "naf_gpu_unnaf_kmers",
 ]
 WHOLE = 2 ** 64 - 1                     # NAF_GPU_WHOLE: (record, 0, WHOLE) is the record as stored
 MAX_SHARDS = 64
@@ -131,6 +132,18 @@ class Run(C.Structure):
 RUN_DTYPE = [("record", "<u8"), ("begin", "<u8"), ("end", "<u8"), ("code", "<u4"), ("reserved", "<u4")]      # numpy's view of a table of runs
 RUN_BYTES = 32
 RUNS_EACH, RUNS_MASKED = 1, 2
+
+
+class KmerRow(C.Structure):
+    """naf_gpu_kmer_row: the k-mers of one record (begin 0, end its length) or, as a total, of `record` records with `end` bases:
+    `positions` start positions that have K bases in their record, `counted` of them whose K bases are all stored as A, C, G or T/U."""
+    _fields_ = [("record", C.c_uint64), ("begin", C.c_uint64), ("end", C.c_uint64), ("positions", C.c_uint64), ("counted", C.c_uint64)]
+
+
+KMER_DTYPE = [("record", "<u8"), ("begin", "<u8"), ("end", "<u8"), ("positions", "<u8"), ("counted", "<u8")]      # numpy's view of a table of rows
+KMER_ROW_BYTES = 40
+KMER_CANONICAL, KMER_PER_RECORD = 1, 2
+KMER_MAX_K = 12
 
 
 class NafGpuError(RuntimeError):
@@ -232,6 +245,10 @@ def load():
         L.naf_gpu_parse_base_class.argtypes = [C.c_char_p, C.POINTER(C.c_uint16)]
         L.naf_gpu_unnaf_runs_count.argtypes = [vp, vp, sz, C.c_uint16, i, C.c_uint64, C.c_uint64, C.c_uint64, u64p, u64p]
         L.naf_gpu_unnaf_runs.argtypes = [vp, vp, sz, C.c_uint16, i, C.c_uint64, C.c_uint64, C.c_uint64, vp, sz, u64p, u64p]
+        L.naf_gpu_kmer_index.argtypes = [C.c_char_p, i, C.POINTER(C.c_uint), u64p]
+        L.naf_gpu_kmer_text.argtypes = [C.c_uint, C.c_uint64, C.c_char_p]
+        L.naf_gpu_unnaf_kmers_rows.argtypes = [vp, vp, sz, C.c_uint, i, C.c_uint64, C.c_uint64, u64p, u64p]
+        L.naf_gpu_unnaf_kmers.argtypes = [vp, vp, sz, C.c_uint, i, C.c_uint64, C.c_uint64, vp, sz, vp, sz, u64p, u64p, C.POINTER(KmerRow)]
         _lib = L
     return _lib
 
@@ -284,6 +301,30 @@ def parse_base_class(text):
     if load().naf_gpu_parse_base_class(b, C.byref(s)):
         raise ValueError("not a base class: %r" % (text,))
     return s.value
+
+
+def kmer_index(text, canonical=False):
+    """Host-only: (k, index) of a k-mer of 1 to 12 letters of ACGTU in either case (naf_gpu_kmer_index): A = 0, C = 1, G = 2, T/U = 3,
+    the first base the most significant; canonical: the smaller of the index and that of the reverse complement.  ValueError for
+    anything else."""
+    b = text.encode("latin1") if isinstance(text, str) else bytes(text)
+    if b"\0" in b:
+        raise ValueError("not a k-mer: %r" % (text,))
+    k, idx = C.c_uint(), C.c_uint64()
+    if load().naf_gpu_kmer_index(b, 1 if canonical else 0, C.byref(k), C.byref(idx)):
+        raise ValueError("not a k-mer: %r" % (text,))
+    return k.value, idx.value
+
+
+def kmer_text(k, index):
+    """Host-only: the k letters (ACGT) of index `index` among the 4**k k-mers (naf_gpu_kmer_text).  ValueError for k outside 1..12 or an
+    index that is not below 4**k."""
+    if not (isinstance(k, int) and isinstance(index, int) and 0 <= k < 2 ** 32 and 0 <= index < 2 ** 64):
+        raise ValueError("not a k-mer: k %r index %r" % (k, index))
+    out = C.create_string_buffer(13)
+    if load().naf_gpu_kmer_text(k, index, out):
+        raise ValueError("not a k-mer: k %r index %r" % (k, index))
+    return out.value.decode()
 
 
 def runs_to_segments(runs, flank=0, lengths=None):
@@ -727,6 +768,49 @@ class Context:
             rc = call(buf, cap)
         self._check(rc)
         return np.frombuffer(buf[:RUN_BYTES * n.value].cpu().numpy().tobytes(), dtype=RUN_DTYPE), nb.value
+
+    def unnaf_kmers_rows(self, d_naf, k, canonical=False, per_record=False, first=0, count=None):
+        """(n_rows, n_counters) of the tables unnaf_kmers gives for records [first, first + count) (naf_gpu_unnaf_kmers_rows: the lengths
+        only, no sequence is decoded)."""
+        flags = (KMER_CANONICAL if canonical else 0) | (KMER_PER_RECORD if per_record else 0)
+        n, nc = C.c_uint64(), C.c_uint64()
+        self._check(self.L.naf_gpu_unnaf_kmers_rows(self.h, _ptr(d_naf), d_naf.numel(), int(k), flags, int(first), WHOLE if count is None else int(count),
+                                                    C.byref(n), C.byref(nc)))
+        return n.value, nc.value
+
+    def unnaf_kmers(self, d_naf, k, canonical=False, per_record=False, first=0, count=None, out=None, out_rows=None):
+        """(counts, rows, total): the exact counts of all 4**k k-mers (k = 1..12) of records [first, first + count) -- one table for the
+        selection or, with per_record, one per record -- as a device torch.int64 tensor of shape (n_rows, 4**k); the rows (KMER_DTYPE:
+        record, begin, end, positions, counted) as a structured numpy array, None without per_record; and their sum as a KmerRow (its
+        record: the records covered, its end: their bases).  canonical: a k-mer and its reverse complement share the smaller index.
+        out: a device torch.int64 tensor to take the tables; `counts` is then a view of it, and too small a tensor raises
+        NafGpuError(E_CAP).  out_rows: a uint8 device tensor to take the rows (40 bytes a row); `rows` is then the torch view of the bytes
+        written.  Without them the sizes are asked for first (naf_gpu_unnaf_kmers_rows)."""
+        import numpy as np
+        import torch
+        flags = (KMER_CANONICAL if canonical else 0) | (KMER_PER_RECORD if per_record else 0)
+        cnt = WHOLE if count is None else int(count)
+        n, nc, tot = C.c_uint64(), C.c_uint64(), KmerRow()
+        if out is None or (per_record and out_rows is None):
+            self._check(self.L.naf_gpu_unnaf_kmers_rows(self.h, _ptr(d_naf), d_naf.numel(), int(k), flags, int(first), cnt, C.byref(n), C.byref(nc)))
+        if out is None:
+            buf = torch.empty(max(nc.value, 1), dtype=torch.int64, device=self.device)
+        else:
+            if out.dtype != torch.int64 or not out.is_contiguous():
+                raise ValueError("out: a contiguous torch.int64 tensor")
+            buf = out.view(-1)
+        rows_buf = None
+        if per_record:
+            rows_buf = out_rows if out_rows is not None else torch.empty(max(KMER_ROW_BYTES * n.value, 1), dtype=torch.uint8, device=self.device)
+        self._check(self.L.naf_gpu_unnaf_kmers(self.h, _ptr(d_naf), d_naf.numel(), int(k), flags, int(first), cnt, _ptr(buf), buf.numel(),
+                                               _ptr(rows_buf) if rows_buf is not None else None, rows_buf.numel() // KMER_ROW_BYTES if rows_buf is not None else 0,
+                                               C.byref(n), C.byref(nc), C.byref(tot)))
+        counts = buf[:nc.value].view(n.value, 4 ** int(k))
+        rows = None
+        if per_record:
+            view = rows_buf[:KMER_ROW_BYTES * n.value]
+            rows = view if out_rows is not None else np.frombuffer(view.cpu().numpy().tobytes(), dtype=KMER_DTYPE)
+        return counts, rows, tot
 
     def histogram(self, d_buf):
         """Byte counts of a device buffer (unnaf --charcount)."""

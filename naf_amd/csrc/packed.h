@@ -1,4 +1,4 @@
-// packed.h -- what the kernels that scan the packed 4-bit stream share on the device (locate.h, composition.h, runs.h; the row copy
+// packed.h -- what the kernels that scan the packed 4-bit stream share on the device (locate.h, composition.h, runs.h, kmers.h; the row copy
 // serves quality.h too).  Part of emit.hip (included by it at its top); the host parts these callers share are payload.h's.
 // A tile starts on an even base, so a lane's first base g is the low nibble of byte g >> 1 (the first base of a byte is its low nibble),
 // and base j of a lane is nibble j & 7 of dword j >> 3.  packed_tail is the ONLY loop that reads next to the stream's end.
@@ -39,6 +39,15 @@ __device__ __forceinline__ u32 packed_behind(const u8 *seq, u64 b_end, u64 g, bo
     if (active && lane == 63 && (g >> 1) + 32 < b_end) nc = seq[(g >> 1) + 32];
     const u32 dn = (u32)__shfl_down((int)x[0], 1);
     return (lane != 63 ? dn : nc) & 15u;
+}
+// The codes of the twelve bases behind a lane's 64 as 48 bits, the nearest in the low nibble (0 where there is none to read).  Every lane of
+// the wave calls it (two shuffles); lane 63 reads the six bytes from (g >> 1) + 32 on that lie in front of b_end.
+__device__ __forceinline__ u64 packed_behind12(const u8 *seq, u64 b_end, u64 g, bool active, u32 lane, const u32 (&x)[8])
+{
+    u16 w[3] = { 0, 0, 0 };
+    if (active && lane == 63) packed_tail<3>(seq, b_end, (g >> 1) + 32, w);
+    const u32 d0 = (u32)__shfl_down((int)x[0], 1), d1 = (u32)__shfl_down((int)x[1], 1) & 0xFFFFu;
+    return lane != 63 ? (u64)d0 | ((u64)d1 << 32) : (u64)w[0] | ((u64)w[1] << 16) | ((u64)w[2] << 32);
 }
 // The code of the base in front of a lane's first (0 where there is none to read); as above, lane 0 reads byte (g >> 1) - 1 when
 // g > p_lo: base g - 1 >= p_lo is then one of the range, in a decoded byte.

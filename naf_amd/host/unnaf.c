@@ -27,6 +27,8 @@ static bool quality = false, cycles_given = false; static unsigned long long qua
 /* --runs CLASS / --masked-runs [--min-run N] [--each]: runs of a base class or soft-masked intervals, as BED4 (this implementation only) */
 static const char *runs_class = NULL; static uint16_t runs_set = 0; static bool masked_runs = false, runs_each = false, min_run_given = false;
 static unsigned long long min_run = 1;
+/* --kmers K [--canonical] [--per-record]: exact counts of all 4^K k-mers of the selection, or of every record (this implementation only) */
+static unsigned kmers_k = 0; static bool kmers_canonical = false, kmers_per_record = false;
 
 static void done(int status, void *arg)
 {
@@ -126,6 +128,18 @@ static void set_min_run(const char *v)
     min_run = a; min_run_given = true;
 }
 
+static void set_kmers(const char *v)
+{
+    if (kmers_k) die("only one --kmers length can be counted at a time\n");
+    unsigned a = 0; bool digit = false;
+    for (const char *p = v; *p; p++) {
+        if (*p < '0' || *p > '9' || a > 12) die("can't parse the value of --kmers parameter (a k-mer length of 1 to 12)\n");
+        a = a * 10 + (unsigned)(*p - '0'); digit = true;
+    }
+    if (!digit || a < 1 || a > 12) die("can't parse the value of --kmers parameter (a k-mer length of 1 to 12)\n");
+    kmers_k = a;
+}
+
 static void show_help(void)
 {
     msg("Usage: unnaf [OUTPUT-TYPE] [file.naf]\n"
@@ -157,7 +171,11 @@ static void show_help(void)
         "  --runs CLASS    - Every maximal run of bases of CLASS: letters of ACGTU RYSWKM BDHV N and -, taken literally (N is the stored N only); ^CLASS = all other codes\n"
         "  --masked-runs   - Every soft-masked interval (NAME is \"mask\")\n"
         "  --min-run N     - With --runs or --masked-runs: only runs of at least N bases (default 1)\n"
-        "  --each          - With --runs: every letter of CLASS on its own, e.g. homopolymers for ACGT (NAME is the run's letter)\n");
+        "  --each          - With --runs: every letter of CLASS on its own, e.g. homopolymers for ACGT (NAME is the run's letter)\n"
+        "Options for counting k-mers (output: lines \"KMER COUNT\" of the k-mers that occur, tab-separated; with at most one --records A-B or --region ID):\n"
+        "  --kmers K       - Exact counts of all k-mers of K = 1 to 12 bases made of A, C, G, T/U only, never across a sequence's end; case is ignored\n"
+        "  --canonical     - With --kmers: a k-mer and its reverse complement are counted as the one that sorts first\n"
+        "  --per-record    - With --kmers, K up to 6: a table \"#seq length counted\" and one column per k-mer, one line per sequence\n");
 }
 
 static void parse_command_line(int argc, char **argv)
@@ -170,7 +188,7 @@ static void parse_command_line(int argc, char **argv)
         {"--fasta", FASTA}, {"--fastq", FASTQ}, {"--dna", DNA}, {"--masked-dna", MASKED_DNA}, {"--unmasked-dna", UNMASKED_DNA},
         {"--masked-fasta", MASKED_FASTA}, {"--unmasked-fasta", UNMASKED_FASTA} };
     /* the other options (unnaf/src/unnaf.c:282-353), as a table: one that takes a value is only recognised with an argument behind it */
-    enum { OP_LINE_LENGTH, OP_OUT, OP_NO_MASK, OP_IGNORED, OP_HELP, OP_VERBOSE, OP_VERSION, OP_STDOUT, OP_REGION, OP_RECORDS, OP_RC_REGION, OP_REVCOMP, OP_LOCATE, OP_STRAND, OP_COMPOSITION, OP_WINDOW, OP_QUALITY, OP_CYCLES, OP_RUNS, OP_MASKED_RUNS, OP_MIN_RUN, OP_EACH };
+    enum { OP_LINE_LENGTH, OP_OUT, OP_NO_MASK, OP_IGNORED, OP_HELP, OP_VERBOSE, OP_VERSION, OP_STDOUT, OP_REGION, OP_RECORDS, OP_RC_REGION, OP_REVCOMP, OP_LOCATE, OP_STRAND, OP_COMPOSITION, OP_WINDOW, OP_QUALITY, OP_CYCLES, OP_RUNS, OP_MASKED_RUNS, OP_MIN_RUN, OP_EACH, OP_KMERS, OP_CANONICAL, OP_PER_RECORD };
     static const struct { const char *name; int op; bool value; } option_table[] = {
         { "--line-length", OP_LINE_LENGTH, true }, { "-o", OP_OUT, true }, { "--no-mask", OP_NO_MASK, false }, { "--binary-stdout", OP_IGNORED, false },
         { "--binary-stderr", OP_IGNORED, false }, { "--binary", OP_IGNORED, false }, { "--help", OP_HELP, false }, { "-h", OP_HELP, false },
@@ -178,7 +196,8 @@ static void parse_command_line(int argc, char **argv)
         { "--region", OP_REGION, true }, { "--records", OP_RECORDS, true }, { "--rc-region", OP_RC_REGION, true }, { "--revcomp", OP_REVCOMP, false },
         { "--locate", OP_LOCATE, true }, { "--strand", OP_STRAND, true }, { "--composition", OP_COMPOSITION, false }, { "--window", OP_WINDOW, true },
         { "--quality", OP_QUALITY, false }, { "--cycles", OP_CYCLES, true },
-        { "--runs", OP_RUNS, true }, { "--masked-runs", OP_MASKED_RUNS, false }, { "--min-run", OP_MIN_RUN, true }, { "--each", OP_EACH, false } };
+        { "--runs", OP_RUNS, true }, { "--masked-runs", OP_MASKED_RUNS, false }, { "--min-run", OP_MIN_RUN, true }, { "--each", OP_EACH, false },
+        { "--kmers", OP_KMERS, true }, { "--canonical", OP_CANONICAL, false }, { "--per-record", OP_PER_RECORD, false } };
     for (int i = 1; i < argc; i++) {
         char *arg = argv[i];
         if (arg[0] != '-') {
@@ -217,6 +236,9 @@ static void parse_command_line(int argc, char **argv)
         case OP_MASKED_RUNS: masked_runs = true; break;
         case OP_MIN_RUN: set_min_run(v); break;
         case OP_EACH: runs_each = true; break;
+        case OP_KMERS: set_kmers(v); break;
+        case OP_CANONICAL: kmers_canonical = true; break;
+        case OP_PER_RECORD: kmers_per_record = true; break;
         }
     }
     if (print_version) {
@@ -276,6 +298,23 @@ static void parse_command_line(int argc, char **argv)
         if (n_selections && selections[0].region) {
             size_t l; uint64_t b, e; naf_gpu_parse_region(selections[0].region, &l, &b, &e);
             if (!(b == 0 && e == NAF_GPU_WHOLE)) die("%s can be restricted to a whole sequence only: --region ID, without a range\n", me);
+        }
+    }
+    if (kmers_canonical && !kmers_k) die("--canonical can be used only with --kmers\n");
+    if (kmers_per_record && !kmers_k) die("--per-record can be used only with --kmers\n");
+    if (kmers_k) {
+        if (n_locate) die("--kmers and --locate can't be used together\n");
+        if (composition) die("--kmers and --composition can't be used together\n");
+        if (quality) die("--kmers and --quality can't be used together\n");
+        if (runs_class || masked_runs) die("--kmers and %s can't be used together\n", runs_class ? "--runs" : "--masked-runs");
+        if (out_type != UNDECIDED) die("--kmers writes a table: no output type can be given with it\n");
+        if (kmers_per_record && kmers_k > 6) die("--per-record writes one column per k-mer: --kmers can be 6 at the most with it\n");
+        if (revcomp) die("--kmers counts the sequences as stored: --revcomp can't be used with it\n");
+        if (n_selections > 1) die("--kmers can be restricted by one --records or one --region only\n");
+        if (n_selections && selections[0].rc) die("--kmers counts the sequences as stored: --rc-region can't be used with it\n");
+        if (n_selections && selections[0].region) {
+            size_t l; uint64_t b, e; naf_gpu_parse_region(selections[0].region, &l, &b, &e);
+            if (!(b == 0 && e == NAF_GPU_WHOLE)) die("--kmers can be restricted to a whole sequence only: --region ID, without a range\n");
         }
     }
     if ((n_selections || revcomp) && !(out_type == UNDECIDED || out_type == FASTA || out_type == FASTQ || out_type == SEQ || out_type == SEQUENCES))
@@ -656,6 +695,86 @@ static void run_runs(bool has_ids, bool has_names)
     }
 }
 
+/* --kmers: the tables are made on the device (naf_gpu_unnaf_kmers: one sweep over the packed stream); the lines are formatted here, on the
+ * host, from the downloaded counters, a chunk at a time -- the one table of a selection 2^20 counters at a time, the tables of --per-record
+ * in calls of as many records as give 2^22 counters. */
+static void run_kmers(bool has_ids, bool has_names)
+{
+    upload();
+    const unsigned long long N = H.n_sequences;
+    const unsigned K = kmers_k;
+    const uint64_t nk = 1ull << (2 * K);
+    const bool rna = H.seq_type == NAF_SEQ_RNA;
+    uint64_t first, count;
+    one_record_range(has_ids, &first, &count);
+    const int flags = (kmers_canonical ? NAF_GPU_KMER_CANONICAL : 0) | (kmers_per_record ? NAF_GPU_KMER_PER_RECORD : 0);
+    uint64_t n_rows = 0, n_counters = 0;
+    GPU_TRY(naf_gpu_unnaf_kmers_rows(gpu, d_naf, naf_len, K, flags, first, count, &n_rows, &n_counters));
+    phase("kmers: rows");
+    char km[13];
+    if (!kmers_per_record) {
+        if (!n_rows) return;
+        void *d_counts; GPU_TRY(naf_gpu_malloc(gpu, (size_t)n_counters * 8, &d_counts));
+        GPU_TRY(naf_gpu_unnaf_kmers(gpu, d_naf, naf_len, K, flags, first, count, (uint64_t *)d_counts, (size_t)n_counters, NULL, 0, &n_rows, &n_counters, NULL));
+        if (n_rows != 1 || n_counters != nk) die("can't decompress sequence\n");
+        phase("kmers: count");
+        const size_t chunk = 1 << 20;
+        uint64_t *cnt = (uint64_t *)malloc((nk < chunk ? (size_t)nk : chunk) * sizeof *cnt); if (!cnt) die("can't allocate memory\n");
+        for (uint64_t a = 0; a < nk; a += chunk) {
+            const size_t m = nk - a < chunk ? (size_t)(nk - a) : chunk;
+            GPU_TRY(naf_gpu_download(gpu, cnt, (const uint64_t *)d_counts + a, m * sizeof *cnt));
+            for (size_t k = 0; k < m; k++) if (cnt[k]) {
+                naf_gpu_kmer_text(K, a + k, km);
+                if (rna) for (char *q = km; *q; q++) if (*q == 'T') *q = 'U';
+                fprintf(OUT, "%s\t%llu\n", km, (unsigned long long)cnt[k]);
+            }
+        }
+        free(cnt); naf_gpu_free(gpu, d_counts);
+        phase("kmers: download + lines");
+        return;
+    }
+    /* the columns: every k-mer, or the canonical ones */
+    uint32_t *col = (uint32_t *)malloc((size_t)nk * sizeof *col); size_t n_col = 0; if (!col) die("can't allocate memory\n");
+    fprintf(OUT, "#seq\tlength\tcounted");
+    for (uint64_t x = 0; x < nk; x++) {
+        unsigned k2; uint64_t can = x;
+        naf_gpu_kmer_text(K, x, km);
+        if (kmers_canonical) naf_gpu_kmer_index(km, 1, &k2, &can);
+        if (can != x) continue;
+        col[n_col++] = (uint32_t)x;
+        if (rna) for (char *q = km; *q; q++) if (*q == 'T') *q = 'U';
+        fprintf(OUT, "\t%s", km);
+    }
+    fputc('\n', OUT);
+    if (n_rows) {
+        unsigned char *text; const char **name = record_names(has_ids, has_names, &text);
+        const uint64_t total = n_rows, per_call = ((1ull << 22) >> (2 * K)) < total ? ((1ull << 22) >> (2 * K)) : total;
+        void *d_counts, *d_rows;
+        GPU_TRY(naf_gpu_malloc(gpu, (size_t)(per_call * nk) * 8, &d_counts)); GPU_TRY(naf_gpu_malloc(gpu, (size_t)per_call * sizeof(naf_gpu_kmer_row), &d_rows));
+        uint64_t *cnt = (uint64_t *)malloc((size_t)(per_call * nk) * sizeof *cnt); naf_gpu_kmer_row *rows = (naf_gpu_kmer_row *)malloc((size_t)per_call * sizeof *rows);
+        if (!cnt || !rows) die("can't allocate memory\n");
+        for (uint64_t a = 0; a < total; a += per_call) {
+            const uint64_t m = total - a < per_call ? total - a : per_call;
+            uint64_t got_rows = 0, got_counters = 0;
+            GPU_TRY(naf_gpu_unnaf_kmers(gpu, d_naf, naf_len, K, flags, first + a, m, (uint64_t *)d_counts, (size_t)(per_call * nk), (naf_gpu_kmer_row *)d_rows, (size_t)per_call,
+                                        &got_rows, &got_counters, NULL));
+            if (got_rows != m || got_counters != m * nk) die("can't decompress sequence\n");
+            GPU_TRY(naf_gpu_download(gpu, cnt, d_counts, (size_t)(m * nk) * sizeof *cnt));
+            GPU_TRY(naf_gpu_download(gpu, rows, d_rows, (size_t)m * sizeof *rows));
+            for (uint64_t k = 0; k < m; k++) {
+                const naf_gpu_kmer_row *x = &rows[k];
+                if (x->record >= N) die("can't decompress sequence\n");
+                fprintf(OUT, "%s\t%llu\t%llu", name[x->record], (unsigned long long)x->end, (unsigned long long)x->counted);
+                for (size_t q = 0; q < n_col; q++) fprintf(OUT, "\t%llu", (unsigned long long)cnt[k * nk + col[q]]);
+                fputc('\n', OUT);
+            }
+        }
+        free(cnt); free(rows); free(name); free(text); naf_gpu_free(gpu, d_counts); naf_gpu_free(gpu, d_rows);
+        phase("kmers: count + download + lines");
+    }
+    free(col);
+}
+
 int main(int argc, char **argv)
 {
     prog_name = "unnaf";
@@ -697,7 +816,7 @@ int main(int argc, char **argv)
     bool large = out_type == IDS || out_type == NAMES || out_type == LENGTHS || out_type == MASK || out_type == FOUR_BIT || out_type == DNA ||
                  out_type == MASKED_DNA || out_type == UNMASKED_DNA || out_type == SEQ || out_type == FASTA || out_type == MASKED_FASTA ||
                  out_type == UNMASKED_FASTA || out_type == FASTQ;
-    if (large && !n_locate && !composition && !quality && !runs_class && !masked_runs && !force_stdout && isatty(fileno(OUT)))
+    if (large && !n_locate && !composition && !quality && !runs_class && !masked_runs && !kmers_k && !force_stdout && isatty(fileno(OUT)))
         die("output file not specified - please either specify output file with '-o' or '>', or use '-c' option to force writing to console\n");
 
     unsigned long long N = H.n_sequences;
@@ -713,6 +832,10 @@ int main(int argc, char **argv)
     else if (runs_class || masked_runs) {
         if (H.seq_type >= NAF_SEQ_PROTEIN) die("runs of bases cannot be listed in %s sequences\n", tn[H.seq_type]);
         run_runs(has_ids, has_names);
+    }
+    else if (kmers_k) {
+        if (H.seq_type >= NAF_SEQ_PROTEIN) die("k-mers cannot be counted in %s sequences\n", tn[H.seq_type]);
+        run_kmers(has_ids, has_names);
     }
     else if (n_selections) {
         if (out_type == FASTQ && !has_quality) die("FASTQ output requested, but input has no qualities\n");
