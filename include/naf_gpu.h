@@ -243,6 +243,41 @@ int  naf_gpu_unnaf_locate_count(naf_gpu_ctx *ctx, const void *d_naf, size_t naf_
 int  naf_gpu_unnaf_locate(naf_gpu_ctx *ctx, const void *d_naf, size_t naf_len, const char *h_patterns, size_t patterns_bytes, size_t n_patterns,
                           int strands, uint64_t first, uint64_t count, naf_gpu_hit *d_hits, size_t hit_cap, uint64_t *n_hits);
 
+/* ---- unnaf: IUPAC motifs with mismatches and must-match letters ------------------------------------------------
+ * What seqkit locate -m and an off-target screen answer from the text: every place within a budget of mismatches of a pattern.
+ *   Patterns  those of naf_gpu_compile_motif, and a run of letters in square brackets must match: GAGTCCGAGCAGAAGAAGAA[NGG], [GAATTC],
+ *             [TTTV]NNNNNNNNNNNNNNNNNNNNNNN.  Brackets do not nest and are not empty; there may be several runs; 1 to 32 letters, the
+ *             brackets not counted.  Everything else is rejected as there; last_error names the pattern number and the position.
+ *   Letters   the exact search's rule: stored code c matches letter set p when c != 0 && (c & ~p) == 0; a position that does not match
+ *             is a mismatch.  A stored N under a pattern A is one mismatch; a stored gap under anything is one, pattern N included; a
+ *             stored R under R, D, V or N is none.  Case and the mask play no part.
+ *   Hit       a start position of pattern k where all of the pattern's letters lie inside one record, no bracketed letter mismatches and
+ *             the mismatches among the others number at most max_mismatches[k].  Every start position counts, overlapping ones too.
+ *             Bases behind the last record of a malformed archive and the padding nibble of an odd stream are in no hit.
+ *   Budget    per pattern, 0 to NAF_GPU_LOCATE_MAX_MISMATCHES.  A budget above 0 must be smaller than the pattern's number of unbracketed
+ *             letters (or every window would be a hit): NAF_GPU_EARG otherwise.
+ *   Strands   as in the exact search: a reverse hit at [begin, begin + m) says that the reverse complement of those stored bases is
+ *             within the budget of the pattern; coordinates are the forward ones; a palindrome on both strands gives two hits.
+ *   where     bit j set when the pattern's letter j mismatched, j the index in the pattern as written, brackets not counted; on the
+ *             reverse strand letter j faces stored base begin + m - 1 - j.  popcount(where) == mismatches.
+ *   Order     ascending (record, begin), then pattern number, then strand; the same on every run and for every piece size.
+ * With every budget 0 and no brackets the table is naf_gpu_unnaf_locate's, row for row, with mismatches = where = 0. */
+#define NAF_GPU_LOCATE_MAX_MISMATCHES 8
+typedef struct { uint64_t record, begin; uint32_t pattern, strand; uint32_t mismatches, where; } naf_gpu_near_hit;   /* 32 bytes */
+
+/* host only, no device: naf_gpu_compile_motif for a pattern that may hold brackets; *fixed has bit j set when letter j (brackets not
+ * counted) stands in brackets, *len is the number of letters.  NAF_GPU_EARG for what is no pattern; nothing is written then. */
+int  naf_gpu_compile_motif_near(const char *text, uint8_t fwd[32], uint8_t rev[32], uint32_t *fixed, size_t *len);
+
+/* As naf_gpu_unnaf_locate_count / naf_gpu_unnaf_locate (the same patterns blob, limits, archives, first / count, pieces through
+ * NAF_GPU_LOCATE_PIECE), with h_max_mismatches: n_patterns budgets in HOST memory.  per_pattern (HOST, n_patterns x 2 x 9 entries, may
+ * be NULL) receives at [(2 k + s) * 9 + d] the hits of pattern k on strand s with exactly d mismatches.  d_hits is DEVICE memory of any
+ * alignment, 32 bytes a hit: with hit_cap too small the call returns NAF_GPU_ECAP, sets *n_hits to the whole count and writes nothing. */
+int  naf_gpu_unnaf_locate_near_count(naf_gpu_ctx *ctx, const void *d_naf, size_t naf_len, const char *h_patterns, size_t patterns_bytes, size_t n_patterns,
+                                     const uint32_t *h_max_mismatches, int strands, uint64_t first, uint64_t count, uint64_t *n_hits, uint64_t *per_pattern);
+int  naf_gpu_unnaf_locate_near(naf_gpu_ctx *ctx, const void *d_naf, size_t naf_len, const char *h_patterns, size_t patterns_bytes, size_t n_patterns,
+                               const uint32_t *h_max_mismatches, int strands, uint64_t first, uint64_t count, naf_gpu_near_hit *d_hits, size_t hit_cap, uint64_t *n_hits);
+
 /* ---- unnaf: base composition per record and per window, counted in the packed stream --------------------------
  * What faCount, seqkit fx2tab -g -B and bedtools nuc answer from the text, counted from the 4-bit codes without expanding them.
  *   Rows      window == 0: exactly one row per record, [0, len); an empty record gives a row of zeros.  window == W > 0: a record of len

@@ -30,6 +30,7 @@ EXPORTS = [
     "naf_gpu_unnaf_find", "naf_gpu_unnaf_record_table", "naf_gpu_unnaf_select_size", "naf_gpu_unnaf_select", "naf_gpu_parse_region",
     "naf_gpu_unnaf_select_stranded_size", "naf_gpu_unnaf_select_stranded",
     "naf_gpu_compile_motif", "naf_gpu_unnaf_locate_count", "naf_gpu_unnaf_locate",
+    "naf_gpu_compile_motif_near", "naf_gpu_unnaf_locate_near_count", "naf_gpu_unnaf_locate_near",
     "naf_gpu_composition_rows_of", "naf_gpu_unnaf_composition_rows", "naf_gpu_unnaf_composition",
     "naf_gpu_quality_error_table", "naf_gpu_unnaf_quality_rows", "naf_gpu_unnaf_quality",
     "naf_gpu_parse_base_class", "naf_gpu_unnaf_runs_count", "naf_gpu_unnaf_runs",
@@ -98,6 +99,17 @@ class Hit(C.Structure):
 
 HIT_DTYPE = [("record", "<u8"), ("begin", "<u8"), ("pattern", "<u4"), ("strand", "<u4")]      # numpy's view of a table of hits
 STRAND_FORWARD, STRAND_REVERSE, STRAND_BOTH = 1, 2, 3
+
+
+class NearHit(C.Structure):
+    """naf_gpu_near_hit: pattern number `pattern` lies at bases [begin, begin + its length) of `record` with `mismatches` letters that
+    do not match; `where` has bit j set when letter j of the pattern as written (brackets not counted) is one of them."""
+    _fields_ = [("record", C.c_uint64), ("begin", C.c_uint64), ("pattern", C.c_uint32), ("strand", C.c_uint32), ("mismatches", C.c_uint32), ("where", C.c_uint32)]
+
+
+NEAR_HIT_DTYPE = [("record", "<u8"), ("begin", "<u8"), ("pattern", "<u4"), ("strand", "<u4"), ("mismatches", "<u4"), ("where", "<u4")]      # numpy's view of a table of near hits
+NEAR_HIT_BYTES = 32
+LOCATE_MAX_MISMATCHES = 8
 
 
 class CompRow(C.Structure):
@@ -235,6 +247,10 @@ def load():
         L.naf_gpu_compile_motif.argtypes = [C.c_char_p, u8p, u8p, C.POINTER(sz)]
         L.naf_gpu_unnaf_locate_count.argtypes = [vp, vp, sz, C.c_char_p, sz, sz, i, C.c_uint64, C.c_uint64, u64p, u64p]
         L.naf_gpu_unnaf_locate.argtypes = [vp, vp, sz, C.c_char_p, sz, sz, i, C.c_uint64, C.c_uint64, vp, sz, u64p]
+        u32p = C.POINTER(C.c_uint32)
+        L.naf_gpu_compile_motif_near.argtypes = [C.c_char_p, u8p, u8p, u32p, C.POINTER(sz)]
+        L.naf_gpu_unnaf_locate_near_count.argtypes = [vp, vp, sz, C.c_char_p, sz, sz, u32p, i, C.c_uint64, C.c_uint64, u64p, u64p]
+        L.naf_gpu_unnaf_locate_near.argtypes = [vp, vp, sz, C.c_char_p, sz, sz, u32p, i, C.c_uint64, C.c_uint64, vp, sz, u64p]
         L.naf_gpu_composition_rows_of.argtypes = [C.c_uint64, C.c_uint64]
         L.naf_gpu_composition_rows_of.restype = C.c_uint64
         L.naf_gpu_unnaf_composition_rows.argtypes = [vp, vp, sz, C.c_uint64, C.c_uint64, C.c_uint64, u64p]
@@ -274,6 +290,24 @@ def compile_motif(text):
     if load().naf_gpu_compile_motif(b, fwd, rev, C.byref(n)):
         raise ValueError("not a pattern: %r" % (text,))
     return bytes(fwd[:n.value]), bytes(rev[:n.value])
+
+
+def compile_motif_near(text):
+    """Host-only: (fwd, rev, fixed) of an IUPAC pattern that may hold bracketed runs of must-match letters (naf_gpu_compile_motif_near):
+    the 4-bit sets as compile_motif gives them, and the bit mask of the bracketed letters by their index in the pattern, brackets not
+    counted.  ValueError for what is no pattern."""
+    b = text.encode("latin1") if isinstance(text, str) else bytes(text)
+    if b"\0" in b:
+        raise ValueError("not a pattern: %r" % (text,))
+    fwd, rev, fixed, n = (C.c_uint8 * 32)(), (C.c_uint8 * 32)(), C.c_uint32(), C.c_size_t()
+    if load().naf_gpu_compile_motif_near(b, fwd, rev, C.byref(fixed), C.byref(n)):
+        raise ValueError("not a pattern: %r" % (text,))
+    return bytes(fwd[:n.value]), bytes(rev[:n.value]), fixed.value
+
+
+def motif_letters(pattern):
+    """A pattern's letters without the brackets of must-match runs (str or bytes, as given)."""
+    return pattern.replace("[", "").replace("]", "") if isinstance(pattern, str) else bytes(pattern).replace(b"[", b"").replace(b"]", b"")
 
 
 def composition_rows_of(n, window):
@@ -341,12 +375,12 @@ def runs_to_segments(runs, flank=0, lengths=None):
 
 
 def hits_to_segments(hits, patterns, flank=0, lengths=None):
-    """The (record, begin, end, reverse) tuples unnaf_select takes, one per hit (rows of the table unnaf_locate returns), for the patterns
-    the search was made with.  flank: that many bases more on either side, clamped to the record -- to its start always, to its end when
+    """The (record, begin, end, reverse) tuples unnaf_select takes, one per hit (rows of the table unnaf_locate or unnaf_locate_near
+    returns), for the patterns the search was made with; brackets do not count for a pattern's length.  flank: that many bases more on either side, clamped to the record -- to its start always, to its end when
     `lengths` (the n_bases of unnaf_record_table, indexed by record number) is given; unnaf_select clamps an end beyond the record itself."""
     out = []
     for h in hits:
-        r, b, e = int(h["record"]), int(h["begin"]), int(h["begin"]) + len(patterns[int(h["pattern"])])
+        r, b, e = int(h["record"]), int(h["begin"]), int(h["begin"]) + len(motif_letters(patterns[int(h["pattern"])]))
         b, e = max(0, b - flank), e + flank
         if lengths is not None:
             e = min(e, int(lengths[r]))
@@ -653,6 +687,48 @@ class Context:
         self._check(self.L.naf_gpu_unnaf_locate(self.h, _ptr(d_naf), d_naf.numel(), blob, len(blob), n, int(strands), int(first), cnt,
                                                 _ptr(buf), total.value, C.byref(total)))
         return np.frombuffer(buf[:24 * total.value].cpu().numpy().tobytes(), dtype=HIT_DTYPE), total.value
+
+    @staticmethod
+    def _budgets(mismatches, n):
+        try:
+            vals = [mismatches.__index__()] * n                                   # one for all patterns (any integer type)
+        except (AttributeError, TypeError):
+            vals = list(mismatches)                                               # or one each
+        if len(vals) != n:
+            raise ValueError("%d budgets of mismatches for %d patterns" % (len(vals), n))
+        if any(not 0 <= int(v) < 2 ** 32 for v in vals):
+            raise ValueError("a budget of mismatches is a uint32_t (the library accepts 0 to %d and names the pattern of any other)" % LOCATE_MAX_MISMATCHES)
+        return (C.c_uint32 * max(n, 1))(*[int(v) for v in vals])
+
+    def unnaf_locate_near_count(self, d_naf, patterns, mismatches, strands=3, first=0, count=None):
+        """(hits in all, [[forward, reverse] per pattern], each a list of 9 counts by number of mismatches) of IUPAC patterns within
+        their budget of mismatches -- one int for all patterns or one per pattern; letters in square brackets must match
+        (naf_gpu_unnaf_locate_near_count).  The rest as unnaf_locate_count."""
+        blob, n = self._patterns(patterns)
+        total, per = C.c_uint64(), (C.c_uint64 * max(18 * n, 1))()
+        self._check(self.L.naf_gpu_unnaf_locate_near_count(self.h, _ptr(d_naf), d_naf.numel(), blob, len(blob), n, self._budgets(mismatches, n), int(strands), int(first),
+                                                           WHOLE if count is None else int(count), C.byref(total), per))
+        return total.value, [[[int(per[(2 * k + s) * 9 + d]) for d in range(9)] for s in (0, 1)] for k in range(n)]
+
+    def unnaf_locate_near(self, d_naf, patterns, mismatches, strands=3, first=0, count=None, out=None):
+        """(hits, total): the near hits as a structured numpy array (NEAR_HIT_DTYPE: record, begin, pattern, strand, mismatches, where) in
+        the order of the contract.  out: a uint8 device tensor to take the table (32 bytes a hit); then `hits` is the torch view of its
+        first 32 * total bytes and too small a tensor raises NafGpuError(E_CAP).  Without it the table is counted first."""
+        import numpy as np
+        import torch
+        blob, n = self._patterns(patterns)
+        budgets = self._budgets(mismatches, n)
+        total = C.c_uint64()
+        cnt = WHOLE if count is None else int(count)
+        if out is not None:
+            self._check(self.L.naf_gpu_unnaf_locate_near(self.h, _ptr(d_naf), d_naf.numel(), blob, len(blob), n, budgets, int(strands), int(first), cnt,
+                                                         _ptr(out), out.numel() // 32, C.byref(total)))
+            return out[:32 * total.value], total.value
+        self._check(self.L.naf_gpu_unnaf_locate_near_count(self.h, _ptr(d_naf), d_naf.numel(), blob, len(blob), n, budgets, int(strands), int(first), cnt, C.byref(total), None))
+        buf = torch.empty(max(32 * total.value, 1), dtype=torch.uint8, device=self.device)
+        self._check(self.L.naf_gpu_unnaf_locate_near(self.h, _ptr(d_naf), d_naf.numel(), blob, len(blob), n, budgets, int(strands), int(first), cnt,
+                                                     _ptr(buf), total.value, C.byref(total)))
+        return np.frombuffer(buf[:32 * total.value].cpu().numpy().tobytes(), dtype=NEAR_HIT_DTYPE), total.value
 
     def unnaf_composition_rows(self, d_naf, window=0, first=0, count=None):
         """The rows unnaf_composition gives for records [first, first + count) under `window` (naf_gpu_unnaf_composition_rows: the lengths

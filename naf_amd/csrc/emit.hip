@@ -2205,6 +2205,7 @@ extern "C" int naf_gpu_unnaf_range(naf_gpu_ctx *c, const void *d_naf, size_t naf
 // ---- records and regions by number, id or range ------------------------------------------------------------------------------
 #include "emit_select.h"
 #include "locate.h"
+#include "locate_near.h"
 #include "composition.h"
 #include "quality.h"
 #include "runs.h"

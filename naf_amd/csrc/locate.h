@@ -139,6 +139,67 @@ static LocCombo motif_masks(const u8 code[32], size_t m)
     return q;
 }
 
+// ---- what the exact search and the one with mismatches (locate_near.h) share on the host; who: the caller's name in the messages ----
+// The checks of the arguments and the walk over the blob of patterns: each(k, text) takes pattern k and returns 0 or the error it set.
+template <typename Each>
+static int motif_walk(naf_gpu_ctx *c, const char *who, const char *h_patterns, size_t patterns_bytes, size_t n_patterns, int strands, Each each)
+{
+    if (n_patterns < 1 || n_patterns > LOC_MAX_PATTERNS) return ctx_fail(c, NAF_GPU_EARG, "%s: %zu patterns given, 1 to %d can be searched in one call", who, n_patterns, LOC_MAX_PATTERNS);
+    if (strands < 1 || strands > 3) return ctx_fail(c, NAF_GPU_EARG, "%s: strand mask %d is none of 1 (as stored), 2 (reverse), 3 (both)", who, strands);
+    if (!h_patterns) return ctx_fail(c, NAF_GPU_EARG, "%s: no patterns given (h_patterns is NULL)", who);
+    size_t at = 0;
+    for (size_t k = 0; k < n_patterns; k++) {
+        const void *z = at < patterns_bytes ? memchr(h_patterns + at, 0, patterns_bytes - at) : nullptr;
+        if (!z) return ctx_fail(c, NAF_GPU_EARG, "%s: %zu patterns announced, %zu zero-terminated strings in %zu bytes", who, n_patterns, k, patterns_bytes);
+        const int rc = each(k, h_patterns + at); if (rc) return rc;
+        at = (size_t)((const char *)z - h_patterns) + 1;
+    }
+    return 0;
+}
+static int motif_length_fail(naf_gpu_ctx *c, const char *who, size_t k, size_t letters)
+{
+    return ctx_fail(c, NAF_GPU_EARG, "%s: pattern %zu has %zu letters, a pattern has 1 to 32", who, k, letters);
+}
+// pos: the 1-based position in the text of the letter that is none
+static int motif_letter_fail(naf_gpu_ctx *c, const char *who, size_t k, const char *text, int pos)
+{
+    const unsigned char ch = (unsigned char)text[pos - 1];
+    if (ch >= 33 && ch < 127) return ctx_fail(c, NAF_GPU_EARG, "%s: pattern %zu: letter '%c' (position %d) is no IUPAC nucleotide code", who, k, ch, pos);
+    return ctx_fail(c, NAF_GPU_EARG, "%s: pattern %zu: letter '\\x%02X' (position %d) is no IUPAC nucleotide code", who, k, ch, pos);
+}
+// The front of the call and its pieces; count comes back 0 when there is nothing to search.
+static int locate_front(naf_gpu_ctx *c, const u8 *d_naf, size_t naf_len, const char *who, u64 first, u64 *count, UnnafPlan &pl, std::vector<RecPiece> &pieces)
+{
+    int rc = records_front(c, d_naf, naf_len, FRONT_4BIT, who, "nucleotide motifs cannot be searched", first, count, pl);
+    if (rc || !*count) return rc;
+    return piece_plan(c, pl.P, first, *count, "LOCATE_PIECE", LOC_PIECE_DEFAULT, pieces);
+}
+// The two passes over the pieces.  launch(writing, pc, tl, tile_cnt, lane_cnt, before) launches the caller's kernel: the counting one
+// (tile_cnt, lane_cnt and the caller's sums) or the one that writes (tile_cnt scanned: the tiles' offsets; before: the hits of the pieces
+// in front).  d_sums: the caller's device counters, zeroed before every sweep.  Too small a capacity is found before anything is written.
+template <typename Launch>
+static int locate_sweeps(PieceSweep &sw, const std::vector<RecPiece> &pieces, bool write, const void *d_hits, size_t hit_cap, void *d_sums, size_t sums_bytes, u64 *n_hits, Launch launch)
+{
+    naf_gpu_ctx *c = sw.c;
+    return count_then_write(sw, pieces, LOC_TILE, { "hits", write, hit_cap, d_sums, sums_bytes }, n_hits,
+                            [&](const RecPiece &pc, const PieceSweep::Tiles &tl, bool writing, u64 before, u64 *here) -> int {
+        const u64 ntiles = tl.ntiles;
+        u64 *tile_cnt = arena_new<u64>(c, ntiles + 2); u32 *lane_cnt = arena_new<u32>(c, ntiles * 64);
+        if (!tile_cnt || !lane_cnt) return NAF_GPU_ENOMEM;
+        HIP_TRY(c, hipMemsetAsync(tile_cnt + ntiles, 0, 8, c->stream));
+        launch(false, pc, tl, tile_cnt, lane_cnt, before);
+        int r = tile_totals(c, ntiles, tile_cnt, here); if (r) return r;
+        if (writing && *here) {
+            if (before + *here > hit_cap) return NAF_GPU_ECAP;
+            if (!d_hits) return NAF_GPU_EARG;
+            launch(true, pc, tl, tile_cnt, lane_cnt, before);
+            HIP_TRY(c, hipGetLastError());
+            HIP_TRY(c, hipStreamSynchronize(c->stream));
+        }
+        return 0;
+    });
+}
+
 // per_pattern: n_patterns x 2 counts (host), or nullptr.  write: the hits go to d_hits (hit_cap entries); too small a capacity is found
 // before anything is written.
 static int locate_run(naf_gpu_ctx *c, const u8 *d_naf, size_t naf_len, const char *h_patterns, size_t patterns_bytes, size_t n_patterns, int strands,
@@ -146,60 +207,34 @@ static int locate_run(naf_gpu_ctx *c, const u8 *d_naf, size_t naf_len, const cha
 {
     if (!c || !d_naf || !n_hits) return NAF_GPU_EARG;
     *n_hits = 0;
-    if (n_patterns < 1 || n_patterns > LOC_MAX_PATTERNS) return ctx_fail(c, NAF_GPU_EARG, "locate: %zu patterns given, 1 to %d can be searched in one call", n_patterns, LOC_MAX_PATTERNS);
-    if (strands < 1 || strands > 3) return ctx_fail(c, NAF_GPU_EARG, "locate: strand mask %d is none of 1 (as stored), 2 (reverse), 3 (both)", strands);
-    if (!h_patterns) return ctx_fail(c, NAF_GPU_EARG, "locate: no patterns given (h_patterns is NULL)");
     LocPats Q; memset(&Q, 0, sizeof Q);
     bool any_long = false;
-    { size_t at = 0;
-      for (size_t k = 0; k < n_patterns; k++) {
-          const void *z = at < patterns_bytes ? memchr(h_patterns + at, 0, patterns_bytes - at) : nullptr;
-          if (!z) return ctx_fail(c, NAF_GPU_EARG, "locate: %zu patterns announced, %zu zero-terminated strings in %zu bytes", n_patterns, k, patterns_bytes);
-          const char *text = h_patterns + at;
-          u8 fwd[32], rev[32]; size_t m = 0;
-          const int bad = motif_compile(text, fwd, rev, &m);
-          if (bad < 0) return ctx_fail(c, NAF_GPU_EARG, "locate: pattern %zu has %zu letters, a pattern has 1 to 32", k, strlen(text));
-          if (bad > 0) {
-              const unsigned char ch = (unsigned char)text[bad - 1];
-              if (ch >= 33 && ch < 127) return ctx_fail(c, NAF_GPU_EARG, "locate: pattern %zu: letter '%c' (position %d) is no IUPAC nucleotide code", k, ch, bad);
-              return ctx_fail(c, NAF_GPU_EARG, "locate: pattern %zu: letter '\\x%02X' (position %d) is no IUPAC nucleotide code", k, ch, bad);
-          }
-          for (int s = 0; s < 2; s++) if (strands & (1 << s)) {
-              Q.c[Q.n] = motif_masks(s ? rev : fwd, m); Q.len[Q.n] = (u32)m; Q.pat[Q.n] = (u8)k; Q.strand[Q.n] = (u8)s; Q.n++;
-          }
-          any_long = any_long || m > 16;
-          at = (size_t)((const char *)z - h_patterns) + 1;
-      } }
+    int rc = motif_walk(c, "locate", h_patterns, patterns_bytes, n_patterns, strands, [&](size_t k, const char *text) -> int {
+        u8 fwd[32], rev[32]; size_t m = 0;
+        const int bad = motif_compile(text, fwd, rev, &m);
+        if (bad < 0) return motif_length_fail(c, "locate", k, strlen(text));
+        if (bad > 0) return motif_letter_fail(c, "locate", k, text, bad);
+        for (int s = 0; s < 2; s++) if (strands & (1 << s)) {
+            Q.c[Q.n] = motif_masks(s ? rev : fwd, m); Q.len[Q.n] = (u32)m; Q.pat[Q.n] = (u8)k; Q.strand[Q.n] = (u8)s; Q.n++;
+        }
+        any_long = any_long || m > 16;
+        return 0;
+    });
+    if (rc) return rc;
     if (per_pattern) for (size_t k = 0; k < 2 * n_patterns; k++) per_pattern[k] = 0;
-    UnnafPlan pl;
-    int rc = records_front(c, d_naf, naf_len, FRONT_4BIT, "locate", "nucleotide motifs cannot be searched", first, &count, pl);
+    UnnafPlan pl; std::vector<RecPiece> pieces;
+    rc = locate_front(c, d_naf, naf_len, "locate", first, &count, pl, pieces);
     if (rc || !count) return rc;
     const EmitP &P = pl.P;
-    std::vector<RecPiece> pieces;
-    if ((rc = piece_plan(c, P, first, count, "LOCATE_PIECE", LOC_PIECE_DEFAULT, pieces))) return rc;
 
     u64 *combo_cnt = arena_new<u64>(c, LOC_MAX_COMBOS); if (!combo_cnt) return NAF_GPU_ENOMEM;
     PieceSweep sw(c, d_naf, pl, "locate");
-    rc = count_then_write(sw, pieces, LOC_TILE, { "hits", write, hit_cap, combo_cnt, LOC_MAX_COMBOS * 8 }, n_hits,
-                          [&](const RecPiece &pc, const PieceSweep::Tiles &tl, bool writing, u64 before, u64 *here) -> int {
-        const u64 ntiles = tl.ntiles;
-        u64 *tile_cnt = arena_new<u64>(c, ntiles + 2); u32 *lane_cnt = arena_new<u32>(c, ntiles * 64);
-        if (!tile_cnt || !lane_cnt) return NAF_GPU_ENOMEM;
-        HIP_TRY(c, hipMemsetAsync(tile_cnt + ntiles, 0, 8, c->stream));
-#define LOC_LAUNCH(W, name) do { \
-            if (any_long) LAUNCH(c, name, (k_locate<W, true>), (u32)ntiles, 64, 0, Q, tl.seq, tl.b_hi, P.rec_base, pc.r_lo, pc.r_hi, pc.p_lo, pc.p_hi, tl.t0, tile_cnt, lane_cnt, (unsigned long long *)combo_cnt, (const u64 *)tile_cnt, before, d_hits, (u64)hit_cap); \
-            else LAUNCH(c, name, (k_locate<W, false>), (u32)ntiles, 64, 0, Q, tl.seq, tl.b_hi, P.rec_base, pc.r_lo, pc.r_hi, pc.p_lo, pc.p_hi, tl.t0, tile_cnt, lane_cnt, (unsigned long long *)combo_cnt, (const u64 *)tile_cnt, before, d_hits, (u64)hit_cap); } while (0)
-        LOC_LAUNCH(false, "unnaf_locate_count");
-        int r = tile_totals(c, ntiles, tile_cnt, here); if (r) return r;
-        if (writing && *here) {
-            if (before + *here > hit_cap) return NAF_GPU_ECAP;
-            if (!d_hits) return NAF_GPU_EARG;
-            LOC_LAUNCH(true, "unnaf_locate_write");
-            HIP_TRY(c, hipGetLastError());
-            HIP_TRY(c, hipStreamSynchronize(c->stream));
-        }
+    rc = locate_sweeps(sw, pieces, write, d_hits, hit_cap, combo_cnt, LOC_MAX_COMBOS * 8, n_hits,
+                       [&](bool writing, const RecPiece &pc, const PieceSweep::Tiles &tl, u64 *tile_cnt, u32 *lane_cnt, u64 before) {
+#define LOC_LAUNCH(W, L, name) LAUNCH(c, name, (k_locate<W, L>), (u32)tl.ntiles, 64, 0, Q, tl.seq, tl.b_hi, P.rec_base, pc.r_lo, pc.r_hi, pc.p_lo, pc.p_hi, tl.t0, tile_cnt, lane_cnt, (unsigned long long *)combo_cnt, (const u64 *)tile_cnt, before, d_hits, (u64)hit_cap)
+        if (writing) { if (any_long) LOC_LAUNCH(true, true, "unnaf_locate_write"); else LOC_LAUNCH(true, false, "unnaf_locate_write"); }
+        else { if (any_long) LOC_LAUNCH(false, true, "unnaf_locate_count"); else LOC_LAUNCH(false, false, "unnaf_locate_count"); }
 #undef LOC_LAUNCH
-        return 0;
     });
     if (rc) return rc;
     if (per_pattern) {

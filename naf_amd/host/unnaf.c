@@ -20,6 +20,9 @@ static bool revcomp = false;                                      /* --revcomp: 
 enum { MAX_LOCATE = 16 };
 static const char *locate_patterns[MAX_LOCATE]; static size_t n_locate = 0;
 static int locate_strands = 3; static bool strand_given = false;
+/* --mismatches N, or a pattern with [letters that must match]: the near search, BED6 with the count in column 5 and the site as a 7th column */
+static unsigned locate_mismatches = 0; static bool mismatches_given = false, locate_bracketed = false;
+static size_t locate_free_letters[MAX_LOCATE];                    /* a pattern's letters outside brackets */
 /* --composition [--window N]: base composition per record or per window, as a tab-separated table (this implementation only) */
 static bool composition = false, window_given = false; static unsigned long long comp_window = 0;
 /* --quality [--cycles N]: quality statistics per read or per bin of N read positions, as a tab-separated table (this implementation only) */
@@ -74,10 +77,20 @@ static void add_records(const char *spec)
 
 static void add_locate(const char *pattern)
 {
-    uint8_t fwd[32], rev[32]; size_t len;
-    if (naf_gpu_compile_motif(pattern, fwd, rev, &len)) die("can't parse the value of --locate parameter (1 to 32 IUPAC nucleotide letters)\n");
+    uint8_t fwd[32], rev[32]; size_t len; uint32_t fixed;
+    if (naf_gpu_compile_motif_near(pattern, fwd, rev, &fixed, &len))            /* (a pattern without brackets: the message it always had) */
+        die(strpbrk(pattern, "[]") ? "can't parse the value of --locate parameter (1 to 32 IUPAC nucleotide letters, [] around those that must match)\n"
+                                   : "can't parse the value of --locate parameter (1 to 32 IUPAC nucleotide letters)\n");
     if (n_locate == MAX_LOCATE) die("at most %d --locate patterns can be searched at once\n", (int)MAX_LOCATE);
+    if (strchr(pattern, '[')) locate_bracketed = true;
+    locate_free_letters[n_locate] = len - (size_t)__builtin_popcount(fixed);
     locate_patterns[n_locate++] = pattern;
+}
+static void set_mismatches(const char *v)
+{
+    if (mismatches_given) die("only one --mismatches value can be given\n");
+    if (!(v[0] >= '0' && v[0] <= '0' + NAF_GPU_LOCATE_MAX_MISMATCHES && !v[1])) die("can't parse the value of --mismatches parameter (0 to %d)\n", NAF_GPU_LOCATE_MAX_MISMATCHES);
+    locate_mismatches = (unsigned)(v[0] - '0'); mismatches_given = true;
 }
 static void set_strand(const char *v)
 {
@@ -162,6 +175,8 @@ static void show_help(void)
         "Options for searching (output: BED6 lines \"ID begin end PATTERN 0 strand\", 0-based half-open; with at most one --records A-B or --region ID):\n"
         "  --locate PATTERN - Every place where the IUPAC pattern (1 to 32 letters, e.g. NGG) matches; repeatable, up to 16 patterns\n"
         "  --strand +|-|both - Search the sequences as stored, their reverse complement, or both (default)\n"
+        "  --mismatches N  - With --locate: every place within N = 0 to 8 mismatches of a pattern; letters in [] must match, e.g. GAGTCCGAGCAGAAGAAGAA[NGG].\n"
+        "                    With it, or with [] in a pattern, lines are \"ID begin end PATTERN mismatches strand SITE\": SITE is the pattern, mismatched letters in lower case\n"
         "Options for counting (output: a tab-separated table \"#seq start end A C G T N other gap masked CpG GC\"; with at most one --records A-B or --region ID):\n"
         "  --composition   - Base composition of every sequence: bases per letter, soft-masked bases, CpG, GC fraction (--no-mask: masked = 0)\n"
         "  --window N      - With --composition: one line per window of N bases instead of one per sequence\n"
@@ -188,13 +203,13 @@ static void parse_command_line(int argc, char **argv)
         {"--fasta", FASTA}, {"--fastq", FASTQ}, {"--dna", DNA}, {"--masked-dna", MASKED_DNA}, {"--unmasked-dna", UNMASKED_DNA},
         {"--masked-fasta", MASKED_FASTA}, {"--unmasked-fasta", UNMASKED_FASTA} };
     /* the other options (unnaf/src/unnaf.c:282-353), as a table: one that takes a value is only recognised with an argument behind it */
-    enum { OP_LINE_LENGTH, OP_OUT, OP_NO_MASK, OP_IGNORED, OP_HELP, OP_VERBOSE, OP_VERSION, OP_STDOUT, OP_REGION, OP_RECORDS, OP_RC_REGION, OP_REVCOMP, OP_LOCATE, OP_STRAND, OP_COMPOSITION, OP_WINDOW, OP_QUALITY, OP_CYCLES, OP_RUNS, OP_MASKED_RUNS, OP_MIN_RUN, OP_EACH, OP_KMERS, OP_CANONICAL, OP_PER_RECORD };
+    enum { OP_LINE_LENGTH, OP_OUT, OP_NO_MASK, OP_IGNORED, OP_HELP, OP_VERBOSE, OP_VERSION, OP_STDOUT, OP_REGION, OP_RECORDS, OP_RC_REGION, OP_REVCOMP, OP_LOCATE, OP_STRAND, OP_MISMATCHES, OP_COMPOSITION, OP_WINDOW, OP_QUALITY, OP_CYCLES, OP_RUNS, OP_MASKED_RUNS, OP_MIN_RUN, OP_EACH, OP_KMERS, OP_CANONICAL, OP_PER_RECORD };
     static const struct { const char *name; int op; bool value; } option_table[] = {
         { "--line-length", OP_LINE_LENGTH, true }, { "-o", OP_OUT, true }, { "--no-mask", OP_NO_MASK, false }, { "--binary-stdout", OP_IGNORED, false },
         { "--binary-stderr", OP_IGNORED, false }, { "--binary", OP_IGNORED, false }, { "--help", OP_HELP, false }, { "-h", OP_HELP, false },
         { "--verbose", OP_VERBOSE, false }, { "--version", OP_VERSION, false }, { "-V", OP_VERSION, false }, { "-c", OP_STDOUT, false },
         { "--region", OP_REGION, true }, { "--records", OP_RECORDS, true }, { "--rc-region", OP_RC_REGION, true }, { "--revcomp", OP_REVCOMP, false },
-        { "--locate", OP_LOCATE, true }, { "--strand", OP_STRAND, true }, { "--composition", OP_COMPOSITION, false }, { "--window", OP_WINDOW, true },
+        { "--locate", OP_LOCATE, true }, { "--strand", OP_STRAND, true }, { "--mismatches", OP_MISMATCHES, true }, { "--composition", OP_COMPOSITION, false }, { "--window", OP_WINDOW, true },
         { "--quality", OP_QUALITY, false }, { "--cycles", OP_CYCLES, true },
         { "--runs", OP_RUNS, true }, { "--masked-runs", OP_MASKED_RUNS, false }, { "--min-run", OP_MIN_RUN, true }, { "--each", OP_EACH, false },
         { "--kmers", OP_KMERS, true }, { "--canonical", OP_CANONICAL, false }, { "--per-record", OP_PER_RECORD, false } };
@@ -228,6 +243,7 @@ static void parse_command_line(int argc, char **argv)
         case OP_RECORDS: add_records(v); break;
         case OP_LOCATE: add_locate(v); break;
         case OP_STRAND: set_strand(v); break;
+        case OP_MISMATCHES: set_mismatches(v); break;
         case OP_COMPOSITION: composition = true; break;
         case OP_WINDOW: set_window(v); break;
         case OP_QUALITY: quality = true; break;
@@ -248,6 +264,9 @@ static void parse_command_line(int argc, char **argv)
     }
     if (force_stdout && out_file_path) die("-c and -o arguments can't be used together\n");
     if (strand_given && !n_locate) die("--strand can be used only with --locate\n");
+    if (mismatches_given && !n_locate) die("--mismatches can be used only with --locate\n");
+    if (locate_mismatches) for (size_t k = 0; k < n_locate; k++) if (locate_mismatches >= locate_free_letters[k])
+        die("--mismatches %u leaves nothing of --locate %s to match: it must be smaller than the pattern's %zu letters outside brackets\n", locate_mismatches, locate_patterns[k], locate_free_letters[k]);
     if (n_locate) {
         if (out_type != UNDECIDED) die("--locate writes BED lines: no output type can be given with it\n");
         if (revcomp) die("--locate searches both strands itself (--strand): --revcomp can't be used with it\n");
@@ -569,6 +588,54 @@ static void run_locate(bool has_ids, bool has_names)
     free(pats);
 }
 
+/* --locate with --mismatches or a bracketed pattern: the near search (naf_gpu_unnaf_locate_near); a line carries the number of mismatches in
+ * column 5 and, as a 7th column, the pattern's letters in upper case with the mismatched ones in lower case (from the hit's `where`). */
+static void run_locate_near(bool has_ids, bool has_names)
+{
+    upload();
+    const unsigned long long N = H.n_sequences;
+    uint64_t first, count;
+    one_record_range(has_ids, &first, &count);
+    size_t bytes = 0; for (size_t k = 0; k < n_locate; k++) bytes += strlen(locate_patterns[k]) + 1;
+    char *pats = (char *)malloc(bytes + 1); if (!pats) die("can't allocate memory\n");
+    char letters[MAX_LOCATE][33]; size_t plen[MAX_LOCATE]; uint32_t budget[MAX_LOCATE];
+    for (size_t k = 0, at = 0; k < n_locate; k++) {
+        const size_t l = strlen(locate_patterns[k]);
+        memcpy(pats + at, locate_patterns[k], l + 1); at += l + 1;
+        plen[k] = 0; for (const char *p = locate_patterns[k]; *p; p++) if (*p != '[' && *p != ']') letters[k][plen[k]++] = *p;
+        letters[k][plen[k]] = 0; budget[k] = locate_mismatches;
+    }
+    uint64_t n = 0;
+    GPU_TRY(naf_gpu_unnaf_locate_near_count(gpu, d_naf, naf_len, pats, bytes, n_locate, budget, locate_strands, first, count, &n, NULL));
+    phase("locate-near: count");
+    if (n) {
+        void *d_hits; GPU_TRY(naf_gpu_malloc(gpu, (size_t)n * sizeof(naf_gpu_near_hit), &d_hits));
+        uint64_t got = 0;
+        GPU_TRY(naf_gpu_unnaf_locate_near(gpu, d_naf, naf_len, pats, bytes, n_locate, budget, locate_strands, first, count, (naf_gpu_near_hit *)d_hits, (size_t)n, &got));
+        if (got != n) die("can't decompress sequence\n");
+        phase("locate-near: hits");
+        unsigned char *text; const char **name = record_names(has_ids, has_names, &text);
+        const size_t chunk = 1 << 20;
+        naf_gpu_near_hit *hits = (naf_gpu_near_hit *)malloc((n < chunk ? (size_t)n : chunk) * sizeof *hits); if (!hits) die("can't allocate memory\n");
+        for (uint64_t a = 0; a < n; a += chunk) {
+            const size_t m = n - a < chunk ? (size_t)(n - a) : chunk;
+            GPU_TRY(naf_gpu_download(gpu, hits, (const naf_gpu_near_hit *)d_hits + a, m * sizeof *hits));
+            for (size_t k = 0; k < m; k++) {
+                const naf_gpu_near_hit *x = &hits[k];
+                if (x->record >= N || x->pattern >= n_locate) die("can't decompress sequence\n");
+                char site[33];
+                for (size_t j = 0; j < plen[x->pattern]; j++) { const char ch = letters[x->pattern][j]; const bool low = ch >= 'a' && ch <= 'z'; site[j] = (char)(x->where >> j & 1 ? (low ? ch : ch + 32) : (low ? ch - 32 : ch)); }
+                site[plen[x->pattern]] = 0;
+                fprintf(OUT, "%s\t%llu\t%llu\t%s\t%u\t%c\t%s\n", name[x->record], (unsigned long long)x->begin, (unsigned long long)(x->begin + plen[x->pattern]),
+                        letters[x->pattern], (unsigned)x->mismatches, x->strand ? '-' : '+', site);
+            }
+        }
+        free(hits); free(name); free(text); naf_gpu_free(gpu, d_hits);
+        phase("locate-near: download + BED lines");
+    }
+    free(pats);
+}
+
 /* --composition: the table of rows is made on the device (naf_gpu_unnaf_composition: one sweep over the packed stream); the lines are
  * formatted here, on the host, from the downloaded rows, a chunk at a time -- text for people and scripts, not a hot path. */
 static void run_composition(bool has_ids, bool has_names)
@@ -822,7 +889,7 @@ int main(int argc, char **argv)
     unsigned long long N = H.n_sequences;
     if (n_locate) {
         if (H.seq_type >= NAF_SEQ_PROTEIN) die("nucleotide motifs cannot be searched in %s sequences\n", tn[H.seq_type]);
-        run_locate(has_ids, has_names);
+        if (mismatches_given || locate_bracketed) run_locate_near(has_ids, has_names); else run_locate(has_ids, has_names);
     }
     else if (composition) {
         if (H.seq_type >= NAF_SEQ_PROTEIN) die("nucleotides cannot be counted in %s sequences\n", tn[H.seq_type]);
