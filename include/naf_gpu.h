@@ -454,6 +454,61 @@ int  naf_gpu_unnaf_kmers(naf_gpu_ctx *ctx, const void *d_naf, size_t naf_len, un
                          uint64_t *d_counts, size_t count_cap, naf_gpu_kmer_row *d_rows, size_t row_cap,
                          uint64_t *n_rows, uint64_t *n_counters, naf_gpu_kmer_row *h_total);
 
+/* ---- unnaf: open reading frames on the six frames of every record, listed from the packed stream --------------------
+ * What getorf, NCBI ORFfinder, orfipy and seqkit translate -F answer from the text -- where the open reading frames lie -- as a table of
+ * (record, begin, end, strand) rows, made without expanding the codes.  Nothing is translated to amino acids.
+ *   Codon set   a uint64_t: bit i is the codon whose index is i under naf_gpu_kmer_index at K = 3 (A = 0, C = 1, G = 2, T/U = 3, the first
+ *               base the most significant): TAA = 48, TAG = 50, TGA = 56, ATG = 14.  naf_gpu_parse_codon_set takes comma-separated
+ *               three-letter codons, either case, U = T; the IUPAC letters RYSWKM BDHV N expand ("TAR,TGA" is the three standard
+ *               stops).  '-', any other character, an empty item, an item of another length and the empty string are NAF_GPU_EARG, and
+ *               nothing is written then.
+ *   Known       a codon is three consecutive bases of ONE record at offsets o, o + 1, o + 2.  It is known when each is stored as exactly
+ *               A, C, G or T/U (codes 8, 4, 2, 1 of "-TGKCYSBAWRDMHVN"); any other stored code -- N, an ambiguity code, the gap -- makes
+ *               it unknown, and an unknown codon is never a stop and never a start.  Case (the soft mask) plays no part and the mask
+ *               section is never decoded.  A codon that straddles two records does not exist.
+ *   Never       Bases behind the last record of a malformed archive and the padding nibble of an odd stream are in no codon.
+ *   Frames      strand 0: the frame of a codon is o mod 3.  strand 1 is the reverse complement of the record's L bases: the reverse
+ *               codon over forward offsets [o, o + 3) reads comp(o + 2) comp(o + 1) comp(o), and its frame is (L - (o + 3)) mod 3.  This is
+ *               the "reverse-complement, then frame 1..3" convention of ORFfinder and seqkit, NOT that of EMBOSS (whose -1..-3 count
+ *               from the forward offset).  begin and end are always forward offsets, as naf_gpu_unnaf_select_stranded takes them.
+ *   Stretch     for one strand and frame of one record, a maximal series of consecutive in-frame codons none of which is a stop -- with
+ *               NAF_GPU_ORF_SPLIT_UNKNOWN none of which is unknown either.  It is bounded on each side by such a codon or by the
+ *               record's edge: the first forward codon of frame f is at offset f, the last ends at f + 3 floor((L - f) / 3).
+ *   ORF         starts == 0: the whole stretch ("stop to stop", getorf -find 0).  starts != 0: from the 5'-most start codon of the
+ *               stretch, in reading direction (on strand 1 the start codon with the greatest forward offset), to the stretch's 3' end;
+ *               only that longest ORF of a stretch is listed, no nested ones, and a stretch without a start gives none.  The stop codon
+ *               is not part of [begin, end); end - begin is a multiple of 3 and at least min_len.  An empty stretch gives nothing.
+ *   Row flags   NAF_GPU_ORF_STOP3: a stop codon lies directly behind the 3' end -- [end, end + 3) on strand 0, [begin - 3, begin) on
+ *               strand 1.  NAF_GPU_ORF_STOP5: a stop codon lies directly in front of the STRETCH's 5' end.  Without the bit the stretch
+ *               was ended there by the record's edge or, with SPLIT_UNKNOWN, by an unknown codon.
+ *   Call flags  NAF_GPU_ORF_SPLIT_UNKNOWN; NAF_GPU_ORF_CLOSED: only rows with STOP3.  strands: 1 forward, 2 reverse, 3 both, as in
+ *               naf_gpu_unnaf_locate.
+ *   Order       ascending (record, begin, end), then strand; the same bytes on every run and for every piece size.
+ *   Errors      NAF_GPU_EARG, last_error saying which: stops == 0; starts & stops != 0; min_len == 0; strands outside 1 .. 3; unknown
+ *               flag bits.  Archives, first and count are those of naf_gpu_unnaf_composition: protein archives, text archives and
+ *               archives that store no sequence are NAF_GPU_EARG, an archive without records gives 0 rows, count = NAF_GPU_WHOLE means
+ *               to the last record.
+ *   Outputs     *n_orfs is always the whole count; *n_bases (may be NULL) the sum of end - begin; per_frame (may be NULL) the rows per
+ *               [3 * strand + frame].  d_orfs is DEVICE memory of any alignment; exactly 32 * n_orfs bytes are written and nothing else.
+ *               With orf_cap too small the call returns NAF_GPU_ECAP, sets *n_orfs and writes nothing.
+ *   Pieces      more bases than NAF_GPU_ORFS_PIECE (default 2^31) are decoded and swept in pieces of whole records, so no stretch
+ *               crosses a piece; only the zstd blocks behind the records are decoded when the frame allows it.  The lists of stops,
+ *               starts and record bounds of a piece live in the context's scratch arena (in random sequence an eighth of an entry per
+ *               base): when it cannot hold them the call returns NAF_GPU_ENOMEM and last_error names NAF_GPU_ORFS_PIECE.
+ * A row is exactly the (record, begin, end, strand) that naf_gpu_unnaf_select_stranded takes: the rows, selected, are the coding texts.
+ * TRACE=1: "[orfs] orfs R stretches S stops B pieces P sequence bytes decoded X of Y" per call that reaches the records. */
+typedef struct { uint64_t record, begin, end; uint32_t strand; uint16_t frame, flags; } naf_gpu_orf;   /* 32 bytes */
+enum { NAF_GPU_ORF_STOP3 = 1, NAF_GPU_ORF_STOP5 = 2 };              /* naf_gpu_orf.flags */
+enum { NAF_GPU_ORF_SPLIT_UNKNOWN = 1, NAF_GPU_ORF_CLOSED = 2 };     /* the calls' flags */
+
+/* host only, no device */
+int  naf_gpu_parse_codon_set(const char *text, uint64_t *set);
+
+int  naf_gpu_unnaf_orfs_count(naf_gpu_ctx *ctx, const void *d_naf, size_t naf_len, uint64_t stops, uint64_t starts, uint64_t min_len, int strands, int flags,
+                              uint64_t first, uint64_t count, uint64_t *n_orfs, uint64_t *n_bases, uint64_t per_frame[6]);
+int  naf_gpu_unnaf_orfs(naf_gpu_ctx *ctx, const void *d_naf, size_t naf_len, uint64_t stops, uint64_t starts, uint64_t min_len, int strands, int flags,
+                        uint64_t first, uint64_t count, naf_gpu_orf *d_orfs, size_t orf_cap, uint64_t *n_orfs, uint64_t *n_bases);
+
 /* ---- ennaf ------------------------------------------------------------------------------------------ */
 typedef struct {
     int      format;            /* NAF_FMT_* (AUTO = sniff, process.c:547-583) */

@@ -35,6 +35,7 @@ EXPORTS = [
     "naf_gpu_quality_error_table", "naf_gpu_unnaf_quality_rows", "naf_gpu_unnaf_quality",
     "naf_gpu_parse_base_class", "naf_gpu_unnaf_runs_count", "naf_gpu_unnaf_runs",
     "naf_gpu_kmer_index", "naf_gpu_kmer_text", "naf_gpu_unnaf_kmers_rows", "naf_gpu_unnaf_kmers",
+    "naf_gpu_parse_codon_set", "naf_gpu_unnaf_orfs_count", "naf_gpu_unnaf_orfs",
 ]
 WHOLE = 2 ** 64 - 1                     # NAF_GPU_WHOLE: (record, 0, WHOLE) is the record as stored
 MAX_SHARDS = 64
@@ -158,6 +159,18 @@ KMER_CANONICAL, KMER_PER_RECORD = 1, 2
 KMER_MAX_K = 12
 
 
+class Orf(C.Structure):
+    """naf_gpu_orf: bases [begin, end) of `record` (forward offsets, the stop codon not included) are an open reading frame of strand 0
+    (as stored) or 1 (the reverse complement), frame 0..2 (reverse: counted from the record's end); flags: ORF_STOP3, ORF_STOP5."""
+    _fields_ = [("record", C.c_uint64), ("begin", C.c_uint64), ("end", C.c_uint64), ("strand", C.c_uint32), ("frame", C.c_uint16), ("flags", C.c_uint16)]
+
+
+ORF_DTYPE = [("record", "<u8"), ("begin", "<u8"), ("end", "<u8"), ("strand", "<u4"), ("frame", "<u2"), ("flags", "<u2")]      # numpy's view of a table of ORFs
+ORF_BYTES = 32
+ORF_STOP3, ORF_STOP5 = 1, 2                   # a row's flags
+ORF_SPLIT_UNKNOWN, ORF_CLOSED = 1, 2          # a call's flags
+
+
 class NafGpuError(RuntimeError):
     def __init__(self, code, msg):
         super().__init__("naf_gpu error %d: %s" % (code, msg))
@@ -264,6 +277,9 @@ def load():
         L.naf_gpu_kmer_index.argtypes = [C.c_char_p, i, C.POINTER(C.c_uint), u64p]
         L.naf_gpu_kmer_text.argtypes = [C.c_uint, C.c_uint64, C.c_char_p]
         L.naf_gpu_unnaf_kmers_rows.argtypes = [vp, vp, sz, C.c_uint, i, C.c_uint64, C.c_uint64, u64p, u64p]
+        L.naf_gpu_parse_codon_set.argtypes = [C.c_char_p, u64p]
+        L.naf_gpu_unnaf_orfs_count.argtypes = [vp, vp, sz, C.c_uint64, C.c_uint64, C.c_uint64, i, i, C.c_uint64, C.c_uint64, u64p, u64p, u64p]
+        L.naf_gpu_unnaf_orfs.argtypes = [vp, vp, sz, C.c_uint64, C.c_uint64, C.c_uint64, i, i, C.c_uint64, C.c_uint64, vp, sz, u64p, u64p]
         L.naf_gpu_unnaf_kmers.argtypes = [vp, vp, sz, C.c_uint, i, C.c_uint64, C.c_uint64, vp, sz, vp, sz, u64p, u64p, C.POINTER(KmerRow)]
         _lib = L
     return _lib
@@ -359,6 +375,34 @@ def kmer_text(k, index):
     if load().naf_gpu_kmer_text(k, index, out):
         raise ValueError("not a k-mer: k %r index %r" % (k, index))
     return out.value.decode()
+
+
+def parse_codon_set(text):
+    """Host-only: the 64-bit set of a comma-separated list of codons (naf_gpu_parse_codon_set) -- bit i for the codon of index i under
+    kmer_index at K = 3 --; three letters each, either case, U = T, the IUPAC letters RYSWKM BDHV N expand.  ValueError for anything else."""
+    b = text.encode("latin1") if isinstance(text, str) else bytes(text)
+    if b"\0" in b:
+        raise ValueError("not a list of codons: %r" % (text,))
+    s = C.c_uint64()
+    if load().naf_gpu_parse_codon_set(b, C.byref(s)):
+        raise ValueError("not a list of codons: %r" % (text,))
+    return s.value
+
+
+def orfs_to_segments(rows, include_stop=False):
+    """The (record, begin, end, reverse) tuples unnaf_select takes, one per open reading frame (rows of the table unnaf_orfs returns):
+    selected, they are the coding texts in reading direction.  include_stop: the stop codon too, on the 3' side (behind `end` on strand
+    0, in front of `begin` on strand 1), for the rows that have one (ORF_STOP3)."""
+    out = []
+    for x in rows:
+        r, b, e, s = int(x["record"]), int(x["begin"]), int(x["end"]), int(x["strand"])
+        if include_stop and int(x["flags"]) & ORF_STOP3:
+            if s:
+                b -= 3
+            else:
+                e += 3
+        out.append((r, b, e, s))
+    return out
 
 
 def runs_to_segments(runs, flank=0, lengths=None):
@@ -844,6 +888,53 @@ class Context:
             rc = call(buf, cap)
         self._check(rc)
         return np.frombuffer(buf[:RUN_BYTES * n.value].cpu().numpy().tobytes(), dtype=RUN_DTYPE), nb.value
+
+    @staticmethod
+    def _orf_args(stops, starts, strands, split_unknown, closed):
+        """(stops, starts, strands, flags) of an ORF call; the codon sets as text (parse_codon_set) or as 64-bit sets, starts None or 0:
+        stop to stop."""
+        st = parse_codon_set(stops) if isinstance(stops, (str, bytes)) else int(stops)
+        sa = 0 if starts is None else parse_codon_set(starts) if isinstance(starts, (str, bytes)) else int(starts)
+        if not (0 <= st < 2 ** 64 and 0 <= sa < 2 ** 64):
+            raise ValueError("not a codon set: %r %r" % (stops, starts))
+        return st, sa, int(strands), (ORF_SPLIT_UNKNOWN if split_unknown else 0) | (ORF_CLOSED if closed else 0)
+
+    def unnaf_orfs_count(self, d_naf, stops="TAA,TAG,TGA", starts="ATG", min_len=75, strands=STRAND_BOTH, split_unknown=False, closed=False, first=0, count=None):
+        """(n_orfs, n_bases, per_frame) of the rows unnaf_orfs lists (naf_gpu_unnaf_orfs_count); per_frame: the six counts [3 * strand + frame]."""
+        st, sa, sd, flags = self._orf_args(stops, starts, strands, split_unknown, closed)
+        n, nb, pf = C.c_uint64(), C.c_uint64(), (C.c_uint64 * 6)()
+        self._check(self.L.naf_gpu_unnaf_orfs_count(self.h, _ptr(d_naf), d_naf.numel(), st, sa, int(min_len), sd, flags, int(first), WHOLE if count is None else int(count),
+                                                    C.byref(n), C.byref(nb), pf))
+        return n.value, nb.value, [int(v) for v in pf]
+
+    def unnaf_orfs(self, d_naf, stops="TAA,TAG,TGA", starts="ATG", min_len=75, strands=STRAND_BOTH, split_unknown=False, closed=False, first=0, count=None, out=None):
+        """(rows, n_bases): the open reading frames of at least min_len bases on the strands asked for (STRAND_FORWARD, STRAND_REVERSE,
+        STRAND_BOTH) of records [first, first + count) -- stops, starts: codon sets as text (parse_codon_set) or as 64-bit sets; starts
+        None or 0: from stop to stop; split_unknown: a codon with N or another ambiguity code ends a reading frame; closed: only those
+        that end in a stop -- as a structured numpy array (ORF_DTYPE: record, begin, end, strand, frame, flags) in ascending (record,
+        begin, end, strand), and the sum of their lengths.  out: a uint8 device tensor to take the table (32 bytes a row); then `rows`
+        is the torch view of its first 32 * n bytes and too small a tensor raises NafGpuError(E_CAP).  Without it a table sized by a
+        guess is tried first and one of the whole count when that was too small (the call reports it with E_CAP)."""
+        import numpy as np
+        import torch
+        st, sa, sd, flags = self._orf_args(stops, starts, strands, split_unknown, closed)
+        n, nb = C.c_uint64(), C.c_uint64()
+        cnt = WHOLE if count is None else int(count)
+
+        def call(buf, cap):
+            return self.L.naf_gpu_unnaf_orfs(self.h, _ptr(d_naf), d_naf.numel(), st, sa, int(min_len), sd, flags, int(first), cnt, _ptr(buf), cap, C.byref(n), C.byref(nb))
+        if out is not None:
+            self._check(call(out, out.numel() // ORF_BYTES))
+            return out[:ORF_BYTES * n.value], nb.value
+        cap = 4096
+        buf = torch.empty(ORF_BYTES * cap, dtype=torch.uint8, device=self.device)
+        rc = call(buf, cap)
+        if rc == E_CAP:
+            cap = n.value
+            buf = torch.empty(ORF_BYTES * cap, dtype=torch.uint8, device=self.device)
+            rc = call(buf, cap)
+        self._check(rc)
+        return np.frombuffer(buf[:ORF_BYTES * n.value].cpu().numpy().tobytes(), dtype=ORF_DTYPE), nb.value
 
     def unnaf_kmers_rows(self, d_naf, k, canonical=False, per_record=False, first=0, count=None):
         """(n_rows, n_counters) of the tables unnaf_kmers gives for records [first, first + count) (naf_gpu_unnaf_kmers_rows: the lengths

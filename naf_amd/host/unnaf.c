@@ -32,6 +32,11 @@ static const char *runs_class = NULL; static uint16_t runs_set = 0; static bool 
 static unsigned long long min_run = 1;
 /* --kmers K [--canonical] [--per-record]: exact counts of all 4^K k-mers of the selection, or of every record (this implementation only) */
 static unsigned kmers_k = 0; static bool kmers_canonical = false, kmers_per_record = false;
+/* --orfs [--min-orf N] [--stops LIST] [--starts LIST | --stop-to-stop] [--strand +|-|both] [--closed] [--split-unknown]: open reading frames on
+ * the six frames, one tab-separated line each (this implementation only) */
+static bool orfs = false, min_orf_given = false, stop_to_stop = false, orfs_closed = false, orfs_split = false;
+static const char *orf_stops_text = NULL, *orf_starts_text = NULL; static uint64_t orf_stops = 0, orf_starts = 0;
+static unsigned long long min_orf = 75;
 
 static void done(int status, void *arg)
 {
@@ -153,6 +158,24 @@ static void set_kmers(const char *v)
     kmers_k = a;
 }
 
+static void set_codons(const char *opt, const char *v, const char **text, uint64_t *set)
+{
+    if (*text) die("only one %s list can be given\n", opt);
+    if (naf_gpu_parse_codon_set(v, set)) die("can't parse the value of %s parameter (comma-separated codons of three IUPAC nucleotide letters, e.g. TAA,TAG,TGA)\n", opt);
+    *text = v;
+}
+static void set_min_orf(const char *v)
+{
+    unsigned long long a = 0; bool digit = false;
+    for (const char *p = v; *p; p++) {
+        if (*p == ',') continue;
+        if (*p < '0' || *p > '9' || a > (ULLONG_MAX - (unsigned)(*p - '0')) / 10) die("can't parse the value of --min-orf parameter (a positive number of bases)\n");
+        a = a * 10 + (unsigned)(*p - '0'); digit = true;
+    }
+    if (!digit || a == 0) die("can't parse the value of --min-orf parameter (a positive number of bases)\n");
+    min_orf = a; min_orf_given = true;
+}
+
 static void show_help(void)
 {
     msg("Usage: unnaf [OUTPUT-TYPE] [file.naf]\n"
@@ -190,7 +213,17 @@ static void show_help(void)
         "Options for counting k-mers (output: lines \"KMER COUNT\" of the k-mers that occur, tab-separated; with at most one --records A-B or --region ID):\n"
         "  --kmers K       - Exact counts of all k-mers of K = 1 to 12 bases made of A, C, G, T/U only, never across a sequence's end; case is ignored\n"
         "  --canonical     - With --kmers: a k-mer and its reverse complement are counted as the one that sorts first\n"
-        "  --per-record    - With --kmers, K up to 6: a table \"#seq length counted\" and one column per k-mer, one line per sequence\n");
+        "  --per-record    - With --kmers, K up to 6: a table \"#seq length counted\" and one column per k-mer, one line per sequence\n"
+        "Options for listing open reading frames (output: lines \"ID begin end FRAME CODONS STRAND stop|open\", tab-separated, 0-based half-open, the stop codon not included;\n"
+        "    FRAME is +1..+3, or -1..-3 counted from the end of the sequence; with at most one --records A-B or --region ID):\n"
+        "  --orfs          - Every open reading frame on the six frames of every sequence, from its first start codon to the stop; codons with N or another ambiguity code are no stops\n"
+        "  --min-orf N     - With --orfs: only reading frames of at least N bases (default 75)\n"
+        "  --stops LIST    - With --orfs: the stop codons, comma-separated, IUPAC letters allowed (default TAA,TAG,TGA)\n"
+        "  --starts LIST   - With --orfs: the start codons (default ATG)\n"
+        "  --stop-to-stop  - With --orfs: the whole stretch between two stops, whether it has a start codon or not\n"
+        "  --closed        - With --orfs: only reading frames that end in a stop codon, none that run into the end of the sequence\n"
+        "  --split-unknown - With --orfs: a codon with N or another ambiguity code ends a reading frame\n"
+        "  --strand +|-|both - With --orfs: the sequences as stored, their reverse complement, or both (default)\n");
 }
 
 static void parse_command_line(int argc, char **argv)
@@ -203,7 +236,7 @@ static void parse_command_line(int argc, char **argv)
         {"--fasta", FASTA}, {"--fastq", FASTQ}, {"--dna", DNA}, {"--masked-dna", MASKED_DNA}, {"--unmasked-dna", UNMASKED_DNA},
         {"--masked-fasta", MASKED_FASTA}, {"--unmasked-fasta", UNMASKED_FASTA} };
     /* the other options (unnaf/src/unnaf.c:282-353), as a table: one that takes a value is only recognised with an argument behind it */
-    enum { OP_LINE_LENGTH, OP_OUT, OP_NO_MASK, OP_IGNORED, OP_HELP, OP_VERBOSE, OP_VERSION, OP_STDOUT, OP_REGION, OP_RECORDS, OP_RC_REGION, OP_REVCOMP, OP_LOCATE, OP_STRAND, OP_MISMATCHES, OP_COMPOSITION, OP_WINDOW, OP_QUALITY, OP_CYCLES, OP_RUNS, OP_MASKED_RUNS, OP_MIN_RUN, OP_EACH, OP_KMERS, OP_CANONICAL, OP_PER_RECORD };
+    enum { OP_LINE_LENGTH, OP_OUT, OP_NO_MASK, OP_IGNORED, OP_HELP, OP_VERBOSE, OP_VERSION, OP_STDOUT, OP_REGION, OP_RECORDS, OP_RC_REGION, OP_REVCOMP, OP_LOCATE, OP_STRAND, OP_MISMATCHES, OP_COMPOSITION, OP_WINDOW, OP_QUALITY, OP_CYCLES, OP_RUNS, OP_MASKED_RUNS, OP_MIN_RUN, OP_EACH, OP_KMERS, OP_CANONICAL, OP_PER_RECORD, OP_ORFS, OP_MIN_ORF, OP_STOPS, OP_STARTS, OP_STOP_TO_STOP, OP_CLOSED, OP_SPLIT_UNKNOWN };
     static const struct { const char *name; int op; bool value; } option_table[] = {
         { "--line-length", OP_LINE_LENGTH, true }, { "-o", OP_OUT, true }, { "--no-mask", OP_NO_MASK, false }, { "--binary-stdout", OP_IGNORED, false },
         { "--binary-stderr", OP_IGNORED, false }, { "--binary", OP_IGNORED, false }, { "--help", OP_HELP, false }, { "-h", OP_HELP, false },
@@ -212,7 +245,9 @@ static void parse_command_line(int argc, char **argv)
         { "--locate", OP_LOCATE, true }, { "--strand", OP_STRAND, true }, { "--mismatches", OP_MISMATCHES, true }, { "--composition", OP_COMPOSITION, false }, { "--window", OP_WINDOW, true },
         { "--quality", OP_QUALITY, false }, { "--cycles", OP_CYCLES, true },
         { "--runs", OP_RUNS, true }, { "--masked-runs", OP_MASKED_RUNS, false }, { "--min-run", OP_MIN_RUN, true }, { "--each", OP_EACH, false },
-        { "--kmers", OP_KMERS, true }, { "--canonical", OP_CANONICAL, false }, { "--per-record", OP_PER_RECORD, false } };
+        { "--kmers", OP_KMERS, true }, { "--canonical", OP_CANONICAL, false }, { "--per-record", OP_PER_RECORD, false },
+        { "--orfs", OP_ORFS, false }, { "--min-orf", OP_MIN_ORF, true }, { "--stops", OP_STOPS, true }, { "--starts", OP_STARTS, true }, { "--stop-to-stop", OP_STOP_TO_STOP, false },
+        { "--closed", OP_CLOSED, false }, { "--split-unknown", OP_SPLIT_UNKNOWN, false } };
     for (int i = 1; i < argc; i++) {
         char *arg = argv[i];
         if (arg[0] != '-') {
@@ -255,6 +290,13 @@ static void parse_command_line(int argc, char **argv)
         case OP_KMERS: set_kmers(v); break;
         case OP_CANONICAL: kmers_canonical = true; break;
         case OP_PER_RECORD: kmers_per_record = true; break;
+        case OP_ORFS: orfs = true; break;
+        case OP_MIN_ORF: set_min_orf(v); break;
+        case OP_STOPS: set_codons("--stops", v, &orf_stops_text, &orf_stops); break;
+        case OP_STARTS: set_codons("--starts", v, &orf_starts_text, &orf_starts); break;
+        case OP_STOP_TO_STOP: stop_to_stop = true; break;
+        case OP_CLOSED: orfs_closed = true; break;
+        case OP_SPLIT_UNKNOWN: orfs_split = true; break;
         }
     }
     if (print_version) {
@@ -263,7 +305,7 @@ static void parse_command_line(int argc, char **argv)
         exit(0);
     }
     if (force_stdout && out_file_path) die("-c and -o arguments can't be used together\n");
-    if (strand_given && !n_locate) die("--strand can be used only with --locate\n");
+    if (strand_given && !n_locate && !orfs) die("--strand can be used only with --locate\n");
     if (mismatches_given && !n_locate) die("--mismatches can be used only with --locate\n");
     if (locate_mismatches) for (size_t k = 0; k < n_locate; k++) if (locate_mismatches >= locate_free_letters[k])
         die("--mismatches %u leaves nothing of --locate %s to match: it must be smaller than the pattern's %zu letters outside brackets\n", locate_mismatches, locate_patterns[k], locate_free_letters[k]);
@@ -334,6 +376,32 @@ static void parse_command_line(int argc, char **argv)
         if (n_selections && selections[0].region) {
             size_t l; uint64_t b, e; naf_gpu_parse_region(selections[0].region, &l, &b, &e);
             if (!(b == 0 && e == NAF_GPU_WHOLE)) die("--kmers can be restricted to a whole sequence only: --region ID, without a range\n");
+        }
+    }
+    if (!orfs) {
+        if (min_orf_given) die("--min-orf can be used only with --orfs\n");
+        if (orf_stops_text) die("--stops can be used only with --orfs\n");
+        if (orf_starts_text) die("--starts can be used only with --orfs\n");
+        if (stop_to_stop) die("--stop-to-stop can be used only with --orfs\n");
+        if (orfs_closed) die("--closed can be used only with --orfs\n");
+        if (orfs_split) die("--split-unknown can be used only with --orfs\n");
+    } else {
+        if (n_locate) die("--orfs and --locate can't be used together\n");
+        if (composition) die("--orfs and --composition can't be used together\n");
+        if (quality) die("--orfs and --quality can't be used together\n");
+        if (runs_class || masked_runs) die("--orfs and %s can't be used together\n", runs_class ? "--runs" : "--masked-runs");
+        if (kmers_k) die("--orfs and --kmers can't be used together\n");
+        if (out_type != UNDECIDED) die("--orfs writes a table: no output type can be given with it\n");
+        if (stop_to_stop && orf_starts_text) die("--stop-to-stop and --starts can't be used together\n");
+        if (!orf_stops_text) naf_gpu_parse_codon_set("TAA,TAG,TGA", &orf_stops);
+        if (stop_to_stop) orf_starts = 0; else if (!orf_starts_text) naf_gpu_parse_codon_set("ATG", &orf_starts);
+        if (orf_starts & orf_stops) die("--starts and --stops share a codon: a codon can't both open and close a reading frame\n");
+        if (revcomp) die("--orfs reads both strands itself (--strand): --revcomp can't be used with it\n");
+        if (n_selections > 1) die("--orfs can be restricted by one --records or one --region only\n");
+        if (n_selections && selections[0].rc) die("--orfs reads both strands itself (--strand): --rc-region can't be used with it\n");
+        if (n_selections && selections[0].region) {
+            size_t l; uint64_t b, e; naf_gpu_parse_region(selections[0].region, &l, &b, &e);
+            if (!(b == 0 && e == NAF_GPU_WHOLE)) die("--orfs can be restricted to a whole sequence only: --region ID, without a range\n");
         }
     }
     if ((n_selections || revcomp) && !(out_type == UNDECIDED || out_type == FASTA || out_type == FASTQ || out_type == SEQ || out_type == SEQUENCES))
@@ -762,6 +830,42 @@ static void run_runs(bool has_ids, bool has_names)
     }
 }
 
+/* --orfs: the table of reading frames is made on the device (naf_gpu_unnaf_orfs: the stops, starts and record bounds of the packed stream as
+ * six lists, a stretch between two neighbours of one list); the lines are formatted here, on the host, from the downloaded table. */
+static void run_orfs(bool has_ids, bool has_names)
+{
+    upload();
+    const unsigned long long N = H.n_sequences;
+    uint64_t first, count;
+    one_record_range(has_ids, &first, &count);
+    const int flags = (orfs_split ? NAF_GPU_ORF_SPLIT_UNKNOWN : 0) | (orfs_closed ? NAF_GPU_ORF_CLOSED : 0);
+    uint64_t n = 0;
+    GPU_TRY(naf_gpu_unnaf_orfs_count(gpu, d_naf, naf_len, orf_stops, orf_starts, min_orf, locate_strands, flags, first, count, &n, NULL, NULL));
+    phase("orfs: count");
+    if (n) {
+        void *d_orfs; GPU_TRY(naf_gpu_malloc(gpu, (size_t)n * sizeof(naf_gpu_orf), &d_orfs));
+        uint64_t got = 0;
+        GPU_TRY(naf_gpu_unnaf_orfs(gpu, d_naf, naf_len, orf_stops, orf_starts, min_orf, locate_strands, flags, first, count, (naf_gpu_orf *)d_orfs, (size_t)n, &got, NULL));
+        if (got != n) die("can't decompress sequence\n");
+        phase("orfs: rows");
+        unsigned char *text; const char **name = record_names(has_ids, has_names, &text);
+        const size_t chunk = 1 << 20;
+        naf_gpu_orf *rows = (naf_gpu_orf *)malloc((n < chunk ? (size_t)n : chunk) * sizeof *rows); if (!rows) die("can't allocate memory\n");
+        for (uint64_t a = 0; a < n; a += chunk) {
+            const size_t m = n - a < chunk ? (size_t)(n - a) : chunk;
+            GPU_TRY(naf_gpu_download(gpu, rows, (const naf_gpu_orf *)d_orfs + a, m * sizeof *rows));
+            for (size_t k = 0; k < m; k++) {
+                const naf_gpu_orf *x = &rows[k];
+                if (x->record >= N || x->strand > 1 || x->frame > 2 || x->end <= x->begin) die("can't decompress sequence\n");
+                fprintf(OUT, "%s\t%llu\t%llu\t%c%u\t%llu\t%c\t%s\n", name[x->record], (unsigned long long)x->begin, (unsigned long long)x->end, x->strand ? '-' : '+', x->frame + 1u,
+                        (unsigned long long)((x->end - x->begin) / 3), x->strand ? '-' : '+', (x->flags & NAF_GPU_ORF_STOP3) ? "stop" : "open");
+            }
+        }
+        free(rows); free(name); free(text); naf_gpu_free(gpu, d_orfs);
+        phase("orfs: download + lines");
+    }
+}
+
 /* --kmers: the tables are made on the device (naf_gpu_unnaf_kmers: one sweep over the packed stream); the lines are formatted here, on the
  * host, from the downloaded counters, a chunk at a time -- the one table of a selection 2^20 counters at a time, the tables of --per-record
  * in calls of as many records as give 2^22 counters. */
@@ -883,7 +987,7 @@ int main(int argc, char **argv)
     bool large = out_type == IDS || out_type == NAMES || out_type == LENGTHS || out_type == MASK || out_type == FOUR_BIT || out_type == DNA ||
                  out_type == MASKED_DNA || out_type == UNMASKED_DNA || out_type == SEQ || out_type == FASTA || out_type == MASKED_FASTA ||
                  out_type == UNMASKED_FASTA || out_type == FASTQ;
-    if (large && !n_locate && !composition && !quality && !runs_class && !masked_runs && !kmers_k && !force_stdout && isatty(fileno(OUT)))
+    if (large && !n_locate && !composition && !quality && !runs_class && !masked_runs && !kmers_k && !orfs && !force_stdout && isatty(fileno(OUT)))
         die("output file not specified - please either specify output file with '-o' or '>', or use '-c' option to force writing to console\n");
 
     unsigned long long N = H.n_sequences;
@@ -903,6 +1007,10 @@ int main(int argc, char **argv)
     else if (kmers_k) {
         if (H.seq_type >= NAF_SEQ_PROTEIN) die("k-mers cannot be counted in %s sequences\n", tn[H.seq_type]);
         run_kmers(has_ids, has_names);
+    }
+    else if (orfs) {
+        if (H.seq_type >= NAF_SEQ_PROTEIN) die("open reading frames cannot be listed in %s sequences\n", tn[H.seq_type]);
+        run_orfs(has_ids, has_names);
     }
     else if (n_selections) {
         if (out_type == FASTQ && !has_quality) die("FASTQ output requested, but input has no qualities\n");
