@@ -74,7 +74,7 @@ int         naf_gpu_reserve(naf_gpu_ctx *ctx, size_t bytes);
 int  naf_gpu_malloc(naf_gpu_ctx *ctx, size_t bytes, void **d_ptr);
 int  naf_gpu_free(naf_gpu_ctx *ctx, void *d_ptr);
 /* free / total device memory as the runtime sees it now (the hosts size their chunks of an input larger than HBM with it);
- * the scratch arena of the context counts as used: naf_gpu_release_scratch gives it back */
+ * the scratch arenas of the context (its own and those of its side chains) count as used: naf_gpu_release_scratch gives them back */
 int  naf_gpu_mem_info(naf_gpu_ctx *ctx, size_t *free_bytes, size_t *total_bytes);
 int  naf_gpu_release_scratch(naf_gpu_ctx *ctx);
 int  naf_gpu_host_alloc(naf_gpu_ctx *ctx, size_t bytes, void **h_pinned);

@@ -242,6 +242,12 @@ def load():
         L.naf_gpu_read_file.argtypes = [vp, i, C.c_uint64, sz, vp]
         L.naf_gpu_write_fd.argtypes = [vp, i, vp, sz]
         L.naf_gpu_release_scratch.argtypes = [vp]
+        L.naf_gpu_mem_info.argtypes = [vp, C.POINTER(sz), C.POINTER(sz)]
+        L.naf_gpu_host_alloc.argtypes = [vp, sz, C.POINTER(vp)]
+        L.naf_gpu_host_free.argtypes = [vp, vp]
+        L.naf_gpu_upload.argtypes = [vp, vp, vp, sz]
+        L.naf_gpu_download.argtypes = [vp, vp, vp, sz]
+        L.naf_gpu_download_async.argtypes = [vp, vp, vp, sz]
         L.naf_gpu_get_timing_streams.argtypes = [vp, C.POINTER(C.c_float)]
         L.naf_gpu_gather_ranges.argtypes = [vp, vp, C.POINTER(vp), C.POINTER(vp), u64p, C.POINTER(sz), i]
         L.naf_gpu_set_option.argtypes = [vp, C.c_char_p, C.c_char_p]
@@ -570,8 +576,52 @@ class Context:
         self._check(self.L.naf_gpu_write_file(self.h, int(fd), C.c_uint64(int(file_off)), _ptr(t), int(t.numel())))
 
     def release_scratch(self):
-        """Give the context's scratch arena back to the device (the next call grows it again)."""
+        """Give the context's scratch arenas back to the device (the next call grows them again)."""
         self._check(self.L.naf_gpu_release_scratch(self.h))
+
+    def set_stream(self, stream):
+        """naf_gpu_set_stream: a torch.cuda.Stream, a raw hipStream_t as an int, or None for HIP's null stream."""
+        s = getattr(stream, "cuda_stream", stream)
+        self._check(self.L.naf_gpu_set_stream(self.h, C.c_void_p(s or None)))
+
+    def mem_info(self):
+        """(free, total) bytes of the device as the runtime sees them now (naf_gpu_mem_info)."""
+        fr, tot = C.c_size_t(), C.c_size_t()
+        self._check(self.L.naf_gpu_mem_info(self.h, C.byref(fr), C.byref(tot)))
+        return fr.value, tot.value
+
+    def host_alloc(self, nbytes):
+        """naf_gpu_host_alloc: the address of nbytes of pinned host memory (host_free gives it back)."""
+        p = C.c_void_p()
+        self._check(self.L.naf_gpu_host_alloc(self.h, int(nbytes), C.byref(p)))
+        return p.value
+
+    def host_free(self, addr):
+        self._check(self.L.naf_gpu_host_free(self.h, C.c_void_p(addr)))
+
+    def upload(self, t, h_src, nbytes):
+        """naf_gpu_upload: nbytes from host address h_src into device tensor t, asynchronous on the stream."""
+        self._check(self.L.naf_gpu_upload(self.h, _ptr(t), C.c_void_p(h_src), int(nbytes)))
+
+    def download(self, h_dst, t, nbytes):
+        """naf_gpu_download: nbytes of device tensor t to host address h_dst; returns after completion."""
+        self._check(self.L.naf_gpu_download(self.h, C.c_void_p(h_dst), _ptr(t), int(nbytes)))
+
+    def download_async(self, h_pinned, t, nbytes):
+        """naf_gpu_download_async: the same into pinned memory without waiting; pair with synchronize()."""
+        self._check(self.L.naf_gpu_download_async(self.h, C.c_void_p(h_pinned), _ptr(t), int(nbytes)))
+
+    def copy(self, dst, src, nbytes):
+        """naf_gpu_copy: device to device, asynchronous on the stream."""
+        self._check(self.L.naf_gpu_copy(self.h, _ptr(dst), _ptr(src), int(nbytes)))
+
+    def read_file(self, fd, file_off, t, nbytes=None):
+        """naf_gpu_read_file: bytes [file_off, file_off + nbytes) of descriptor fd (a regular file) into device tensor t."""
+        self._check(self.L.naf_gpu_read_file(self.h, int(fd), C.c_uint64(int(file_off)), int(t.numel() if nbytes is None else nbytes), _ptr(t)))
+
+    def write_fd(self, fd, t):
+        """naf_gpu_write_fd: the bytes of device tensor t to a descriptor that is written in order (a pipe, an O_APPEND file)."""
+        self._check(self.L.naf_gpu_write_fd(self.h, int(fd), _ptr(t), int(t.numel())))
 
     def gather_ranges(self, out, parts):
         """naf_gpu_gather_ranges: parts = [(ctx, tensor, dst_offset)] -- every part is pushed into `out` (a tensor on this context's

@@ -299,10 +299,16 @@ extern "C" int naf_gpu_mem_info(naf_gpu_ctx *c, size_t *free_bytes, size_t *tota
 extern "C" int naf_gpu_release_scratch(naf_gpu_ctx *c)
 {
     if (!c) return NAF_GPU_EARG;
-    hipStreamSynchronize(c->stream);
+    HIP_TRY(c, hipSetDevice(c->device));
+    int rc = ctx_sides_ready(c); if (rc) return rc;
     ennaf_shard_state_free(c);                                    // a shard between its begin and its finish lives in the arena
-    for (auto &ch : c->chunks) hipFree(ch.base);
-    c->chunks.clear();
+    // the side contexts' arenas too (naf_gpu_reserve gave each an eighth, a whole call grew them): between calls nothing of theirs is live
+    for (naf_gpu_ctx *x : { c, c->side, c->side2, c->side3, c->side4 }) {
+        if (!x) continue;
+        hipStreamSynchronize(x->stream);
+        for (auto &ch : x->chunks) hipFree(ch.base);
+        x->chunks.clear();
+    }
     return 0;
 }
 static int reserve_one(naf_gpu_ctx *c, size_t bytes);
