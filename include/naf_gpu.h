@@ -456,7 +456,7 @@ int  naf_gpu_unnaf_kmers(naf_gpu_ctx *ctx, const void *d_naf, size_t naf_len, un
 
 /* ---- unnaf: open reading frames on the six frames of every record, listed from the packed stream --------------------
  * What getorf, NCBI ORFfinder, orfipy and seqkit translate -F answer from the text -- where the open reading frames lie -- as a table of
- * (record, begin, end, strand) rows, made without expanding the codes.  Nothing is translated to amino acids.
+ * (record, begin, end, strand) rows, made without expanding the codes.  The rows feed naf_gpu_unnaf_translate, which writes their proteins.
  *   Codon set   a uint64_t: bit i is the codon whose index is i under naf_gpu_kmer_index at K = 3 (A = 0, C = 1, G = 2, T/U = 3, the first
  *               base the most significant): TAA = 48, TAG = 50, TGA = 56, ATG = 14.  naf_gpu_parse_codon_set takes comma-separated
  *               three-letter codons, either case, U = T; the IUPAC letters RYSWKM BDHV N expand ("TAR,TGA" is the three standard
@@ -508,6 +508,44 @@ int  naf_gpu_unnaf_orfs_count(naf_gpu_ctx *ctx, const void *d_naf, size_t naf_le
                               uint64_t first, uint64_t count, uint64_t *n_orfs, uint64_t *n_bases, uint64_t per_frame[6]);
 int  naf_gpu_unnaf_orfs(naf_gpu_ctx *ctx, const void *d_naf, size_t naf_len, uint64_t stops, uint64_t starts, uint64_t min_len, int strands, int flags,
                         uint64_t first, uint64_t count, naf_gpu_orf *d_orfs, size_t orf_cap, uint64_t *n_orfs, uint64_t *n_bases);
+
+/* ---- unnaf: segments and ORFs as protein, translated from the packed stream -------------------------------------------
+ * What the same tools print behind the table: the amino acids of a list of segments -- ORF rows, locate hits, runs, frames of whole
+ * records -- without the nucleotide text ever being written.
+ *   Code        naf_gpu_genetic_code.aa[i] is the letter of the codon whose index is i under naf_gpu_kmer_index at K = 3 (the codon sets'
+ *               order: ATG = 14, TAA = 48, TGA = 56); '*' is a stop.  naf_gpu_genetic_code_by_id knows NCBI's tables 1 .. 6, 9 .. 16 and
+ *               21 .. 26; naf_gpu_genetic_code_parse takes 64 letters 'A' .. 'Z' or '*', either case, in that index order (NOT NCBI's TCAG
+ *               order).  Another id, a NULL, a string of another length or with another character is NAF_GPU_EARG, and nothing is written
+ *               then.  naf_gpu_genetic_code_stops gives the codon set of the '*' letters: what naf_gpu_unnaf_orfs takes as stops.
+ *   Table       naf_gpu_codon_lut: 4096 letters, index (c0 << 8) | (c1 << 4) | c2 of the stored codes of "-TGKCYSBAWRDMHVN" in reading
+ *               order.  Three of A, C, G, T/U: aa[..].  No gap and an ambiguity code: the letter all expansions share (GCN is A, TAR is
+ *               '*'), else 'X'.  Three gaps: '-'.  Any other codon with a gap: 'X'.  Upper case always; the mask is never decoded.
+ *   Segments    segs and strand are HOST arrays with the meaning they have in naf_gpu_unnaf_select_stranded (strand may be NULL), and the
+ *               same errors with the segment named in last_error: a record that is not there, begin >= end after clamping unless the
+ *               segment is a whole record, a strand byte other than 0 and 1.
+ *   Text        always FASTA-shaped; of opts only line_length is used.  Per segment, in the order given: the header line that
+ *               naf_gpu_unnaf_select_stranded writes for it in FASTA mode (">id:a-b", ">id:a-b/rc", a whole record's stored header, or
+ *               that with "/rc"), then floor(n / 3) letters read from the segment's first base in reading direction -- on strand 1 the
+ *               first codon is the reverse complement of forward bases [end - 3, end) --, wrapped at the line length counted in letters
+ *               (0: one line) with a final newline.  One or two trailing bases are dropped; fewer than three bases give the header line
+ *               alone.  Stops are '*' and nothing is trimmed.
+ *   Archives    DNA and RNA (U is stored as T: the same letters), with or without qualities (the header character is '>').  Protein and
+ *               text archives and archives that store no sequence are NAF_GPU_EARG.
+ *   Outputs     n_segs = 0 gives *out_len = 0.  With out_cap too small the call returns NAF_GPU_ECAP, sets *out_len to the whole size and
+ *               writes nothing; otherwise exactly *out_len bytes are written.  Only the zstd blocks behind the segments are decoded.
+ * TRACE=1: "[translate] segments S codons C ranges R sequence bytes decoded X of Y" per call that reaches the records. */
+typedef struct { char aa[64]; } naf_gpu_genetic_code;
+
+/* host only, no device */
+int  naf_gpu_genetic_code_by_id(int ncbi_id, naf_gpu_genetic_code *code);
+int  naf_gpu_genetic_code_parse(const char *letters64, naf_gpu_genetic_code *code);
+int  naf_gpu_genetic_code_stops(const naf_gpu_genetic_code *code, uint64_t *stops);
+int  naf_gpu_codon_lut(const naf_gpu_genetic_code *code, uint8_t lut[4096]);
+
+int  naf_gpu_unnaf_translate_size(naf_gpu_ctx *ctx, const void *d_naf, size_t naf_len, const naf_gpu_unnaf_opts *opts, const naf_gpu_genetic_code *code,
+                                  const naf_gpu_segment *segs, const uint8_t *strand, size_t n_segs, size_t *out_len);
+int  naf_gpu_unnaf_translate(naf_gpu_ctx *ctx, const void *d_naf, size_t naf_len, const naf_gpu_unnaf_opts *opts, const naf_gpu_genetic_code *code,
+                             const naf_gpu_segment *segs, const uint8_t *strand, size_t n_segs, void *d_out, size_t out_cap, size_t *out_len);
 
 /* ---- ennaf ------------------------------------------------------------------------------------------ */
 typedef struct {

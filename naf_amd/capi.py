@@ -36,6 +36,8 @@ EXPORTS = [
     "naf_gpu_parse_base_class", "naf_gpu_unnaf_runs_count", "naf_gpu_unnaf_runs",
     "naf_gpu_kmer_index", "naf_gpu_kmer_text", "naf_gpu_unnaf_kmers_rows", "naf_gpu_unnaf_kmers",
     "naf_gpu_parse_codon_set", "naf_gpu_unnaf_orfs_count", "naf_gpu_unnaf_orfs",
+    "naf_gpu_genetic_code_by_id", "naf_gpu_genetic_code_parse", "naf_gpu_genetic_code_stops", "naf_gpu_codon_lut",
+    "naf_gpu_unnaf_translate_size", "naf_gpu_unnaf_translate",
 ]
 WHOLE = 2 ** 64 - 1                     # NAF_GPU_WHOLE: (record, 0, WHOLE) is the record as stored
 MAX_SHARDS = 64
@@ -90,6 +92,15 @@ class StitchSeg(C.Structure):
 class Segment(C.Structure):
     """naf_gpu_segment: bases [begin, end) of a record, 0-based."""
     _fields_ = [("record", C.c_uint64), ("begin", C.c_uint64), ("end", C.c_uint64)]
+
+
+class GeneticCode(C.Structure):
+    """naf_gpu_genetic_code: aa[i] is the letter of the codon of index i under kmer_index at K = 3 (AAA AAC AAG AAT ACA ...); '*' = stop."""
+    _fields_ = [("aa", C.c_char * 64)]
+
+    @property
+    def letters(self):
+        return bytes(self.aa).decode("latin1")
 
 
 class Hit(C.Structure):
@@ -287,6 +298,12 @@ def load():
         L.naf_gpu_unnaf_orfs_count.argtypes = [vp, vp, sz, C.c_uint64, C.c_uint64, C.c_uint64, i, i, C.c_uint64, C.c_uint64, u64p, u64p, u64p]
         L.naf_gpu_unnaf_orfs.argtypes = [vp, vp, sz, C.c_uint64, C.c_uint64, C.c_uint64, i, i, C.c_uint64, C.c_uint64, vp, sz, u64p, u64p]
         L.naf_gpu_unnaf_kmers.argtypes = [vp, vp, sz, C.c_uint, i, C.c_uint64, C.c_uint64, vp, sz, vp, sz, u64p, u64p, C.POINTER(KmerRow)]
+        L.naf_gpu_genetic_code_by_id.argtypes = [i, C.POINTER(GeneticCode)]
+        L.naf_gpu_genetic_code_parse.argtypes = [C.c_char_p, C.POINTER(GeneticCode)]
+        L.naf_gpu_genetic_code_stops.argtypes = [C.POINTER(GeneticCode), u64p]
+        L.naf_gpu_codon_lut.argtypes = [C.POINTER(GeneticCode), u8p]
+        L.naf_gpu_unnaf_translate_size.argtypes = [vp, vp, sz, C.POINTER(UnnafOpts), C.POINTER(GeneticCode), C.POINTER(Segment), u8p, sz, C.POINTER(sz)]
+        L.naf_gpu_unnaf_translate.argtypes = [vp, vp, sz, C.POINTER(UnnafOpts), C.POINTER(GeneticCode), C.POINTER(Segment), u8p, sz, vp, sz, C.POINTER(sz)]
         _lib = L
     return _lib
 
@@ -393,6 +410,64 @@ def parse_codon_set(text):
     if load().naf_gpu_parse_codon_set(b, C.byref(s)):
         raise ValueError("not a list of codons: %r" % (text,))
     return s.value
+
+
+def genetic_code(id_or_letters=1):
+    """Host-only: a GeneticCode from an NCBI table number (naf_gpu_genetic_code_by_id: 1 .. 6, 9 .. 16, 21 .. 26) or from 64 letters A .. Z
+    or '*' in the order AAA AAC AAG AAT ACA ... TTT (naf_gpu_genetic_code_parse); a GeneticCode is returned as it is.  ValueError for
+    anything else."""
+    if isinstance(id_or_letters, GeneticCode):
+        return id_or_letters
+    g = GeneticCode()
+    if isinstance(id_or_letters, int) and not isinstance(id_or_letters, bool):
+        if not -2 ** 31 <= id_or_letters < 2 ** 31 or load().naf_gpu_genetic_code_by_id(id_or_letters, C.byref(g)):
+            raise ValueError("not a genetic code: %r" % (id_or_letters,))
+        return g
+    if not isinstance(id_or_letters, (str, bytes)):
+        raise ValueError("not a genetic code: %r" % (id_or_letters,))
+    b = id_or_letters.encode("latin1") if isinstance(id_or_letters, str) else bytes(id_or_letters)
+    if b"\0" in b or load().naf_gpu_genetic_code_parse(b, C.byref(g)):
+        raise ValueError("not a genetic code: %r" % (id_or_letters,))
+    return g
+
+
+def codon_lut(code=1):
+    """Host-only: the 4096 letters of naf_gpu_codon_lut as bytes -- index (c0 << 8) | (c1 << 4) | c2 of the stored 4-bit codes of
+    "-TGKCYSBAWRDMHVN" in reading order."""
+    g = genetic_code(code)
+    out = (C.c_uint8 * 4096)()
+    if load().naf_gpu_codon_lut(C.byref(g), out):
+        raise ValueError("not a genetic code: %r" % (code,))
+    return bytes(out)
+
+
+def genetic_code_stops(code=1):
+    """Host-only: the codon set of a code's stops (naf_gpu_genetic_code_stops), as unnaf_orfs takes it."""
+    g = genetic_code(code)
+    s = C.c_uint64()
+    if load().naf_gpu_genetic_code_stops(C.byref(g), C.byref(s)):
+        raise ValueError("not a genetic code: %r" % (code,))
+    return s.value
+
+
+def frames_to_segments(lengths, frames, records=None):
+    """The (record, begin, end, reverse) tuples unnaf_translate takes for the reading frames `frames` (out of 1, 2, 3, -1, -2, -3) of whole
+    records: `lengths` are the records' lengths from record 0 on, `records` the record numbers to take (None: all), and the frames of one
+    record stand side by side in the order listed.  Frame f > 0 is the record from base f - 1 on; frame -f its reverse complement from
+    base f - 1 on, which is forward bases [0, length - (f - 1)) with reverse = 1 (ORFfinder's and seqkit's numbering, as in unnaf_orfs).
+    Frames 1 and -1 are the whole record, (record, 0, WHOLE, reverse); a frame that has no base is left out."""
+    out = []
+    for r in (range(len(lengths)) if records is None else records):
+        n = int(lengths[r])
+        for f in frames:
+            if f not in (1, 2, 3, -1, -2, -3):
+                raise ValueError("not a reading frame: %r" % (f,))
+            skip = abs(f) - 1
+            if skip == 0:
+                out.append((r, 0, WHOLE, 1 if f < 0 else 0))
+            elif skip < n:
+                out.append((r, skip, n, 0) if f > 0 else (r, 0, n - skip, 1))
+    return out
 
 
 def orfs_to_segments(rows, include_stop=False):
@@ -745,6 +820,29 @@ class Context:
             self._check(self.L.naf_gpu_unnaf_select(self.h, _ptr(d_naf), d_naf.numel(), C.byref(o), segs, len(segments), _ptr(out), out.numel(), C.byref(n)))
         else:
             self._check(self.L.naf_gpu_unnaf_select_stranded(self.h, _ptr(d_naf), d_naf.numel(), C.byref(o), segs, strands, len(segments), _ptr(out), out.numel(), C.byref(n)))
+        return out[:n.value]
+
+    def unnaf_translate_size(self, d_naf, segments, code=1, line_length=-1):
+        o = UnnafOpts(OUT_FASTA, 0, line_length)
+        g = genetic_code(code)
+        n = C.c_size_t()
+        self._check(self.L.naf_gpu_unnaf_translate_size(self.h, _ptr(d_naf), d_naf.numel(), C.byref(o), C.byref(g), self._segments(segments), self._strands(segments), len(segments), C.byref(n)))
+        return n.value
+
+    def unnaf_translate(self, d_naf, segments, code=1, line_length=-1, out=None):
+        """The segments as protein FASTA (naf_gpu_unnaf_translate): per segment -- as unnaf_select takes them, 4-tuples for strands -- the
+        header line unnaf_select writes in FASTA mode, then floor(bases / 3) letters read from the segment's first base in reading
+        direction, wrapped at line_length letters (-1: the archive's line length, 0: one line).  code: an NCBI table number, 64 letters or
+        a GeneticCode."""
+        import torch
+        o = UnnafOpts(OUT_FASTA, 0, line_length)
+        g = genetic_code(code)
+        segs, strands = self._segments(segments), self._strands(segments)
+        n = C.c_size_t()
+        if out is None:
+            self._check(self.L.naf_gpu_unnaf_translate_size(self.h, _ptr(d_naf), d_naf.numel(), C.byref(o), C.byref(g), segs, strands, len(segments), C.byref(n)))
+            out = torch.empty(max(n.value, 1), dtype=torch.uint8, device=self.device)
+        self._check(self.L.naf_gpu_unnaf_translate(self.h, _ptr(d_naf), d_naf.numel(), C.byref(o), C.byref(g), segs, strands, len(segments), _ptr(out), out.numel(), C.byref(n)))
         return out[:n.value]
 
     @staticmethod

@@ -15,6 +15,9 @@
 // composer loads the 16 forward bases (or quality bytes) that end where the chunk begins, expands and masks them at their forward
 // positions -- a base keeps its own case -- and turns the 16 bytes round in registers (k_emit_select<true, true>, launched only for a
 // call that holds such a segment).  Everything on the host, the decoded blocks among it, is the same for both strands.
+//
+// The same front serves the translation (translate.h: naf_gpu_unnaf_translate): select_run takes the bases to a byte of the body (1, or 3 for
+// amino acids) and the launch of the kernel that writes the text; everything in front of that launch is one code for both.
 #pragma once
 #include <algorithm>
 
@@ -37,7 +40,8 @@ __device__ __forceinline__ u32 dec_digits(u64 v) { u32 n = 1; while (v >= 10) { 
 
 // One lane per segment: validation, geometry, text size.  status[0] receives the number of the first segment that cannot be
 // produced (atomicMin; ~0 = none).  size[] / hsize[] are scanned into the text offsets and the header stream offsets.
-__global__ __launch_bounds__(256) void k_select_layout(EmitP P, const naf_gpu_segment *in, const u8 *strand, u64 S, SelSeg *sg, u64 *size, u64 *hsize, u64 *iv, unsigned long long *status)
+// per: bases per byte of the body, 1 for the bases themselves, 3 for their translation (translate.h; FASTA only): the wrap counts the bytes.
+__global__ __launch_bounds__(256) void k_select_layout(EmitP P, const naf_gpu_segment *in, const u8 *strand, u64 S, u32 per, SelSeg *sg, u64 *size, u64 *hsize, u64 *iv, unsigned long long *status)
 {
     const u64 s = (u64)blockIdx.x * 256 + threadIdx.x;
     if (s >= S) return;
@@ -60,7 +64,7 @@ __global__ __launch_bounds__(256) void k_select_layout(EmitP P, const naf_gpu_se
     if (P.mode == EM_FASTQ) body = 2 * g.n + 4;
     else if (P.mode == EM_SEQUENCES) body = g.n + 1;
     else if (P.mode == EM_SEQ) body = g.n;
-    else body = g.n ? g.n + (P.L ? (g.n + P.L - 1) / P.L : 1) : 0;                 // as rec_size_of
+    else { const u64 nb = per == 1 ? g.n : g.n / per; body = nb ? nb + (P.L ? (nb + P.L - 1) / P.L : 1) : 0; }   // as rec_size_of
     if (P.masking) { g.klo = upper_bound_u64(P.toggles, 0, P.n_toggles, g.g0); g.khi = upper_bound_u64(P.toggles, g.klo, P.n_toggles, g.g0 + g.n); }
     size[s] = h + body; hsize[s] = h;
     iv[2 * s] = g.g0; iv[2 * s + 1] = g.g0 + g.n;
@@ -414,9 +418,30 @@ extern "C" int naf_gpu_unnaf_record_table(naf_gpu_ctx *c, const void *d_naf, siz
     return 0;
 }
 
-// h_strand: one byte per segment, 1 = its reverse complement; nullptr = none
+// What the kernel that writes a selection's text is launched with: the tables select_run made, every segment bound to its decoded range.
+struct SelCall {
+    UnnafPlan &pl; const SelSeg *sg; const u64 *seg_out; u64 S; const u8 *hdr_text; u64 total; u8 *d_out;
+    bool any_rc; size_t ranges; u64 decoded, letters;                            // letters: the sum of floor(bases / per) over the segments
+};
+// The text of naf_gpu_unnaf_select: the bases (or bytes) themselves
+static int select_emit(naf_gpu_ctx *c, const SelCall &k)
+{
+    const EmitP &P = k.pl.P;
+    const u32 grid = cdiv(k.total, 4096);
+    if (k.any_rc) LAUNCH(c, "unnaf_emit_select_rc", (k_emit_select<true, true>), grid, 64, 0, P, k.sg, k.seg_out, k.S, k.hdr_text, k.total, k.d_out);
+    else if (k.pl.fourbit) LAUNCH(c, "unnaf_emit_select", k_emit_select<true>, grid, 64, 0, P, k.sg, k.seg_out, k.S, k.hdr_text, k.total, k.d_out);
+    else LAUNCH(c, "unnaf_emit_select", k_emit_select<false>, grid, 64, 0, P, k.sg, k.seg_out, k.S, k.hdr_text, k.total, k.d_out);
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipStreamSynchronize(c->stream));                                 // (the uploaded range table is this call's)
+    if (ctx_tracing(c)) ctx_trace(c, "[select] segments %zu ranges %zu sequence bytes decoded %llu of %llu side sections 1\n", (size_t)k.S, k.ranges, (unsigned long long)k.decoded, (unsigned long long)k.pl.seq_bytes);
+    return 0;
+}
+
+// h_strand: one byte per segment, 1 = its reverse complement; nullptr = none.  per, emit: 1 and select_emit; 3 and translate.h's for the
+// translation, which is FASTA-shaped whatever the archive and needs a 4-bit stream.
+template <typename Emit>
 static int select_run(naf_gpu_ctx *c, const u8 *d_naf, size_t naf_len, const naf_gpu_unnaf_opts *o, const naf_gpu_segment *h_segs, const u8 *h_strand, size_t S,
-                      u8 *d_out, size_t out_cap, size_t *out_len, bool size_only)
+                      u8 *d_out, size_t out_cap, size_t *out_len, bool size_only, u32 per, Emit emit)
 {
     if (!c || !d_naf || !o || !out_len || (S && !h_segs)) return NAF_GPU_EARG;
     arena_reset(c);
@@ -429,6 +454,10 @@ static int select_run(naf_gpu_ctx *c, const u8 *d_naf, size_t naf_len, const naf
     const bool any_rc = first_rc < S;
     UnnafPlan pl;
     int rc = select_tables(c, d_naf, naf_len, o, pl); if (rc) return rc;
+    if (per != 1) {
+        if (!pl.fourbit) return ctx_fail(c, NAF_GPU_EARG, "translate: %s sequences cannot be translated", pl.h.seq_type == NAF_SEQ_PROTEIN ? "protein" : "text");
+        if (!((pl.h.flags >> 1) & 1)) return ctx_fail(c, NAF_GPU_EARG, "translate: the archive stores no sequence");
+    }
     if (any_rc && !pl.fourbit) return ctx_fail(c, NAF_GPU_EARG, "segment %zu: a %s sequence has no reverse complement", first_rc, pl.h.seq_type == NAF_SEQ_PROTEIN ? "protein" : "text");
     if (S == 0) return 0;
     const naf_gpu_header &h = pl.h;
@@ -449,7 +478,7 @@ static int select_run(naf_gpu_ctx *c, const u8 *d_naf, size_t naf_len, const naf
     HIP_TRY(c, hipMemsetAsync(d_status, 0xFF, 8, c->stream));
     HIP_TRY(c, hipMemsetAsync(seg_out + S, 0, 8, c->stream));
     HIP_TRY(c, hipMemsetAsync(hoff + S, 0, 8, c->stream));
-    LAUNCH(c, "unnaf_select_layout", k_select_layout, cdiv(S, 256), 256, 0, P, (const naf_gpu_segment *)d_in, (const u8 *)d_strand, (u64)S, sg, seg_out, hoff, iv, d_status);
+    LAUNCH(c, "unnaf_select_layout", k_select_layout, cdiv(S, 256), 256, 0, P, (const naf_gpu_segment *)d_in, (const u8 *)d_strand, (u64)S, per, sg, seg_out, hoff, iv, d_status);
     if ((rc = scan_exclusive_u64(c, seg_out, S + 1, (u64 *)nullptr))) return rc;
     if ((rc = scan_exclusive_u64(c, hoff, S + 1, (u64 *)nullptr))) return rc;
     u64 first_bad = 0, total = 0, htotal = 0;
@@ -473,7 +502,8 @@ static int select_run(naf_gpu_ctx *c, const u8 *d_naf, size_t naf_len, const naf
     std::vector<std::pair<u64, u64>> ivs(S);
     HIP_TRY(c, hipMemcpyAsync(ivs.data(), iv, S * 16, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
-    { size_t k = 0; for (size_t i = 0; i < S; i++) if (ivs[i].second > ivs[i].first) ivs[k++] = ivs[i]; ivs.resize(k); }
+    u64 letters = 0;
+    { size_t k = 0; for (size_t i = 0; i < S; i++) { letters += (ivs[i].second - ivs[i].first) / per; if (ivs[i].second > ivs[i].first) ivs[k++] = ivs[i]; } ivs.resize(k); }
     std::sort(ivs.begin(), ivs.end());
     const u64 per_byte = pl.fourbit ? 2 : 1;
     std::vector<std::pair<u64, u64>> rgs;
@@ -506,37 +536,30 @@ static int select_run(naf_gpu_ctx *c, const u8 *d_naf, size_t naf_len, const naf
         HIP_TRY(c, hipMemcpyAsync(d_rg, hr.data(), hr.size() * sizeof(SelRange), hipMemcpyHostToDevice, c->stream));
         LAUNCH(c, "unnaf_select_bind", k_select_bind, cdiv(S, 256), 256, 0, sg, (u64)S, (const SelRange *)d_rg, (u32)hr.size());
     }
-    const u32 grid = cdiv(total, 4096);
-    if (any_rc) LAUNCH(c, "unnaf_emit_select_rc", (k_emit_select<true, true>), grid, 64, 0, P, (const SelSeg *)sg, (const u64 *)seg_out, (u64)S, (const u8 *)hdr_text, total, d_out);
-    else if (pl.fourbit) LAUNCH(c, "unnaf_emit_select", k_emit_select<true>, grid, 64, 0, P, (const SelSeg *)sg, (const u64 *)seg_out, (u64)S, (const u8 *)hdr_text, total, d_out);
-    else LAUNCH(c, "unnaf_emit_select", k_emit_select<false>, grid, 64, 0, P, (const SelSeg *)sg, (const u64 *)seg_out, (u64)S, (const u8 *)hdr_text, total, d_out);
-    HIP_TRY(c, hipGetLastError());
-    HIP_TRY(c, hipStreamSynchronize(c->stream));                                 // (hr, the uploaded table, is this call's)
-    if (ctx_tracing(c)) ctx_trace(c, "[select] segments %zu ranges %zu sequence bytes decoded %llu of %llu side sections 1\n", S, hr.size(), (unsigned long long)decoded, (unsigned long long)pl.seq_bytes);
-    return 0;
+    return emit(c, SelCall{ pl, sg, seg_out, (u64)S, hdr_text, total, d_out, any_rc, hr.size(), decoded, letters });
 }
 
 extern "C" int naf_gpu_unnaf_select_size(naf_gpu_ctx *c, const void *d_naf, size_t naf_len, const naf_gpu_unnaf_opts *o,
                                          const naf_gpu_segment *segs, size_t n_segs, size_t *out_len)
 {
-    return select_run(c, (const u8 *)d_naf, naf_len, o, segs, nullptr, n_segs, nullptr, 0, out_len, true);
+    return select_run(c, (const u8 *)d_naf, naf_len, o, segs, nullptr, n_segs, nullptr, 0, out_len, true, 1, select_emit);
 }
 extern "C" int naf_gpu_unnaf_select(naf_gpu_ctx *c, const void *d_naf, size_t naf_len, const naf_gpu_unnaf_opts *o,
                                     const naf_gpu_segment *segs, size_t n_segs, void *d_out, size_t out_cap, size_t *out_len)
 {
-    int rc = select_run(c, (const u8 *)d_naf, naf_len, o, segs, nullptr, n_segs, (u8 *)d_out, out_cap, out_len, false);
+    int rc = select_run(c, (const u8 *)d_naf, naf_len, o, segs, nullptr, n_segs, (u8 *)d_out, out_cap, out_len, false, 1, select_emit);
     if (c) arena_settle(c);
     return rc;
 }
 extern "C" int naf_gpu_unnaf_select_stranded_size(naf_gpu_ctx *c, const void *d_naf, size_t naf_len, const naf_gpu_unnaf_opts *o,
                                                   const naf_gpu_segment *segs, const uint8_t *strand, size_t n_segs, size_t *out_len)
 {
-    return select_run(c, (const u8 *)d_naf, naf_len, o, segs, strand, n_segs, nullptr, 0, out_len, true);
+    return select_run(c, (const u8 *)d_naf, naf_len, o, segs, strand, n_segs, nullptr, 0, out_len, true, 1, select_emit);
 }
 extern "C" int naf_gpu_unnaf_select_stranded(naf_gpu_ctx *c, const void *d_naf, size_t naf_len, const naf_gpu_unnaf_opts *o,
                                              const naf_gpu_segment *segs, const uint8_t *strand, size_t n_segs, void *d_out, size_t out_cap, size_t *out_len)
 {
-    int rc = select_run(c, (const u8 *)d_naf, naf_len, o, segs, strand, n_segs, (u8 *)d_out, out_cap, out_len, false);
+    int rc = select_run(c, (const u8 *)d_naf, naf_len, o, segs, strand, n_segs, (u8 *)d_out, out_cap, out_len, false, 1, select_emit);
     if (c) arena_settle(c);
     return rc;
 }

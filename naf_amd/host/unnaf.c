@@ -37,6 +37,9 @@ static unsigned kmers_k = 0; static bool kmers_canonical = false, kmers_per_reco
 static bool orfs = false, min_orf_given = false, stop_to_stop = false, orfs_closed = false, orfs_split = false;
 static const char *orf_stops_text = NULL, *orf_starts_text = NULL; static uint64_t orf_stops = 0, orf_starts = 0;
 static unsigned long long min_orf = 75;
+/* --translate [--frame LIST] [--code N | --code-table LETTERS64]: the selection's frames, or with --orfs every reading frame, as protein FASTA (this implementation only) */
+static bool translate = false; static int frames[6] = { 1 }; static size_t n_frames = 1;
+static const char *frame_text = NULL, *code_text = NULL, *code_table_text = NULL; static naf_gpu_genetic_code genetic_code;
 
 static void done(int status, void *arg)
 {
@@ -176,6 +179,37 @@ static void set_min_orf(const char *v)
     min_orf = a; min_orf_given = true;
 }
 
+static void set_frames(const char *v)
+{
+    if (frame_text) die("only one --frame list can be given\n");
+    frame_text = v; n_frames = 0;
+    if (!strcmp(v, "6")) { static const int all[6] = { 1, 2, 3, -1, -2, -3 }; memcpy(frames, all, sizeof all); n_frames = 6; return; }
+    for (const char *p = v; ; p++) {
+        const bool minus = *p == '-'; if (minus) p++;
+        if (*p < '1' || *p > '3' || (p[1] && p[1] != ',') || n_frames == 6) die("can't parse the value of --frame parameter (comma-separated frames out of 1,2,3,-1,-2,-3, or 6 for all six)\n");
+        const int f = minus ? -(*p - '0') : *p - '0';
+        for (size_t k = 0; k < n_frames; k++) if (frames[k] == f) die("can't parse the value of --frame parameter (comma-separated frames out of 1,2,3,-1,-2,-3, or 6 for all six)\n");
+        frames[n_frames++] = f;
+        if (!*++p) break;
+    }
+}
+static void set_code(const char *v)
+{
+    if (code_text) die("only one --code can be given\n");
+    int id = 0; bool ok = *v != 0;
+    for (const char *p = v; *p && ok; p++) { ok = *p >= '0' && *p <= '9' && id < 100; id = id * 10 + (*p - '0'); }
+    if (!ok || naf_gpu_genetic_code_by_id(id, &genetic_code)) die("can't parse the value of --code parameter (the number of an NCBI genetic code: 1 to 6, 9 to 16, 21 to 26)\n");
+    code_text = v;
+}
+static void set_code_table(const char *v)
+{
+    if (code_table_text) die("only one --code-table can be given\n");
+    naf_gpu_genetic_code g;
+    if (naf_gpu_genetic_code_parse(v, &g)) die("can't parse the value of --code-table parameter (64 letters A to Z or *, the codons in the order AAA AAC AAG AAT ACA ... TTT)\n");
+    code_table_text = v;
+    if (!code_text) genetic_code = g;                                /* (both given is refused later) */
+}
+
 static void show_help(void)
 {
     msg("Usage: unnaf [OUTPUT-TYPE] [file.naf]\n"
@@ -223,7 +257,14 @@ static void show_help(void)
         "  --stop-to-stop  - With --orfs: the whole stretch between two stops, whether it has a start codon or not\n"
         "  --closed        - With --orfs: only reading frames that end in a stop codon, none that run into the end of the sequence\n"
         "  --split-unknown - With --orfs: a codon with N or another ambiguity code ends a reading frame\n"
-        "  --strand +|-|both - With --orfs: the sequences as stored, their reverse complement, or both (default)\n");
+        "  --strand +|-|both - With --orfs: the sequences as stored, their reverse complement, or both (default)\n"
+        "Options for translating (output: protein FASTA, headers as --region and --rc-region write them, stops as *, X for a codon that is not determined;\n"
+        "    with any number of --records, --region, --rc-region; without one, every sequence):\n"
+        "  --translate     - The amino acids of every selected sequence or region, read from its first base; one or two trailing bases are dropped.\n"
+        "                    With --orfs: the protein of every reading frame of the table, in the table's order, instead of the table\n"
+        "  --frame LIST    - With --translate: comma-separated frames out of 1,2,3,-1,-2,-3, or 6 for all six (default 1); -1..-3 count from the end, as in --orfs\n"
+        "  --code N        - With --translate: NCBI genetic code N (1 to 6, 9 to 16, 21 to 26; default 1). With --orfs and without --stops, its stops close the reading frames\n"
+        "  --code-table LETTERS - With --translate: a genetic code of its own, 64 letters A-Z or * for the codons AAA AAC AAG AAT ACA ... TTT\n");
 }
 
 static void parse_command_line(int argc, char **argv)
@@ -236,7 +277,7 @@ static void parse_command_line(int argc, char **argv)
         {"--fasta", FASTA}, {"--fastq", FASTQ}, {"--dna", DNA}, {"--masked-dna", MASKED_DNA}, {"--unmasked-dna", UNMASKED_DNA},
         {"--masked-fasta", MASKED_FASTA}, {"--unmasked-fasta", UNMASKED_FASTA} };
     /* the other options (unnaf/src/unnaf.c:282-353), as a table: one that takes a value is only recognised with an argument behind it */
-    enum { OP_LINE_LENGTH, OP_OUT, OP_NO_MASK, OP_IGNORED, OP_HELP, OP_VERBOSE, OP_VERSION, OP_STDOUT, OP_REGION, OP_RECORDS, OP_RC_REGION, OP_REVCOMP, OP_LOCATE, OP_STRAND, OP_MISMATCHES, OP_COMPOSITION, OP_WINDOW, OP_QUALITY, OP_CYCLES, OP_RUNS, OP_MASKED_RUNS, OP_MIN_RUN, OP_EACH, OP_KMERS, OP_CANONICAL, OP_PER_RECORD, OP_ORFS, OP_MIN_ORF, OP_STOPS, OP_STARTS, OP_STOP_TO_STOP, OP_CLOSED, OP_SPLIT_UNKNOWN };
+    enum { OP_LINE_LENGTH, OP_OUT, OP_NO_MASK, OP_IGNORED, OP_HELP, OP_VERBOSE, OP_VERSION, OP_STDOUT, OP_REGION, OP_RECORDS, OP_RC_REGION, OP_REVCOMP, OP_LOCATE, OP_STRAND, OP_MISMATCHES, OP_COMPOSITION, OP_WINDOW, OP_QUALITY, OP_CYCLES, OP_RUNS, OP_MASKED_RUNS, OP_MIN_RUN, OP_EACH, OP_KMERS, OP_CANONICAL, OP_PER_RECORD, OP_ORFS, OP_MIN_ORF, OP_STOPS, OP_STARTS, OP_STOP_TO_STOP, OP_CLOSED, OP_SPLIT_UNKNOWN, OP_TRANSLATE, OP_FRAME, OP_CODE, OP_CODE_TABLE };
     static const struct { const char *name; int op; bool value; } option_table[] = {
         { "--line-length", OP_LINE_LENGTH, true }, { "-o", OP_OUT, true }, { "--no-mask", OP_NO_MASK, false }, { "--binary-stdout", OP_IGNORED, false },
         { "--binary-stderr", OP_IGNORED, false }, { "--binary", OP_IGNORED, false }, { "--help", OP_HELP, false }, { "-h", OP_HELP, false },
@@ -247,7 +288,8 @@ static void parse_command_line(int argc, char **argv)
         { "--runs", OP_RUNS, true }, { "--masked-runs", OP_MASKED_RUNS, false }, { "--min-run", OP_MIN_RUN, true }, { "--each", OP_EACH, false },
         { "--kmers", OP_KMERS, true }, { "--canonical", OP_CANONICAL, false }, { "--per-record", OP_PER_RECORD, false },
         { "--orfs", OP_ORFS, false }, { "--min-orf", OP_MIN_ORF, true }, { "--stops", OP_STOPS, true }, { "--starts", OP_STARTS, true }, { "--stop-to-stop", OP_STOP_TO_STOP, false },
-        { "--closed", OP_CLOSED, false }, { "--split-unknown", OP_SPLIT_UNKNOWN, false } };
+        { "--closed", OP_CLOSED, false }, { "--split-unknown", OP_SPLIT_UNKNOWN, false },
+        { "--translate", OP_TRANSLATE, false }, { "--frame", OP_FRAME, true }, { "--code", OP_CODE, true }, { "--code-table", OP_CODE_TABLE, true } };
     for (int i = 1; i < argc; i++) {
         char *arg = argv[i];
         if (arg[0] != '-') {
@@ -297,6 +339,10 @@ static void parse_command_line(int argc, char **argv)
         case OP_STOP_TO_STOP: stop_to_stop = true; break;
         case OP_CLOSED: orfs_closed = true; break;
         case OP_SPLIT_UNKNOWN: orfs_split = true; break;
+        case OP_TRANSLATE: translate = true; break;
+        case OP_FRAME: set_frames(v); break;
+        case OP_CODE: set_code(v); break;
+        case OP_CODE_TABLE: set_code_table(v); break;
         }
     }
     if (print_version) {
@@ -393,16 +439,32 @@ static void parse_command_line(int argc, char **argv)
         if (kmers_k) die("--orfs and --kmers can't be used together\n");
         if (out_type != UNDECIDED) die("--orfs writes a table: no output type can be given with it\n");
         if (stop_to_stop && orf_starts_text) die("--stop-to-stop and --starts can't be used together\n");
-        if (!orf_stops_text) naf_gpu_parse_codon_set("TAA,TAG,TGA", &orf_stops);
+        if (!orf_stops_text && translate && (code_text || code_table_text)) naf_gpu_genetic_code_stops(&genetic_code, &orf_stops);      /* the code's own stops close the frames */
+        else if (!orf_stops_text) naf_gpu_parse_codon_set("TAA,TAG,TGA", &orf_stops);
         if (stop_to_stop) orf_starts = 0; else if (!orf_starts_text) naf_gpu_parse_codon_set("ATG", &orf_starts);
         if (orf_starts & orf_stops) die("--starts and --stops share a codon: a codon can't both open and close a reading frame\n");
         if (revcomp) die("--orfs reads both strands itself (--strand): --revcomp can't be used with it\n");
+        if (frame_text && translate) die("--frame can't be used with --orfs: every reading frame of the table is translated in its own frame\n");
         if (n_selections > 1) die("--orfs can be restricted by one --records or one --region only\n");
         if (n_selections && selections[0].rc) die("--orfs reads both strands itself (--strand): --rc-region can't be used with it\n");
         if (n_selections && selections[0].region) {
             size_t l; uint64_t b, e; naf_gpu_parse_region(selections[0].region, &l, &b, &e);
             if (!(b == 0 && e == NAF_GPU_WHOLE)) die("--orfs can be restricted to a whole sequence only: --region ID, without a range\n");
         }
+    }
+    if (!translate) {
+        if (frame_text) die("--frame can be used only with --translate\n");
+        if (code_text) die("--code can be used only with --translate\n");
+        if (code_table_text) die("--code-table can be used only with --translate\n");
+    } else {
+        if (out_type != UNDECIDED) die("--translate writes protein FASTA: no output type can be given with it\n");
+        if (n_locate) die("--translate and --locate can't be used together\n");
+        if (composition) die("--translate and --composition can't be used together\n");
+        if (quality) die("--translate and --quality can't be used together\n");
+        if (runs_class || masked_runs) die("--translate and %s can't be used together\n", runs_class ? "--runs" : "--masked-runs");
+        if (kmers_k) die("--translate and --kmers can't be used together\n");
+        if (code_text && code_table_text) die("--code and --code-table can't be used together\n");
+        if (!code_text && !code_table_text) naf_gpu_genetic_code_by_id(1, &genetic_code);
     }
     if ((n_selections || revcomp) && !(out_type == UNDECIDED || out_type == FASTA || out_type == FASTQ || out_type == SEQ || out_type == SEQUENCES))
         die("--region can be used only with sequence output\n");
@@ -564,18 +626,53 @@ static void *sel_buf = NULL; static size_t sel_cap = 0;
 static void emit_segments(const naf_gpu_unnaf_opts *o, const naf_gpu_segment *segs, const uint8_t *strand, size_t n)
 {
     /* a selection larger than the range buffer is produced in pieces of whole segments: halves until a piece fits (or is one segment) */
-    size_t need = 0; GPU_TRY(naf_gpu_unnaf_select_stranded_size(gpu, d_naf, naf_len, o, segs, strand, n, &need));
+    /* (--translate: the same segments as protein, naf_gpu_unnaf_translate) */
+    size_t need = 0;
+    if (translate) GPU_TRY(naf_gpu_unnaf_translate_size(gpu, d_naf, naf_len, o, &genetic_code, segs, strand, n, &need));
+    else GPU_TRY(naf_gpu_unnaf_select_stranded_size(gpu, d_naf, naf_len, o, segs, strand, n, &need));
     if (!need) return;
     if (need > range_bytes() && n > 1) { emit_segments(o, segs, strand, n / 2); emit_segments(o, segs + n / 2, strand ? strand + n / 2 : NULL, n - n / 2); return; }
     if (need > sel_cap) { if (sel_buf) naf_gpu_free(gpu, sel_buf); GPU_TRY(naf_gpu_malloc(gpu, need + 64, &sel_buf)); sel_cap = need; }
-    size_t got = 0; GPU_TRY(naf_gpu_unnaf_select_stranded(gpu, d_naf, naf_len, o, segs, strand, n, sel_buf, sel_cap, &got));
+    size_t got = 0;
+    if (translate) GPU_TRY(naf_gpu_unnaf_translate(gpu, d_naf, naf_len, o, &genetic_code, segs, strand, n, sel_buf, sel_cap, &got));
+    else GPU_TRY(naf_gpu_unnaf_select_stranded(gpu, d_naf, naf_len, o, segs, strand, n, sel_buf, sel_cap, &got));
     if (got != need) die("can't decompress sequence\n");
     write_from_device(OUT, sel_buf, got);
+}
+/* --translate: every segment of a selection becomes its frames, side by side in the order of --frame.  Frame f > 0 is the segment from its
+ * base f - 1 on, frame -f its reverse complement from base f - 1 on (forward bases [begin, end - (f - 1)), strand 1); for a reverse selection
+ * the two swap.  Frame 1 or -1 of a whole record stays the whole record (its stored header); a frame that has no base is left out. */
+static void segments_to_frames(naf_gpu_segment **segs, uint8_t **strand, size_t *n_segs, bool *any_rc)
+{
+    const unsigned long long N = H.n_sequences;
+    uint64_t *len = (uint64_t *)malloc((size_t)(N + 1) * sizeof *len), *off = (uint64_t *)malloc((size_t)(N + 2) * sizeof *off);
+    naf_gpu_segment *out = (naf_gpu_segment *)malloc((*n_segs * n_frames + 1) * sizeof *out);
+    uint8_t *ost = (uint8_t *)malloc(*n_segs * n_frames + 1);
+    if (!len || !off || !out || !ost) die("can't allocate memory\n");
+    naf_gpu_unnaf_opts o = { NAF_OUT_FASTA, 0, -1 };
+    if (N) GPU_TRY(naf_gpu_unnaf_record_table(gpu, d_naf, naf_len, &o, 0, N, len, off));
+    size_t m = 0;
+    for (size_t k = 0; k < *n_segs; k++) {
+        const naf_gpu_segment g = (*segs)[k];
+        const bool whole = g.begin == 0 && g.end == NAF_GPU_WHOLE;
+        const uint64_t L = g.record < N ? len[g.record] : 0, e = g.end < L ? g.end : L;
+        for (size_t q = 0; q < n_frames; q++) {
+            const uint64_t skip = (uint64_t)(frames[q] < 0 ? -frames[q] : frames[q]) - 1;
+            const bool rc = (frames[q] < 0) != ((*strand)[k] != 0);
+            if (skip == 0 && (whole || g.begin >= e)) { ost[m] = rc; out[m++] = g; }                  /* the segment as it is (one that selects nothing: the call says so) */
+            else if (g.begin + skip < e) { ost[m] = rc; out[m++] = rc ? (naf_gpu_segment){ g.record, g.begin, e - skip } : (naf_gpu_segment){ g.record, g.begin + skip, e }; }
+        }
+    }
+    *any_rc = false;
+    for (size_t k = 0; k < m; k++) *any_rc = *any_rc || ost[k];
+    free(len); free(off); free(*segs); free(*strand);
+    *segs = out; *strand = ost; *n_segs = m;
 }
 static void run_select(int mode, bool has_ids)
 {
     upload();
     const unsigned long long N = H.n_sequences;
+    if (translate && !n_selections && N) add_selection(NULL, 1, N, false);        /* --translate without a selection: every record */
     /* the ids of the regions, looked up in one call */
     size_t n_regions = 0, ids_bytes = 0, n_segs = 0;
     for (size_t k = 0; k < n_selections; k++) {
@@ -609,6 +706,7 @@ static void run_select(int mode, bool has_ids)
         } else for (unsigned long long r = s->first; r <= s->last; r++) { strand[m] = s->rc; segs[m++] = (naf_gpu_segment){ r - 1, 0, NAF_GPU_WHOLE }; }
         any_rc = any_rc || s->rc;
     }
+    if (translate) segments_to_frames(&segs, &strand, &n_segs, &any_rc);
     naf_gpu_unnaf_opts o = { mode, mode != NAF_OUT_FASTQ && use_mask, line_length_is_specified ? requested_line_length : -1 };
     fflush(OUT);
     emit_segments(&o, segs, any_rc ? strand : NULL, n_segs);
@@ -854,6 +952,19 @@ static void run_orfs(bool has_ids, bool has_names)
         for (uint64_t a = 0; a < n; a += chunk) {
             const size_t m = n - a < chunk ? (size_t)(n - a) : chunk;
             GPU_TRY(naf_gpu_download(gpu, rows, (const naf_gpu_orf *)d_orfs + a, m * sizeof *rows));
+            if (translate) {                                                      /* the rows are the segments: their proteins instead of the lines */
+                naf_gpu_segment *segs = (naf_gpu_segment *)malloc(m * sizeof *segs); uint8_t *strand = (uint8_t *)malloc(m);
+                if (!segs || !strand) die("can't allocate memory\n");
+                for (size_t k = 0; k < m; k++) {
+                    if (rows[k].record >= N || rows[k].strand > 1 || rows[k].end <= rows[k].begin) die("can't decompress sequence\n");
+                    segs[k] = (naf_gpu_segment){ rows[k].record, rows[k].begin, rows[k].end }; strand[k] = (uint8_t)rows[k].strand;
+                }
+                naf_gpu_unnaf_opts o = { NAF_OUT_FASTA, 0, line_length_is_specified ? requested_line_length : -1 };
+                fflush(OUT);
+                emit_segments(&o, segs, strand, m);
+                free(segs); free(strand);
+                continue;
+            }
             for (size_t k = 0; k < m; k++) {
                 const naf_gpu_orf *x = &rows[k];
                 if (x->record >= N || x->strand > 1 || x->frame > 2 || x->end <= x->begin) die("can't decompress sequence\n");
@@ -861,6 +972,7 @@ static void run_orfs(bool has_ids, bool has_names)
                         (unsigned long long)((x->end - x->begin) / 3), x->strand ? '-' : '+', (x->flags & NAF_GPU_ORF_STOP3) ? "stop" : "open");
             }
         }
+        if (sel_buf) { naf_gpu_free(gpu, sel_buf); sel_buf = NULL; sel_cap = 0; }
         free(rows); free(name); free(text); naf_gpu_free(gpu, d_orfs);
         phase("orfs: download + lines");
     }
@@ -987,7 +1099,7 @@ int main(int argc, char **argv)
     bool large = out_type == IDS || out_type == NAMES || out_type == LENGTHS || out_type == MASK || out_type == FOUR_BIT || out_type == DNA ||
                  out_type == MASKED_DNA || out_type == UNMASKED_DNA || out_type == SEQ || out_type == FASTA || out_type == MASKED_FASTA ||
                  out_type == UNMASKED_FASTA || out_type == FASTQ;
-    if (large && !n_locate && !composition && !quality && !runs_class && !masked_runs && !kmers_k && !orfs && !force_stdout && isatty(fileno(OUT)))
+    if (large && !n_locate && !composition && !quality && !runs_class && !masked_runs && !kmers_k && !orfs && !translate && !force_stdout && isatty(fileno(OUT)))
         die("output file not specified - please either specify output file with '-o' or '>', or use '-c' option to force writing to console\n");
 
     unsigned long long N = H.n_sequences;
@@ -1011,6 +1123,11 @@ int main(int argc, char **argv)
     else if (orfs) {
         if (H.seq_type >= NAF_SEQ_PROTEIN) die("open reading frames cannot be listed in %s sequences\n", tn[H.seq_type]);
         run_orfs(has_ids, has_names);
+    }
+    else if (translate) {
+        if (H.seq_type >= NAF_SEQ_PROTEIN) die("%s sequences cannot be translated\n", tn[H.seq_type]);
+        if (!has_data) die("the archive stores no sequence to translate\n");
+        run_select(NAF_OUT_FASTA, has_ids);
     }
     else if (n_selections) {
         if (out_type == FASTQ && !has_quality) die("FASTQ output requested, but input has no qualities\n");
