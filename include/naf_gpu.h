@@ -547,6 +547,57 @@ int  naf_gpu_unnaf_translate_size(naf_gpu_ctx *ctx, const void *d_naf, size_t na
 int  naf_gpu_unnaf_translate(naf_gpu_ctx *ctx, const void *d_naf, size_t naf_len, const naf_gpu_unnaf_opts *opts, const naf_gpu_genetic_code *code,
                              const naf_gpu_segment *segs, const uint8_t *strand, size_t n_segs, void *d_out, size_t out_cap, size_t *out_len);
 
+/* ---- unnaf: perfect tandem repeats (microsatellites) of period 1 to 16 per record, listed from the packed stream ------
+ * What MISA, PERF, pytrf findstr and seqtk hrun (period 1 only) answer from the text -- where (CA)17, (GATA)12 and the poly-A tails lie --
+ * as a table of (record, begin, end, motif, period) rows, made without expanding the codes.
+ *   Repeat    of period p, 1 <= p <= 16: a maximal interval [begin, end) of bases of ONE record in which every base is stored as exactly
+ *             A, C, G or T/U (codes 8, 4, 2, 1 of "-TGKCYSBAWRDMHVN"), x[i] == x[i + p] holds for every begin <= i < end - p, and
+ *             end - begin >= 2p.  Case (the soft mask) plays no part and the mask section is never decoded; an N, an ambiguity code or
+ *             the gap ends the interval.  Maximal: it cannot be extended by one base on either side; a record's end always ends it, so a
+ *             repeat that reaches the last base of record r and one that starts at base 0 of the next non-empty record are two rows.
+ *             Two repeats of the same period may overlap by up to p - 1 bases: ACACAGAGAG holds (AC) at [0, 5) and (AG) at [4, 10).
+ *   Motif     the first p bases of the repeat: base i (0 = first) at bits 2i and 2i + 1 of `motif`, A = 0, C = 1, G = 2, T/U = 3; the bits
+ *             above 2p are 0.  A repeat whose motif is itself a whole power of a shorter word (AAAA at p = 2, ACAC at p = 4) is NOT a row,
+ *             whether or not the shorter period is searched, as in MISA and PERF: the interval is exactly the maximal repeat of that
+ *             shorter period.
+ *   Spec      min_copies[p - 1] = 0: period p is not searched; otherwise >= 2.  naf_gpu_parse_repeat_spec takes MISA's definition syntax,
+ *             PERIOD-COPIES pairs joined by commas ("1-10,2-6,3-5"), each period 1 .. 16 at most once, copies 2 .. 2^32 - 1; the word
+ *             "misa" stands for 1-10,2-6,3-5,4-5,5-5,6-5.  Everything else is NAF_GPU_EARG and nothing is written then: the empty string,
+ *             a period listed twice, period 0 or 17, copies 0 or 1, blanks, a trailing comma.
+ *   Filters   copies = floor((end - begin) / p).  A row is kept when copies >= min_copies[p - 1] and end - begin >= min_len.  With
+ *             NAF_GPU_REPEATS_WHOLE_UNITS end is cut to begin + copies * p before the min_len test and in the row: what MISA and PERF print.
+ *   Class     naf_gpu_repeat_class gives the smallest, in A < C < G < T order from the first base on, of the 2p rotations of the motif
+ *             and of its reverse complement, in the encoding of `motif`: MISA groups (CA)n, (AC)n, (TG)n and (GT)n under AC.  A period
+ *             outside 1 .. 16 and motif bits above 2p are NAF_GPU_EARG.
+ *   Never     Bases behind the last record of a malformed archive and the padding nibble of an odd stream are in no repeat.
+ *   Order     ascending (record, begin, period); the same bytes on every run and for every piece size.
+ *   Errors    NAF_GPU_EARG, last_error saying which: a spec that searches no period; a min_copies of 1; unknown flag bits; min_len == 0;
+ *             first > n_sequences or a range past the last record, as for naf_gpu_unnaf_runs; protein and text archives; an archive
+ *             that stores no sequence.  An archive without records gives 0 rows.
+ *   Outputs   *n_repeats is always the whole count; *n_bases (may be NULL) the sum of end - begin over the rows, overlaps counted twice;
+ *             per_period (may be NULL) the rows of period p at [p - 1].  d_rows is DEVICE memory of any alignment; exactly
+ *             32 * n_repeats bytes are written and nothing else.  With row_cap too small the call returns NAF_GPU_ECAP, sets *n_repeats
+ *             to the whole count and writes nothing.
+ *   Pieces    more bases than NAF_GPU_REPEATS_PIECE (default 2^31) are decoded and swept in pieces of whole records, so no repeat crosses
+ *             a piece; only the zstd blocks behind the records are decoded when the frame allows it.  The candidate tables of a piece
+ *             (a start and an end per run of continuing bases that the prefilter cannot drop) live in the context's scratch arena: when it
+ *             cannot hold them the call returns NAF_GPU_ENOMEM and last_error names NAF_GPU_REPEATS_PIECE.
+ * A row's (record, begin, end) is what naf_gpu_unnaf_select takes: the selected text of a row is its motif repeated and cut to its length.
+ * TRACE=1: "[repeats] rows R candidates K periods P pieces N sequence bytes decoded X of Y" per call that reaches the records. */
+typedef struct { uint64_t record, begin, end; uint32_t motif; uint8_t period, reserved[3]; } naf_gpu_repeat;   /* 32 bytes; reserved = 0 */
+typedef struct { uint32_t min_copies[16]; } naf_gpu_repeat_spec;
+enum { NAF_GPU_REPEATS_WHOLE_UNITS = 1 };
+
+/* host only, no device */
+int  naf_gpu_parse_repeat_spec(const char *text, naf_gpu_repeat_spec *spec);
+int  naf_gpu_repeat_class(uint32_t motif, unsigned period, uint32_t *cls);
+
+int  naf_gpu_unnaf_repeats_count(naf_gpu_ctx *ctx, const void *d_naf, size_t naf_len, const naf_gpu_repeat_spec *spec, int flags, uint64_t min_len,
+                                 uint64_t first, uint64_t count, uint64_t *n_repeats, uint64_t *n_bases, uint64_t per_period[16]);
+int  naf_gpu_unnaf_repeats(naf_gpu_ctx *ctx, const void *d_naf, size_t naf_len, const naf_gpu_repeat_spec *spec, int flags, uint64_t min_len,
+                           uint64_t first, uint64_t count, naf_gpu_repeat *d_rows, size_t row_cap, uint64_t *n_repeats, uint64_t *n_bases,
+                           uint64_t per_period[16]);
+
 /* ---- ennaf ------------------------------------------------------------------------------------------ */
 typedef struct {
     int      format;            /* NAF_FMT_* (AUTO = sniff, process.c:547-583) */

@@ -38,6 +38,7 @@ EXPORTS = [
     "naf_gpu_parse_codon_set", "naf_gpu_unnaf_orfs_count", "naf_gpu_unnaf_orfs",
     "naf_gpu_genetic_code_by_id", "naf_gpu_genetic_code_parse", "naf_gpu_genetic_code_stops", "naf_gpu_codon_lut",
     "naf_gpu_unnaf_translate_size", "naf_gpu_unnaf_translate",
+    "naf_gpu_parse_repeat_spec", "naf_gpu_repeat_class", "naf_gpu_unnaf_repeats_count", "naf_gpu_unnaf_repeats",
 ]
 WHOLE = 2 ** 64 - 1                     # NAF_GPU_WHOLE: (record, 0, WHOLE) is the record as stored
 MAX_SHARDS = 64
@@ -182,6 +183,24 @@ ORF_STOP3, ORF_STOP5 = 1, 2                   # a row's flags
 ORF_SPLIT_UNKNOWN, ORF_CLOSED = 1, 2          # a call's flags
 
 
+class Repeat(C.Structure):
+    """naf_gpu_repeat: bases [begin, end) of `record` are a tandem repeat of `period` bases; motif: its first `period` bases, base i at bits
+    2i and 2i + 1 (A 0, C 1, G 2, T/U 3)."""
+    _fields_ = [("record", C.c_uint64), ("begin", C.c_uint64), ("end", C.c_uint64), ("motif", C.c_uint32), ("period", C.c_uint8), ("reserved", C.c_uint8 * 3)]
+
+
+class RepeatSpec(C.Structure):
+    """naf_gpu_repeat_spec: min_copies[p - 1] = the copies a repeat of period p needs (>= 2), 0: the period is not searched."""
+    _fields_ = [("min_copies", C.c_uint32 * 16)]
+
+
+# numpy's view of a table of tandem repeats (naf_gpu_repeat): bases [begin, end) of `record` repeat the `period` bases of `motif` (base i at
+# bits 2i, 2i + 1: A 0, C 1, G 2, T/U 3)
+REPEAT_DTYPE = [("record", "<u8"), ("begin", "<u8"), ("end", "<u8"), ("motif", "<u4"), ("period", "u1"), ("reserved", "u1", (3,))]
+REPEAT_BYTES = 32
+REPEATS_WHOLE_UNITS = 1
+
+
 class NafGpuError(RuntimeError):
     def __init__(self, code, msg):
         super().__init__("naf_gpu error %d: %s" % (code, msg))
@@ -304,6 +323,10 @@ def load():
         L.naf_gpu_codon_lut.argtypes = [C.POINTER(GeneticCode), u8p]
         L.naf_gpu_unnaf_translate_size.argtypes = [vp, vp, sz, C.POINTER(UnnafOpts), C.POINTER(GeneticCode), C.POINTER(Segment), u8p, sz, C.POINTER(sz)]
         L.naf_gpu_unnaf_translate.argtypes = [vp, vp, sz, C.POINTER(UnnafOpts), C.POINTER(GeneticCode), C.POINTER(Segment), u8p, sz, vp, sz, C.POINTER(sz)]
+        L.naf_gpu_parse_repeat_spec.argtypes = [C.c_char_p, C.POINTER(RepeatSpec)]
+        L.naf_gpu_repeat_class.argtypes = [C.c_uint32, C.c_uint, u32p]
+        L.naf_gpu_unnaf_repeats_count.argtypes = [vp, vp, sz, C.POINTER(RepeatSpec), i, C.c_uint64, C.c_uint64, C.c_uint64, u64p, u64p, u64p]
+        L.naf_gpu_unnaf_repeats.argtypes = [vp, vp, sz, C.POINTER(RepeatSpec), i, C.c_uint64, C.c_uint64, C.c_uint64, vp, sz, u64p, u64p, u64p]
         _lib = L
     return _lib
 
@@ -497,6 +520,39 @@ def runs_to_segments(runs, flank=0, lengths=None):
             e = min(e, int(lengths[r]))
         out.append((r, b, e))
     return out
+
+
+def parse_repeat_spec(text):
+    """Host-only: the sixteen min_copies of a repeat spec in MISA's definition syntax -- "1-10,2-6,3-5", or the word "misa"
+    (naf_gpu_parse_repeat_spec) -- as a list, [p - 1] for period p, 0 where the period is not searched.  ValueError for what is no spec."""
+    b = text.encode("latin1") if isinstance(text, str) else bytes(text)
+    sp = RepeatSpec()
+    if b"\0" in b or load().naf_gpu_parse_repeat_spec(b, C.byref(sp)):
+        raise ValueError("not a repeat spec: %r" % (text,))
+    return [int(v) for v in sp.min_copies]
+
+
+def repeat_class(motif, period):
+    """Host-only: the motif class (naf_gpu_repeat_class) -- the smallest, in A < C < G < T order, of the rotations of the motif and of its
+    reverse complement, in the row's encoding.  ValueError for a period outside 1 .. 16 or motif bits above 2 * period."""
+    out = C.c_uint32()
+    if not (0 <= int(motif) < 2 ** 32 and 0 <= int(period) < 2 ** 32) or load().naf_gpu_repeat_class(int(motif), int(period), C.byref(out)):
+        raise ValueError("not a motif: %r of period %r" % (motif, period))
+    return out.value
+
+
+def repeat_motif_text(motif, period, rna=False):
+    """The `period` letters of a row's motif, upper case; rna: U for T."""
+    if not 1 <= int(period) <= 16 or int(motif) >> (2 * int(period)):
+        raise ValueError("not a motif: %r of period %r" % (motif, period))
+    return "".join(("ACGU" if rna else "ACGT")[(int(motif) >> (2 * k)) & 3] for k in range(int(period)))
+
+
+def repeats_to_segments(rows, flank=0, lengths=None):
+    """The (record, begin, end) tuples unnaf_select takes, one per tandem repeat (rows of the table unnaf_repeats returns).  flank: that
+    many bases more on either side, clamped to the record -- to its start always, to its end when `lengths` (the n_bases of
+    unnaf_record_table, indexed by record number) is given; unnaf_select clamps an end beyond the record itself."""
+    return runs_to_segments(rows, flank, lengths)
 
 
 def hits_to_segments(hits, patterns, flank=0, lengths=None):
@@ -1036,6 +1092,52 @@ class Context:
             rc = call(buf, cap)
         self._check(rc)
         return np.frombuffer(buf[:RUN_BYTES * n.value].cpu().numpy().tobytes(), dtype=RUN_DTYPE), nb.value
+
+    @staticmethod
+    def _repeat_spec(spec):
+        """The RepeatSpec of a repeats call; spec: text (parse_repeat_spec) or a sequence of 16 numbers, [p - 1] the copies of period p."""
+        vals = parse_repeat_spec(spec) if isinstance(spec, (str, bytes)) else [int(v) for v in spec]
+        if len(vals) != 16 or not all(0 <= v < 2 ** 32 for v in vals):
+            raise ValueError("not a repeat spec: %r" % (spec,))
+        return RepeatSpec((C.c_uint32 * 16)(*vals))
+
+    def unnaf_repeats_count(self, d_naf, spec="misa", min_len=1, whole_units=False, first=0, count=None):
+        """(n_repeats, n_bases, per_period) of the rows unnaf_repeats lists (naf_gpu_unnaf_repeats_count); per_period: the sixteen counts,
+        [p - 1] for period p."""
+        sp = self._repeat_spec(spec)
+        n, nb, pp = C.c_uint64(), C.c_uint64(), (C.c_uint64 * 16)()
+        self._check(self.L.naf_gpu_unnaf_repeats_count(self.h, _ptr(d_naf), d_naf.numel(), C.byref(sp), REPEATS_WHOLE_UNITS if whole_units else 0, int(min_len), int(first),
+                                                       WHOLE if count is None else int(count), C.byref(n), C.byref(nb), pp))
+        return n.value, nb.value, [int(v) for v in pp]
+
+    def unnaf_repeats(self, d_naf, spec="misa", min_len=1, whole_units=False, first=0, count=None, out=None):
+        """(rows, n_bases, per_period): the perfect tandem repeats of records [first, first + count) -- spec: MISA's definition syntax
+        ("1-10,2-6,3-5", or "misa") or 16 numbers, the copies a repeat of period 1 .. 16 needs, 0: not searched; min_len: the bases a
+        repeat needs; whole_units: a row's end is cut to a whole number of copies -- as a structured numpy array (REPEAT_DTYPE: record,
+        begin, end, motif, period, reserved) in ascending (record, begin, period), the sum of their lengths and the rows per period.
+        out: a uint8 device tensor to take the table (32 bytes a row); then `rows` is the torch view of its first 32 * n bytes and too
+        small a tensor raises NafGpuError(E_CAP).  Without it a table sized by a guess is tried first and one of the whole count when
+        that was too small (the call reports it with E_CAP)."""
+        import numpy as np
+        import torch
+        sp = self._repeat_spec(spec)
+        n, nb, pp = C.c_uint64(), C.c_uint64(), (C.c_uint64 * 16)()
+        cnt, flags = WHOLE if count is None else int(count), REPEATS_WHOLE_UNITS if whole_units else 0
+
+        def call(buf, cap):
+            return self.L.naf_gpu_unnaf_repeats(self.h, _ptr(d_naf), d_naf.numel(), C.byref(sp), flags, int(min_len), int(first), cnt, _ptr(buf), cap, C.byref(n), C.byref(nb), pp)
+        if out is not None:
+            self._check(call(out, out.numel() // REPEAT_BYTES))
+            return out[:REPEAT_BYTES * n.value], nb.value, [int(v) for v in pp]
+        cap = 4096
+        buf = torch.empty(REPEAT_BYTES * cap, dtype=torch.uint8, device=self.device)
+        rc = call(buf, cap)
+        if rc == E_CAP:
+            cap = n.value
+            buf = torch.empty(REPEAT_BYTES * cap, dtype=torch.uint8, device=self.device)
+            rc = call(buf, cap)
+        self._check(rc)
+        return np.frombuffer(buf[:REPEAT_BYTES * n.value].cpu().numpy().tobytes(), dtype=REPEAT_DTYPE), nb.value, [int(v) for v in pp]
 
     @staticmethod
     def _orf_args(stops, starts, strands, split_unknown, closed):

@@ -527,3 +527,47 @@ extern "C" int naf_gpu_get_timing_streams(naf_gpu_ctx *c, float ms[5])
     for (int k = 0; k < 5; k++) ms[k] = c->stream_ms[k];
     return 0;
 }
+
+// ---- tandem repeats: the two host-only functions (plain C; the calls are repeats.h's) -----------------------------------------
+// MISA's definition syntax: PERIOD-COPIES pairs joined by commas, or the word "misa".  0, or NAF_GPU_EARG for anything else.
+extern "C" int naf_gpu_parse_repeat_spec(const char *text, naf_gpu_repeat_spec *spec)
+{
+    if (!text || !spec) return NAF_GPU_EARG;
+    if (!strcmp(text, "misa")) text = "1-10,2-6,3-5,4-5,5-5,6-5";
+    naf_gpu_repeat_spec s; memset(&s, 0, sizeof s);
+    const char *p = text;
+    for (;;) {
+        unsigned long long v[2];
+        for (int k = 0; k < 2; k++) {
+            if (*p < '0' || *p > '9') return NAF_GPU_EARG;
+            for (v[k] = 0; *p >= '0' && *p <= '9'; p++) { v[k] = v[k] * 10 + (unsigned)(*p - '0'); if (v[k] > 0xFFFFFFFFull) return NAF_GPU_EARG; }
+            if (k == 0) { if (*p != '-') return NAF_GPU_EARG; p++; }
+        }
+        if (v[0] < 1 || v[0] > 16 || v[1] < 2 || s.min_copies[v[0] - 1]) return NAF_GPU_EARG;
+        s.min_copies[v[0] - 1] = (uint32_t)v[1];
+        if (!*p) break;
+        if (*p != ',') return NAF_GPU_EARG;
+        p++;
+    }
+    *spec = s;
+    return 0;
+}
+// The smallest, in A < C < G < T order from the first base on, of the rotations of the motif and of its reverse complement.
+// motif, *cls: base i at bits 2i, 2i + 1.  NAF_GPU_EARG: a period outside 1 .. 16, bits above 2 period.
+extern "C" int naf_gpu_repeat_class(uint32_t motif, unsigned period, uint32_t *cls)
+{
+    if (!cls || period < 1 || period > 16 || (period < 16 && (motif >> (2 * period)))) return NAF_GPU_EARG;
+    unsigned char w[2][16];
+    for (unsigned i = 0; i < period; i++) { w[0][i] = (motif >> (2 * i)) & 3u; w[1][period - 1 - i] = 3u - w[0][i]; }
+    uint64_t best = ~0ull;
+    for (int s = 0; s < 2; s++)
+        for (unsigned r = 0; r < period; r++) {
+            uint64_t key = 0;                                                      /* the first base the most significant */
+            for (unsigned i = 0; i < period; i++) key = key << 2 | w[s][(r + i) % period];
+            if (key < best) best = key;
+        }
+    uint32_t c = 0;
+    for (unsigned i = 0; i < period; i++) c |= (uint32_t)((best >> (2 * (period - 1 - i))) & 3u) << (2 * i);
+    *cls = c;
+    return 0;
+}

@@ -37,6 +37,9 @@ static unsigned kmers_k = 0; static bool kmers_canonical = false, kmers_per_reco
 static bool orfs = false, min_orf_given = false, stop_to_stop = false, orfs_closed = false, orfs_split = false;
 static const char *orf_stops_text = NULL, *orf_starts_text = NULL; static uint64_t orf_stops = 0, orf_starts = 0;
 static unsigned long long min_orf = 75;
+/* --repeats SPEC [--min-repeat N] [--whole-units]: perfect tandem repeats of period 1 to 16, as a table (this implementation only) */
+static const char *repeats_text = NULL; static naf_gpu_repeat_spec repeats_spec; static bool min_repeat_given = false, whole_units = false;
+static unsigned long long min_repeat = 1;
 /* --translate [--frame LIST] [--code N | --code-table LETTERS64]: the selection's frames, or with --orfs every reading frame, as protein FASTA (this implementation only) */
 static bool translate = false; static int frames[6] = { 1 }; static size_t n_frames = 1;
 static const char *frame_text = NULL, *code_text = NULL, *code_table_text = NULL; static naf_gpu_genetic_code genetic_code;
@@ -147,6 +150,24 @@ static void set_min_run(const char *v)
     }
     if (!digit || a == 0) die("can't parse the value of --min-run parameter (a positive number of bases)\n");
     min_run = a; min_run_given = true;
+}
+
+static void set_repeats(const char *v)
+{
+    if (repeats_text) die("only one --repeats definition can be given\n");
+    if (naf_gpu_parse_repeat_spec(v, &repeats_spec)) die("can't parse the value of --repeats parameter (PERIOD-COPIES pairs joined by commas, periods 1 to 16, at least 2 copies, e.g. 1-10,2-6,3-5; or misa)\n");
+    repeats_text = v;
+}
+static void set_min_repeat(const char *v)
+{
+    unsigned long long a = 0; bool digit = false;
+    for (const char *p = v; *p; p++) {
+        if (*p == ',') continue;
+        if (*p < '0' || *p > '9' || a > (ULLONG_MAX - (unsigned)(*p - '0')) / 10) die("can't parse the value of --min-repeat parameter (a positive number of bases)\n");
+        a = a * 10 + (unsigned)(*p - '0'); digit = true;
+    }
+    if (!digit || a == 0) die("can't parse the value of --min-repeat parameter (a positive number of bases)\n");
+    min_repeat = a; min_repeat_given = true;
 }
 
 static void set_kmers(const char *v)
@@ -264,7 +285,10 @@ static void show_help(void)
         "                    With --orfs: the protein of every reading frame of the table, in the table's order, instead of the table\n"
         "  --frame LIST    - With --translate: comma-separated frames out of 1,2,3,-1,-2,-3, or 6 for all six (default 1); -1..-3 count from the end, as in --orfs\n"
         "  --code N        - With --translate: NCBI genetic code N (1 to 6, 9 to 16, 21 to 26; default 1). With --orfs and without --stops, its stops close the reading frames\n"
-        "  --code-table LETTERS - With --translate: a genetic code of its own, 64 letters A-Z or * for the codons AAA AAC AAG AAT ACA ... TTT\n");
+        "  --code-table LETTERS - With --translate: a genetic code of its own, 64 letters A-Z or * for the codons AAA AAC AAG AAT ACA ... TTT\n"
+        "  --repeats SPEC  - Every perfect tandem repeat, as lines \"ID begin end PERIOD MOTIF COPIES CLASS\" (0-based half-open): SPEC is PERIOD-COPIES pairs, e.g. 1-10,2-6,3-5, periods 1 to 16; or misa\n"
+        "  --min-repeat N  - With --repeats: only repeats of at least N bases (default 1)\n"
+        "  --whole-units   - With --repeats: the end of a repeat is cut to a whole number of copies, as MISA and PERF print it\n");
 }
 
 static void parse_command_line(int argc, char **argv)
@@ -277,7 +301,7 @@ static void parse_command_line(int argc, char **argv)
         {"--fasta", FASTA}, {"--fastq", FASTQ}, {"--dna", DNA}, {"--masked-dna", MASKED_DNA}, {"--unmasked-dna", UNMASKED_DNA},
         {"--masked-fasta", MASKED_FASTA}, {"--unmasked-fasta", UNMASKED_FASTA} };
     /* the other options (unnaf/src/unnaf.c:282-353), as a table: one that takes a value is only recognised with an argument behind it */
-    enum { OP_LINE_LENGTH, OP_OUT, OP_NO_MASK, OP_IGNORED, OP_HELP, OP_VERBOSE, OP_VERSION, OP_STDOUT, OP_REGION, OP_RECORDS, OP_RC_REGION, OP_REVCOMP, OP_LOCATE, OP_STRAND, OP_MISMATCHES, OP_COMPOSITION, OP_WINDOW, OP_QUALITY, OP_CYCLES, OP_RUNS, OP_MASKED_RUNS, OP_MIN_RUN, OP_EACH, OP_KMERS, OP_CANONICAL, OP_PER_RECORD, OP_ORFS, OP_MIN_ORF, OP_STOPS, OP_STARTS, OP_STOP_TO_STOP, OP_CLOSED, OP_SPLIT_UNKNOWN, OP_TRANSLATE, OP_FRAME, OP_CODE, OP_CODE_TABLE };
+    enum { OP_LINE_LENGTH, OP_OUT, OP_NO_MASK, OP_IGNORED, OP_HELP, OP_VERBOSE, OP_VERSION, OP_STDOUT, OP_REGION, OP_RECORDS, OP_RC_REGION, OP_REVCOMP, OP_LOCATE, OP_STRAND, OP_MISMATCHES, OP_COMPOSITION, OP_WINDOW, OP_QUALITY, OP_CYCLES, OP_RUNS, OP_MASKED_RUNS, OP_MIN_RUN, OP_EACH, OP_KMERS, OP_CANONICAL, OP_PER_RECORD, OP_ORFS, OP_MIN_ORF, OP_STOPS, OP_STARTS, OP_STOP_TO_STOP, OP_CLOSED, OP_SPLIT_UNKNOWN, OP_TRANSLATE, OP_FRAME, OP_CODE, OP_CODE_TABLE, OP_REPEATS, OP_MIN_REPEAT, OP_WHOLE_UNITS };
     static const struct { const char *name; int op; bool value; } option_table[] = {
         { "--line-length", OP_LINE_LENGTH, true }, { "-o", OP_OUT, true }, { "--no-mask", OP_NO_MASK, false }, { "--binary-stdout", OP_IGNORED, false },
         { "--binary-stderr", OP_IGNORED, false }, { "--binary", OP_IGNORED, false }, { "--help", OP_HELP, false }, { "-h", OP_HELP, false },
@@ -289,7 +313,8 @@ static void parse_command_line(int argc, char **argv)
         { "--kmers", OP_KMERS, true }, { "--canonical", OP_CANONICAL, false }, { "--per-record", OP_PER_RECORD, false },
         { "--orfs", OP_ORFS, false }, { "--min-orf", OP_MIN_ORF, true }, { "--stops", OP_STOPS, true }, { "--starts", OP_STARTS, true }, { "--stop-to-stop", OP_STOP_TO_STOP, false },
         { "--closed", OP_CLOSED, false }, { "--split-unknown", OP_SPLIT_UNKNOWN, false },
-        { "--translate", OP_TRANSLATE, false }, { "--frame", OP_FRAME, true }, { "--code", OP_CODE, true }, { "--code-table", OP_CODE_TABLE, true } };
+        { "--translate", OP_TRANSLATE, false }, { "--frame", OP_FRAME, true }, { "--code", OP_CODE, true }, { "--code-table", OP_CODE_TABLE, true },
+        { "--repeats", OP_REPEATS, true }, { "--min-repeat", OP_MIN_REPEAT, true }, { "--whole-units", OP_WHOLE_UNITS, false } };
     for (int i = 1; i < argc; i++) {
         char *arg = argv[i];
         if (arg[0] != '-') {
@@ -343,6 +368,9 @@ static void parse_command_line(int argc, char **argv)
         case OP_FRAME: set_frames(v); break;
         case OP_CODE: set_code(v); break;
         case OP_CODE_TABLE: set_code_table(v); break;
+        case OP_REPEATS: set_repeats(v); break;
+        case OP_MIN_REPEAT: set_min_repeat(v); break;
+        case OP_WHOLE_UNITS: whole_units = true; break;
         }
     }
     if (print_version) {
@@ -465,6 +493,25 @@ static void parse_command_line(int argc, char **argv)
         if (kmers_k) die("--translate and --kmers can't be used together\n");
         if (code_text && code_table_text) die("--code and --code-table can't be used together\n");
         if (!code_text && !code_table_text) naf_gpu_genetic_code_by_id(1, &genetic_code);
+    }
+    if (min_repeat_given && !repeats_text) die("--min-repeat can be used only with --repeats\n");
+    if (whole_units && !repeats_text) die("--whole-units can be used only with --repeats\n");
+    if (repeats_text) {
+        if (n_locate) die("--repeats and --locate can't be used together\n");
+        if (composition) die("--repeats and --composition can't be used together\n");
+        if (quality) die("--repeats and --quality can't be used together\n");
+        if (runs_class || masked_runs) die("--repeats and %s can't be used together\n", runs_class ? "--runs" : "--masked-runs");
+        if (kmers_k) die("--repeats and --kmers can't be used together\n");
+        if (orfs) die("--repeats and --orfs can't be used together\n");
+        if (translate) die("--repeats and --translate can't be used together\n");
+        if (out_type != UNDECIDED) die("--repeats writes a table: no output type can be given with it\n");
+        if (revcomp) die("--repeats lists the sequences as stored: --revcomp can't be used with it\n");
+        if (n_selections > 1) die("--repeats can be restricted by one --records or one --region only\n");
+        if (n_selections && selections[0].rc) die("--repeats lists the sequences as stored: --rc-region can't be used with it\n");
+        if (n_selections && selections[0].region) {
+            size_t l; uint64_t b, e; naf_gpu_parse_region(selections[0].region, &l, &b, &e);
+            if (!(b == 0 && e == NAF_GPU_WHOLE)) die("--repeats can be restricted to a whole sequence only: --region ID, without a range\n");
+        }
     }
     if ((n_selections || revcomp) && !(out_type == UNDECIDED || out_type == FASTA || out_type == FASTQ || out_type == SEQ || out_type == SEQUENCES))
         die("--region can be used only with sequence output\n");
@@ -928,6 +975,47 @@ static void run_runs(bool has_ids, bool has_names)
     }
 }
 
+/* --repeats: the table of tandem repeats is made on the device (naf_gpu_unnaf_repeats: the run starts and ends of "equals the base p in front"
+ * per period, paired by rank and merged without a sort); the lines are formatted here, on the host, from the downloaded table. */
+static void run_repeats(bool has_ids, bool has_names)
+{
+    upload();
+    const unsigned long long N = H.n_sequences;
+    uint64_t first, count;
+    one_record_range(has_ids, &first, &count);
+    const int flags = whole_units ? NAF_GPU_REPEATS_WHOLE_UNITS : 0;
+    uint64_t n = 0;
+    GPU_TRY(naf_gpu_unnaf_repeats_count(gpu, d_naf, naf_len, &repeats_spec, flags, min_repeat, first, count, &n, NULL, NULL));
+    phase("repeats: count");
+    if (n) {
+        void *d_rows; GPU_TRY(naf_gpu_malloc(gpu, (size_t)n * sizeof(naf_gpu_repeat), &d_rows));
+        uint64_t got = 0;
+        GPU_TRY(naf_gpu_unnaf_repeats(gpu, d_naf, naf_len, &repeats_spec, flags, min_repeat, first, count, (naf_gpu_repeat *)d_rows, (size_t)n, &got, NULL, NULL));
+        if (got != n) die("can't decompress sequence\n");
+        phase("repeats: rows");
+        unsigned char *text; const char **name = record_names(has_ids, has_names, &text);
+        const size_t chunk = 1 << 20;
+        naf_gpu_repeat *rows = (naf_gpu_repeat *)malloc((n < chunk ? (size_t)n : chunk) * sizeof *rows); if (!rows) die("can't allocate memory\n");
+        const char *letters = H.seq_type == NAF_SEQ_RNA ? "ACGU" : "ACGT";
+        for (uint64_t a = 0; a < n; a += chunk) {
+            const size_t m = n - a < chunk ? (size_t)(n - a) : chunk;
+            GPU_TRY(naf_gpu_download(gpu, rows, (const naf_gpu_repeat *)d_rows + a, m * sizeof *rows));
+            for (size_t k = 0; k < m; k++) {
+                const naf_gpu_repeat *x = &rows[k];
+                uint32_t cls;
+                if (x->record >= N || x->end <= x->begin || naf_gpu_repeat_class(x->motif, x->period, &cls)) die("can't decompress sequence\n");
+                char motif[17], cl[17];
+                for (unsigned i = 0; i < x->period; i++) { motif[i] = letters[(x->motif >> (2 * i)) & 3]; cl[i] = letters[(cls >> (2 * i)) & 3]; }
+                motif[x->period] = cl[x->period] = 0;
+                fprintf(OUT, "%s\t%llu\t%llu\t%u\t%s\t%llu\t%s\n", name[x->record], (unsigned long long)x->begin, (unsigned long long)x->end, (unsigned)x->period, motif,
+                        (unsigned long long)((x->end - x->begin) / x->period), cl);
+            }
+        }
+        free(rows); free(name); free(text); naf_gpu_free(gpu, d_rows);
+        phase("repeats: download + lines");
+    }
+}
+
 /* --orfs: the table of reading frames is made on the device (naf_gpu_unnaf_orfs: the stops, starts and record bounds of the packed stream as
  * six lists, a stretch between two neighbours of one list); the lines are formatted here, on the host, from the downloaded table. */
 static void run_orfs(bool has_ids, bool has_names)
@@ -1099,7 +1187,7 @@ int main(int argc, char **argv)
     bool large = out_type == IDS || out_type == NAMES || out_type == LENGTHS || out_type == MASK || out_type == FOUR_BIT || out_type == DNA ||
                  out_type == MASKED_DNA || out_type == UNMASKED_DNA || out_type == SEQ || out_type == FASTA || out_type == MASKED_FASTA ||
                  out_type == UNMASKED_FASTA || out_type == FASTQ;
-    if (large && !n_locate && !composition && !quality && !runs_class && !masked_runs && !kmers_k && !orfs && !translate && !force_stdout && isatty(fileno(OUT)))
+    if (large && !n_locate && !composition && !quality && !runs_class && !masked_runs && !kmers_k && !orfs && !translate && !repeats_text && !force_stdout && isatty(fileno(OUT)))
         die("output file not specified - please either specify output file with '-o' or '>', or use '-c' option to force writing to console\n");
 
     unsigned long long N = H.n_sequences;
@@ -1123,6 +1211,10 @@ int main(int argc, char **argv)
     else if (orfs) {
         if (H.seq_type >= NAF_SEQ_PROTEIN) die("open reading frames cannot be listed in %s sequences\n", tn[H.seq_type]);
         run_orfs(has_ids, has_names);
+    }
+    else if (repeats_text) {
+        if (H.seq_type >= NAF_SEQ_PROTEIN) die("tandem repeats cannot be listed in %s sequences\n", tn[H.seq_type]);
+        run_repeats(has_ids, has_names);
     }
     else if (translate) {
         if (H.seq_type >= NAF_SEQ_PROTEIN) die("%s sequences cannot be translated\n", tn[H.seq_type]);
