@@ -331,6 +331,15 @@ def load():
     return _lib
 
 
+def _text_arg(text, what):
+    """The bytes of a text argument of a host-only parser (str: as latin1); one with a zero byte, where the C side would see the text
+    end, is ValueError("not WHAT: ...") like any other text the parser refuses."""
+    b = text.encode("latin1") if isinstance(text, str) else bytes(text)
+    if b"\0" in b:
+        raise ValueError("not %s: %r" % (what, text))
+    return b
+
+
 def parse_region(text):
     """Host-only: "ID", "ID:a-b", "ID:a-", "ID:a" (1-based, inclusive) -> (id, begin, end), 0-based half-open; a whole record is
     (id, 0, WHOLE).  ValueError when the text is no region (naf_gpu_parse_region)."""
@@ -345,9 +354,7 @@ def parse_region(text):
 def compile_motif(text):
     """Host-only: (fwd, rev) -- the 4-bit sets of an IUPAC pattern and of its reverse complement, as bytes of the pattern's length
     (naf_gpu_compile_motif).  ValueError for what is no pattern."""
-    b = text.encode("latin1") if isinstance(text, str) else bytes(text)
-    if b"\0" in b:
-        raise ValueError("not a pattern: %r" % (text,))
+    b = _text_arg(text, "a pattern")
     fwd, rev, n = (C.c_uint8 * 32)(), (C.c_uint8 * 32)(), C.c_size_t()
     if load().naf_gpu_compile_motif(b, fwd, rev, C.byref(n)):
         raise ValueError("not a pattern: %r" % (text,))
@@ -358,9 +365,7 @@ def compile_motif_near(text):
     """Host-only: (fwd, rev, fixed) of an IUPAC pattern that may hold bracketed runs of must-match letters (naf_gpu_compile_motif_near):
     the 4-bit sets as compile_motif gives them, and the bit mask of the bracketed letters by their index in the pattern, brackets not
     counted.  ValueError for what is no pattern."""
-    b = text.encode("latin1") if isinstance(text, str) else bytes(text)
-    if b"\0" in b:
-        raise ValueError("not a pattern: %r" % (text,))
+    b = _text_arg(text, "a pattern")
     fwd, rev, fixed, n = (C.c_uint8 * 32)(), (C.c_uint8 * 32)(), C.c_uint32(), C.c_size_t()
     if load().naf_gpu_compile_motif_near(b, fwd, rev, C.byref(fixed), C.byref(n)):
         raise ValueError("not a pattern: %r" % (text,))
@@ -390,9 +395,7 @@ def quality_error_table():
 def parse_base_class(text):
     """Host-only: the 16-bit set of a base class (naf_gpu_parse_base_class) -- bit c for 4-bit code c of "-TGKCYSBAWRDMHVN"; letters of
     ACGTU RYSWKM BDHV N and '-' in either case, a leading '^' complements.  ValueError for what is no class."""
-    b = text.encode("latin1") if isinstance(text, str) else bytes(text)
-    if b"\0" in b:
-        raise ValueError("not a base class: %r" % (text,))
+    b = _text_arg(text, "a base class")
     s = C.c_uint16()
     if load().naf_gpu_parse_base_class(b, C.byref(s)):
         raise ValueError("not a base class: %r" % (text,))
@@ -403,9 +406,7 @@ def kmer_index(text, canonical=False):
     """Host-only: (k, index) of a k-mer of 1 to 12 letters of ACGTU in either case (naf_gpu_kmer_index): A = 0, C = 1, G = 2, T/U = 3,
     the first base the most significant; canonical: the smaller of the index and that of the reverse complement.  ValueError for
     anything else."""
-    b = text.encode("latin1") if isinstance(text, str) else bytes(text)
-    if b"\0" in b:
-        raise ValueError("not a k-mer: %r" % (text,))
+    b = _text_arg(text, "a k-mer")
     k, idx = C.c_uint(), C.c_uint64()
     if load().naf_gpu_kmer_index(b, 1 if canonical else 0, C.byref(k), C.byref(idx)):
         raise ValueError("not a k-mer: %r" % (text,))
@@ -426,9 +427,7 @@ def kmer_text(k, index):
 def parse_codon_set(text):
     """Host-only: the 64-bit set of a comma-separated list of codons (naf_gpu_parse_codon_set) -- bit i for the codon of index i under
     kmer_index at K = 3 --; three letters each, either case, U = T, the IUPAC letters RYSWKM BDHV N expand.  ValueError for anything else."""
-    b = text.encode("latin1") if isinstance(text, str) else bytes(text)
-    if b"\0" in b:
-        raise ValueError("not a list of codons: %r" % (text,))
+    b = _text_arg(text, "a list of codons")
     s = C.c_uint64()
     if load().naf_gpu_parse_codon_set(b, C.byref(s)):
         raise ValueError("not a list of codons: %r" % (text,))
@@ -448,8 +447,7 @@ def genetic_code(id_or_letters=1):
         return g
     if not isinstance(id_or_letters, (str, bytes)):
         raise ValueError("not a genetic code: %r" % (id_or_letters,))
-    b = id_or_letters.encode("latin1") if isinstance(id_or_letters, str) else bytes(id_or_letters)
-    if b"\0" in b or load().naf_gpu_genetic_code_parse(b, C.byref(g)):
+    if load().naf_gpu_genetic_code_parse(_text_arg(id_or_letters, "a genetic code"), C.byref(g)):
         raise ValueError("not a genetic code: %r" % (id_or_letters,))
     return g
 
@@ -525,9 +523,8 @@ def runs_to_segments(runs, flank=0, lengths=None):
 def parse_repeat_spec(text):
     """Host-only: the sixteen min_copies of a repeat spec in MISA's definition syntax -- "1-10,2-6,3-5", or the word "misa"
     (naf_gpu_parse_repeat_spec) -- as a list, [p - 1] for period p, 0 where the period is not searched.  ValueError for what is no spec."""
-    b = text.encode("latin1") if isinstance(text, str) else bytes(text)
     sp = RepeatSpec()
-    if b"\0" in b or load().naf_gpu_parse_repeat_spec(b, C.byref(sp)):
+    if load().naf_gpu_parse_repeat_spec(_text_arg(text, "a repeat spec"), C.byref(sp)):
         raise ValueError("not a repeat spec: %r" % (text,))
     return [int(v) for v in sp.min_copies]
 
@@ -901,6 +898,39 @@ class Context:
         self._check(self.L.naf_gpu_unnaf_translate(self.h, _ptr(d_naf), d_naf.numel(), C.byref(o), C.byref(g), segs, strands, len(segments), _ptr(out), out.numel(), C.byref(n)))
         return out[:n.value]
 
+    def _guessed_table(self, call, n, row_bytes, dtype, out):
+        """The table of rows that `call(tensor, capacity in rows)` writes, leaving the number of rows in `n` and returning the library's
+        code.  out: the caller's uint8 device tensor takes it, and the torch view of the bytes written is returned.  Without it the rows
+        come back as a structured numpy array, from a table sized by a guess of 4096 rows first and by the whole number when that was
+        too small (the call reports it with E_CAP)."""
+        import numpy as np
+        import torch
+        if out is not None:
+            self._check(call(out, out.numel() // row_bytes))
+            return out[:row_bytes * n.value]
+        cap = 4096
+        buf = torch.empty(row_bytes * cap, dtype=torch.uint8, device=self.device)
+        rc = call(buf, cap)
+        if rc == E_CAP:
+            cap = n.value
+            buf = torch.empty(row_bytes * cap, dtype=torch.uint8, device=self.device)
+            rc = call(buf, cap)
+        self._check(rc)
+        return np.frombuffer(buf[:row_bytes * n.value].cpu().numpy().tobytes(), dtype=dtype)
+
+    def _counted_table(self, count, call, n, row_bytes, dtype, out):
+        """As _guessed_table, for a table that is counted first: without `out`, `count()` leaves the number of rows in `n` and the
+        table is made that large."""
+        import numpy as np
+        import torch
+        if out is not None:
+            self._check(call(out, out.numel() // row_bytes))
+            return out[:row_bytes * n.value]
+        self._check(count())
+        buf = torch.empty(max(row_bytes * n.value, 1), dtype=torch.uint8, device=self.device)
+        self._check(call(buf, n.value))
+        return np.frombuffer(buf[:row_bytes * n.value].cpu().numpy().tobytes(), dtype=dtype)
+
     @staticmethod
     def _patterns(patterns):
         raw = [p.encode("latin1") if isinstance(p, str) else bytes(p) for p in patterns]
@@ -921,20 +951,17 @@ class Context:
         """(hits, total): the hits as a structured numpy array (HIT_DTYPE: record, begin, pattern, strand) in the order of the contract --
         (record, begin), pattern number, strand.  out: a uint8 device tensor to take the table (24 bytes a hit); then `hits` is the torch
         view of its first 24 * total bytes and too small a tensor raises NafGpuError(E_CAP).  Without it the table is counted first."""
-        import numpy as np
-        import torch
         blob, n = self._patterns(patterns)
         total = C.c_uint64()
         cnt = WHOLE if count is None else int(count)
-        if out is not None:
-            self._check(self.L.naf_gpu_unnaf_locate(self.h, _ptr(d_naf), d_naf.numel(), blob, len(blob), n, int(strands), int(first), cnt,
-                                                    _ptr(out), out.numel() // 24, C.byref(total)))
-            return out[:24 * total.value], total.value
-        self._check(self.L.naf_gpu_unnaf_locate_count(self.h, _ptr(d_naf), d_naf.numel(), blob, len(blob), n, int(strands), int(first), cnt, C.byref(total), None))
-        buf = torch.empty(max(24 * total.value, 1), dtype=torch.uint8, device=self.device)
-        self._check(self.L.naf_gpu_unnaf_locate(self.h, _ptr(d_naf), d_naf.numel(), blob, len(blob), n, int(strands), int(first), cnt,
-                                                _ptr(buf), total.value, C.byref(total)))
-        return np.frombuffer(buf[:24 * total.value].cpu().numpy().tobytes(), dtype=HIT_DTYPE), total.value
+
+        def counted():
+            return self.L.naf_gpu_unnaf_locate_count(self.h, _ptr(d_naf), d_naf.numel(), blob, len(blob), n, int(strands), int(first), cnt, C.byref(total), None)
+
+        def call(buf, cap):
+            return self.L.naf_gpu_unnaf_locate(self.h, _ptr(d_naf), d_naf.numel(), blob, len(blob), n, int(strands), int(first), cnt, _ptr(buf), cap, C.byref(total))
+        hits = self._counted_table(counted, call, total, 24, HIT_DTYPE, out)
+        return hits, total.value
 
     @staticmethod
     def _budgets(mismatches, n):
@@ -962,21 +989,18 @@ class Context:
         """(hits, total): the near hits as a structured numpy array (NEAR_HIT_DTYPE: record, begin, pattern, strand, mismatches, where) in
         the order of the contract.  out: a uint8 device tensor to take the table (32 bytes a hit); then `hits` is the torch view of its
         first 32 * total bytes and too small a tensor raises NafGpuError(E_CAP).  Without it the table is counted first."""
-        import numpy as np
-        import torch
         blob, n = self._patterns(patterns)
         budgets = self._budgets(mismatches, n)
         total = C.c_uint64()
         cnt = WHOLE if count is None else int(count)
-        if out is not None:
-            self._check(self.L.naf_gpu_unnaf_locate_near(self.h, _ptr(d_naf), d_naf.numel(), blob, len(blob), n, budgets, int(strands), int(first), cnt,
-                                                         _ptr(out), out.numel() // 32, C.byref(total)))
-            return out[:32 * total.value], total.value
-        self._check(self.L.naf_gpu_unnaf_locate_near_count(self.h, _ptr(d_naf), d_naf.numel(), blob, len(blob), n, budgets, int(strands), int(first), cnt, C.byref(total), None))
-        buf = torch.empty(max(32 * total.value, 1), dtype=torch.uint8, device=self.device)
-        self._check(self.L.naf_gpu_unnaf_locate_near(self.h, _ptr(d_naf), d_naf.numel(), blob, len(blob), n, budgets, int(strands), int(first), cnt,
-                                                     _ptr(buf), total.value, C.byref(total)))
-        return np.frombuffer(buf[:32 * total.value].cpu().numpy().tobytes(), dtype=NEAR_HIT_DTYPE), total.value
+
+        def counted():
+            return self.L.naf_gpu_unnaf_locate_near_count(self.h, _ptr(d_naf), d_naf.numel(), blob, len(blob), n, budgets, int(strands), int(first), cnt, C.byref(total), None)
+
+        def call(buf, cap):
+            return self.L.naf_gpu_unnaf_locate_near(self.h, _ptr(d_naf), d_naf.numel(), blob, len(blob), n, budgets, int(strands), int(first), cnt, _ptr(buf), cap, C.byref(total))
+        hits = self._counted_table(counted, call, total, 32, NEAR_HIT_DTYPE, out)
+        return hits, total.value
 
     def unnaf_composition_rows(self, d_naf, window=0, first=0, count=None):
         """The rows unnaf_composition gives for records [first, first + count) under `window` (naf_gpu_unnaf_composition_rows: the lengths
@@ -991,20 +1015,17 @@ class Context:
         (its record: the records covered, its end: their bases).  mask: count the soft-masked bases (NAF_GPU_COMP_MASK).  out: a uint8
         device tensor to take the table (168 bytes a row); then `rows` is the torch view of its first 168 * n bytes and too small a
         tensor raises NafGpuError(E_CAP).  Without it the rows are counted first (naf_gpu_unnaf_composition_rows)."""
-        import numpy as np
-        import torch
         n, tot = C.c_uint64(), CompRow()
         cnt = WHOLE if count is None else int(count)
         flags = COMP_MASK if mask else 0
-        if out is not None:
-            self._check(self.L.naf_gpu_unnaf_composition(self.h, _ptr(d_naf), d_naf.numel(), int(window), flags, int(first), cnt,
-                                                         _ptr(out), out.numel() // COMP_ROW_BYTES, C.byref(n), C.byref(tot)))
-            return out[:COMP_ROW_BYTES * n.value], tot
-        self._check(self.L.naf_gpu_unnaf_composition_rows(self.h, _ptr(d_naf), d_naf.numel(), int(window), int(first), cnt, C.byref(n)))
-        buf = torch.empty(max(COMP_ROW_BYTES * n.value, 1), dtype=torch.uint8, device=self.device)
-        self._check(self.L.naf_gpu_unnaf_composition(self.h, _ptr(d_naf), d_naf.numel(), int(window), flags, int(first), cnt,
-                                                     _ptr(buf), n.value, C.byref(n), C.byref(tot)))
-        return np.frombuffer(buf[:COMP_ROW_BYTES * n.value].cpu().numpy().tobytes(), dtype=COMP_DTYPE), tot
+
+        def counted():
+            return self.L.naf_gpu_unnaf_composition_rows(self.h, _ptr(d_naf), d_naf.numel(), int(window), int(first), cnt, C.byref(n))
+
+        def call(buf, cap):
+            return self.L.naf_gpu_unnaf_composition(self.h, _ptr(d_naf), d_naf.numel(), int(window), flags, int(first), cnt, _ptr(buf), cap, C.byref(n), C.byref(tot))
+        rows = self._counted_table(counted, call, n, COMP_ROW_BYTES, COMP_DTYPE, out)
+        return rows, tot
 
     def unnaf_quality_rows(self, d_naf, cycle_bin=0, first=0, count=None):
         """(record rows, cycle rows) that unnaf_quality gives for records [first, first + count) under `cycle_bin`
@@ -1072,26 +1093,14 @@ class Context:
         and the sum of their lengths.  out: a uint8 device tensor to take the table (32 bytes a run); then `rows` is the torch view of
         its first 32 * n bytes and too small a tensor raises NafGpuError(E_CAP).  Without it a table sized by a guess is tried first and
         one of the whole count when that was too small (the call reports it with E_CAP)."""
-        import numpy as np
-        import torch
         s, flags = self._run_class(cls, each, masked)
         n, nb = C.c_uint64(), C.c_uint64()
         cnt = WHOLE if count is None else int(count)
 
         def call(buf, cap):
             return self.L.naf_gpu_unnaf_runs(self.h, _ptr(d_naf), d_naf.numel(), s, flags, int(min_len), int(first), cnt, _ptr(buf), cap, C.byref(n), C.byref(nb))
-        if out is not None:
-            self._check(call(out, out.numel() // RUN_BYTES))
-            return out[:RUN_BYTES * n.value], nb.value
-        cap = 4096
-        buf = torch.empty(RUN_BYTES * cap, dtype=torch.uint8, device=self.device)
-        rc = call(buf, cap)
-        if rc == E_CAP:
-            cap = n.value
-            buf = torch.empty(RUN_BYTES * cap, dtype=torch.uint8, device=self.device)
-            rc = call(buf, cap)
-        self._check(rc)
-        return np.frombuffer(buf[:RUN_BYTES * n.value].cpu().numpy().tobytes(), dtype=RUN_DTYPE), nb.value
+        rows = self._guessed_table(call, n, RUN_BYTES, RUN_DTYPE, out)
+        return rows, nb.value
 
     @staticmethod
     def _repeat_spec(spec):
@@ -1118,26 +1127,14 @@ class Context:
         out: a uint8 device tensor to take the table (32 bytes a row); then `rows` is the torch view of its first 32 * n bytes and too
         small a tensor raises NafGpuError(E_CAP).  Without it a table sized by a guess is tried first and one of the whole count when
         that was too small (the call reports it with E_CAP)."""
-        import numpy as np
-        import torch
         sp = self._repeat_spec(spec)
         n, nb, pp = C.c_uint64(), C.c_uint64(), (C.c_uint64 * 16)()
         cnt, flags = WHOLE if count is None else int(count), REPEATS_WHOLE_UNITS if whole_units else 0
 
         def call(buf, cap):
             return self.L.naf_gpu_unnaf_repeats(self.h, _ptr(d_naf), d_naf.numel(), C.byref(sp), flags, int(min_len), int(first), cnt, _ptr(buf), cap, C.byref(n), C.byref(nb), pp)
-        if out is not None:
-            self._check(call(out, out.numel() // REPEAT_BYTES))
-            return out[:REPEAT_BYTES * n.value], nb.value, [int(v) for v in pp]
-        cap = 4096
-        buf = torch.empty(REPEAT_BYTES * cap, dtype=torch.uint8, device=self.device)
-        rc = call(buf, cap)
-        if rc == E_CAP:
-            cap = n.value
-            buf = torch.empty(REPEAT_BYTES * cap, dtype=torch.uint8, device=self.device)
-            rc = call(buf, cap)
-        self._check(rc)
-        return np.frombuffer(buf[:REPEAT_BYTES * n.value].cpu().numpy().tobytes(), dtype=REPEAT_DTYPE), nb.value, [int(v) for v in pp]
+        rows = self._guessed_table(call, n, REPEAT_BYTES, REPEAT_DTYPE, out)
+        return rows, nb.value, [int(v) for v in pp]
 
     @staticmethod
     def _orf_args(stops, starts, strands, split_unknown, closed):
@@ -1165,26 +1162,14 @@ class Context:
         begin, end, strand), and the sum of their lengths.  out: a uint8 device tensor to take the table (32 bytes a row); then `rows`
         is the torch view of its first 32 * n bytes and too small a tensor raises NafGpuError(E_CAP).  Without it a table sized by a
         guess is tried first and one of the whole count when that was too small (the call reports it with E_CAP)."""
-        import numpy as np
-        import torch
         st, sa, sd, flags = self._orf_args(stops, starts, strands, split_unknown, closed)
         n, nb = C.c_uint64(), C.c_uint64()
         cnt = WHOLE if count is None else int(count)
 
         def call(buf, cap):
             return self.L.naf_gpu_unnaf_orfs(self.h, _ptr(d_naf), d_naf.numel(), st, sa, int(min_len), sd, flags, int(first), cnt, _ptr(buf), cap, C.byref(n), C.byref(nb))
-        if out is not None:
-            self._check(call(out, out.numel() // ORF_BYTES))
-            return out[:ORF_BYTES * n.value], nb.value
-        cap = 4096
-        buf = torch.empty(ORF_BYTES * cap, dtype=torch.uint8, device=self.device)
-        rc = call(buf, cap)
-        if rc == E_CAP:
-            cap = n.value
-            buf = torch.empty(ORF_BYTES * cap, dtype=torch.uint8, device=self.device)
-            rc = call(buf, cap)
-        self._check(rc)
-        return np.frombuffer(buf[:ORF_BYTES * n.value].cpu().numpy().tobytes(), dtype=ORF_DTYPE), nb.value
+        rows = self._guessed_table(call, n, ORF_BYTES, ORF_DTYPE, out)
+        return rows, nb.value
 
     def unnaf_kmers_rows(self, d_naf, k, canonical=False, per_record=False, first=0, count=None):
         """(n_rows, n_counters) of the tables unnaf_kmers gives for records [first, first + count) (naf_gpu_unnaf_kmers_rows: the lengths

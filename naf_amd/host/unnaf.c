@@ -110,28 +110,18 @@ static void set_strand(const char *v)
     strand_given = true;
 }
 
-static void set_window(const char *v)
+/* --window, --cycles, --min-run, --min-orf, --min-repeat: a positive number of `unit`; commas are skipped (1,000) */
+static unsigned long long positive_number(const char *opt, const char *unit, const char *v)
 {
-    unsigned long long a = 0; bool digit = false;
+    unsigned long long a = 0; bool ok = false;
     for (const char *p = v; *p; p++) {
         if (*p == ',') continue;
-        if (*p < '0' || *p > '9' || a > (ULLONG_MAX - (unsigned)(*p - '0')) / 10) die("can't parse the value of --window parameter (a positive number of bases)\n");
-        a = a * 10 + (unsigned)(*p - '0'); digit = true;
+        ok = *p >= '0' && *p <= '9' && a <= (ULLONG_MAX - (unsigned)(*p - '0')) / 10;
+        if (!ok) break;
+        a = a * 10 + (unsigned)(*p - '0');
     }
-    if (!digit || a == 0) die("can't parse the value of --window parameter (a positive number of bases)\n");
-    comp_window = a; window_given = true;
-}
-
-static void set_cycles(const char *v)
-{
-    unsigned long long a = 0; bool digit = false;
-    for (const char *p = v; *p; p++) {
-        if (*p == ',') continue;
-        if (*p < '0' || *p > '9' || a > (ULLONG_MAX - (unsigned)(*p - '0')) / 10) die("can't parse the value of --cycles parameter (a positive number of read positions)\n");
-        a = a * 10 + (unsigned)(*p - '0'); digit = true;
-    }
-    if (!digit || a == 0) die("can't parse the value of --cycles parameter (a positive number of read positions)\n");
-    qual_cycles = a; cycles_given = true;
+    if (!ok || a == 0) die("can't parse the value of %s parameter (a positive number of %s)\n", opt, unit);
+    return a;
 }
 
 static void set_runs(const char *v)
@@ -140,34 +130,12 @@ static void set_runs(const char *v)
     if (naf_gpu_parse_base_class(v, &runs_set) || !runs_set) die("can't parse the value of --runs parameter (letters of ACGTU RYSWKM BDHV N and -, ^ in front for all the others)\n");
     runs_class = v;
 }
-static void set_min_run(const char *v)
-{
-    unsigned long long a = 0; bool digit = false;
-    for (const char *p = v; *p; p++) {
-        if (*p == ',') continue;
-        if (*p < '0' || *p > '9' || a > (ULLONG_MAX - (unsigned)(*p - '0')) / 10) die("can't parse the value of --min-run parameter (a positive number of bases)\n");
-        a = a * 10 + (unsigned)(*p - '0'); digit = true;
-    }
-    if (!digit || a == 0) die("can't parse the value of --min-run parameter (a positive number of bases)\n");
-    min_run = a; min_run_given = true;
-}
 
 static void set_repeats(const char *v)
 {
     if (repeats_text) die("only one --repeats definition can be given\n");
     if (naf_gpu_parse_repeat_spec(v, &repeats_spec)) die("can't parse the value of --repeats parameter (PERIOD-COPIES pairs joined by commas, periods 1 to 16, at least 2 copies, e.g. 1-10,2-6,3-5; or misa)\n");
     repeats_text = v;
-}
-static void set_min_repeat(const char *v)
-{
-    unsigned long long a = 0; bool digit = false;
-    for (const char *p = v; *p; p++) {
-        if (*p == ',') continue;
-        if (*p < '0' || *p > '9' || a > (ULLONG_MAX - (unsigned)(*p - '0')) / 10) die("can't parse the value of --min-repeat parameter (a positive number of bases)\n");
-        a = a * 10 + (unsigned)(*p - '0'); digit = true;
-    }
-    if (!digit || a == 0) die("can't parse the value of --min-repeat parameter (a positive number of bases)\n");
-    min_repeat = a; min_repeat_given = true;
 }
 
 static void set_kmers(const char *v)
@@ -187,17 +155,6 @@ static void set_codons(const char *opt, const char *v, const char **text, uint64
     if (*text) die("only one %s list can be given\n", opt);
     if (naf_gpu_parse_codon_set(v, set)) die("can't parse the value of %s parameter (comma-separated codons of three IUPAC nucleotide letters, e.g. TAA,TAG,TGA)\n", opt);
     *text = v;
-}
-static void set_min_orf(const char *v)
-{
-    unsigned long long a = 0; bool digit = false;
-    for (const char *p = v; *p; p++) {
-        if (*p == ',') continue;
-        if (*p < '0' || *p > '9' || a > (ULLONG_MAX - (unsigned)(*p - '0')) / 10) die("can't parse the value of --min-orf parameter (a positive number of bases)\n");
-        a = a * 10 + (unsigned)(*p - '0'); digit = true;
-    }
-    if (!digit || a == 0) die("can't parse the value of --min-orf parameter (a positive number of bases)\n");
-    min_orf = a; min_orf_given = true;
 }
 
 static void set_frames(const char *v)
@@ -291,6 +248,107 @@ static void show_help(void)
         "  --whole-units   - With --repeats: the end of a repeat is cut to a whole number of copies, as MISA and PERF print it\n");
 }
 
+/* ---- the table modes ---------------------------------------------------------------------------------------------------------------
+ * --locate, --composition, --quality, --runs / --masked-runs, --kmers, --orfs, --translate and --repeats write a table of their own
+ * instead of an output type.  A mode is a row here -- what its refusals say, its options, its runner -- plus the checks that are
+ * really its own; parse_command_line walks the rows once, in this order, and main runs the first one asked for (--orfs in front
+ * of --translate: the one legal pair). */
+typedef struct { bool given, fits; const char *refusal; } satellite;        /* an option of a mode: given; given together with what it belongs to */
+typedef struct table_mode {
+    bool asked; const char *name;                   /* the option, as messages name the mode */
+    const char *writes;                             /* "NAME writes WRITES: no output type can be given with it" */
+    const char *strands;                            /* "NAME STRANDS: --revcomp [--rc-region] can't be used with it" */
+    bool one_selection;                             /* at most one --records or one --region ID, as stored (not --translate: any selection) */
+    bool type_first;                                /* the output type is refused in front of another mode, not behind it */
+    satellite sat[7];                               /* refused without the mode, in this order; ends at the first without a refusal */
+    void (*early)(void);                            /* what holds whether the mode was asked for or not, behind the satellites */
+    void (*own)(const struct table_mode *);         /* the mode's own checks and defaults, behind the output type */
+    const char *protein;                            /* main's refusal of protein and text archives (%s: which), NULL: none */
+    void (*run)(bool has_ids, bool has_names);
+} table_mode;
+enum { M_LOCATE, M_COMPOSITION, M_QUALITY, M_RUNS, M_KMERS, M_ORFS, M_TRANSLATE, M_REPEATS, N_MODES };
+static table_mode modes[N_MODES];
+static void run_locate(bool, bool), run_composition(bool, bool), run_quality(bool, bool), run_runs(bool, bool), run_kmers(bool, bool), run_orfs(bool, bool),
+            run_translate(bool, bool), run_repeats(bool, bool);
+
+static void refuse_output_type(const table_mode *m) { if (out_type != UNDECIDED) die("%s writes %s: no output type can be given with it\n", m->name, m->writes); }
+static void refuse_revcomp(const table_mode *m) { if (revcomp) die("%s %s: --revcomp can't be used with it\n", m->name, m->strands); }
+static void one_whole_selection(const table_mode *m)
+{
+    refuse_revcomp(m);
+    if (n_selections > 1) die("%s can be restricted by one --records or one --region only\n", m->name);
+    if (n_selections && selections[0].rc) die("%s %s: --rc-region can't be used with it\n", m->name, m->strands);
+    if (n_selections && selections[0].region) {
+        size_t l; uint64_t b, e; naf_gpu_parse_region(selections[0].region, &l, &b, &e);
+        if (!(b == 0 && e == NAF_GPU_WHOLE)) die("%s can be restricted to a whole sequence only: --region ID, without a range\n", m->name);
+    }
+}
+
+static void locate_early(void)
+{
+    if (locate_mismatches) for (size_t k = 0; k < n_locate; k++) if (locate_mismatches >= locate_free_letters[k])
+        die("--mismatches %u leaves nothing of --locate %s to match: it must be smaller than the pattern's %zu letters outside brackets\n", locate_mismatches, locate_patterns[k], locate_free_letters[k]);
+}
+static void runs_early(void) { if (runs_class && masked_runs) die("--runs and --masked-runs can't be used together\n"); }
+static void kmers_own(const table_mode *m)
+{
+    (void)m;
+    if (kmers_per_record && kmers_k > 6) die("--per-record writes one column per k-mer: --kmers can be 6 at the most with it\n");
+}
+static void orfs_own(const table_mode *m)
+{
+    if (stop_to_stop && orf_starts_text) die("--stop-to-stop and --starts can't be used together\n");
+    if (!orf_stops_text && translate && (code_text || code_table_text)) naf_gpu_genetic_code_stops(&genetic_code, &orf_stops);      /* the code's own stops close the frames */
+    else if (!orf_stops_text) naf_gpu_parse_codon_set("TAA,TAG,TGA", &orf_stops);
+    if (stop_to_stop) orf_starts = 0; else if (!orf_starts_text) naf_gpu_parse_codon_set("ATG", &orf_starts);
+    if (orf_starts & orf_stops) die("--starts and --stops share a codon: a codon can't both open and close a reading frame\n");
+    refuse_revcomp(m);                                              /* (in front of --frame, where it always stood) */
+    if (frame_text && translate) die("--frame can't be used with --orfs: every reading frame of the table is translated in its own frame\n");
+}
+static void translate_own(const table_mode *m)
+{
+    (void)m;
+    if (code_text && code_table_text) die("--code and --code-table can't be used together\n");
+    if (!code_text && !code_table_text) naf_gpu_genetic_code_by_id(1, &genetic_code);
+}
+
+/* the rows, from the options as they were given */
+static void fill_modes(void)
+{
+    const bool runs = runs_class || masked_runs;
+    modes[M_LOCATE] = (table_mode){ .asked = n_locate != 0, .name = "--locate", .writes = "BED lines", .strands = "searches both strands itself (--strand)", .one_selection = true,
+        .sat = { { strand_given, n_locate || orfs, "--strand can be used only with --locate\n" }, { mismatches_given, n_locate != 0, "--mismatches can be used only with --locate\n" } },
+        .early = locate_early, .protein = "nucleotide motifs cannot be searched in %s sequences\n", .run = run_locate };
+    modes[M_COMPOSITION] = (table_mode){ .asked = composition, .name = "--composition", .writes = "a table", .strands = "counts the sequences as stored", .one_selection = true,
+        .sat = { { window_given, composition, "--window can be used only with --composition\n" } },
+        .protein = "nucleotides cannot be counted in %s sequences\n", .run = run_composition };
+    modes[M_QUALITY] = (table_mode){ .asked = quality, .name = "--quality", .writes = "a table", .strands = "reads the qualities as stored", .one_selection = true,
+        .sat = { { cycles_given, quality, "--cycles can be used only with --quality\n" } }, .run = run_quality };
+    modes[M_RUNS] = (table_mode){ .asked = runs, .name = runs_class ? "--runs" : "--masked-runs", .writes = "BED lines", .strands = "lists the sequences as stored", .one_selection = true,
+        .sat = { { min_run_given, runs, "--min-run can be used only with --runs or --masked-runs\n" }, { runs_each, runs_class != NULL, "--each can be used only with --runs\n" } },
+        .early = runs_early, .protein = "runs of bases cannot be listed in %s sequences\n", .run = run_runs };
+    modes[M_KMERS] = (table_mode){ .asked = kmers_k != 0, .name = "--kmers", .writes = "a table", .strands = "counts the sequences as stored", .one_selection = true,
+        .sat = { { kmers_canonical, kmers_k != 0, "--canonical can be used only with --kmers\n" }, { kmers_per_record, kmers_k != 0, "--per-record can be used only with --kmers\n" } },
+        .own = kmers_own, .protein = "k-mers cannot be counted in %s sequences\n", .run = run_kmers };
+    modes[M_ORFS] = (table_mode){ .asked = orfs, .name = "--orfs", .writes = "a table", .strands = "reads both strands itself (--strand)", .one_selection = true,
+        .sat = { { min_orf_given, orfs, "--min-orf can be used only with --orfs\n" }, { orf_stops_text != NULL, orfs, "--stops can be used only with --orfs\n" },
+                 { orf_starts_text != NULL, orfs, "--starts can be used only with --orfs\n" }, { stop_to_stop, orfs, "--stop-to-stop can be used only with --orfs\n" },
+                 { orfs_closed, orfs, "--closed can be used only with --orfs\n" }, { orfs_split, orfs, "--split-unknown can be used only with --orfs\n" } },
+        .own = orfs_own, .protein = "open reading frames cannot be listed in %s sequences\n", .run = run_orfs };
+    modes[M_TRANSLATE] = (table_mode){ .asked = translate, .name = "--translate", .writes = "protein FASTA", .type_first = true,
+        .sat = { { frame_text != NULL, translate, "--frame can be used only with --translate\n" }, { code_text != NULL, translate, "--code can be used only with --translate\n" },
+                 { code_table_text != NULL, translate, "--code-table can be used only with --translate\n" } },
+        .own = translate_own, .protein = "%s sequences cannot be translated\n", .run = run_translate };
+    modes[M_REPEATS] = (table_mode){ .asked = repeats_text != NULL, .name = "--repeats", .writes = "a table", .strands = "lists the sequences as stored", .one_selection = true,
+        .sat = { { min_repeat_given, repeats_text != NULL, "--min-repeat can be used only with --repeats\n" }, { whole_units, repeats_text != NULL, "--whole-units can be used only with --repeats\n" } },
+        .protein = "tandem repeats cannot be listed in %s sequences\n", .run = run_repeats };
+}
+static const table_mode *asked_mode(void)
+{
+    for (const table_mode *m = modes; m < modes + N_MODES; m++) if (m->asked) return m;
+    return NULL;
+}
+
 static void parse_command_line(int argc, char **argv)
 {
     bool print_version = false;
@@ -347,18 +405,18 @@ static void parse_command_line(int argc, char **argv)
         case OP_STRAND: set_strand(v); break;
         case OP_MISMATCHES: set_mismatches(v); break;
         case OP_COMPOSITION: composition = true; break;
-        case OP_WINDOW: set_window(v); break;
+        case OP_WINDOW: comp_window = positive_number("--window", "bases", v); window_given = true; break;
         case OP_QUALITY: quality = true; break;
-        case OP_CYCLES: set_cycles(v); break;
+        case OP_CYCLES: qual_cycles = positive_number("--cycles", "read positions", v); cycles_given = true; break;
         case OP_RUNS: set_runs(v); break;
         case OP_MASKED_RUNS: masked_runs = true; break;
-        case OP_MIN_RUN: set_min_run(v); break;
+        case OP_MIN_RUN: min_run = positive_number("--min-run", "bases", v); min_run_given = true; break;
         case OP_EACH: runs_each = true; break;
         case OP_KMERS: set_kmers(v); break;
         case OP_CANONICAL: kmers_canonical = true; break;
         case OP_PER_RECORD: kmers_per_record = true; break;
         case OP_ORFS: orfs = true; break;
-        case OP_MIN_ORF: set_min_orf(v); break;
+        case OP_MIN_ORF: min_orf = positive_number("--min-orf", "bases", v); min_orf_given = true; break;
         case OP_STOPS: set_codons("--stops", v, &orf_stops_text, &orf_stops); break;
         case OP_STARTS: set_codons("--starts", v, &orf_starts_text, &orf_starts); break;
         case OP_STOP_TO_STOP: stop_to_stop = true; break;
@@ -369,7 +427,7 @@ static void parse_command_line(int argc, char **argv)
         case OP_CODE: set_code(v); break;
         case OP_CODE_TABLE: set_code_table(v); break;
         case OP_REPEATS: set_repeats(v); break;
-        case OP_MIN_REPEAT: set_min_repeat(v); break;
+        case OP_MIN_REPEAT: min_repeat = positive_number("--min-repeat", "bases", v); min_repeat_given = true; break;
         case OP_WHOLE_UNITS: whole_units = true; break;
         }
     }
@@ -379,139 +437,18 @@ static void parse_command_line(int argc, char **argv)
         exit(0);
     }
     if (force_stdout && out_file_path) die("-c and -o arguments can't be used together\n");
-    if (strand_given && !n_locate && !orfs) die("--strand can be used only with --locate\n");
-    if (mismatches_given && !n_locate) die("--mismatches can be used only with --locate\n");
-    if (locate_mismatches) for (size_t k = 0; k < n_locate; k++) if (locate_mismatches >= locate_free_letters[k])
-        die("--mismatches %u leaves nothing of --locate %s to match: it must be smaller than the pattern's %zu letters outside brackets\n", locate_mismatches, locate_patterns[k], locate_free_letters[k]);
-    if (n_locate) {
-        if (out_type != UNDECIDED) die("--locate writes BED lines: no output type can be given with it\n");
-        if (revcomp) die("--locate searches both strands itself (--strand): --revcomp can't be used with it\n");
-        if (n_selections > 1) die("--locate can be restricted by one --records or one --region only\n");
-        if (n_selections && selections[0].rc) die("--locate searches both strands itself (--strand): --rc-region can't be used with it\n");
-        if (n_selections && selections[0].region) {
-            size_t l; uint64_t b, e; naf_gpu_parse_region(selections[0].region, &l, &b, &e);
-            if (!(b == 0 && e == NAF_GPU_WHOLE)) die("--locate can be restricted to a whole sequence only: --region ID, without a range\n");
-        }
-    }
-    if (window_given && !composition) die("--window can be used only with --composition\n");
-    if (composition) {
-        if (n_locate) die("--composition and --locate can't be used together\n");
-        if (out_type != UNDECIDED) die("--composition writes a table: no output type can be given with it\n");
-        if (revcomp) die("--composition counts the sequences as stored: --revcomp can't be used with it\n");
-        if (n_selections > 1) die("--composition can be restricted by one --records or one --region only\n");
-        if (n_selections && selections[0].rc) die("--composition counts the sequences as stored: --rc-region can't be used with it\n");
-        if (n_selections && selections[0].region) {
-            size_t l; uint64_t b, e; naf_gpu_parse_region(selections[0].region, &l, &b, &e);
-            if (!(b == 0 && e == NAF_GPU_WHOLE)) die("--composition can be restricted to a whole sequence only: --region ID, without a range\n");
-        }
-    }
-    if (cycles_given && !quality) die("--cycles can be used only with --quality\n");
-    if (quality) {
-        if (n_locate) die("--quality and --locate can't be used together\n");
-        if (composition) die("--quality and --composition can't be used together\n");
-        if (out_type != UNDECIDED) die("--quality writes a table: no output type can be given with it\n");
-        if (revcomp) die("--quality reads the qualities as stored: --revcomp can't be used with it\n");
-        if (n_selections > 1) die("--quality can be restricted by one --records or one --region only\n");
-        if (n_selections && selections[0].rc) die("--quality reads the qualities as stored: --rc-region can't be used with it\n");
-        if (n_selections && selections[0].region) {
-            size_t l; uint64_t b, e; naf_gpu_parse_region(selections[0].region, &l, &b, &e);
-            if (!(b == 0 && e == NAF_GPU_WHOLE)) die("--quality can be restricted to a whole sequence only: --region ID, without a range\n");
-        }
-    }
-    if (min_run_given && !runs_class && !masked_runs) die("--min-run can be used only with --runs or --masked-runs\n");
-    if (runs_each && !runs_class) die("--each can be used only with --runs\n");
-    if (runs_class || masked_runs) {
-        const char *me = runs_class ? "--runs" : "--masked-runs";
-        if (runs_class && masked_runs) die("--runs and --masked-runs can't be used together\n");
-        if (n_locate) die("%s and --locate can't be used together\n", me);
-        if (composition) die("%s and --composition can't be used together\n", me);
-        if (quality) die("%s and --quality can't be used together\n", me);
-        if (out_type != UNDECIDED) die("%s writes BED lines: no output type can be given with it\n", me);
-        if (revcomp) die("%s lists the sequences as stored: --revcomp can't be used with it\n", me);
-        if (n_selections > 1) die("%s can be restricted by one --records or one --region only\n", me);
-        if (n_selections && selections[0].rc) die("%s lists the sequences as stored: --rc-region can't be used with it\n", me);
-        if (n_selections && selections[0].region) {
-            size_t l; uint64_t b, e; naf_gpu_parse_region(selections[0].region, &l, &b, &e);
-            if (!(b == 0 && e == NAF_GPU_WHOLE)) die("%s can be restricted to a whole sequence only: --region ID, without a range\n", me);
-        }
-    }
-    if (kmers_canonical && !kmers_k) die("--canonical can be used only with --kmers\n");
-    if (kmers_per_record && !kmers_k) die("--per-record can be used only with --kmers\n");
-    if (kmers_k) {
-        if (n_locate) die("--kmers and --locate can't be used together\n");
-        if (composition) die("--kmers and --composition can't be used together\n");
-        if (quality) die("--kmers and --quality can't be used together\n");
-        if (runs_class || masked_runs) die("--kmers and %s can't be used together\n", runs_class ? "--runs" : "--masked-runs");
-        if (out_type != UNDECIDED) die("--kmers writes a table: no output type can be given with it\n");
-        if (kmers_per_record && kmers_k > 6) die("--per-record writes one column per k-mer: --kmers can be 6 at the most with it\n");
-        if (revcomp) die("--kmers counts the sequences as stored: --revcomp can't be used with it\n");
-        if (n_selections > 1) die("--kmers can be restricted by one --records or one --region only\n");
-        if (n_selections && selections[0].rc) die("--kmers counts the sequences as stored: --rc-region can't be used with it\n");
-        if (n_selections && selections[0].region) {
-            size_t l; uint64_t b, e; naf_gpu_parse_region(selections[0].region, &l, &b, &e);
-            if (!(b == 0 && e == NAF_GPU_WHOLE)) die("--kmers can be restricted to a whole sequence only: --region ID, without a range\n");
-        }
-    }
-    if (!orfs) {
-        if (min_orf_given) die("--min-orf can be used only with --orfs\n");
-        if (orf_stops_text) die("--stops can be used only with --orfs\n");
-        if (orf_starts_text) die("--starts can be used only with --orfs\n");
-        if (stop_to_stop) die("--stop-to-stop can be used only with --orfs\n");
-        if (orfs_closed) die("--closed can be used only with --orfs\n");
-        if (orfs_split) die("--split-unknown can be used only with --orfs\n");
-    } else {
-        if (n_locate) die("--orfs and --locate can't be used together\n");
-        if (composition) die("--orfs and --composition can't be used together\n");
-        if (quality) die("--orfs and --quality can't be used together\n");
-        if (runs_class || masked_runs) die("--orfs and %s can't be used together\n", runs_class ? "--runs" : "--masked-runs");
-        if (kmers_k) die("--orfs and --kmers can't be used together\n");
-        if (out_type != UNDECIDED) die("--orfs writes a table: no output type can be given with it\n");
-        if (stop_to_stop && orf_starts_text) die("--stop-to-stop and --starts can't be used together\n");
-        if (!orf_stops_text && translate && (code_text || code_table_text)) naf_gpu_genetic_code_stops(&genetic_code, &orf_stops);      /* the code's own stops close the frames */
-        else if (!orf_stops_text) naf_gpu_parse_codon_set("TAA,TAG,TGA", &orf_stops);
-        if (stop_to_stop) orf_starts = 0; else if (!orf_starts_text) naf_gpu_parse_codon_set("ATG", &orf_starts);
-        if (orf_starts & orf_stops) die("--starts and --stops share a codon: a codon can't both open and close a reading frame\n");
-        if (revcomp) die("--orfs reads both strands itself (--strand): --revcomp can't be used with it\n");
-        if (frame_text && translate) die("--frame can't be used with --orfs: every reading frame of the table is translated in its own frame\n");
-        if (n_selections > 1) die("--orfs can be restricted by one --records or one --region only\n");
-        if (n_selections && selections[0].rc) die("--orfs reads both strands itself (--strand): --rc-region can't be used with it\n");
-        if (n_selections && selections[0].region) {
-            size_t l; uint64_t b, e; naf_gpu_parse_region(selections[0].region, &l, &b, &e);
-            if (!(b == 0 && e == NAF_GPU_WHOLE)) die("--orfs can be restricted to a whole sequence only: --region ID, without a range\n");
-        }
-    }
-    if (!translate) {
-        if (frame_text) die("--frame can be used only with --translate\n");
-        if (code_text) die("--code can be used only with --translate\n");
-        if (code_table_text) die("--code-table can be used only with --translate\n");
-    } else {
-        if (out_type != UNDECIDED) die("--translate writes protein FASTA: no output type can be given with it\n");
-        if (n_locate) die("--translate and --locate can't be used together\n");
-        if (composition) die("--translate and --composition can't be used together\n");
-        if (quality) die("--translate and --quality can't be used together\n");
-        if (runs_class || masked_runs) die("--translate and %s can't be used together\n", runs_class ? "--runs" : "--masked-runs");
-        if (kmers_k) die("--translate and --kmers can't be used together\n");
-        if (code_text && code_table_text) die("--code and --code-table can't be used together\n");
-        if (!code_text && !code_table_text) naf_gpu_genetic_code_by_id(1, &genetic_code);
-    }
-    if (min_repeat_given && !repeats_text) die("--min-repeat can be used only with --repeats\n");
-    if (whole_units && !repeats_text) die("--whole-units can be used only with --repeats\n");
-    if (repeats_text) {
-        if (n_locate) die("--repeats and --locate can't be used together\n");
-        if (composition) die("--repeats and --composition can't be used together\n");
-        if (quality) die("--repeats and --quality can't be used together\n");
-        if (runs_class || masked_runs) die("--repeats and %s can't be used together\n", runs_class ? "--runs" : "--masked-runs");
-        if (kmers_k) die("--repeats and --kmers can't be used together\n");
-        if (orfs) die("--repeats and --orfs can't be used together\n");
-        if (translate) die("--repeats and --translate can't be used together\n");
-        if (out_type != UNDECIDED) die("--repeats writes a table: no output type can be given with it\n");
-        if (revcomp) die("--repeats lists the sequences as stored: --revcomp can't be used with it\n");
-        if (n_selections > 1) die("--repeats can be restricted by one --records or one --region only\n");
-        if (n_selections && selections[0].rc) die("--repeats lists the sequences as stored: --rc-region can't be used with it\n");
-        if (n_selections && selections[0].region) {
-            size_t l; uint64_t b, e; naf_gpu_parse_region(selections[0].region, &l, &b, &e);
-            if (!(b == 0 && e == NAF_GPU_WHOLE)) die("--repeats can be restricted to a whole sequence only: --region ID, without a range\n");
-        }
+    /* row by row: a message's place among the others is part of what the program does */
+    fill_modes();
+    for (const table_mode *m = modes; m < modes + N_MODES; m++) {
+        for (const satellite *s = m->sat; s->refusal; s++) if (s->given && !s->fits) die("%s", s->refusal);
+        if (m->early) m->early();
+        if (!m->asked) continue;
+        if (m->type_first) refuse_output_type(m);
+        for (const table_mode *e = modes; e < m; e++)
+            if (e->asked && !(e == &modes[M_ORFS] && m == &modes[M_TRANSLATE])) die("%s and %s can't be used together\n", m->name, e->name);
+        refuse_output_type(m);
+        if (m->own) m->own(m);
+        if (m->one_selection) one_whole_selection(m);
     }
     if ((n_selections || revcomp) && !(out_type == UNDECIDED || out_type == FASTA || out_type == FASTQ || out_type == SEQ || out_type == SEQUENCES))
         die("--region can be used only with sequence output\n");
@@ -640,20 +577,23 @@ static void check_records(const selection *s)
 {
     if (s->last > H.n_sequences) die("--records: sequence %llu requested, the archive has %llu\n", s->last, (unsigned long long)H.n_sequences);
 }
-/* --locate / --composition: the one --records or --region they allow as (first, count); none = every record */
-static void one_record_range(bool has_ids, uint64_t *first, uint64_t *count)
+/* where every table mode's runner starts: the archive on the device, and the one --records or --region that the mode allows as
+ * records rng_first .. rng_first + rng_count; none = every record */
+static uint64_t rng_first, rng_count;
+static void table_range(bool has_ids)
 {
-    *first = 0; *count = NAF_GPU_WHOLE;
+    upload();
+    rng_first = 0; rng_count = NAF_GPU_WHOLE;
     if (!n_selections) return;
     const selection *s = &selections[0];
     if (s->region) {
         uint64_t rec = UINT64_MAX;
         if (has_ids && H.n_sequences) GPU_TRY(naf_gpu_unnaf_find(gpu, d_naf, naf_len, s->region, strlen(s->region) + 1, 1, &rec));
         if (rec == UINT64_MAX) die("sequence \"%s\" not found\n", s->region);
-        *first = rec; *count = 1;
+        rng_first = rec; rng_count = 1;
     } else {
         check_records(s);
-        *first = s->first - 1; *count = s->last - s->first + 1;
+        rng_first = s->first - 1; rng_count = s->last - s->first + 1;
     }
 }
 /* the first column of their tables, per record: ids, or the stored names of an archive without ids (*text holds them; both are the caller's to free) */
@@ -761,359 +701,316 @@ static void run_select(int mode, bool has_ids)
     free(ids); free(recs); free(segs); free(strand);
 }
 
-/* --locate: the table of hits is made on the device (naf_gpu_unnaf_locate: two passes over the packed stream); the BED lines are
- * formatted here, on the host, from the downloaded table, a chunk at a time -- text for people and scripts, not a hot path. */
+/* ---- the table modes' runners ------------------------------------------------------------------------------------------------------
+ * A table of rows is made on the device (a count call, then a fill call into a table of that size) and written as lines here, on the host,
+ * from the downloaded rows, a chunk at a time -- text for people and scripts, not a hot path.  write_rows is what all of them share; a
+ * runner is its count call, its fill call and its formatter of a chunk's lines. */
+typedef struct {
+    size_t row_bytes, chunk;                                /* of one row; rows per download */
+    const char *what, *filled, *written;                    /* "can't decompress WHAT"; the phase() behind the fill call and behind the lines */
+    uint64_t (*fill)(void *d_rows, size_t cap);             /* the library call that writes the table: the rows it wrote */
+    void (*lines)(const void *rows, size_t m, uint64_t at, const char **name);      /* rows at .. at + m of the table, downloaded; name: per record, NULL if not wanted */
+} row_table;
+static void write_rows(const row_table *t, uint64_t n, bool names, bool has_ids, bool has_names)
+{
+    void *d_rows; GPU_TRY(naf_gpu_malloc(gpu, (size_t)n * t->row_bytes, &d_rows));
+    if (t->fill(d_rows, (size_t)n) != n) die("can't decompress %s\n", t->what);
+    phase(t->filled);
+    unsigned char *text = NULL; const char **name = names ? record_names(has_ids, has_names, &text) : NULL;
+    void *rows = malloc((n < t->chunk ? (size_t)n : t->chunk) * t->row_bytes); if (!rows) die("can't allocate memory\n");
+    for (uint64_t a = 0; a < n; a += t->chunk) {
+        const size_t m = n - a < t->chunk ? (size_t)(n - a) : t->chunk;
+        GPU_TRY(naf_gpu_download(gpu, rows, (const char *)d_rows + a * t->row_bytes, m * t->row_bytes));
+        t->lines(rows, m, a, name);
+    }
+    free(rows); free(name); free(text); naf_gpu_free(gpu, d_rows);
+    phase(t->written);
+}
+
+/* --locate: BED6 lines of the hits (naf_gpu_unnaf_locate: two passes over the packed stream).  With --mismatches or a bracketed pattern the
+ * near search (naf_gpu_unnaf_locate_near): a line carries the number of mismatches in column 5 and, as a 7th column, the pattern's letters
+ * in upper case with the mismatched ones in lower case (from the hit's `where`). */
+static struct { char *blob; size_t bytes, len[MAX_LOCATE]; char letters[MAX_LOCATE][33]; uint32_t budget[MAX_LOCATE]; } pat;      /* the patterns as the calls take them; their letters without brackets */
+static uint64_t fill_hits(void *d, size_t cap)
+{
+    uint64_t got = 0;
+    GPU_TRY(naf_gpu_unnaf_locate(gpu, d_naf, naf_len, pat.blob, pat.bytes, n_locate, locate_strands, rng_first, rng_count, (naf_gpu_hit *)d, cap, &got));
+    return got;
+}
+static void hit_lines(const void *rows, size_t m, uint64_t at, const char **name)
+{
+    (void)at;
+    for (const naf_gpu_hit *x = (const naf_gpu_hit *)rows; x < (const naf_gpu_hit *)rows + m; x++) {
+        if (x->record >= H.n_sequences || x->pattern >= n_locate) die("can't decompress sequence\n");
+        fprintf(OUT, "%s\t%llu\t%llu\t%s\t0\t%c\n", name[x->record], (unsigned long long)x->begin, (unsigned long long)(x->begin + pat.len[x->pattern]),
+                locate_patterns[x->pattern], x->strand ? '-' : '+');
+    }
+}
+static uint64_t fill_near_hits(void *d, size_t cap)
+{
+    uint64_t got = 0;
+    GPU_TRY(naf_gpu_unnaf_locate_near(gpu, d_naf, naf_len, pat.blob, pat.bytes, n_locate, pat.budget, locate_strands, rng_first, rng_count, (naf_gpu_near_hit *)d, cap, &got));
+    return got;
+}
+static void near_hit_lines(const void *rows, size_t m, uint64_t at, const char **name)
+{
+    (void)at;
+    for (const naf_gpu_near_hit *x = (const naf_gpu_near_hit *)rows; x < (const naf_gpu_near_hit *)rows + m; x++) {
+        if (x->record >= H.n_sequences || x->pattern >= n_locate) die("can't decompress sequence\n");
+        const char *letters = pat.letters[x->pattern]; const size_t len = pat.len[x->pattern];
+        char site[33];
+        for (size_t j = 0; j < len; j++) { const char ch = letters[j]; const bool low = ch >= 'a' && ch <= 'z'; site[j] = (char)(x->where >> j & 1 ? (low ? ch : ch + 32) : (low ? ch - 32 : ch)); }
+        site[len] = 0;
+        fprintf(OUT, "%s\t%llu\t%llu\t%s\t%u\t%c\t%s\n", name[x->record], (unsigned long long)x->begin, (unsigned long long)(x->begin + len),
+                letters, (unsigned)x->mismatches, x->strand ? '-' : '+', site);
+    }
+}
 static void run_locate(bool has_ids, bool has_names)
 {
-    upload();
-    const unsigned long long N = H.n_sequences;
-    uint64_t first, count;
-    one_record_range(has_ids, &first, &count);
-    size_t bytes = 0; for (size_t k = 0; k < n_locate; k++) bytes += strlen(locate_patterns[k]) + 1;
-    char *pats = (char *)malloc(bytes + 1); if (!pats) die("can't allocate memory\n");
-    size_t plen[MAX_LOCATE];
-    for (size_t k = 0, at = 0; k < n_locate; k++) { plen[k] = strlen(locate_patterns[k]); memcpy(pats + at, locate_patterns[k], plen[k] + 1); at += plen[k] + 1; }
-    uint64_t n = 0;
-    GPU_TRY(naf_gpu_unnaf_locate_count(gpu, d_naf, naf_len, pats, bytes, n_locate, locate_strands, first, count, &n, NULL));
-    phase("locate: count");
-    if (n) {
-        void *d_hits; GPU_TRY(naf_gpu_malloc(gpu, (size_t)n * sizeof(naf_gpu_hit), &d_hits));
-        uint64_t got = 0;
-        GPU_TRY(naf_gpu_unnaf_locate(gpu, d_naf, naf_len, pats, bytes, n_locate, locate_strands, first, count, (naf_gpu_hit *)d_hits, (size_t)n, &got));
-        if (got != n) die("can't decompress sequence\n");
-        phase("locate: hits");
-        unsigned char *text; const char **name = record_names(has_ids, has_names, &text);
-        const size_t chunk = 1 << 20;
-        naf_gpu_hit *hits = (naf_gpu_hit *)malloc((n < chunk ? (size_t)n : chunk) * sizeof *hits); if (!hits) die("can't allocate memory\n");
-        for (uint64_t a = 0; a < n; a += chunk) {
-            const size_t m = n - a < chunk ? (size_t)(n - a) : chunk;
-            GPU_TRY(naf_gpu_download(gpu, hits, (const naf_gpu_hit *)d_hits + a, m * sizeof *hits));
-            for (size_t k = 0; k < m; k++) {
-                const naf_gpu_hit *x = &hits[k];
-                if (x->record >= N || x->pattern >= n_locate) die("can't decompress sequence\n");
-                fprintf(OUT, "%s\t%llu\t%llu\t%s\t0\t%c\n", name[x->record], (unsigned long long)x->begin, (unsigned long long)(x->begin + plen[x->pattern]),
-                        locate_patterns[x->pattern], x->strand ? '-' : '+');
-            }
-        }
-        free(hits); free(name); free(text); naf_gpu_free(gpu, d_hits);
-        phase("locate: download + BED lines");
-    }
-    free(pats);
-}
-
-/* --locate with --mismatches or a bracketed pattern: the near search (naf_gpu_unnaf_locate_near); a line carries the number of mismatches in
- * column 5 and, as a 7th column, the pattern's letters in upper case with the mismatched ones in lower case (from the hit's `where`). */
-static void run_locate_near(bool has_ids, bool has_names)
-{
-    upload();
-    const unsigned long long N = H.n_sequences;
-    uint64_t first, count;
-    one_record_range(has_ids, &first, &count);
-    size_t bytes = 0; for (size_t k = 0; k < n_locate; k++) bytes += strlen(locate_patterns[k]) + 1;
-    char *pats = (char *)malloc(bytes + 1); if (!pats) die("can't allocate memory\n");
-    char letters[MAX_LOCATE][33]; size_t plen[MAX_LOCATE]; uint32_t budget[MAX_LOCATE];
+    static const row_table exact = { sizeof(naf_gpu_hit), 1 << 20, "sequence", "locate: hits", "locate: download + BED lines", fill_hits, hit_lines },
+                           near = { sizeof(naf_gpu_near_hit), 1 << 20, "sequence", "locate-near: hits", "locate-near: download + BED lines", fill_near_hits, near_hit_lines };
+    const bool is_near = mismatches_given || locate_bracketed;
+    table_range(has_ids);
+    pat.bytes = 0; for (size_t k = 0; k < n_locate; k++) pat.bytes += strlen(locate_patterns[k]) + 1;
+    pat.blob = (char *)malloc(pat.bytes + 1); if (!pat.blob) die("can't allocate memory\n");
     for (size_t k = 0, at = 0; k < n_locate; k++) {
         const size_t l = strlen(locate_patterns[k]);
-        memcpy(pats + at, locate_patterns[k], l + 1); at += l + 1;
-        plen[k] = 0; for (const char *p = locate_patterns[k]; *p; p++) if (*p != '[' && *p != ']') letters[k][plen[k]++] = *p;
-        letters[k][plen[k]] = 0; budget[k] = locate_mismatches;
+        memcpy(pat.blob + at, locate_patterns[k], l + 1); at += l + 1;
+        pat.len[k] = 0; for (const char *p = locate_patterns[k]; *p; p++) if (*p != '[' && *p != ']') pat.letters[k][pat.len[k]++] = *p;
+        pat.letters[k][pat.len[k]] = 0; pat.budget[k] = locate_mismatches;
     }
     uint64_t n = 0;
-    GPU_TRY(naf_gpu_unnaf_locate_near_count(gpu, d_naf, naf_len, pats, bytes, n_locate, budget, locate_strands, first, count, &n, NULL));
-    phase("locate-near: count");
-    if (n) {
-        void *d_hits; GPU_TRY(naf_gpu_malloc(gpu, (size_t)n * sizeof(naf_gpu_near_hit), &d_hits));
-        uint64_t got = 0;
-        GPU_TRY(naf_gpu_unnaf_locate_near(gpu, d_naf, naf_len, pats, bytes, n_locate, budget, locate_strands, first, count, (naf_gpu_near_hit *)d_hits, (size_t)n, &got));
-        if (got != n) die("can't decompress sequence\n");
-        phase("locate-near: hits");
-        unsigned char *text; const char **name = record_names(has_ids, has_names, &text);
-        const size_t chunk = 1 << 20;
-        naf_gpu_near_hit *hits = (naf_gpu_near_hit *)malloc((n < chunk ? (size_t)n : chunk) * sizeof *hits); if (!hits) die("can't allocate memory\n");
-        for (uint64_t a = 0; a < n; a += chunk) {
-            const size_t m = n - a < chunk ? (size_t)(n - a) : chunk;
-            GPU_TRY(naf_gpu_download(gpu, hits, (const naf_gpu_near_hit *)d_hits + a, m * sizeof *hits));
-            for (size_t k = 0; k < m; k++) {
-                const naf_gpu_near_hit *x = &hits[k];
-                if (x->record >= N || x->pattern >= n_locate) die("can't decompress sequence\n");
-                char site[33];
-                for (size_t j = 0; j < plen[x->pattern]; j++) { const char ch = letters[x->pattern][j]; const bool low = ch >= 'a' && ch <= 'z'; site[j] = (char)(x->where >> j & 1 ? (low ? ch : ch + 32) : (low ? ch - 32 : ch)); }
-                site[plen[x->pattern]] = 0;
-                fprintf(OUT, "%s\t%llu\t%llu\t%s\t%u\t%c\t%s\n", name[x->record], (unsigned long long)x->begin, (unsigned long long)(x->begin + plen[x->pattern]),
-                        letters[x->pattern], (unsigned)x->mismatches, x->strand ? '-' : '+', site);
-            }
-        }
-        free(hits); free(name); free(text); naf_gpu_free(gpu, d_hits);
-        phase("locate-near: download + BED lines");
-    }
-    free(pats);
+    if (is_near) GPU_TRY(naf_gpu_unnaf_locate_near_count(gpu, d_naf, naf_len, pat.blob, pat.bytes, n_locate, pat.budget, locate_strands, rng_first, rng_count, &n, NULL));
+    else GPU_TRY(naf_gpu_unnaf_locate_count(gpu, d_naf, naf_len, pat.blob, pat.bytes, n_locate, locate_strands, rng_first, rng_count, &n, NULL));
+    phase(is_near ? "locate-near: count" : "locate: count");
+    if (n) write_rows(is_near ? &near : &exact, n, true, has_ids, has_names);
+    free(pat.blob);
 }
 
-/* --composition: the table of rows is made on the device (naf_gpu_unnaf_composition: one sweep over the packed stream); the lines are
- * formatted here, on the host, from the downloaded rows, a chunk at a time -- text for people and scripts, not a hot path. */
+/* --composition [--window N]: naf_gpu_unnaf_composition, one sweep over the packed stream */
+static uint64_t fill_composition(void *d, size_t cap)
+{
+    uint64_t got = 0;
+    GPU_TRY(naf_gpu_unnaf_composition(gpu, d_naf, naf_len, comp_window, use_mask ? NAF_GPU_COMP_MASK : 0, rng_first, rng_count, (naf_gpu_comp_row *)d, cap, &got, NULL));
+    return got;
+}
+static void composition_lines(const void *rows, size_t m, uint64_t at, const char **name)
+{
+    (void)at;
+    for (const naf_gpu_comp_row *x = (const naf_gpu_comp_row *)rows; x < (const naf_gpu_comp_row *)rows + m; x++) {
+        if (x->record >= H.n_sequences) die("can't decompress sequence\n");
+        const unsigned long long A = x->n[8], Cc = x->n[4], G = x->n[2], T = x->n[1], Nn = x->n[15], gap = x->n[0];
+        unsigned long long other = 0; for (int q = 0; q < 16; q++) other += x->n[q];
+        other -= A + Cc + G + T + Nn + gap;
+        fprintf(OUT, "%s\t%llu\t%llu\t%llu\t%llu\t%llu\t%llu\t%llu\t%llu\t%llu\t%llu\t%llu\t", name[x->record], (unsigned long long)x->begin, (unsigned long long)x->end,
+                A, Cc, G, T, Nn, other, gap, (unsigned long long)x->masked, (unsigned long long)x->cpg);
+        if (A + Cc + G + T) fprintf(OUT, "%.6f\n", (double)(Cc + G) / (double)(A + Cc + G + T)); else fprintf(OUT, "NA\n");
+    }
+}
 static void run_composition(bool has_ids, bool has_names)
 {
-    upload();
-    const unsigned long long N = H.n_sequences;
-    uint64_t first, count;
-    one_record_range(has_ids, &first, &count);
+    static const row_table t = { sizeof(naf_gpu_comp_row), 1 << 18, "sequence", "composition: count", "composition: download + lines", fill_composition, composition_lines };
+    table_range(has_ids);
     uint64_t n = 0;
-    GPU_TRY(naf_gpu_unnaf_composition_rows(gpu, d_naf, naf_len, comp_window, first, count, &n));
+    GPU_TRY(naf_gpu_unnaf_composition_rows(gpu, d_naf, naf_len, comp_window, rng_first, rng_count, &n));
     phase("composition: rows");
     fprintf(OUT, "#seq\tstart\tend\tA\tC\tG\t%c\tN\tother\tgap\tmasked\tCpG\tGC\n", H.seq_type == NAF_SEQ_RNA ? 'U' : 'T');
-    if (n) {
-        void *d_rows; GPU_TRY(naf_gpu_malloc(gpu, (size_t)n * sizeof(naf_gpu_comp_row), &d_rows));
-        uint64_t got = 0;
-        GPU_TRY(naf_gpu_unnaf_composition(gpu, d_naf, naf_len, comp_window, use_mask ? NAF_GPU_COMP_MASK : 0, first, count, (naf_gpu_comp_row *)d_rows, (size_t)n, &got, NULL));
-        if (got != n) die("can't decompress sequence\n");
-        phase("composition: count");
-        unsigned char *text; const char **name = record_names(has_ids, has_names, &text);
-        const size_t chunk = 1 << 18;
-        naf_gpu_comp_row *rows = (naf_gpu_comp_row *)malloc((n < chunk ? (size_t)n : chunk) * sizeof *rows); if (!rows) die("can't allocate memory\n");
-        for (uint64_t a = 0; a < n; a += chunk) {
-            const size_t m = n - a < chunk ? (size_t)(n - a) : chunk;
-            GPU_TRY(naf_gpu_download(gpu, rows, (const naf_gpu_comp_row *)d_rows + a, m * sizeof *rows));
-            for (size_t k = 0; k < m; k++) {
-                const naf_gpu_comp_row *x = &rows[k];
-                if (x->record >= N) die("can't decompress sequence\n");
-                const unsigned long long A = x->n[8], Cc = x->n[4], G = x->n[2], T = x->n[1], Nn = x->n[15], gap = x->n[0];
-                unsigned long long other = 0; for (int q = 0; q < 16; q++) other += x->n[q];
-                other -= A + Cc + G + T + Nn + gap;
-                fprintf(OUT, "%s\t%llu\t%llu\t%llu\t%llu\t%llu\t%llu\t%llu\t%llu\t%llu\t%llu\t%llu\t", name[x->record], (unsigned long long)x->begin, (unsigned long long)x->end,
-                        A, Cc, G, T, Nn, other, gap, (unsigned long long)x->masked, (unsigned long long)x->cpg);
-                if (A + Cc + G + T) fprintf(OUT, "%.6f\n", (double)(Cc + G) / (double)(A + Cc + G + T)); else fprintf(OUT, "NA\n");
-            }
-        }
-        free(rows); free(name); free(text); naf_gpu_free(gpu, d_rows);
-        phase("composition: download + lines");
-    }
+    if (n) write_rows(&t, n, true, has_ids, has_names);
 }
 
-/* --quality [--cycles N]: the rows are made on the device (naf_gpu_unnaf_quality: one sweep over the quality stream); the lines are
- * formatted here, on the host, from the downloaded rows, a chunk at a time. */
-static void quality_stats(FILE *f, const naf_gpu_qual_row *x)
+/* --quality [--cycles N]: naf_gpu_unnaf_quality, one sweep over the quality stream; a row per read, or per bin of N read positions */
+static uint64_t qual_far;                                           /* the longest selected read: one row per read position at the most */
+static uint64_t fill_quality(void *d, size_t cap)
 {
-    if (x->n) fprintf(f, "%.4f\t%d\t%d", (double)x->sum / (double)x->n - 33.0, (int)x->min - 33, (int)x->max - 33); else fprintf(f, "NA\tNA\tNA");
-    fprintf(f, "\t%llu\t%llu\t%.6f\n", (unsigned long long)x->n_q20, (unsigned long long)x->n_q30, (double)x->ee / 4294967296.0);
+    uint64_t got_rec = 0, got_cyc = 0;
+    if (cycles_given) GPU_TRY(naf_gpu_unnaf_quality(gpu, d_naf, naf_len, qual_cycles, rng_first, rng_count, NULL, 0, (naf_gpu_qual_row *)d, cap, &got_rec, &got_cyc, NULL, NULL));
+    else GPU_TRY(naf_gpu_unnaf_quality(gpu, d_naf, naf_len, 0, rng_first, rng_count, (naf_gpu_qual_row *)d, cap, NULL, 0, &got_rec, &got_cyc, NULL, NULL));
+    return cycles_given ? got_cyc : got_rec;
+}
+static void quality_lines(const void *rows, size_t m, uint64_t at, const char **name)
+{
+    const uint64_t W = qual_cycles, far = qual_far;
+    for (size_t k = 0; k < m; k++) {
+        const naf_gpu_qual_row *x = (const naf_gpu_qual_row *)rows + k;
+        if (cycles_given) {
+            if (x->key != at + k) die("can't decompress quality\n");
+            const unsigned long long b = x->key * W + 1, e = far - x->key * W > W ? (x->key + 1) * W : far;
+            fprintf(OUT, "%llu\t%llu\t%llu\t", b, e, (unsigned long long)x->n);
+        } else {
+            if (x->key >= H.n_sequences) die("can't decompress quality\n");
+            fprintf(OUT, "%s\t%llu\t", name[x->key], (unsigned long long)x->n);
+        }
+        if (x->n) fprintf(OUT, "%.4f\t%d\t%d", (double)x->sum / (double)x->n - 33.0, (int)x->min - 33, (int)x->max - 33); else fprintf(OUT, "NA\tNA\tNA");
+        fprintf(OUT, "\t%llu\t%llu\t%.6f\n", (unsigned long long)x->n_q20, (unsigned long long)x->n_q30, (double)x->ee / 4294967296.0);
+    }
 }
 static void run_quality(bool has_ids, bool has_names)
 {
-    upload();
-    const unsigned long long N = H.n_sequences;
-    uint64_t first, count;
-    one_record_range(has_ids, &first, &count);
-    uint64_t n_rec = 0, far = 0;                                   /* (one row per read position: the longest selected read) */
-    GPU_TRY(naf_gpu_unnaf_quality_rows(gpu, d_naf, naf_len, 1, first, count, &n_rec, &far));
-    const uint64_t W = qual_cycles, n = cycles_given ? far / W + (far % W != 0) : n_rec;
+    static const row_table t = { sizeof(naf_gpu_qual_row), 1 << 18, "quality", "quality: count", "quality: download + lines", fill_quality, quality_lines };
+    table_range(has_ids);
+    uint64_t n_rec = 0;
+    GPU_TRY(naf_gpu_unnaf_quality_rows(gpu, d_naf, naf_len, 1, rng_first, rng_count, &n_rec, &qual_far));
+    const uint64_t n = cycles_given ? qual_far / qual_cycles + (qual_far % qual_cycles != 0) : n_rec;
     phase("quality: rows");
     fprintf(OUT, cycles_given ? "#cycle_begin\tcycle_end\tn\tmean\tmin\tmax\tq20\tq30\tee\n" : "#seq\tlength\tmean\tmin\tmax\tq20\tq30\tee\n");
-    if (!n) return;
-    void *d_rows; GPU_TRY(naf_gpu_malloc(gpu, (size_t)n * sizeof(naf_gpu_qual_row), &d_rows));
-    uint64_t got_rec = 0, got_cyc = 0;
-    if (cycles_given) GPU_TRY(naf_gpu_unnaf_quality(gpu, d_naf, naf_len, W, first, count, NULL, 0, (naf_gpu_qual_row *)d_rows, (size_t)n, &got_rec, &got_cyc, NULL, NULL));
-    else GPU_TRY(naf_gpu_unnaf_quality(gpu, d_naf, naf_len, 0, first, count, (naf_gpu_qual_row *)d_rows, (size_t)n, NULL, 0, &got_rec, &got_cyc, NULL, NULL));
-    if ((cycles_given ? got_cyc : got_rec) != n) die("can't decompress quality\n");
-    phase("quality: count");
-    unsigned char *text = NULL; const char **name = cycles_given ? NULL : record_names(has_ids, has_names, &text);
-    const size_t chunk = 1 << 18;
-    naf_gpu_qual_row *rows = (naf_gpu_qual_row *)malloc((n < chunk ? (size_t)n : chunk) * sizeof *rows); if (!rows) die("can't allocate memory\n");
-    for (uint64_t a = 0; a < n; a += chunk) {
-        const size_t m = n - a < chunk ? (size_t)(n - a) : chunk;
-        GPU_TRY(naf_gpu_download(gpu, rows, (const naf_gpu_qual_row *)d_rows + a, m * sizeof *rows));
-        for (size_t k = 0; k < m; k++) {
-            const naf_gpu_qual_row *x = &rows[k];
-            if (cycles_given) {
-                if (x->key != a + k) die("can't decompress quality\n");
-                const unsigned long long b = x->key * W + 1, e = far - x->key * W > W ? (x->key + 1) * W : far;
-                fprintf(OUT, "%llu\t%llu\t%llu\t", b, e, (unsigned long long)x->n);
-            } else {
-                if (x->key >= N) die("can't decompress quality\n");
-                fprintf(OUT, "%s\t%llu\t", name[x->key], (unsigned long long)x->n);
-            }
-            quality_stats(OUT, x);
-        }
-    }
-    free(rows); free(name); free(text); naf_gpu_free(gpu, d_rows);
-    phase("quality: download + lines");
+    if (n) write_rows(&t, n, !cycles_given, has_ids, has_names);
 }
 
-/* --runs / --masked-runs: the table of runs is made on the device (naf_gpu_unnaf_runs: the packed stream's run starts and ends, paired by
- * rank; the mask's toggle list); the BED lines are formatted here, on the host, from the downloaded table, a chunk at a time. */
+/* --runs / --masked-runs: BED4 lines (naf_gpu_unnaf_runs: the packed stream's run starts and ends, paired by rank; the mask's toggle list) */
+static int runs_flags(void) { return masked_runs ? NAF_GPU_RUNS_MASKED : runs_each ? NAF_GPU_RUNS_EACH : 0; }
+static uint64_t fill_runs(void *d, size_t cap)
+{
+    uint64_t got = 0;
+    GPU_TRY(naf_gpu_unnaf_runs(gpu, d_naf, naf_len, masked_runs ? 0 : runs_set, runs_flags(), min_run, rng_first, rng_count, (naf_gpu_run *)d, cap, &got, NULL));
+    return got;
+}
+static void run_lines(const void *rows, size_t m, uint64_t at, const char **name)
+{
+    (void)at;
+    const char *letters = H.seq_type == NAF_SEQ_RNA ? "-UGKCYSBAWRDMHVN" : "-TGKCYSBAWRDMHVN";
+    for (const naf_gpu_run *x = (const naf_gpu_run *)rows; x < (const naf_gpu_run *)rows + m; x++) {
+        if (x->record >= H.n_sequences || x->code > 15) die("can't decompress sequence\n");
+        fprintf(OUT, "%s\t%llu\t%llu\t", name[x->record], (unsigned long long)x->begin, (unsigned long long)x->end);
+        if (masked_runs) fprintf(OUT, "mask\n"); else if (runs_each) fprintf(OUT, "%c\n", letters[x->code]); else fprintf(OUT, "%s\n", runs_class);
+    }
+}
 static void run_runs(bool has_ids, bool has_names)
 {
-    upload();
-    const unsigned long long N = H.n_sequences;
-    uint64_t first, count;
-    one_record_range(has_ids, &first, &count);
-    const int flags = masked_runs ? NAF_GPU_RUNS_MASKED : runs_each ? NAF_GPU_RUNS_EACH : 0;
-    const uint16_t set = masked_runs ? 0 : runs_set;
+    static const row_table t = { sizeof(naf_gpu_run), 1 << 20, "sequence", "runs: rows", "runs: download + BED lines", fill_runs, run_lines };
+    table_range(has_ids);
     uint64_t n = 0;
-    GPU_TRY(naf_gpu_unnaf_runs_count(gpu, d_naf, naf_len, set, flags, min_run, first, count, &n, NULL));
+    GPU_TRY(naf_gpu_unnaf_runs_count(gpu, d_naf, naf_len, masked_runs ? 0 : runs_set, runs_flags(), min_run, rng_first, rng_count, &n, NULL));
     phase("runs: count");
-    if (n) {
-        void *d_runs; GPU_TRY(naf_gpu_malloc(gpu, (size_t)n * sizeof(naf_gpu_run), &d_runs));
-        uint64_t got = 0;
-        GPU_TRY(naf_gpu_unnaf_runs(gpu, d_naf, naf_len, set, flags, min_run, first, count, (naf_gpu_run *)d_runs, (size_t)n, &got, NULL));
-        if (got != n) die("can't decompress sequence\n");
-        phase("runs: rows");
-        unsigned char *text; const char **name = record_names(has_ids, has_names, &text);
-        const size_t chunk = 1 << 20;
-        naf_gpu_run *rows = (naf_gpu_run *)malloc((n < chunk ? (size_t)n : chunk) * sizeof *rows); if (!rows) die("can't allocate memory\n");
-        const char *letters = H.seq_type == NAF_SEQ_RNA ? "-UGKCYSBAWRDMHVN" : "-TGKCYSBAWRDMHVN";
-        for (uint64_t a = 0; a < n; a += chunk) {
-            const size_t m = n - a < chunk ? (size_t)(n - a) : chunk;
-            GPU_TRY(naf_gpu_download(gpu, rows, (const naf_gpu_run *)d_runs + a, m * sizeof *rows));
-            for (size_t k = 0; k < m; k++) {
-                const naf_gpu_run *x = &rows[k];
-                if (x->record >= N || x->code > 15) die("can't decompress sequence\n");
-                fprintf(OUT, "%s\t%llu\t%llu\t", name[x->record], (unsigned long long)x->begin, (unsigned long long)x->end);
-                if (masked_runs) fprintf(OUT, "mask\n"); else if (runs_each) fprintf(OUT, "%c\n", letters[x->code]); else fprintf(OUT, "%s\n", runs_class);
-            }
-        }
-        free(rows); free(name); free(text); naf_gpu_free(gpu, d_runs);
-        phase("runs: download + BED lines");
-    }
+    if (n) write_rows(&t, n, true, has_ids, has_names);
 }
 
-/* --repeats: the table of tandem repeats is made on the device (naf_gpu_unnaf_repeats: the run starts and ends of "equals the base p in front"
- * per period, paired by rank and merged without a sort); the lines are formatted here, on the host, from the downloaded table. */
+/* --repeats: naf_gpu_unnaf_repeats -- the run starts and ends of "equals the base p in front" per period, paired by rank and merged without a sort */
+static uint64_t fill_repeats(void *d, size_t cap)
+{
+    uint64_t got = 0;
+    GPU_TRY(naf_gpu_unnaf_repeats(gpu, d_naf, naf_len, &repeats_spec, whole_units ? NAF_GPU_REPEATS_WHOLE_UNITS : 0, min_repeat, rng_first, rng_count, (naf_gpu_repeat *)d, cap, &got, NULL, NULL));
+    return got;
+}
+static void repeat_lines(const void *rows, size_t m, uint64_t at, const char **name)
+{
+    (void)at;
+    const char *letters = H.seq_type == NAF_SEQ_RNA ? "ACGU" : "ACGT";
+    for (const naf_gpu_repeat *x = (const naf_gpu_repeat *)rows; x < (const naf_gpu_repeat *)rows + m; x++) {
+        uint32_t cls;
+        if (x->record >= H.n_sequences || x->end <= x->begin || naf_gpu_repeat_class(x->motif, x->period, &cls)) die("can't decompress sequence\n");
+        char motif[17], cl[17];
+        for (unsigned i = 0; i < x->period; i++) { motif[i] = letters[(x->motif >> (2 * i)) & 3]; cl[i] = letters[(cls >> (2 * i)) & 3]; }
+        motif[x->period] = cl[x->period] = 0;
+        fprintf(OUT, "%s\t%llu\t%llu\t%u\t%s\t%llu\t%s\n", name[x->record], (unsigned long long)x->begin, (unsigned long long)x->end, (unsigned)x->period, motif,
+                (unsigned long long)((x->end - x->begin) / x->period), cl);
+    }
+}
 static void run_repeats(bool has_ids, bool has_names)
 {
-    upload();
-    const unsigned long long N = H.n_sequences;
-    uint64_t first, count;
-    one_record_range(has_ids, &first, &count);
-    const int flags = whole_units ? NAF_GPU_REPEATS_WHOLE_UNITS : 0;
+    static const row_table t = { sizeof(naf_gpu_repeat), 1 << 20, "sequence", "repeats: rows", "repeats: download + lines", fill_repeats, repeat_lines };
+    table_range(has_ids);
     uint64_t n = 0;
-    GPU_TRY(naf_gpu_unnaf_repeats_count(gpu, d_naf, naf_len, &repeats_spec, flags, min_repeat, first, count, &n, NULL, NULL));
+    GPU_TRY(naf_gpu_unnaf_repeats_count(gpu, d_naf, naf_len, &repeats_spec, whole_units ? NAF_GPU_REPEATS_WHOLE_UNITS : 0, min_repeat, rng_first, rng_count, &n, NULL, NULL));
     phase("repeats: count");
-    if (n) {
-        void *d_rows; GPU_TRY(naf_gpu_malloc(gpu, (size_t)n * sizeof(naf_gpu_repeat), &d_rows));
-        uint64_t got = 0;
-        GPU_TRY(naf_gpu_unnaf_repeats(gpu, d_naf, naf_len, &repeats_spec, flags, min_repeat, first, count, (naf_gpu_repeat *)d_rows, (size_t)n, &got, NULL, NULL));
-        if (got != n) die("can't decompress sequence\n");
-        phase("repeats: rows");
-        unsigned char *text; const char **name = record_names(has_ids, has_names, &text);
-        const size_t chunk = 1 << 20;
-        naf_gpu_repeat *rows = (naf_gpu_repeat *)malloc((n < chunk ? (size_t)n : chunk) * sizeof *rows); if (!rows) die("can't allocate memory\n");
-        const char *letters = H.seq_type == NAF_SEQ_RNA ? "ACGU" : "ACGT";
-        for (uint64_t a = 0; a < n; a += chunk) {
-            const size_t m = n - a < chunk ? (size_t)(n - a) : chunk;
-            GPU_TRY(naf_gpu_download(gpu, rows, (const naf_gpu_repeat *)d_rows + a, m * sizeof *rows));
-            for (size_t k = 0; k < m; k++) {
-                const naf_gpu_repeat *x = &rows[k];
-                uint32_t cls;
-                if (x->record >= N || x->end <= x->begin || naf_gpu_repeat_class(x->motif, x->period, &cls)) die("can't decompress sequence\n");
-                char motif[17], cl[17];
-                for (unsigned i = 0; i < x->period; i++) { motif[i] = letters[(x->motif >> (2 * i)) & 3]; cl[i] = letters[(cls >> (2 * i)) & 3]; }
-                motif[x->period] = cl[x->period] = 0;
-                fprintf(OUT, "%s\t%llu\t%llu\t%u\t%s\t%llu\t%s\n", name[x->record], (unsigned long long)x->begin, (unsigned long long)x->end, (unsigned)x->period, motif,
-                        (unsigned long long)((x->end - x->begin) / x->period), cl);
-            }
-        }
-        free(rows); free(name); free(text); naf_gpu_free(gpu, d_rows);
-        phase("repeats: download + lines");
-    }
+    if (n) write_rows(&t, n, true, has_ids, has_names);
 }
 
-/* --orfs: the table of reading frames is made on the device (naf_gpu_unnaf_orfs: the stops, starts and record bounds of the packed stream as
- * six lists, a stretch between two neighbours of one list); the lines are formatted here, on the host, from the downloaded table. */
+/* --orfs: naf_gpu_unnaf_orfs -- the stops, starts and record bounds of the packed stream as six lists, a stretch between two neighbours of one
+ * list.  With --translate a chunk's rows are the segments: their proteins instead of the lines. */
+static int orfs_flags(void) { return (orfs_split ? NAF_GPU_ORF_SPLIT_UNKNOWN : 0) | (orfs_closed ? NAF_GPU_ORF_CLOSED : 0); }
+static uint64_t fill_orfs(void *d, size_t cap)
+{
+    uint64_t got = 0;
+    GPU_TRY(naf_gpu_unnaf_orfs(gpu, d_naf, naf_len, orf_stops, orf_starts, min_orf, locate_strands, orfs_flags(), rng_first, rng_count, (naf_gpu_orf *)d, cap, &got, NULL));
+    return got;
+}
+static void orf_lines(const void *rows, size_t m, uint64_t at, const char **name)
+{
+    (void)at;
+    for (const naf_gpu_orf *x = (const naf_gpu_orf *)rows; x < (const naf_gpu_orf *)rows + m; x++) {
+        if (x->record >= H.n_sequences || x->strand > 1 || x->frame > 2 || x->end <= x->begin) die("can't decompress sequence\n");
+        fprintf(OUT, "%s\t%llu\t%llu\t%c%u\t%llu\t%c\t%s\n", name[x->record], (unsigned long long)x->begin, (unsigned long long)x->end, x->strand ? '-' : '+', x->frame + 1u,
+                (unsigned long long)((x->end - x->begin) / 3), x->strand ? '-' : '+', (x->flags & NAF_GPU_ORF_STOP3) ? "stop" : "open");
+    }
+}
+static void orf_proteins(const void *rows, size_t m, uint64_t at, const char **name)
+{
+    (void)at; (void)name;
+    const naf_gpu_orf *x = (const naf_gpu_orf *)rows;
+    naf_gpu_segment *segs = (naf_gpu_segment *)malloc(m * sizeof *segs); uint8_t *strand = (uint8_t *)malloc(m);
+    if (!segs || !strand) die("can't allocate memory\n");
+    for (size_t k = 0; k < m; k++) {
+        if (x[k].record >= H.n_sequences || x[k].strand > 1 || x[k].end <= x[k].begin) die("can't decompress sequence\n");
+        segs[k] = (naf_gpu_segment){ x[k].record, x[k].begin, x[k].end }; strand[k] = (uint8_t)x[k].strand;
+    }
+    naf_gpu_unnaf_opts o = { NAF_OUT_FASTA, 0, line_length_is_specified ? requested_line_length : -1 };
+    fflush(OUT);
+    emit_segments(&o, segs, strand, m);
+    free(segs); free(strand);
+}
 static void run_orfs(bool has_ids, bool has_names)
 {
-    upload();
-    const unsigned long long N = H.n_sequences;
-    uint64_t first, count;
-    one_record_range(has_ids, &first, &count);
-    const int flags = (orfs_split ? NAF_GPU_ORF_SPLIT_UNKNOWN : 0) | (orfs_closed ? NAF_GPU_ORF_CLOSED : 0);
+    static const row_table lines = { sizeof(naf_gpu_orf), 1 << 20, "sequence", "orfs: rows", "orfs: download + lines", fill_orfs, orf_lines },
+                           proteins = { sizeof(naf_gpu_orf), 1 << 20, "sequence", "orfs: rows", "orfs: download + lines", fill_orfs, orf_proteins };
+    table_range(has_ids);
     uint64_t n = 0;
-    GPU_TRY(naf_gpu_unnaf_orfs_count(gpu, d_naf, naf_len, orf_stops, orf_starts, min_orf, locate_strands, flags, first, count, &n, NULL, NULL));
+    GPU_TRY(naf_gpu_unnaf_orfs_count(gpu, d_naf, naf_len, orf_stops, orf_starts, min_orf, locate_strands, orfs_flags(), rng_first, rng_count, &n, NULL, NULL));
     phase("orfs: count");
-    if (n) {
-        void *d_orfs; GPU_TRY(naf_gpu_malloc(gpu, (size_t)n * sizeof(naf_gpu_orf), &d_orfs));
-        uint64_t got = 0;
-        GPU_TRY(naf_gpu_unnaf_orfs(gpu, d_naf, naf_len, orf_stops, orf_starts, min_orf, locate_strands, flags, first, count, (naf_gpu_orf *)d_orfs, (size_t)n, &got, NULL));
-        if (got != n) die("can't decompress sequence\n");
-        phase("orfs: rows");
-        unsigned char *text; const char **name = record_names(has_ids, has_names, &text);
-        const size_t chunk = 1 << 20;
-        naf_gpu_orf *rows = (naf_gpu_orf *)malloc((n < chunk ? (size_t)n : chunk) * sizeof *rows); if (!rows) die("can't allocate memory\n");
-        for (uint64_t a = 0; a < n; a += chunk) {
-            const size_t m = n - a < chunk ? (size_t)(n - a) : chunk;
-            GPU_TRY(naf_gpu_download(gpu, rows, (const naf_gpu_orf *)d_orfs + a, m * sizeof *rows));
-            if (translate) {                                                      /* the rows are the segments: their proteins instead of the lines */
-                naf_gpu_segment *segs = (naf_gpu_segment *)malloc(m * sizeof *segs); uint8_t *strand = (uint8_t *)malloc(m);
-                if (!segs || !strand) die("can't allocate memory\n");
-                for (size_t k = 0; k < m; k++) {
-                    if (rows[k].record >= N || rows[k].strand > 1 || rows[k].end <= rows[k].begin) die("can't decompress sequence\n");
-                    segs[k] = (naf_gpu_segment){ rows[k].record, rows[k].begin, rows[k].end }; strand[k] = (uint8_t)rows[k].strand;
-                }
-                naf_gpu_unnaf_opts o = { NAF_OUT_FASTA, 0, line_length_is_specified ? requested_line_length : -1 };
-                fflush(OUT);
-                emit_segments(&o, segs, strand, m);
-                free(segs); free(strand);
-                continue;
-            }
-            for (size_t k = 0; k < m; k++) {
-                const naf_gpu_orf *x = &rows[k];
-                if (x->record >= N || x->strand > 1 || x->frame > 2 || x->end <= x->begin) die("can't decompress sequence\n");
-                fprintf(OUT, "%s\t%llu\t%llu\t%c%u\t%llu\t%c\t%s\n", name[x->record], (unsigned long long)x->begin, (unsigned long long)x->end, x->strand ? '-' : '+', x->frame + 1u,
-                        (unsigned long long)((x->end - x->begin) / 3), x->strand ? '-' : '+', (x->flags & NAF_GPU_ORF_STOP3) ? "stop" : "open");
-            }
-        }
-        if (sel_buf) { naf_gpu_free(gpu, sel_buf); sel_buf = NULL; sel_cap = 0; }
-        free(rows); free(name); free(text); naf_gpu_free(gpu, d_orfs);
-        phase("orfs: download + lines");
-    }
+    if (n) write_rows(translate ? &proteins : &lines, n, true, has_ids, has_names);
+    if (sel_buf) { naf_gpu_free(gpu, sel_buf); sel_buf = NULL; sel_cap = 0; }
+}
+
+/* --translate without --orfs: the selection's frames, through run_select */
+static void run_translate(bool has_ids, bool has_names)
+{
+    (void)has_names;
+    if (!((H.flags >> 1) & 1)) die("the archive stores no sequence to translate\n");
+    run_select(NAF_OUT_FASTA, has_ids);
 }
 
 /* --kmers: the tables are made on the device (naf_gpu_unnaf_kmers: one sweep over the packed stream); the lines are formatted here, on the
  * host, from the downloaded counters, a chunk at a time -- the one table of a selection 2^20 counters at a time, the tables of --per-record
  * in calls of as many records as give 2^22 counters. */
+static int kmers_flags(void) { return (kmers_canonical ? NAF_GPU_KMER_CANONICAL : 0) | (kmers_per_record ? NAF_GPU_KMER_PER_RECORD : 0); }
+static void kmer_letters(uint64_t index, char *km)
+{
+    naf_gpu_kmer_text(kmers_k, index, km);
+    if (H.seq_type == NAF_SEQ_RNA) for (char *q = km; *q; q++) if (*q == 'T') *q = 'U';
+}
+static uint64_t fill_kmers(void *d, size_t cap)                     /* the one table of a selection: its 4^K counters are the rows */
+{
+    uint64_t n_rows = 0, n_counters = 0;
+    GPU_TRY(naf_gpu_unnaf_kmers(gpu, d_naf, naf_len, kmers_k, kmers_flags(), rng_first, rng_count, (uint64_t *)d, cap, NULL, 0, &n_rows, &n_counters, NULL));
+    return n_rows == 1 && n_counters == 1ull << (2 * kmers_k) ? n_counters : UINT64_MAX;
+}
+static void kmer_lines(const void *rows, size_t m, uint64_t at, const char **name)
+{
+    (void)name;
+    const uint64_t *cnt = (const uint64_t *)rows; char km[13];
+    for (size_t k = 0; k < m; k++) if (cnt[k]) { kmer_letters(at + k, km); fprintf(OUT, "%s\t%llu\n", km, (unsigned long long)cnt[k]); }
+}
 static void run_kmers(bool has_ids, bool has_names)
 {
-    upload();
+    static const row_table one = { sizeof(uint64_t), 1 << 20, "sequence", "kmers: count", "kmers: download + lines", fill_kmers, kmer_lines };
+    table_range(has_ids);
     const unsigned long long N = H.n_sequences;
     const unsigned K = kmers_k;
-    const uint64_t nk = 1ull << (2 * K);
-    const bool rna = H.seq_type == NAF_SEQ_RNA;
-    uint64_t first, count;
-    one_record_range(has_ids, &first, &count);
-    const int flags = (kmers_canonical ? NAF_GPU_KMER_CANONICAL : 0) | (kmers_per_record ? NAF_GPU_KMER_PER_RECORD : 0);
+    const uint64_t nk = 1ull << (2 * K), first = rng_first;
+    const int flags = kmers_flags();
     uint64_t n_rows = 0, n_counters = 0;
-    GPU_TRY(naf_gpu_unnaf_kmers_rows(gpu, d_naf, naf_len, K, flags, first, count, &n_rows, &n_counters));
+    GPU_TRY(naf_gpu_unnaf_kmers_rows(gpu, d_naf, naf_len, K, flags, rng_first, rng_count, &n_rows, &n_counters));
     phase("kmers: rows");
+    if (!kmers_per_record) { if (n_rows) write_rows(&one, n_counters, false, has_ids, has_names); return; }
     char km[13];
-    if (!kmers_per_record) {
-        if (!n_rows) return;
-        void *d_counts; GPU_TRY(naf_gpu_malloc(gpu, (size_t)n_counters * 8, &d_counts));
-        GPU_TRY(naf_gpu_unnaf_kmers(gpu, d_naf, naf_len, K, flags, first, count, (uint64_t *)d_counts, (size_t)n_counters, NULL, 0, &n_rows, &n_counters, NULL));
-        if (n_rows != 1 || n_counters != nk) die("can't decompress sequence\n");
-        phase("kmers: count");
-        const size_t chunk = 1 << 20;
-        uint64_t *cnt = (uint64_t *)malloc((nk < chunk ? (size_t)nk : chunk) * sizeof *cnt); if (!cnt) die("can't allocate memory\n");
-        for (uint64_t a = 0; a < nk; a += chunk) {
-            const size_t m = nk - a < chunk ? (size_t)(nk - a) : chunk;
-            GPU_TRY(naf_gpu_download(gpu, cnt, (const uint64_t *)d_counts + a, m * sizeof *cnt));
-            for (size_t k = 0; k < m; k++) if (cnt[k]) {
-                naf_gpu_kmer_text(K, a + k, km);
-                if (rna) for (char *q = km; *q; q++) if (*q == 'T') *q = 'U';
-                fprintf(OUT, "%s\t%llu\n", km, (unsigned long long)cnt[k]);
-            }
-        }
-        free(cnt); naf_gpu_free(gpu, d_counts);
-        phase("kmers: download + lines");
-        return;
-    }
     /* the columns: every k-mer, or the canonical ones */
     uint32_t *col = (uint32_t *)malloc((size_t)nk * sizeof *col); size_t n_col = 0; if (!col) die("can't allocate memory\n");
     fprintf(OUT, "#seq\tlength\tcounted");
     for (uint64_t x = 0; x < nk; x++) {
         unsigned k2; uint64_t can = x;
-        naf_gpu_kmer_text(K, x, km);
+        kmer_letters(x, km);
         if (kmers_canonical) naf_gpu_kmer_index(km, 1, &k2, &can);
         if (can != x) continue;
         col[n_col++] = (uint32_t)x;
-        if (rna) for (char *q = km; *q; q++) if (*q == 'T') *q = 'U';
         fprintf(OUT, "\t%s", km);
     }
     fputc('\n', OUT);
@@ -1156,8 +1053,7 @@ int main(int argc, char **argv)
     if (!IN) die("can't open input file\n");
     phase("start");
     /* every output but the few that the header alone answers needs the device: its start runs beside the reading of the archive */
-    if (!(out_type == FORMAT_NAME || out_type == PART_LIST || out_type == PART_SIZES || out_type == NUMBER_OF_SEQUENCES || out_type == TITLE || out_type == TOTAL_LENGTH)) detach_teardown();
-    if (!(out_type == FORMAT_NAME || out_type == PART_LIST || out_type == PART_SIZES || out_type == NUMBER_OF_SEQUENCES || out_type == TITLE || out_type == TOTAL_LENGTH)) gpu_open_early();
+    if (!(out_type == FORMAT_NAME || out_type == PART_LIST || out_type == PART_SIZES || out_type == NUMBER_OF_SEQUENCES || out_type == TITLE || out_type == TOTAL_LENGTH)) { detach_teardown(); gpu_open_early(); }
     struct stat ist;
     if (fd_is_regular(fileno(IN)) && fstat(fileno(IN), &ist) == 0 && ist.st_size > 0) {
         void *m = mmap(NULL, (size_t)ist.st_size, PROT_READ, MAP_PRIVATE, fileno(IN), 0);
@@ -1187,39 +1083,14 @@ int main(int argc, char **argv)
     bool large = out_type == IDS || out_type == NAMES || out_type == LENGTHS || out_type == MASK || out_type == FOUR_BIT || out_type == DNA ||
                  out_type == MASKED_DNA || out_type == UNMASKED_DNA || out_type == SEQ || out_type == FASTA || out_type == MASKED_FASTA ||
                  out_type == UNMASKED_FASTA || out_type == FASTQ;
-    if (large && !n_locate && !composition && !quality && !runs_class && !masked_runs && !kmers_k && !orfs && !translate && !repeats_text && !force_stdout && isatty(fileno(OUT)))
+    const table_mode *mode = asked_mode();
+    if (large && !mode && !force_stdout && isatty(fileno(OUT)))
         die("output file not specified - please either specify output file with '-o' or '>', or use '-c' option to force writing to console\n");
 
     unsigned long long N = H.n_sequences;
-    if (n_locate) {
-        if (H.seq_type >= NAF_SEQ_PROTEIN) die("nucleotide motifs cannot be searched in %s sequences\n", tn[H.seq_type]);
-        if (mismatches_given || locate_bracketed) run_locate_near(has_ids, has_names); else run_locate(has_ids, has_names);
-    }
-    else if (composition) {
-        if (H.seq_type >= NAF_SEQ_PROTEIN) die("nucleotides cannot be counted in %s sequences\n", tn[H.seq_type]);
-        run_composition(has_ids, has_names);
-    }
-    else if (quality) run_quality(has_ids, has_names);
-    else if (runs_class || masked_runs) {
-        if (H.seq_type >= NAF_SEQ_PROTEIN) die("runs of bases cannot be listed in %s sequences\n", tn[H.seq_type]);
-        run_runs(has_ids, has_names);
-    }
-    else if (kmers_k) {
-        if (H.seq_type >= NAF_SEQ_PROTEIN) die("k-mers cannot be counted in %s sequences\n", tn[H.seq_type]);
-        run_kmers(has_ids, has_names);
-    }
-    else if (orfs) {
-        if (H.seq_type >= NAF_SEQ_PROTEIN) die("open reading frames cannot be listed in %s sequences\n", tn[H.seq_type]);
-        run_orfs(has_ids, has_names);
-    }
-    else if (repeats_text) {
-        if (H.seq_type >= NAF_SEQ_PROTEIN) die("tandem repeats cannot be listed in %s sequences\n", tn[H.seq_type]);
-        run_repeats(has_ids, has_names);
-    }
-    else if (translate) {
-        if (H.seq_type >= NAF_SEQ_PROTEIN) die("%s sequences cannot be translated\n", tn[H.seq_type]);
-        if (!has_data) die("the archive stores no sequence to translate\n");
-        run_select(NAF_OUT_FASTA, has_ids);
+    if (mode) {
+        if (mode->protein && H.seq_type >= NAF_SEQ_PROTEIN) die(mode->protein, tn[H.seq_type]);
+        mode->run(has_ids, has_names);
     }
     else if (n_selections) {
         if (out_type == FASTQ && !has_quality) die("FASTQ output requested, but input has no qualities\n");

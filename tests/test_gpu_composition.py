@@ -359,3 +359,21 @@ def test_cli_composition_writes_the_table(gpu, oracle, planned, name):
     if name == "seams":
         p = unnaf_cli(["--composition"], golden_bytes("naf", "protein_small.naf"))
         assert p.returncode == 1 and p.stdout == b"" and b"protein" in p.stderr
+
+
+def test_cli_composition_table_longer_than_a_download_chunk(gpu, oracle):
+    """--window 1 on one record of 2^18 + 3 bases: the rows are downloaded 2^18 at a time, so the table takes a second download, of 3 rows"""
+    n = (1 << 18) + 3
+    rng = np.random.default_rng(SEED + 77)
+    seq = rng.choice(np.frombuffer(b"ACGTN", dtype=np.uint8), n, p=[0.24, 0.24, 0.24, 0.24, 0.04])
+    for at in rng.integers(0, n - 64, 200):                          # soft-masked runs of 1 to 63 letters
+        seq[at:at + rng.integers(1, 64)] |= 0x20
+    seq[(1 << 18) - 3:(1 << 18) + 3] = np.frombuffer(b"nNcGcg", dtype=np.uint8)      # a CpG and the end of a masked run across the chunks' seam
+    line = seq.tobytes()
+    naf = oracle.ennaf(b">long one\n" + line + b"\n")
+    lines = CP.lines_of(oracle.unnaf(naf, oracle.MODE_SEQUENCES, True), 1)
+    assert lines == [line] and b"n" in line and b"N" in line
+    want = CP.table(CP.expected_rows(lines, 1), ["long"])
+    p = unnaf_cli(["--composition", "--window", "1"], naf)
+    assert p.returncode == 0 and p.stderr == b""
+    assert p.stdout.count(b"\n") == n + 1 and p.stdout == want

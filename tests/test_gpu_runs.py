@@ -444,3 +444,15 @@ def test_the_contigs_of_a_scaffold_are_the_selected_runs_of_not_n(gpu, planned):
         contigs = [x for ln in A.lines for x in re.split(b"N+", ln.upper()) if x]
         assert len(contigs) == len(segs) > 3
         assert got == b"".join(x + b"\n" for x in contigs)
+
+
+def test_cli_runs_table_longer_than_a_download_chunk(gpu, oracle):
+    """--runs ACGT --each on one record of 2^20 + 3 bases of ACGT repeated: no two neighbours are equal, so every base is a run; the rows
+    are downloaded 2^20 at a time, so the table takes a second download, of 3 rows"""
+    n = (1 << 20) + 3
+    line = (b"ACGT" * (n // 4 + 1))[:n]
+    naf = oracle.ennaf(b">r\n" + line + b"\n")
+    assert oracle.unnaf(naf, oracle.MODE_SEQUENCES, True) == line + b"\n"
+    p = unnaf_cli(["--runs", "ACGT", "--each"], naf)
+    assert p.returncode == 0 and p.stderr == b""
+    assert p.stdout == b"".join(b"r\t%d\t%d\t%c\n" % (i, i + 1, line[i]) for i in range(n))

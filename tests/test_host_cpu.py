@@ -434,3 +434,25 @@ def test_swar_piece_flags_every_byte_every_position(alphabet):
                 assert out[7] == sum(1 << i for i, c in enumerate(p) if not 0x21 <= c <= 0x7E), (fill, pos, b)
                 # the quick test is only ever a sufficient one
                 if out[3]: assert all(is_sp(c) or c in expected for c in p)
+
+
+# ---- unnaf's refusals, as recorded before the host's mode table ---------------------------------------------------------------------------
+def test_unnaf_refusals_are_the_recorded_ones():
+    """tests/golden/cli/refusals.json: stderr and exit status of a matrix of command lines of the table modes on an input path that does not
+    exist -- every decision of parse_command_line falls before the input is opened, so an accepted line ends in "can't open input file"
+    and no case reaches a device.  Which of two refusals a command line with two faults gets is part of the recording."""
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("make_refusals", os.path.join(GOLDEN, "cli", "make_refusals.py"))
+    gen = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(gen)
+    with open(os.path.join(GOLDEN, "cli", "refusals.json")) as f:
+        want = json.load(f)
+    assert [c["args"] for c in want] == gen.cases()                                  # the fixture is the generator's matrix, whole
+    accepted = [c for c in want if c["stderr"] == gen.ACCEPTED]
+    for name in gen.MODE_NAMES:
+        assert any(name in c["args"] for c in accepted), name
+    assert len({c["stderr"] for c in want} - {gen.ACCEPTED}) >= 90 and all(c["status"] == 1 for c in want)
+    got = gen.run_all(os.path.join(BIN, "unnaf"), [c["args"] for c in want])
+    diffs = ["%s: status %d stdout %r stderr %r, recorded status %d stderr %r" % (" ".join(map(repr, w["args"])), g["status"], g["stdout"], g["stderr"], w["status"], w["stderr"])
+             for g, w in zip(got, want) if (g["status"], g["stdout"], g["stderr"]) != (w["status"], "", w["stderr"])]
+    assert not diffs, "%d of %d command lines differ:\n%s" % (len(diffs), len(want), "\n".join(diffs))
