@@ -3352,6 +3352,7 @@ static int ennaf_streams(naf_gpu_ctx *c, EnnafSplit &S, const EnnafCarry &K, Enn
         X.dloc = nullptr;
         if (S.direct && (part & 1)) { X.direct = S.direct; X.nd = S.nd; seq_tail = (u32)(n_seqb & 32767); X.dloc = S.dloc.loc ? &S.dloc : nullptr; }
         X.ptr[4] = s_seq; X.len[4] = n_seqb; X.orig[4] = T; X.present[4] = true; X.tail[4] = seq_tail;   // ennaf.c:582: number of bases
+        if (S.store_qual) X.flags[4] |= ZENC_LONG_LAST;        // (the reference reads a FASTQ's sequence frame from memory, 4 bytes short: zstd_enc.hip)
         X.ptr[5] = S.s_qual; X.len[5] = X.orig[5] = S.n_qual; X.present[5] = S.store_qual;
     }
     if (part & 2) {
@@ -3424,6 +3425,7 @@ static int encode_stream_begin(naf_gpu_ctx *c, const u8 *d_stream, u64 len, int 
     J->sized = false; J->tail_tmp = nullptr; J->tail_len = 0; J->tail_flags = 0;
     int f1 = flags;
     if (J->tail) f1 = ZENC_PART | ((!(flags & ZENC_PART) || (flags & ZENC_PART_FIRST)) ? ZENC_PART_FIRST : 0) | (flags & (ZENC_PREFER_RAW | ZENC_PREFER_FLAT | ZENC_SHORT_CODES | ZENC_FRAME_TREE));
+    J->tail_flags = flags & ZENC_LONG_LAST;
     if (direct && (lz || len - J->tail != (u64)nd << 15)) return ctx_fail(c, NAF_GPU_EARG, "direct blocks need a stream of whole blocks and no match finder");
     int rc = zstd_encode_begin(c, d_stream, len - J->tail, level, f1, lz, block_log, window_log, &J->main, direct, nd, dloc);
     if (rc) { zstd_encode_drop(J->main); J->main = nullptr; }
@@ -3476,7 +3478,7 @@ static int encode_stream(naf_gpu_ctx *c, const u8 *d_stream, u64 len, int level,
     if (!tail || len <= tail) return zstd_encode(c, d_stream, len, level, dst, cap, clen, flags, lz, block_log, window_log);
     const bool part = (flags & ZENC_PART) != 0;
     const int f1 = ZENC_PART | ((!part || (flags & ZENC_PART_FIRST)) ? ZENC_PART_FIRST : 0) | (flags & (ZENC_PREFER_RAW | ZENC_PREFER_FLAT | ZENC_SHORT_CODES | ZENC_FRAME_TREE));
-    const int f2 = ZENC_PART | ((!part || (flags & ZENC_PART_LAST)) ? ZENC_PART_LAST : 0) | (tail >= 2048 ? (flags & (ZENC_PREFER_FLAT | ZENC_SHORT_CODES)) : 0);   // (a ragged block of some size is coded like the blocks in front of it)
+    const int f2 = ZENC_PART | ((!part || (flags & ZENC_PART_LAST)) ? ZENC_PART_LAST : 0) | (flags & ZENC_LONG_LAST) | (tail >= 2048 ? (flags & (ZENC_PREFER_FLAT | ZENC_SHORT_CODES)) : 0);   // (a ragged block of some size is coded like the blocks in front of it)
     size_t a = 0, b = 0;
     int rc = zstd_encode(c, d_stream, len - tail, level, dst, cap, &a, f1, lz, block_log, window_log); if (rc) return rc;
     rc = zstd_encode(c, d_stream + (len - tail), tail, level, dst + a, cap - a, &b, f2, 0, 0, 0); if (rc) return rc;
@@ -3951,7 +3953,7 @@ extern "C" int naf_gpu_ennaf_shard_finish(naf_gpu_ctx *c, const naf_gpu_ennaf_op
             const int flags = ZENC_PART | (V.first[i] ? ZENC_PART_FIRST : 0) | (V.last[i] ? ZENC_PART_LAST : 0) | X.flags[i];
             const u32 tail = part_tail(i);
             if ((rc = encode_stream_begin(w, X.ptr[i], X.len[i], o->level, flags, X.lz[i], X.block_log[i], X.window_log[i], tail, &job[i]))) { if (w != c) ctx_fail(c, rc, "%s", w->err); break; }
-            job[i].tail_flags = tail >= 2048 ? (flags & (ZENC_PREFER_FLAT | ZENC_SHORT_CODES)) : 0;    // (a ragged block of some size is coded like the blocks in front of it: encode_stream)
+            job[i].tail_flags = (flags & ZENC_LONG_LAST) | (tail >= 2048 ? (flags & (ZENC_PREFER_FLAT | ZENC_SHORT_CODES)) : 0);    // (a ragged block of some size is coded like the blocks in front of it: encode_stream)
             begun[i] = true;
         }
         struct Fixed { u8 *at; size_t len; };

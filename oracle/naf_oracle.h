@@ -59,6 +59,23 @@ typedef struct { nafo_zstd_block *blocks; size_t n_blocks, cap_blocks; nafo_zstd
 long long nafo_zstd_sequences(const uint8_t *src, size_t src_len, nafo_zstd_seqlist *list);
 void nafo_zstd_seqlist_free(nafo_zstd_seqlist *list);
 
+/* The literals section of every block of the first frame, as the decoder reads it (tests that hold an encoder's entropy stage to a
+ * model).  A Raw or RLE block has lit_type NAFO_LIT_NONE and zeros behind it. */
+#define NAFO_LIT_NONE 0xFFFFFFFFu
+typedef struct {
+    uint32_t block_type, decoded_size, frame_size;   /* Block_Type; bytes the block decodes to; its bytes in the frame, header included */
+    uint32_t lit_type;                               /* Literals_Block_Type: 0 Raw, 1 RLE, 2 Compressed (Huffman), 3 Treeless */
+    uint32_t regen, comp, header_bytes, n_streams;   /* Regenerated_Size; Compressed_Size (Raw: regen, RLE: 1); 1 to 5; 0 (Raw / RLE), 1 or 4 */
+    uint32_t stream_size[4];                         /* one stream: [0] */
+    uint32_t tree_bytes, tree_fse, n_weights;        /* the tree description of THIS block (0 bytes: none); FSE-coded or direct; weights written */
+    uint32_t n_sequences;
+    uint32_t tree_offset;                            /* where this block's tree description begins, from the frame's first byte */
+    uint8_t  len[256];                               /* code lengths in force for this block's streams (a treeless block: the inherited ones) */
+} nafo_zstd_litblock;
+typedef struct { nafo_zstd_litblock *blocks; size_t n, cap; } nafo_zstd_litlist;
+long long nafo_zstd_literals(const uint8_t *src, size_t src_len, nafo_zstd_litlist *list);
+void nafo_zstd_litlist_free(nafo_zstd_litlist *list);
+
 /* ---- NAF transforms : naf_oracle.c -------------------------------------------------------- */
 enum { NAFO_DNA = 0, NAFO_RNA = 1, NAFO_PROTEIN = 2, NAFO_TEXT = 3 };
 enum { NAFO_FMT_UNKNOWN = 0, NAFO_FMT_FASTA = 1, NAFO_FMT_FASTQ = 2 };

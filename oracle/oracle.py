@@ -65,6 +65,10 @@ class _ZSeq(C.Structure):
                 ("distance", C.c_uint64)]
 
 
+class _ZLitList(C.Structure):
+    _fields_ = [("blocks", C.c_void_p), ("n", C.c_size_t), ("cap", C.c_size_t)]
+
+
 class _ZSeqList(C.Structure):
     _fields_ = [("blocks", C.POINTER(_ZBlock)), ("n_blocks", C.c_size_t), ("cap_blocks", C.c_size_t),
                 ("seqs", C.POINTER(_ZSeq)), ("n_seqs", C.c_size_t), ("cap_seqs", C.c_size_t)]
@@ -83,6 +87,24 @@ class FrameSequences:
 
     def __len__(self):
         return len(self.pos)
+
+
+class FrameLiterals:
+    """What zstd_literals lists, one entry per block, as numpy columns: `block_type` (0 Raw, 1 RLE, 2 Compressed), `decoded_size`,
+    `frame_size` (the block's bytes in the frame, its 3-byte header included); `lit_type` (0 Raw, 1 RLE, 2 Huffman, 3 treeless; -1 for a
+    block that is not Compressed), `regen`, `comp`, `header_bytes` (1 to 5), `n_streams` (0, 1 or 4), `stream_size` (n x 4),
+    `tree_bytes` (of the block's own description, 0 without one), `tree_fse` (1 FSE-coded, 0 direct), `n_weights` (weights written),
+    `n_sequences`, `tree_offset` (of the description, from the frame's first byte), and `len` (n x 256: the code lengths in force, 0 for an absent symbol; a treeless block shows the inherited ones)."""
+
+    def __init__(self, size, rec):
+        self.size = size
+        for k in ("block_type", "decoded_size", "frame_size", "lit_type", "regen", "comp", "header_bytes", "n_streams", "stream_size",
+                  "tree_bytes", "tree_fse", "n_weights", "n_sequences", "tree_offset", "len"):
+            setattr(self, k, rec[k].astype("i8"))
+        self.lit_type[self.lit_type == 0xFFFFFFFF] = -1
+
+    def __len__(self):
+        return len(self.block_type)
 
 
 _lib = None
@@ -105,6 +127,9 @@ def lib():
         L.nafo_zstd_sequences.restype = C.c_longlong
         L.nafo_zstd_sequences.argtypes = [C.c_char_p, C.c_size_t, C.POINTER(_ZSeqList)]
         L.nafo_zstd_seqlist_free.argtypes = [C.POINTER(_ZSeqList)]
+        L.nafo_zstd_literals.restype = C.c_longlong
+        L.nafo_zstd_literals.argtypes = [C.c_char_p, C.c_size_t, C.POINTER(_ZLitList)]
+        L.nafo_zstd_litlist_free.argtypes = [C.POINTER(_ZLitList)]
         L.nafo_split_text.restype = C.c_int
         L.nafo_split_text.argtypes = [C.c_char_p, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(_Split)]
         L.nafo_split_free.argtypes = [C.POINTER(_Split)]
@@ -174,6 +199,25 @@ def zstd_sequences(frame: bytes) -> FrameSequences:
     finally:
         lib().nafo_zstd_seqlist_free(C.byref(l))
     return FrameSequences(int(n), blocks, seqs)
+
+
+def zstd_literals(frame: bytes) -> FrameLiterals:
+    """The literals section of every block of the (first) frame, listed by the decoder as it reads them."""
+    import numpy as np
+    l = _ZLitList()
+    n = lib().nafo_zstd_literals(frame, len(frame), C.byref(l))
+    if n < 0:
+        raise ValueError("oracle zstd: error %d" % n)
+    try:
+        u = "<u4"
+        rt = np.dtype([("block_type", u), ("decoded_size", u), ("frame_size", u), ("lit_type", u), ("regen", u), ("comp", u),
+                       ("header_bytes", u), ("n_streams", u), ("stream_size", u, 4), ("tree_bytes", u), ("tree_fse", u), ("n_weights", u),
+                       ("n_sequences", u), ("tree_offset", u), ("len", "u1", 256)])
+        assert rt.itemsize == 68 + 256
+        rec = np.frombuffer(C.string_at(l.blocks, l.n * rt.itemsize), dtype=rt) if l.n else np.zeros(0, rt)
+    finally:
+        lib().nafo_zstd_litlist_free(C.byref(l))
+    return FrameLiterals(int(n), rec)
 
 
 # ---- ennaf side ------------------------------------------------------------------------------------

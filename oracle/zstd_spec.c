@@ -38,6 +38,11 @@ typedef struct {
     nafo_zstd_frame_info *info;
     nafo_zstd_seqlist *list;        /* nafo_zstd_sequences: every block and sequence as decoded */
     uint32_t block_no;
+    uint8_t huf_len[256];           /* code lengths of the tree in force, 0 for a symbol without a code */
+    uint32_t tree_fse, n_weights;   /* of the tree description read last */
+    nafo_zstd_litlist *lits;        /* nafo_zstd_literals: the literals section of every block */
+    nafo_zstd_litblock cur;
+    const uint8_t *frame_base;      /* first byte of the frame: what tree_offset counts from */
 } frame_ctx;
 
 /* append to the lists of nafo_zstd_sequences; 0, or ERR_DST when memory runs out */
@@ -50,6 +55,17 @@ static int list_block(nafo_zstd_seqlist *l, uint32_t type, uint32_t size)
         l->blocks = nb; l->cap_blocks = cap;
     }
     l->blocks[l->n_blocks].type = type; l->blocks[l->n_blocks].size = size; l->n_blocks++;
+    return 0;
+}
+static int list_lit(nafo_zstd_litlist *l, const nafo_zstd_litblock *r)
+{
+    if (l->n == l->cap) {
+        size_t cap = l->cap ? l->cap * 2 : 64;
+        nafo_zstd_litblock *nb = (nafo_zstd_litblock *)realloc(l->blocks, cap * sizeof *nb);
+        if (!nb) return ERR_DST;
+        l->blocks = nb; l->cap = cap;
+    }
+    l->blocks[l->n++] = *r;
     return 0;
 }
 static int list_seq(nafo_zstd_seqlist *l, uint32_t block, uint64_t pos, uint64_t ll, uint64_t ml, uint64_t off, uint64_t ofv)
@@ -193,6 +209,9 @@ static int huf_build(frame_ctx *c, const uint8_t *weights, int n /* explicit wei
         rank_start[w[i]] += len;
     }
     c->huf_log = log; c->huf_valid = 1;
+    memset(c->huf_len, 0, sizeof c->huf_len);
+    for (int i = 0; i < n; i++) if (w[i]) c->huf_len[i] = (uint8_t)(log + 1 - w[i]);
+    c->n_weights = (uint32_t)(n - 1);
     return 0;
 }
 
@@ -228,6 +247,7 @@ static int huf_read_tree(frame_ctx *c, const uint8_t *p, size_t len)
         }
     }
     int r = huf_build(c, weights, n);
+    c->tree_fse = hb < 128;
     return r < 0 ? r : used;
 }
 
@@ -278,6 +298,8 @@ static long long decode_compressed_block(frame_ctx *c, const uint8_t *src, size_
         else if (sf == 1) { if (len < 2) return ERR_SRC; regen = (p[0] >> 4) + ((size_t)p[1] << 4); hdr = 2; }
         else { if (len < 3) return ERR_SRC; regen = (p[0] >> 4) + ((size_t)p[1] << 4) + ((size_t)p[2] << 12); hdr = 3; }
         if (regen > MAX_BLOCK) return ERR_CORR;
+        c->cur.lit_type = (uint32_t)ltype; c->cur.regen = (uint32_t)regen; c->cur.comp = ltype == 0 ? (uint32_t)regen : 1u;
+        c->cur.header_bytes = (uint32_t)hdr; c->cur.n_streams = 0;
         if (ltype == 0) {
             if (hdr + regen > len) return ERR_SRC;
             lits = p + hdr; p += hdr + regen; if (c->info) c->info->lit_raw++;
@@ -296,8 +318,13 @@ static long long decode_compressed_block(frame_ctx *c, const uint8_t *src, size_
         if (ltype == 2) {
             int used = huf_read_tree(c, q, comp); if (used < 0) return used;
             q += used; if (c->info) c->info->lit_huf++;
+            c->cur.tree_bytes = (uint32_t)used; c->cur.tree_offset = (uint32_t)(q - used - c->frame_base); c->cur.tree_fse = c->tree_fse; c->cur.n_weights = c->n_weights;
         } else { if (!c->huf_valid) return ERR_CORR; if (c->info) c->info->lit_treeless++; }
+        c->cur.lit_type = (uint32_t)ltype; c->cur.regen = (uint32_t)regen; c->cur.comp = (uint32_t)comp;
+        c->cur.header_bytes = (uint32_t)hdr; c->cur.n_streams = (uint32_t)nstreams;
+        memcpy(c->cur.len, c->huf_len, 256);
         if (nstreams == 1) {
+            c->cur.stream_size[0] = (uint32_t)(qend - q);
             int r = huf_decode_stream(c, q, (size_t)(qend - q), litbuf, regen); if (r < 0) return r;
         } else {
             if (qend - q < 6) return ERR_SRC;
@@ -306,6 +333,7 @@ static long long decode_compressed_block(frame_ctx *c, const uint8_t *src, size_
             size_t tot = (size_t)(qend - q);
             if (s1 + s2 + s3 > tot) return ERR_CORR;
             size_t s4 = tot - s1 - s2 - s3;
+            c->cur.stream_size[0] = (uint32_t)s1; c->cur.stream_size[1] = (uint32_t)s2; c->cur.stream_size[2] = (uint32_t)s3; c->cur.stream_size[3] = (uint32_t)s4;
             size_t per = (regen + 3) / 4;
             if (per * 3 > regen) return ERR_CORR;
             int r;
@@ -325,6 +353,7 @@ static long long decode_compressed_block(frame_ctx *c, const uint8_t *src, size_
     else if (p[0] < 255) { if (end - p < 2) return ERR_SRC; nseq = ((uint32_t)(p[0] - 128) << 8) + p[1]; p += 2; }
     else { if (end - p < 3) return ERR_SRC; nseq = p[1] + ((uint32_t)p[2] << 8) + 0x7F00; p += 3; }
 
+    c->cur.n_sequences = nseq;
     uint8_t *out = dst_base + dst_pos; size_t room = dst_cap - dst_pos; size_t op = 0, lp = 0;
     if (nseq == 0) {
         if (p != end) return ERR_CORR;
@@ -387,14 +416,14 @@ static long long decode_compressed_block(frame_ctx *c, const uint8_t *src, size_
 }
 
 static long long decode_frame_x(const uint8_t *src, size_t len, uint8_t *dst, size_t dst_pos, size_t dst_cap,
-                                size_t *consumed, nafo_zstd_frame_info *info, nafo_zstd_seqlist *list);
+                                size_t *consumed, nafo_zstd_frame_info *info, nafo_zstd_seqlist *list, nafo_zstd_litlist *lits);
 static long long decode_frame(const uint8_t *src, size_t len, uint8_t *dst, size_t dst_pos, size_t dst_cap,
                               size_t *consumed, nafo_zstd_frame_info *info)
 {
-    return decode_frame_x(src, len, dst, dst_pos, dst_cap, consumed, info, NULL);
+    return decode_frame_x(src, len, dst, dst_pos, dst_cap, consumed, info, NULL, NULL);
 }
 static long long decode_frame_x(const uint8_t *src, size_t len, uint8_t *dst, size_t dst_pos, size_t dst_cap,
-                                size_t *consumed, nafo_zstd_frame_info *info, nafo_zstd_seqlist *list)
+                                size_t *consumed, nafo_zstd_frame_info *info, nafo_zstd_seqlist *list, nafo_zstd_litlist *lits)
 {
     seq_dump_open();
     if (len < 4) return ERR_SRC;
@@ -432,7 +461,7 @@ static long long decode_frame_x(const uint8_t *src, size_t len, uint8_t *dst, si
 
     frame_ctx *c = (frame_ctx *)calloc(1, sizeof *c);
     if (!c) return ERR_DST;
-    c->rep[0] = 1; c->rep[1] = 4; c->rep[2] = 8; c->info = info; c->list = list;
+    c->rep[0] = 1; c->rep[1] = 4; c->rep[2] = 8; c->info = info; c->list = list; c->lits = lits; c->frame_base = src;
     size_t start = dst_pos; long long rc = 0;
     for (;;) {
         if (end - p < 3) { rc = ERR_SRC; break; }
@@ -440,6 +469,8 @@ static long long decode_frame_x(const uint8_t *src, size_t len, uint8_t *dst, si
         int last = bh & 1, type = (bh >> 1) & 3; size_t bsize = bh >> 3;
         if (info) info->n_blocks++;
         const size_t block_start = dst_pos;
+        memset(&c->cur, 0, sizeof c->cur);
+        c->cur.lit_type = NAFO_LIT_NONE;
         if (type == 0) {
             if (bsize > MAX_BLOCK) { rc = ERR_CORR; break; }
             if ((size_t)(end - p) < bsize) { rc = ERR_SRC; break; }
@@ -458,6 +489,11 @@ static long long decode_frame_x(const uint8_t *src, size_t len, uint8_t *dst, si
             dst_pos += (size_t)n; p += bsize; if (info) info->n_compressed++;
         } else { rc = ERR_CORR; break; }
         if (list && list_block(list, (uint32_t)type, (uint32_t)(dst_pos - block_start)) < 0) { rc = ERR_DST; break; }
+        if (lits) {
+            c->cur.block_type = (uint32_t)type; c->cur.decoded_size = (uint32_t)(dst_pos - block_start);
+            c->cur.frame_size = 3 + (type == 1 ? 1u : (uint32_t)bsize);
+            if (list_lit(lits, &c->cur) < 0) { rc = ERR_DST; break; }
+        }
         c->block_no++;
         if (last) break;
     }
@@ -528,10 +564,33 @@ long long nafo_zstd_sequences(const uint8_t *src, size_t src_len, nafo_zstd_seql
         uint8_t *tmp = (uint8_t *)malloc(cap);
         if (!tmp) return ERR_DST;
         memset(list, 0, sizeof *list);
-        long long n = decode_frame_x(src, src_len, tmp, 0, cap, NULL, NULL, list);
+        long long n = decode_frame_x(src, src_len, tmp, 0, cap, NULL, NULL, list, NULL);
         free(tmp);
         if (n >= 0) return n;
         nafo_zstd_seqlist_free(list);
+        if (n != ERR_DST) return n;
+        cap *= 4;
+        if (cap > ((size_t)1 << 40)) return ERR_DST;
+    }
+}
+
+void nafo_zstd_litlist_free(nafo_zstd_litlist *list)
+{
+    free(list->blocks);
+    memset(list, 0, sizeof *list);
+}
+
+long long nafo_zstd_literals(const uint8_t *src, size_t src_len, nafo_zstd_litlist *list)
+{
+    size_t cap = src_len * 4 + (1u << 20);
+    for (;;) {
+        uint8_t *tmp = (uint8_t *)malloc(cap);
+        if (!tmp) return ERR_DST;
+        memset(list, 0, sizeof *list);
+        long long n = decode_frame_x(src, src_len, tmp, 0, cap, NULL, NULL, NULL, list);
+        free(tmp);
+        if (n >= 0) return n;
+        nafo_zstd_litlist_free(list);
         if (n != ERR_DST) return n;
         cap *= 4;
         if (cap > ((size_t)1 << 40)) return ERR_DST;
