@@ -76,6 +76,29 @@ typedef struct { nafo_zstd_litblock *blocks; size_t n, cap; } nafo_zstd_litlist;
 long long nafo_zstd_literals(const uint8_t *src, size_t src_len, nafo_zstd_litlist *list);
 void nafo_zstd_litlist_free(nafo_zstd_litlist *list);
 
+/* The sequences section of every block of the first frame, as the decoder reads it (tests that hold an encoder's choice of code
+ * tables to a model).  Tables are in the order LL, OF, ML.  A block that is not Compressed has zeros behind block_type; a
+ * Compressed block without sequences has its one-byte section and zeros behind it. */
+typedef struct {
+    uint32_t block_type, n_sequences;
+    uint32_t nseq_header_bytes;                      /* the Number_of_Sequences field: 1, 2 or 3 */
+    uint32_t section_offset, section_bytes;          /* of the Sequences_Section: from the frame's first byte; to the block's end */
+    uint32_t bitstream_bytes;
+    uint32_t mode[3];                                /* 0 Predefined, 1 RLE, 2 FSE_Compressed, 3 Repeat */
+    uint32_t accuracy_log[3];                        /* of the table in force (RLE: 0) */
+    uint32_t rle_symbol[3];
+    uint32_t desc_bytes[3];                          /* the table's own bytes in this block: 0, 1 (RLE) or its description */
+    uint32_t final_state[3];                         /* the states the decoder holds at the block's last sequence */
+    uint32_t bits_consumed;                          /* bits the decoder read from the bitstream, the initial states included */
+    uint32_t marker_bit;                             /* bit position of the final marker, counted from the bitstream's first bit */
+    int16_t  norm[3][64];                            /* probabilities in force: -1 "less than 1", 0 absent (RLE: all 0) */
+} nafo_zstd_seqtab;
+typedef struct { nafo_zstd_seqtab *blocks; size_t n, cap; } nafo_zstd_tablist;
+/* seqs, when not NULL, takes what nafo_zstd_sequences lists, from the same reading.  Unlike the decoders this listing goes on when a
+ * bitstream holds bits that no sequence read (bits_consumed < marker_bit): it reports them. */
+long long nafo_zstd_seq_tables(const uint8_t *src, size_t src_len, nafo_zstd_tablist *list, nafo_zstd_seqlist *seqs);
+void nafo_zstd_tablist_free(nafo_zstd_tablist *list);
+
 /* ---- NAF transforms : naf_oracle.c -------------------------------------------------------- */
 enum { NAFO_DNA = 0, NAFO_RNA = 1, NAFO_PROTEIN = 2, NAFO_TEXT = 3 };
 enum { NAFO_FMT_UNKNOWN = 0, NAFO_FMT_FASTA = 1, NAFO_FMT_FASTQ = 2 };

@@ -107,6 +107,28 @@ class FrameLiterals:
         return len(self.block_type)
 
 
+class _ZTabList(C.Structure):
+    _fields_ = [("blocks", C.c_void_p), ("n", C.c_size_t), ("cap", C.c_size_t)]
+
+
+class FrameSeqTables:
+    """What zstd_seq_tables lists, one entry per block, as numpy columns: `block_type`, `n_sequences`, `nseq_header_bytes` (1 to 3),
+    `section_offset` (of the Sequences_Section, from the frame's first byte), `section_bytes`, `bitstream_bytes`; per table in the order
+    LL, OF, ML (n x 3): `mode` (0 Predefined, 1 RLE, 2 FSE_Compressed, 3 Repeat), `accuracy_log`, `rle_symbol`, `desc_bytes`,
+    `final_state` (the states held at the block's last sequence) and `norm` (n x 3 x 64: the probabilities in force, -1 for "less than
+    1", 0 for absent); `bits_consumed` (from the bitstream, the initial states included) and `marker_bit` (the final marker's position,
+    from the bitstream's first bit).  A block without sequences has zeros behind `section_bytes`."""
+
+    def __init__(self, size, rec):
+        self.size = size
+        for k in ("block_type", "n_sequences", "nseq_header_bytes", "section_offset", "section_bytes", "bitstream_bytes", "mode", "accuracy_log",
+                  "rle_symbol", "desc_bytes", "final_state", "bits_consumed", "marker_bit", "norm"):
+            setattr(self, k, rec[k].astype("i8"))
+
+    def __len__(self):
+        return len(self.block_type)
+
+
 _lib = None
 
 
@@ -130,6 +152,9 @@ def lib():
         L.nafo_zstd_literals.restype = C.c_longlong
         L.nafo_zstd_literals.argtypes = [C.c_char_p, C.c_size_t, C.POINTER(_ZLitList)]
         L.nafo_zstd_litlist_free.argtypes = [C.POINTER(_ZLitList)]
+        L.nafo_zstd_seq_tables.restype = C.c_longlong
+        L.nafo_zstd_seq_tables.argtypes = [C.c_char_p, C.c_size_t, C.POINTER(_ZTabList), C.POINTER(_ZSeqList)]
+        L.nafo_zstd_tablist_free.argtypes = [C.POINTER(_ZTabList)]
         L.nafo_split_text.restype = C.c_int
         L.nafo_split_text.argtypes = [C.c_char_p, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(_Split)]
         L.nafo_split_free.argtypes = [C.POINTER(_Split)]
@@ -192,10 +217,7 @@ def zstd_sequences(frame: bytes) -> FrameSequences:
     if n < 0:
         raise ValueError("oracle zstd: error %d" % n)
     try:
-        bt = np.dtype([("type", "<u4"), ("size", "<u4")])
-        st = np.dtype([("block", "<u4"), ("offset_value", "<u4"), ("pos", "<u8"), ("ll", "<u8"), ("ml", "<u8"), ("distance", "<u8")])
-        blocks = np.frombuffer(C.string_at(l.blocks, l.n_blocks * bt.itemsize), dtype=bt) if l.n_blocks else np.zeros(0, bt)
-        seqs = np.frombuffer(C.string_at(l.seqs, l.n_seqs * st.itemsize), dtype=st) if l.n_seqs else np.zeros(0, st)
+        blocks, seqs = _seqlist_arrays(l)
     finally:
         lib().nafo_zstd_seqlist_free(C.byref(l))
     return FrameSequences(int(n), blocks, seqs)
@@ -218,6 +240,41 @@ def zstd_literals(frame: bytes) -> FrameLiterals:
     finally:
         lib().nafo_zstd_litlist_free(C.byref(l))
     return FrameLiterals(int(n), rec)
+
+
+def _seqlist_arrays(l):
+    import numpy as np
+    bt = np.dtype([("type", "<u4"), ("size", "<u4")])
+    st = np.dtype([("block", "<u4"), ("offset_value", "<u4"), ("pos", "<u8"), ("ll", "<u8"), ("ml", "<u8"), ("distance", "<u8")])
+    blocks = np.frombuffer(C.string_at(l.blocks, l.n_blocks * bt.itemsize), dtype=bt) if l.n_blocks else np.zeros(0, bt)
+    seqs = np.frombuffer(C.string_at(l.seqs, l.n_seqs * st.itemsize), dtype=st) if l.n_seqs else np.zeros(0, st)
+    return blocks, seqs
+
+
+def zstd_seq_tables(frame: bytes, with_sequences=False):
+    """The sequences section of every block of the (first) frame, listed by the decoder as it reads them; with_sequences: a pair of
+    that and what zstd_sequences lists, from the same reading.  Bits of a bitstream that no sequence read are reported (bits_consumed
+    below marker_bit), not refused as the decoders refuse them."""
+    import numpy as np
+    l, sl = _ZTabList(), _ZSeqList()
+    n = lib().nafo_zstd_seq_tables(frame, len(frame), C.byref(l), C.byref(sl) if with_sequences else None)
+    if n < 0:
+        raise ValueError("oracle zstd: error %d" % n)
+    if with_sequences:
+        try:
+            seqs = FrameSequences(int(n), *_seqlist_arrays(sl))
+        finally:
+            lib().nafo_zstd_seqlist_free(C.byref(sl))
+    try:
+        u = "<u4"
+        rt = np.dtype([("block_type", u), ("n_sequences", u), ("nseq_header_bytes", u), ("section_offset", u), ("section_bytes", u),
+                       ("bitstream_bytes", u), ("mode", u, 3), ("accuracy_log", u, 3), ("rle_symbol", u, 3), ("desc_bytes", u, 3),
+                       ("final_state", u, 3), ("bits_consumed", u), ("marker_bit", u), ("norm", "<i2", (3, 64))])
+        assert rt.itemsize == 92 + 384
+        rec = np.frombuffer(C.string_at(l.blocks, l.n * rt.itemsize), dtype=rt) if l.n else np.zeros(0, rt)
+    finally:
+        lib().nafo_zstd_tablist_free(C.byref(l))
+    return (FrameSeqTables(int(n), rec), seqs) if with_sequences else FrameSeqTables(int(n), rec)
 
 
 # ---- ennaf side ------------------------------------------------------------------------------------

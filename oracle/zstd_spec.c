@@ -43,6 +43,9 @@ typedef struct {
     nafo_zstd_litlist *lits;        /* nafo_zstd_literals: the literals section of every block */
     nafo_zstd_litblock cur;
     const uint8_t *frame_base;      /* first byte of the frame: what tree_offset counts from */
+    nafo_zstd_tablist *tabs;        /* nafo_zstd_seq_tables: the sequences section of every block */
+    nafo_zstd_seqtab curt;
+    int16_t tab_norm[3][64]; uint32_t tab_log[3], tab_rle[3];   /* of the tables in force: what Repeat_Mode repeats */
 } frame_ctx;
 
 /* append to the lists of nafo_zstd_sequences; 0, or ERR_DST when memory runs out */
@@ -62,6 +65,17 @@ static int list_lit(nafo_zstd_litlist *l, const nafo_zstd_litblock *r)
     if (l->n == l->cap) {
         size_t cap = l->cap ? l->cap * 2 : 64;
         nafo_zstd_litblock *nb = (nafo_zstd_litblock *)realloc(l->blocks, cap * sizeof *nb);
+        if (!nb) return ERR_DST;
+        l->blocks = nb; l->cap = cap;
+    }
+    l->blocks[l->n++] = *r;
+    return 0;
+}
+static int list_tab(nafo_zstd_tablist *l, const nafo_zstd_seqtab *r)
+{
+    if (l->n == l->cap) {
+        size_t cap = l->cap ? l->cap * 2 : 64;
+        nafo_zstd_seqtab *nb = (nafo_zstd_seqtab *)realloc(l->blocks, cap * sizeof *nb);
         if (!nb) return ERR_DST;
         l->blocks = nb; l->cap = cap;
     }
@@ -264,13 +278,26 @@ static int huf_decode_stream(const frame_ctx *c, const uint8_t *p, size_t len, u
 }
 
 /* ---- block decoding ------------------------------------------------------------------------ */
-static int read_seq_table(frame_ctx *c, int mode, fse_table *t, int *valid, const uint8_t **pp, const uint8_t *end,
+/* what nafo_zstd_seq_tables lists of table k: the table in force is kept for Repeat_Mode */
+static void note_seq_table(frame_ctx *c, int k, int mode, const int16_t *norm, int nsym, int log, int rle, int bytes)
+{
+    if (mode != 3) {
+        memset(c->tab_norm[k], 0, sizeof c->tab_norm[k]);
+        for (int s = 0; s < nsym && s < 64; s++) c->tab_norm[k][s] = norm[s];
+        c->tab_log[k] = (uint32_t)log; c->tab_rle[k] = (uint32_t)rle;
+    }
+    c->curt.mode[k] = (uint32_t)mode; c->curt.accuracy_log[k] = c->tab_log[k]; c->curt.rle_symbol[k] = c->tab_rle[k];
+    c->curt.desc_bytes[k] = (uint32_t)bytes;
+    memcpy(c->curt.norm[k], c->tab_norm[k], sizeof c->tab_norm[k]);
+}
+static int read_seq_table(frame_ctx *c, int k, int mode, fse_table *t, int *valid, const uint8_t **pp, const uint8_t *end,
                           const int16_t *def, int def_n, int def_log, int max_log, int max_sym)
 {
-    if (mode == 0) { *valid = 1; return fse_build(t, def, def_n, def_log); }
+    if (mode == 0) { *valid = 1; note_seq_table(c, k, 0, def, def_n, def_log, 0, 0); return fse_build(t, def, def_n, def_log); }
     if (mode == 1) {
         if (*pp >= end) return ERR_SRC;
         if (**pp > max_sym) return ERR_CORR;
+        note_seq_table(c, k, 1, NULL, 0, 0, **pp, 1);
         t->log = 0; t->e[0].sym = **pp; t->e[0].nbits = 0; t->e[0].base = 0; (*pp)++; *valid = 1; return 0;
     }
     if (mode == 2) {
@@ -278,9 +305,10 @@ static int read_seq_table(frame_ctx *c, int mode, fse_table *t, int *valid, cons
         int d = fse_read_desc(*pp, (size_t)(end - *pp), max_log, max_sym, norm, &nsym, &log);
         if (d < 0) return d;
         *pp += d; *valid = 1;
+        note_seq_table(c, k, 2, norm, nsym, log, 0, d);
         return fse_build(t, norm, nsym, log);
     }
-    (void)c;
+    note_seq_table(c, k, 3, NULL, 0, 0, 0, 0);
     return *valid ? 0 : ERR_CORR;                  /* repeat mode needs a previous table */
 }
 
@@ -347,6 +375,8 @@ static long long decode_compressed_block(frame_ctx *c, const uint8_t *src, size_
 
     /* sequences section */
     if (p >= end) return ERR_SRC;
+    const uint8_t *const section = p;
+    c->curt.section_offset = (uint32_t)(p - c->frame_base); c->curt.section_bytes = (uint32_t)(end - p);
     uint32_t nseq;
     if (p[0] == 0) { nseq = 0; p += 1; }
     else if (p[0] < 128) { nseq = p[0]; p += 1; }
@@ -354,6 +384,7 @@ static long long decode_compressed_block(frame_ctx *c, const uint8_t *src, size_
     else { if (end - p < 3) return ERR_SRC; nseq = p[1] + ((uint32_t)p[2] << 8) + 0x7F00; p += 3; }
 
     c->cur.n_sequences = nseq;
+    c->curt.n_sequences = nseq; c->curt.nseq_header_bytes = (uint32_t)(p - section);
     uint8_t *out = dst_base + dst_pos; size_t room = dst_cap - dst_pos; size_t op = 0, lp = 0;
     if (nseq == 0) {
         if (p != end) return ERR_CORR;
@@ -366,10 +397,11 @@ static long long decode_compressed_block(frame_ctx *c, const uint8_t *src, size_
     if (modes & 3) return ERR_CORR;
     int llm = modes >> 6, ofm = (modes >> 4) & 3, mlm = (modes >> 2) & 3, r;
     if (c->info) { c->info->seq_blocks++; c->info->n_sequences += nseq; c->info->mode_count[0][llm]++; c->info->mode_count[1][ofm]++; c->info->mode_count[2][mlm]++; }
-    if ((r = read_seq_table(c, llm, &c->ll, &c->ll_valid, &p, end, LL_DEFAULT, 36, 6, 9, 35)) < 0) return r;
-    if ((r = read_seq_table(c, ofm, &c->of, &c->of_valid, &p, end, OF_DEFAULT, 29, 5, 8, 31)) < 0) return r;
-    if ((r = read_seq_table(c, mlm, &c->ml, &c->ml_valid, &p, end, ML_DEFAULT, 53, 6, 9, 52)) < 0) return r;
+    if ((r = read_seq_table(c, 0, llm, &c->ll, &c->ll_valid, &p, end, LL_DEFAULT, 36, 6, 9, 35)) < 0) return r;
+    if ((r = read_seq_table(c, 1, ofm, &c->of, &c->of_valid, &p, end, OF_DEFAULT, 29, 5, 8, 31)) < 0) return r;
+    if ((r = read_seq_table(c, 2, mlm, &c->ml, &c->ml_valid, &p, end, ML_DEFAULT, 53, 6, 9, 52)) < 0) return r;
     bwd_bits b; if ((r = bwd_init(&b, p, (size_t)(end - p))) < 0) return r;
+    c->curt.bitstream_bytes = (uint32_t)(end - p); c->curt.marker_bit = (uint32_t)b.bits;
     uint32_t sl = (uint32_t)bwd_read(&b, c->ll.log), so = (uint32_t)bwd_read(&b, c->of.log), sm = (uint32_t)bwd_read(&b, c->ml.log);
     if (b.bits < 0) return ERR_CORR;
     for (uint32_t i = 0; i < nseq; i++) {
@@ -391,6 +423,7 @@ static long long decode_compressed_block(frame_ctx *c, const uint8_t *src, size_
                 c->rep[1] = c->rep[0]; c->rep[0] = off;
             }
         }
+        if (i + 1 == nseq) { c->curt.final_state[0] = sl; c->curt.final_state[1] = so; c->curt.final_state[2] = sm; }
         if (i + 1 < nseq) {
             sl = c->ll.e[sl].base + (uint32_t)bwd_read(&b, c->ll.e[sl].nbits);
             sm = c->ml.e[sm].base + (uint32_t)bwd_read(&b, c->ml.e[sm].nbits);
@@ -407,7 +440,8 @@ static long long decode_compressed_block(frame_ctx *c, const uint8_t *src, size_
         if (c->info && off > c->info->max_offset) c->info->max_offset = off;
         for (uint64_t k = 0; k < ml; k++) { out[op] = out[op - off]; op++; }
     }
-    if (b.bits != 0) return ERR_CORR;
+    c->curt.bits_consumed = (uint32_t)((long long)c->curt.marker_bit - b.bits);
+    if (b.bits != 0 && !c->tabs) return ERR_CORR;               /* (the listing of tables reports unread bits, it does not refuse them) */
     size_t rest = regen - lp;
     if (op + rest > room) return ERR_DST;
     if (op + rest > MAX_BLOCK) return ERR_CORR;
@@ -416,14 +450,14 @@ static long long decode_compressed_block(frame_ctx *c, const uint8_t *src, size_
 }
 
 static long long decode_frame_x(const uint8_t *src, size_t len, uint8_t *dst, size_t dst_pos, size_t dst_cap,
-                                size_t *consumed, nafo_zstd_frame_info *info, nafo_zstd_seqlist *list, nafo_zstd_litlist *lits);
+                                size_t *consumed, nafo_zstd_frame_info *info, nafo_zstd_seqlist *list, nafo_zstd_litlist *lits, nafo_zstd_tablist *tabs);
 static long long decode_frame(const uint8_t *src, size_t len, uint8_t *dst, size_t dst_pos, size_t dst_cap,
                               size_t *consumed, nafo_zstd_frame_info *info)
 {
-    return decode_frame_x(src, len, dst, dst_pos, dst_cap, consumed, info, NULL, NULL);
+    return decode_frame_x(src, len, dst, dst_pos, dst_cap, consumed, info, NULL, NULL, NULL);
 }
 static long long decode_frame_x(const uint8_t *src, size_t len, uint8_t *dst, size_t dst_pos, size_t dst_cap,
-                                size_t *consumed, nafo_zstd_frame_info *info, nafo_zstd_seqlist *list, nafo_zstd_litlist *lits)
+                                size_t *consumed, nafo_zstd_frame_info *info, nafo_zstd_seqlist *list, nafo_zstd_litlist *lits, nafo_zstd_tablist *tabs)
 {
     seq_dump_open();
     if (len < 4) return ERR_SRC;
@@ -461,7 +495,7 @@ static long long decode_frame_x(const uint8_t *src, size_t len, uint8_t *dst, si
 
     frame_ctx *c = (frame_ctx *)calloc(1, sizeof *c);
     if (!c) return ERR_DST;
-    c->rep[0] = 1; c->rep[1] = 4; c->rep[2] = 8; c->info = info; c->list = list; c->lits = lits; c->frame_base = src;
+    c->rep[0] = 1; c->rep[1] = 4; c->rep[2] = 8; c->info = info; c->list = list; c->lits = lits; c->tabs = tabs; c->frame_base = src;
     size_t start = dst_pos; long long rc = 0;
     for (;;) {
         if (end - p < 3) { rc = ERR_SRC; break; }
@@ -471,6 +505,7 @@ static long long decode_frame_x(const uint8_t *src, size_t len, uint8_t *dst, si
         const size_t block_start = dst_pos;
         memset(&c->cur, 0, sizeof c->cur);
         c->cur.lit_type = NAFO_LIT_NONE;
+        memset(&c->curt, 0, sizeof c->curt);
         if (type == 0) {
             if (bsize > MAX_BLOCK) { rc = ERR_CORR; break; }
             if ((size_t)(end - p) < bsize) { rc = ERR_SRC; break; }
@@ -494,6 +529,7 @@ static long long decode_frame_x(const uint8_t *src, size_t len, uint8_t *dst, si
             c->cur.frame_size = 3 + (type == 1 ? 1u : (uint32_t)bsize);
             if (list_lit(lits, &c->cur) < 0) { rc = ERR_DST; break; }
         }
+        if (tabs) { c->curt.block_type = (uint32_t)type; if (list_tab(tabs, &c->curt) < 0) { rc = ERR_DST; break; } }
         c->block_no++;
         if (last) break;
     }
@@ -564,7 +600,7 @@ long long nafo_zstd_sequences(const uint8_t *src, size_t src_len, nafo_zstd_seql
         uint8_t *tmp = (uint8_t *)malloc(cap);
         if (!tmp) return ERR_DST;
         memset(list, 0, sizeof *list);
-        long long n = decode_frame_x(src, src_len, tmp, 0, cap, NULL, NULL, list, NULL);
+        long long n = decode_frame_x(src, src_len, tmp, 0, cap, NULL, NULL, list, NULL, NULL);
         free(tmp);
         if (n >= 0) return n;
         nafo_zstd_seqlist_free(list);
@@ -587,10 +623,35 @@ long long nafo_zstd_literals(const uint8_t *src, size_t src_len, nafo_zstd_litli
         uint8_t *tmp = (uint8_t *)malloc(cap);
         if (!tmp) return ERR_DST;
         memset(list, 0, sizeof *list);
-        long long n = decode_frame_x(src, src_len, tmp, 0, cap, NULL, NULL, NULL, list);
+        long long n = decode_frame_x(src, src_len, tmp, 0, cap, NULL, NULL, NULL, list, NULL);
         free(tmp);
         if (n >= 0) return n;
         nafo_zstd_litlist_free(list);
+        if (n != ERR_DST) return n;
+        cap *= 4;
+        if (cap > ((size_t)1 << 40)) return ERR_DST;
+    }
+}
+
+void nafo_zstd_tablist_free(nafo_zstd_tablist *list)
+{
+    free(list->blocks);
+    memset(list, 0, sizeof *list);
+}
+
+long long nafo_zstd_seq_tables(const uint8_t *src, size_t src_len, nafo_zstd_tablist *list, nafo_zstd_seqlist *seqs)
+{
+    size_t cap = src_len * 4 + (1u << 20);
+    for (;;) {
+        uint8_t *tmp = (uint8_t *)malloc(cap);
+        if (!tmp) return ERR_DST;
+        memset(list, 0, sizeof *list);
+        if (seqs) memset(seqs, 0, sizeof *seqs);
+        long long n = decode_frame_x(src, src_len, tmp, 0, cap, NULL, NULL, seqs, NULL, list);
+        free(tmp);
+        if (n >= 0) return n;
+        nafo_zstd_tablist_free(list);
+        if (seqs) nafo_zstd_seqlist_free(seqs);
         if (n != ERR_DST) return n;
         cap *= 4;
         if (cap > ((size_t)1 << 40)) return ERR_DST;

@@ -262,3 +262,23 @@ extern "C" long long emul_zstd_compress_lzx(const u8 *src, size_t n, u32 block, 
     if (stats) { stats[0] = st_seq; stats[1] = st_rep; stats[2] = st_lit; }
     return p - dst;
 }
+
+// ---- the sequence writers alone: one Sequences_Section from the caller's lists (tests/seq_plan.py) --------------------------------------------
+// ll / ml: literal and match lengths; ofv: Offset_Values (1..3 the repeat codes, else distance + 3).  Returns bytes written, 0 as the writer does.
+extern "C" u32 emul_write_sequences_x(const u16 *ll, const u16 *ml, const u32 *ofv, u32 nseq, u8 *out, u32 cap)
+{
+    if (!nseq) return 0;
+    SeqCTabs T; zenc_build_predefined(T);
+    SeqWS ws;
+    return zenc_write_sequences_x(out, cap, ll, ml, ofv, nseq, T, ws);
+}
+// of: distances (the in-block stage codes every offset as a new one); the lists are padded to a multiple of eight entries, as the writer reads them
+extern "C" u32 emul_write_sequences(const u16 *ll, const u16 *ml, const u16 *of, u32 nseq, u8 *out, u32 cap)
+{
+    if (!nseq) return 0;
+    SeqCTabs T; zenc_build_predefined(T); SeqCTab ct[3]; zenc_seq_ctabs(T, ct);
+    const size_t pad = ((size_t)nseq + 7) & ~(size_t)7;
+    std::vector<u16> a(pad, 0), b(pad, 3), c(pad, 1);
+    memcpy(a.data(), ll, (size_t)nseq * 2); memcpy(b.data(), ml, (size_t)nseq * 2); memcpy(c.data(), of, (size_t)nseq * 2);
+    return zenc_write_sequences(out, cap, a.data(), b.data(), c.data(), nseq, ct);
+}

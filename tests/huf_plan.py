@@ -26,9 +26,12 @@ the treeless sections from the oracle): F flat shortcut, R register construction
 limiting ran, P flat preferred, Q settled by the flat scan, C weights found in the sampled cache, M looked up and missed, D tree
 description deferred to k_zenc_tree, T coded with the frame's code, W Raw, E RLE.
 
-Out of this plan's reach and the next gap: the sequences section's FSE tables (zenc_write_sequences_x, fse_normalize as the sequence
-tables use it, zenc_fse_cost) -- every carrier here runs without the match finder; and the direct blocks of a one-pass FASTA
-(k_zenc_direct_plans), which zstd_encode_begin refuses next to NAF_GPU_BLOCK_LOG and which need 8 MiB of packed bases."""
+Out of this plan's reach: the sequences section's FSE tables (zenc_write_sequences_x, fse_normalize as the sequence tables use it,
+zenc_fse_cost) -- every carrier here runs without the match finder; tests/seq_plan.py holds them to a model of their own, block by
+block.  The next gap: the literals of a block that DOES carry sequences (the second k_zenc_plan over the match finder's literal
+buffer, with per-block lengths and no cache, and k_lz_choose's weighing of the two plans) are held by no model -- seq_plan.py looks at
+such a block's sequences section and at its size against the literal-only block, not at its Huffman code; and the direct blocks of a
+one-pass FASTA (k_zenc_direct_plans), which zstd_encode_begin refuses next to NAF_GPU_BLOCK_LOG and which need 8 MiB of packed bases."""
 import heapq
 import zlib
 from collections import namedtuple
