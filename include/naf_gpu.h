@@ -598,6 +598,56 @@ int  naf_gpu_unnaf_repeats(naf_gpu_ctx *ctx, const void *d_naf, size_t naf_len, 
                            uint64_t first, uint64_t count, naf_gpu_repeat *d_rows, size_t row_cap, uint64_t *n_repeats, uint64_t *n_bases,
                            uint64_t per_period[16]);
 
+/* ---- unnaf: quality trimming and filtering of reads, decided in the quality stream -------------------------------------
+ * What seqtk trimfq, BBDuk qtrim=rl, vsearch --fastq_maxee and cutadapt -q answer from the text -- which stretch of every read to keep,
+ * and which reads to drop -- as a table of (record, begin, end, ee, flags) rows, made from the quality bytes alone: neither the sequence
+ * nor the mask is decoded, and any sequence type is accepted.
+ *   Score     s(b) = (int64)limit - (int64)tab[b] of a quality byte b: tab is naf_gpu_quality_error_table (error probability times 2^32),
+ *             limit the cutoff error rate in the same units, 1 <= limit <= 2^32.  naf_gpu_trim_limit gives tab[33 + phred], the limit of
+ *             "trim below Phred Q" (phred <= 93, else NAF_GPU_EARG; host only); a code exactly at the cutoff scores 0.  All arithmetic is
+ *             64-bit integer arithmetic; a read of fewer than 2^31 codes cannot overflow.
+ *   Stretch   the Phred / Mott rule, which seqtk and BBDuk apply in floating point: of all non-empty intervals [begin, end) of one read,
+ *             the one whose score sum is largest and > 0; among equal sums the smallest begin, then the largest end (so codes that score
+ *             0 at either end of it are kept).  With no interval of positive sum begin = end = 0.  With this order the rule is an
+ *             associative, ordered combine of summaries of neighbouring pieces of a read, so the answer does not depend on where the
+ *             kernels cut the stream.
+ *   No trim   limit = NAF_GPU_TRIM_NONE: the stretch is [0, n) of every read, so the filters can be used alone.
+ *   ee        of a row: the sum of tab[b] over the stretch (expected errors times 2^32), the ee column of naf_gpu_qual_row restricted to
+ *             it: (end - begin) * limit - the stretch's score sum (without a limit: computed as if limit were 0, minus the read's total).
+ *   Filters   min_len >= 1; max_ee in table units, UINT64_MAX = none.  flags: NAF_GPU_TRIM_SHORT iff end - begin < min_len (an empty
+ *             stretch is always short), NAF_GPU_TRIM_ERRORS iff ee > max_ee, NAF_GPU_TRIM_KEPT iff neither.
+ *   Rows      exactly one per selected record, ascending; reserved = 0; the same bytes on every run and for every piece size.  d_rows is
+ *             DEVICE memory of any alignment; exactly 40 * n_records bytes are written and nothing else.  d_rows == NULL: the totals only.
+ *             With row_cap too small the call returns NAF_GPU_ECAP, sets *n_records and writes nothing.
+ *   Total     h_total (HOST memory, may be NULL): reads, kept (rows with NAF_GPU_TRIM_KEPT), bases (all codes of the selected reads),
+ *             kept_bases and kept_ee (sums of end - begin and of ee over the kept rows), n_short, n_errors (rows with that flag).
+ *   Errors    NAF_GPU_EARG, last_error saying which: limit 0, or above 2^32 and not NAF_GPU_TRIM_NONE; min_len 0; an archive with no
+ *             quality section; first > n_sequences or a range past the last record, as for naf_gpu_unnaf_quality.  A quality stream
+ *             shorter than the bases is NAF_GPU_EFORMAT.  An archive without records gives 0 rows.
+ *   Pieces    more quality bytes than NAF_GPU_TRIM_PIECE (default 2^31) are decoded and swept in pieces of whole records.
+ * A kept row's (record, begin, end) is what naf_gpu_unnaf_select_reads takes: the trimmed read under its own header line.
+ * TRACE=1: "[trim] records R kept K pieces P quality bytes decoded X of Y open tiles T" per call that reaches the records (T: parts of
+ * reads that cross a 4096-byte tile of the sweep, joined by a second kernel). */
+#define NAF_GPU_TRIM_NONE UINT64_MAX
+enum { NAF_GPU_TRIM_KEPT = 1, NAF_GPU_TRIM_SHORT = 2, NAF_GPU_TRIM_ERRORS = 4 };
+typedef struct { uint64_t limit, min_len, max_ee; } naf_gpu_trim_opts;
+typedef struct { uint64_t record, begin, end, ee; uint32_t flags, reserved; } naf_gpu_trim_row;   /* 40 bytes; reserved = 0 */
+typedef struct { uint64_t reads, kept, bases, kept_bases, kept_ee, n_short, n_errors; } naf_gpu_trim_total;
+
+int  naf_gpu_trim_limit(unsigned phred, uint64_t *limit);     /* host only, no device */
+int  naf_gpu_unnaf_trim(naf_gpu_ctx *ctx, const void *d_naf, size_t naf_len, const naf_gpu_trim_opts *opts, uint64_t first, uint64_t count,
+                        naf_gpu_trim_row *d_rows, size_t row_cap, uint64_t *n_records, naf_gpu_trim_total *h_total);
+
+/* The selection of naf_gpu_unnaf_select_stranded for READS: everything that call is, except that a sub-range segment keeps the header
+ * line of the whole-record segment of the same strand ('@' or '>' id name; id "/rc" name for strand 1) instead of id ':' begin+1 '-' end,
+ * and is therefore legal in FASTQ: bases [begin, end), "+\n", quality bytes [begin, end) -- both reversed, the bases complemented, for
+ * strand 1 -- then '\n'.  Whole-record segments are byte-identical to naf_gpu_unnaf_select_stranded's; NAF_OUT_4BIT and a segment with
+ * begin >= end after clamping stay NAF_GPU_EARG. */
+int  naf_gpu_unnaf_select_reads_size(naf_gpu_ctx *ctx, const void *d_naf, size_t naf_len, const naf_gpu_unnaf_opts *opts,
+                                     const naf_gpu_segment *segs, const uint8_t *strand, size_t n_segs, size_t *out_len);
+int  naf_gpu_unnaf_select_reads(naf_gpu_ctx *ctx, const void *d_naf, size_t naf_len, const naf_gpu_unnaf_opts *opts,
+                                const naf_gpu_segment *segs, const uint8_t *strand, size_t n_segs, void *d_out, size_t out_cap, size_t *out_len);
+
 /* ---- ennaf ------------------------------------------------------------------------------------------ */
 typedef struct {
     int      format;            /* NAF_FMT_* (AUTO = sniff, process.c:547-583) */

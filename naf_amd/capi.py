@@ -39,6 +39,7 @@ EXPORTS = [
     "naf_gpu_genetic_code_by_id", "naf_gpu_genetic_code_parse", "naf_gpu_genetic_code_stops", "naf_gpu_codon_lut",
     "naf_gpu_unnaf_translate_size", "naf_gpu_unnaf_translate",
     "naf_gpu_parse_repeat_spec", "naf_gpu_repeat_class", "naf_gpu_unnaf_repeats_count", "naf_gpu_unnaf_repeats",
+    "naf_gpu_trim_limit", "naf_gpu_unnaf_trim", "naf_gpu_unnaf_select_reads_size", "naf_gpu_unnaf_select_reads",
 ]
 WHOLE = 2 ** 64 - 1                     # NAF_GPU_WHOLE: (record, 0, WHOLE) is the record as stored
 MAX_SHARDS = 64
@@ -201,6 +202,31 @@ REPEAT_BYTES = 32
 REPEATS_WHOLE_UNITS = 1
 
 
+class TrimOpts(C.Structure):
+    """naf_gpu_trim_opts: the cutoff error rate times 2^32 (TRIM_NONE: no trimming), the bases a kept read needs, the expected errors times
+    2^32 it may have (2^64 - 1: any)."""
+    _fields_ = [("limit", C.c_uint64), ("min_len", C.c_uint64), ("max_ee", C.c_uint64)]
+
+
+class TrimRow(C.Structure):
+    """naf_gpu_trim_row: bases [begin, end) of `record` are the stretch to keep, ee the sum of the error-table entries of its quality codes;
+    flags: TRIM_KEPT, or TRIM_SHORT and / or TRIM_ERRORS."""
+    _fields_ = [("record", C.c_uint64), ("begin", C.c_uint64), ("end", C.c_uint64), ("ee", C.c_uint64), ("flags", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class TrimTotal(C.Structure):
+    """naf_gpu_trim_total: the reads of a call, those kept, all their bases, the bases and the ee of the kept stretches, the rows with
+    TRIM_SHORT and with TRIM_ERRORS."""
+    _fields_ = [("reads", C.c_uint64), ("kept", C.c_uint64), ("bases", C.c_uint64), ("kept_bases", C.c_uint64), ("kept_ee", C.c_uint64),
+                ("n_short", C.c_uint64), ("n_errors", C.c_uint64)]
+
+
+TRIM_DTYPE = [("record", "<u8"), ("begin", "<u8"), ("end", "<u8"), ("ee", "<u8"), ("flags", "<u4"), ("reserved", "<u4")]      # numpy's view of a table of rows
+TRIM_BYTES = 40
+TRIM_KEPT, TRIM_SHORT, TRIM_ERRORS = 1, 2, 4
+TRIM_NONE = 2 ** 64 - 1
+
+
 class NafGpuError(RuntimeError):
     def __init__(self, code, msg):
         super().__init__("naf_gpu error %d: %s" % (code, msg))
@@ -327,6 +353,10 @@ def load():
         L.naf_gpu_repeat_class.argtypes = [C.c_uint32, C.c_uint, u32p]
         L.naf_gpu_unnaf_repeats_count.argtypes = [vp, vp, sz, C.POINTER(RepeatSpec), i, C.c_uint64, C.c_uint64, C.c_uint64, u64p, u64p, u64p]
         L.naf_gpu_unnaf_repeats.argtypes = [vp, vp, sz, C.POINTER(RepeatSpec), i, C.c_uint64, C.c_uint64, C.c_uint64, vp, sz, u64p, u64p, u64p]
+        L.naf_gpu_trim_limit.argtypes = [C.c_uint, u64p]
+        L.naf_gpu_unnaf_trim.argtypes = [vp, vp, sz, C.POINTER(TrimOpts), C.c_uint64, C.c_uint64, vp, sz, u64p, C.POINTER(TrimTotal)]
+        L.naf_gpu_unnaf_select_reads_size.argtypes = [vp, vp, sz, C.POINTER(UnnafOpts), C.POINTER(Segment), u8p, sz, C.POINTER(sz)]
+        L.naf_gpu_unnaf_select_reads.argtypes = [vp, vp, sz, C.POINTER(UnnafOpts), C.POINTER(Segment), u8p, sz, vp, sz, C.POINTER(sz)]
         _lib = L
     return _lib
 
@@ -390,6 +420,38 @@ def quality_error_table():
     if rc:
         raise NafGpuError(rc, load().naf_gpu_strerror(rc).decode())
     return [int(v) for v in tab]
+
+
+def trim_limit(q):
+    """Host-only: the limit of "trim below Phred q" (naf_gpu_trim_limit): the error-table entry of byte 33 + q, q = 0 .. 93."""
+    v = C.c_uint64()
+    rc = load().naf_gpu_trim_limit(int(q), C.byref(v)) if 0 <= int(q) < 2 ** 32 else -8
+    if rc:
+        raise ValueError("not a Phred score to trim at (0 to 93): %r" % (q,))
+    return int(v.value)
+
+
+def ee_units(x):
+    """Expected errors as the trim calls take them: floor(x * 2^32) of an int, a Fraction, or a decimal text of digits with at most one
+    point that has 1 to 9 digits behind it ("2", "0.5", "1.999999999").  No floats: a float is not the number that was written."""
+    from fractions import Fraction
+    if isinstance(x, bool) or isinstance(x, float):
+        raise ValueError("expected errors are given as text, int or Fraction, not as %r" % (x,))
+    if isinstance(x, (bytes, str)):
+        t = x.decode("latin1") if isinstance(x, bytes) else x
+        whole, point, frac = t.partition(".")
+        if not (whole.isascii() and whole.isdigit() and ((not point) or (frac.isascii() and frac.isdigit() and 1 <= len(frac) <= 9))):
+            raise ValueError("not a number of expected errors (digits, or digits.digits with 1 to 9 behind the point): %r" % (x,))
+        x = Fraction(int(whole)) + (Fraction(int(frac), 10 ** len(frac)) if point else 0)
+    v = int(Fraction(x) * 2 ** 32)
+    if not 0 <= v < 2 ** 64 - 1:
+        raise ValueError("expected errors out of range: %r" % (x,))
+    return v
+
+
+def trim_to_segments(rows):
+    """The (record, begin, end) tuples unnaf_select_reads takes: the kept rows of the table unnaf_trim returns, in its order."""
+    return [(int(x["record"]), int(x["begin"]), int(x["end"])) for x in rows if int(x["flags"]) == TRIM_KEPT]
 
 
 def parse_base_class(text):
@@ -875,6 +937,26 @@ class Context:
             self._check(self.L.naf_gpu_unnaf_select_stranded(self.h, _ptr(d_naf), d_naf.numel(), C.byref(o), segs, strands, len(segments), _ptr(out), out.numel(), C.byref(n)))
         return out[:n.value]
 
+    def unnaf_select_reads_size(self, d_naf, segments, out_type=OUT_DEFAULT, use_mask=True, line_length=-1):
+        o = UnnafOpts(out_type, int(use_mask), line_length)
+        n = C.c_size_t()
+        self._check(self.L.naf_gpu_unnaf_select_reads_size(self.h, _ptr(d_naf), d_naf.numel(), C.byref(o), self._segments(segments), self._strands(segments), len(segments), C.byref(n)))
+        return n.value
+
+    def unnaf_select_reads(self, d_naf, segments, out_type=OUT_DEFAULT, use_mask=True, line_length=-1, out=None):
+        """The texts of the segments as READS (naf_gpu_unnaf_select_reads): what unnaf_select gives, 3- and 4-tuples alike, except that a
+        sub-range keeps the header line of its whole record ("/rc" behind the id for a reverse one) and so can be written as FASTQ: bases
+        and quality codes [begin, end).  trim_to_segments gives the segments of a trim table's kept rows."""
+        import torch
+        o = UnnafOpts(out_type, int(use_mask), line_length)
+        segs, strands = self._segments(segments), self._strands(segments)
+        n = C.c_size_t()
+        if out is None:
+            self._check(self.L.naf_gpu_unnaf_select_reads_size(self.h, _ptr(d_naf), d_naf.numel(), C.byref(o), segs, strands, len(segments), C.byref(n)))
+            out = torch.empty(max(n.value, 1), dtype=torch.uint8, device=self.device)
+        self._check(self.L.naf_gpu_unnaf_select_reads(self.h, _ptr(d_naf), d_naf.numel(), C.byref(o), segs, strands, len(segments), _ptr(out), out.numel(), C.byref(n)))
+        return out[:n.value]
+
     def unnaf_translate_size(self, d_naf, segments, code=1, line_length=-1):
         o = UnnafOpts(OUT_FASTA, 0, line_length)
         g = genetic_code(code)
@@ -1068,6 +1150,31 @@ class Context:
             view = buf[:QUAL_ROW_BYTES * n]
             return np.frombuffer(view.cpu().numpy().tobytes(), dtype=QUAL_DTYPE) if own else view
         return table(rb, rown, nr.value), table(cb, cown, nc.value), [int(v) for v in hist], tot
+
+    def unnaf_trim(self, d_naf, limit, min_len=1, max_ee=None, first=0, count=None, out=None):
+        """(rows, total): the stretch to keep of every read of records [first, first + count) and what the filters say of it
+        (naf_gpu_unnaf_trim) -- limit: the cutoff error rate times 2^32 (trim_limit(q) for Phred q; TRIM_NONE: no trimming); min_len: the
+        bases a kept read needs; max_ee: the expected errors times 2^32 it may have (ee_units; None: any) -- as a structured numpy array
+        (TRIM_DTYPE: record, begin, end, ee, flags, reserved), one row per read, and a TrimTotal.  out: a uint8 device tensor to take the
+        table (40 bytes a row); then `rows` is the torch view of its first 40 * n bytes and too small a tensor raises NafGpuError(E_CAP).
+        out=False: the totals only, rows is None."""
+        import numpy as np
+        import torch
+        o = TrimOpts(int(limit), int(min_len), 2 ** 64 - 1 if max_ee is None else int(max_ee))
+        n, tot = C.c_uint64(), TrimTotal()
+        cnt = WHOLE if count is None else int(count)
+        own = out is None
+        if own:
+            have = int(self.parse_header(d_naf).n_sequences)
+            rows = max(0, min(have - int(first), cnt)) if cnt != WHOLE else max(0, have - int(first))
+            out = torch.empty(max(TRIM_BYTES * rows, 1), dtype=torch.uint8, device=self.device)
+        buf = None if out is False else out
+        self._check(self.L.naf_gpu_unnaf_trim(self.h, _ptr(d_naf), d_naf.numel(), C.byref(o), int(first), cnt, _ptr(buf) if buf is not None else None,
+                                              buf.numel() // TRIM_BYTES if buf is not None else 0, C.byref(n), C.byref(tot)))
+        if buf is None:
+            return None, tot
+        view = buf[:TRIM_BYTES * n.value]
+        return (np.frombuffer(view.cpu().numpy().tobytes(), dtype=TRIM_DTYPE) if own else view), tot
 
     @staticmethod
     def _run_class(cls, each, masked):

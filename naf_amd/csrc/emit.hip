@@ -2213,6 +2213,7 @@ extern "C" int naf_gpu_unnaf_range(naf_gpu_ctx *c, const void *d_naf, size_t naf
 #include "orfs.h"
 #include "translate.h"
 #include "repeats.h"
+#include "trim.h"
 
 // ---- byte histogram (unnaf --charcount, output.c:515-605) ------------------------------------------------------------------
 __global__ __launch_bounds__(256) void k_histogram(const u8 *p, u64 n, unsigned long long *counts)

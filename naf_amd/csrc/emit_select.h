@@ -1,5 +1,5 @@
 // emit_select.h -- the selection path of unnaf: records and regions by number, id or range (naf_gpu_unnaf_find,
-// naf_gpu_unnaf_record_table, naf_gpu_unnaf_select, naf_gpu_unnaf_select_stranded).  Part of emit.hip (included by it, behind unnaf_run): it uses that file's
+// naf_gpu_unnaf_record_table, naf_gpu_unnaf_select, naf_gpu_unnaf_select_stranded, naf_gpu_unnaf_select_reads).  Part of emit.hip (included by it, behind unnaf_run): it uses that file's
 // side-section chain (unnaf_prepare, unnaf_sections), the payload decode of payload.h and device helpers as they are, and adds kernels of its own.
 //
 // A selection is a list of SEGMENTS -- bases [begin, end) of a record -- whose texts are laid end to end in the order given.  The
@@ -18,6 +18,9 @@
 //
 // The same front serves the translation (translate.h: naf_gpu_unnaf_translate): select_run takes the bases to a byte of the body (1, or 3 for
 // amino acids) and the launch of the kernel that writes the text; everything in front of that launch is one code for both.
+//
+// A selection of READS (naf_gpu_unnaf_select_reads: trimmed reads) differs in one thing: a sub-range keeps the header line of its whole
+// record (SEL_READ in place of SEL_SUB), and so has a FASTQ form -- the composer takes bases and qualities from g0 / n of any segment.
 #pragma once
 #include <algorithm>
 
@@ -30,10 +33,11 @@ struct SelSeg {
     u64 klo, khi;                            // mask toggles that can fall inside it: toggles[klo .. khi)
     u64 rec, begin;                          // record and 0-based first base inside it
     const u8 *seq, *qual;                    // the decoded range that holds its bases, as pointers to stream byte 0 / quality byte 0
-    u32 hl, sub;                             // header length; SEL_SUB = a sub-range (header '>' id ':' begin+1 '-' end), SEL_RC = reverse complement ("/rc" behind it)
+    u32 hl, sub;                             // header length; SEL_SUB = a sub-range (header '>' id ':' begin+1 '-' end), SEL_RC = reverse complement ("/rc" behind it), SEL_READ = a sub-range under its record's own header
 };
 #define SEL_SUB 1u
 #define SEL_RC 2u
+#define SEL_READ 4u
 struct SelRange { u64 g_lo, g_hi; const u8 *seq, *qual; };
 
 __device__ __forceinline__ u32 dec_digits(u64 v) { u32 n = 1; while (v >= 10) { v /= 10; n++; } return n; }
@@ -41,7 +45,8 @@ __device__ __forceinline__ u32 dec_digits(u64 v) { u32 n = 1; while (v >= 10) { 
 // One lane per segment: validation, geometry, text size.  status[0] receives the number of the first segment that cannot be
 // produced (atomicMin; ~0 = none).  size[] / hsize[] are scanned into the text offsets and the header stream offsets.
 // per: bases per byte of the body, 1 for the bases themselves, 3 for their translation (translate.h; FASTA only): the wrap counts the bytes.
-__global__ __launch_bounds__(256) void k_select_layout(EmitP P, const naf_gpu_segment *in, const u8 *strand, u64 S, u32 per, SelSeg *sg, u64 *size, u64 *hsize, u64 *iv, unsigned long long *status)
+// reads: a sub-range is a read cut short -- its record's header line, FASTQ allowed.
+__global__ __launch_bounds__(256) void k_select_layout(EmitP P, const naf_gpu_segment *in, const u8 *strand, u64 S, u32 per, u32 reads, SelSeg *sg, u64 *size, u64 *hsize, u64 *iv, unsigned long long *status)
 {
     const u64 s = (u64)blockIdx.x * 256 + threadIdx.x;
     if (s >= S) return;
@@ -50,12 +55,12 @@ __global__ __launch_bounds__(256) void k_select_layout(EmitP P, const naf_gpu_se
     SelSeg g; memset(&g, 0, sizeof g);
     bool bad = rec >= P.N;
     u64 len = 0;
-    if (!bad) { len = P.rec_len[rec]; if (e > len) e = len; bad = !whole && (b >= e || P.mode == EM_FASTQ); }
+    if (!bad) { len = P.rec_len[rec]; if (e > len) e = len; bad = !whole && (b >= e || (P.mode == EM_FASTQ && !reads)); }
     if (bad) { atomicMin(status, (unsigned long long)s); size[s] = 0; hsize[s] = 0; iv[2 * s] = iv[2 * s + 1] = 0; sg[s] = g; return; }
-    g.rec = rec; g.begin = whole ? 0 : b; g.n = whole ? len : e - b; g.g0 = P.rec_base[rec] + g.begin; g.sub = (whole ? 0u : SEL_SUB) | (rc ? SEL_RC : 0u);
+    g.rec = rec; g.begin = whole ? 0 : b; g.n = whole ? len : e - b; g.g0 = P.rec_base[rec] + g.begin; g.sub = (whole ? 0u : reads ? SEL_READ : SEL_SUB) | (rc ? SEL_RC : 0u);
     u64 h = 0;
     if (P.mode == EM_FASTA || P.mode == EM_FASTQ) {
-        if (whole) h = P.hdr_len[rec];
+        if (whole || reads) h = P.hdr_len[rec];
         else { const u64 idl = P.has_ids ? P.idz[rec] - (rec ? P.idz[rec - 1] + 1 : 0) : 0; h = 1 + idl + 1 + dec_digits(b + 1) + 1 + dec_digits(e) + 1; }
         if (rc) h += 3;                                                           // "/rc"
     }
@@ -438,10 +443,10 @@ static int select_emit(naf_gpu_ctx *c, const SelCall &k)
 }
 
 // h_strand: one byte per segment, 1 = its reverse complement; nullptr = none.  per, emit: 1 and select_emit; 3 and translate.h's for the
-// translation, which is FASTA-shaped whatever the archive and needs a 4-bit stream.
+// translation, which is FASTA-shaped whatever the archive and needs a 4-bit stream.  reads: naf_gpu_unnaf_select_reads (sub-ranges under their record's header).
 template <typename Emit>
 static int select_run(naf_gpu_ctx *c, const u8 *d_naf, size_t naf_len, const naf_gpu_unnaf_opts *o, const naf_gpu_segment *h_segs, const u8 *h_strand, size_t S,
-                      u8 *d_out, size_t out_cap, size_t *out_len, bool size_only, u32 per, Emit emit)
+                      u8 *d_out, size_t out_cap, size_t *out_len, bool size_only, bool reads, u32 per, Emit emit)
 {
     if (!c || !d_naf || !o || !out_len || (S && !h_segs)) return NAF_GPU_EARG;
     arena_reset(c);
@@ -478,7 +483,7 @@ static int select_run(naf_gpu_ctx *c, const u8 *d_naf, size_t naf_len, const naf
     HIP_TRY(c, hipMemsetAsync(d_status, 0xFF, 8, c->stream));
     HIP_TRY(c, hipMemsetAsync(seg_out + S, 0, 8, c->stream));
     HIP_TRY(c, hipMemsetAsync(hoff + S, 0, 8, c->stream));
-    LAUNCH(c, "unnaf_select_layout", k_select_layout, cdiv(S, 256), 256, 0, P, (const naf_gpu_segment *)d_in, (const u8 *)d_strand, (u64)S, per, sg, seg_out, hoff, iv, d_status);
+    LAUNCH(c, "unnaf_select_layout", k_select_layout, cdiv(S, 256), 256, 0, P, (const naf_gpu_segment *)d_in, (const u8 *)d_strand, (u64)S, per, reads ? 1u : 0u, sg, seg_out, hoff, iv, d_status);
     if ((rc = scan_exclusive_u64(c, seg_out, S + 1, (u64 *)nullptr))) return rc;
     if ((rc = scan_exclusive_u64(c, hoff, S + 1, (u64 *)nullptr))) return rc;
     u64 first_bad = 0, total = 0, htotal = 0;
@@ -487,7 +492,7 @@ static int select_run(naf_gpu_ctx *c, const u8 *d_naf, size_t naf_len, const naf
     if (first_bad != ~0ull) {
         const naf_gpu_segment &sgm = h_segs[first_bad];
         if (sgm.record >= P.N) return ctx_fail(c, NAF_GPU_EARG, "segment %llu: record %llu is not in the archive (%llu records)", (unsigned long long)first_bad, (unsigned long long)sgm.record, (unsigned long long)P.N);
-        if (P.mode == EM_FASTQ) return ctx_fail(c, NAF_GPU_EARG, "segment %llu: a part of a record (bases %llu..%llu of record %llu) has no FASTQ form", (unsigned long long)first_bad, (unsigned long long)sgm.begin, (unsigned long long)sgm.end, (unsigned long long)sgm.record);
+        if (P.mode == EM_FASTQ && !reads) return ctx_fail(c, NAF_GPU_EARG, "segment %llu: a part of a record (bases %llu..%llu of record %llu) has no FASTQ form", (unsigned long long)first_bad, (unsigned long long)sgm.begin, (unsigned long long)sgm.end, (unsigned long long)sgm.record);
         u64 len = 0; if ((rc = ctx_readback(c, &len, P.rec_len + sgm.record, 8))) return rc;
         return ctx_fail(c, NAF_GPU_EARG, "segment %llu: bases %llu..%llu select nothing of record %llu (%llu bases)", (unsigned long long)first_bad, (unsigned long long)sgm.begin, (unsigned long long)sgm.end, (unsigned long long)sgm.record, (unsigned long long)len);
     }
@@ -542,24 +547,36 @@ static int select_run(naf_gpu_ctx *c, const u8 *d_naf, size_t naf_len, const naf
 extern "C" int naf_gpu_unnaf_select_size(naf_gpu_ctx *c, const void *d_naf, size_t naf_len, const naf_gpu_unnaf_opts *o,
                                          const naf_gpu_segment *segs, size_t n_segs, size_t *out_len)
 {
-    return select_run(c, (const u8 *)d_naf, naf_len, o, segs, nullptr, n_segs, nullptr, 0, out_len, true, 1, select_emit);
+    return select_run(c, (const u8 *)d_naf, naf_len, o, segs, nullptr, n_segs, nullptr, 0, out_len, true, false, 1, select_emit);
 }
 extern "C" int naf_gpu_unnaf_select(naf_gpu_ctx *c, const void *d_naf, size_t naf_len, const naf_gpu_unnaf_opts *o,
                                     const naf_gpu_segment *segs, size_t n_segs, void *d_out, size_t out_cap, size_t *out_len)
 {
-    int rc = select_run(c, (const u8 *)d_naf, naf_len, o, segs, nullptr, n_segs, (u8 *)d_out, out_cap, out_len, false, 1, select_emit);
+    int rc = select_run(c, (const u8 *)d_naf, naf_len, o, segs, nullptr, n_segs, (u8 *)d_out, out_cap, out_len, false, false, 1, select_emit);
     if (c) arena_settle(c);
     return rc;
 }
 extern "C" int naf_gpu_unnaf_select_stranded_size(naf_gpu_ctx *c, const void *d_naf, size_t naf_len, const naf_gpu_unnaf_opts *o,
                                                   const naf_gpu_segment *segs, const uint8_t *strand, size_t n_segs, size_t *out_len)
 {
-    return select_run(c, (const u8 *)d_naf, naf_len, o, segs, strand, n_segs, nullptr, 0, out_len, true, 1, select_emit);
+    return select_run(c, (const u8 *)d_naf, naf_len, o, segs, strand, n_segs, nullptr, 0, out_len, true, false, 1, select_emit);
 }
 extern "C" int naf_gpu_unnaf_select_stranded(naf_gpu_ctx *c, const void *d_naf, size_t naf_len, const naf_gpu_unnaf_opts *o,
                                              const naf_gpu_segment *segs, const uint8_t *strand, size_t n_segs, void *d_out, size_t out_cap, size_t *out_len)
 {
-    int rc = select_run(c, (const u8 *)d_naf, naf_len, o, segs, strand, n_segs, (u8 *)d_out, out_cap, out_len, false, 1, select_emit);
+    int rc = select_run(c, (const u8 *)d_naf, naf_len, o, segs, strand, n_segs, (u8 *)d_out, out_cap, out_len, false, false, 1, select_emit);
+    if (c) arena_settle(c);
+    return rc;
+}
+extern "C" int naf_gpu_unnaf_select_reads_size(naf_gpu_ctx *c, const void *d_naf, size_t naf_len, const naf_gpu_unnaf_opts *o,
+                                               const naf_gpu_segment *segs, const uint8_t *strand, size_t n_segs, size_t *out_len)
+{
+    return select_run(c, (const u8 *)d_naf, naf_len, o, segs, strand, n_segs, nullptr, 0, out_len, true, true, 1, select_emit);
+}
+extern "C" int naf_gpu_unnaf_select_reads(naf_gpu_ctx *c, const void *d_naf, size_t naf_len, const naf_gpu_unnaf_opts *o,
+                                          const naf_gpu_segment *segs, const uint8_t *strand, size_t n_segs, void *d_out, size_t out_cap, size_t *out_len)
+{
+    int rc = select_run(c, (const u8 *)d_naf, naf_len, o, segs, strand, n_segs, (u8 *)d_out, out_cap, out_len, false, true, 1, select_emit);
     if (c) arena_settle(c);
     return rc;
 }

@@ -211,7 +211,7 @@ static int translate_run(naf_gpu_ctx *c, const u8 *d_naf, size_t naf_len, const 
     u8 lut[4096];
     if (naf_gpu_codon_lut(code, lut)) return ctx_fail(c, NAF_GPU_EARG, "translate: the genetic code is NULL or holds a byte that is neither a letter A..Z nor '*'");
     const naf_gpu_unnaf_opts fasta = { NAF_OUT_FASTA, 0, o->line_length };       // FASTA-shaped whatever the archive; the mask is not decoded
-    return select_run(c, d_naf, naf_len, &fasta, segs, strand, S, d_out, out_cap, out_len, size_only, 3, [&](naf_gpu_ctx *c, const SelCall &k) -> int {
+    return select_run(c, d_naf, naf_len, &fasta, segs, strand, S, d_out, out_cap, out_len, size_only, false, 3, [&](naf_gpu_ctx *c, const SelCall &k) -> int {
         std::vector<u8> tab(8192);
         tr_kernel_tables(lut, tab.data());
         const size_t tb = k.any_rc ? 8192 : 4096;

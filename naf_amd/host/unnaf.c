@@ -43,6 +43,10 @@ static unsigned long long min_repeat = 1;
 /* --translate [--frame LIST] [--code N | --code-table LETTERS64]: the selection's frames, or with --orfs every reading frame, as protein FASTA (this implementation only) */
 static bool translate = false; static int frames[6] = { 1 }; static size_t n_frames = 1;
 static const char *frame_text = NULL, *code_text = NULL, *code_table_text = NULL; static naf_gpu_genetic_code genetic_code;
+/* --trim Q|none [--min-length N] [--max-ee X] [--trim-table]: the reads cut to their best stretch of quality codes and filtered, or the table of
+ * the stretches (this implementation only) */
+static const char *trim_text = NULL, *max_ee_text = NULL; static naf_gpu_trim_opts trim_opts = { 0, 1, UINT64_MAX };
+static bool min_length_given = false, trim_table = false, reads_selection = false;      /* reads_selection: emit_segments writes reads (naf_gpu_unnaf_select_reads) */
 
 static void done(int status, void *arg)
 {
@@ -110,18 +114,48 @@ static void set_strand(const char *v)
     strand_given = true;
 }
 
-/* --window, --cycles, --min-run, --min-orf, --min-repeat: a positive number of `unit`; commas are skipped (1,000) */
-static unsigned long long positive_number(const char *opt, const char *unit, const char *v)
+/* the n bytes at v as a number: digits, commas are skipped (1,000); false: not one, or too large */
+static bool number_of(const char *v, size_t n, unsigned long long *out)
 {
     unsigned long long a = 0; bool ok = false;
-    for (const char *p = v; *p; p++) {
+    for (const char *p = v; p < v + n; p++) {
         if (*p == ',') continue;
         ok = *p >= '0' && *p <= '9' && a <= (ULLONG_MAX - (unsigned)(*p - '0')) / 10;
         if (!ok) break;
         a = a * 10 + (unsigned)(*p - '0');
     }
-    if (!ok || a == 0) die("can't parse the value of %s parameter (a positive number of %s)\n", opt, unit);
+    *out = a;
+    return ok;
+}
+/* --window, --cycles, --min-run, --min-orf, --min-repeat, --min-length: a positive number of `unit` */
+static unsigned long long positive_number(const char *opt, const char *unit, const char *v)
+{
+    unsigned long long a = 0;
+    if (!number_of(v, strlen(v), &a) || a == 0) die("can't parse the value of %s parameter (a positive number of %s)\n", opt, unit);
     return a;
+}
+
+static void set_trim(const char *v)
+{
+    if (trim_text) die("only one --trim cutoff can be given\n");
+    unsigned long long q = 0;
+    if (!strcmp(v, "none")) trim_opts.limit = NAF_GPU_TRIM_NONE;
+    else if (strchr(v, ',') || !number_of(v, strlen(v), &q) || q > 93 || naf_gpu_trim_limit((unsigned)q, &trim_opts.limit))
+        die("can't parse the value of --trim parameter (a Phred score of 0 to 93, or none)\n");
+    trim_text = v;
+}
+/* --max-ee X: digits, or digits '.' and 1 to 9 digits; floor(X * 2^32) in integers */
+static void set_max_ee(const char *v)
+{
+    if (max_ee_text) die("only one --max-ee value can be given\n");
+    const char *dot = strchr(v, '.');
+    const size_t nw = dot ? (size_t)(dot - v) : strlen(v), nf = dot ? strlen(dot + 1) : 0;
+    unsigned long long whole = 0, frac = 0, pow10 = 1;
+    bool ok = !strchr(v, ',') && number_of(v, nw, &whole) && whole <= 0xFFFFFFFFull && (!dot || (nf >= 1 && nf <= 9 && number_of(dot + 1, nf, &frac)));
+    if (!ok) die("can't parse the value of --max-ee parameter (expected errors: digits, or digits.digits with 1 to 9 behind the point)\n");
+    for (size_t k = 0; k < nf; k++) pow10 *= 10;
+    trim_opts.max_ee = (whole << 32) + (frac << 32) / pow10;                   /* frac < 10^9 < 2^30: no overflow */
+    max_ee_text = v;
 }
 
 static void set_runs(const char *v)
@@ -245,12 +279,17 @@ static void show_help(void)
         "  --code-table LETTERS - With --translate: a genetic code of its own, 64 letters A-Z or * for the codons AAA AAC AAG AAT ACA ... TTT\n"
         "  --repeats SPEC  - Every perfect tandem repeat, as lines \"ID begin end PERIOD MOTIF COPIES CLASS\" (0-based half-open): SPEC is PERIOD-COPIES pairs, e.g. 1-10,2-6,3-5, periods 1 to 16; or misa\n"
         "  --min-repeat N  - With --repeats: only repeats of at least N bases (default 1)\n"
-        "  --whole-units   - With --repeats: the end of a repeat is cut to a whole number of copies, as MISA and PERF print it\n");
+        "  --whole-units   - With --repeats: the end of a repeat is cut to a whole number of copies, as MISA and PERF print it\n"
+        "Options for trimming reads by quality (output: the kept reads, each cut to its stretch, as --fastq (default), --fasta, --sequences or --seq; with at most one --records A-B or --region ID):\n"
+        "  --trim Q        - Of every read the stretch of the largest sum of (error rate of Phred Q) - (error rate of the code), Q = 0 to 93: the Phred / Mott rule of seqtk and BBDuk; none = the whole read\n"
+        "  --min-length N  - With --trim: drop reads whose stretch has fewer than N bases (default 1)\n"
+        "  --max-ee X      - With --trim: drop reads whose stretch has more than X expected errors, e.g. 2 or 0.5\n"
+        "  --trim-table    - With --trim: instead of the reads, a table \"#seq length begin end ee status\" of all reads (0-based half-open; status kept, short, errors or short,errors)\n");
 }
 
 /* ---- the table modes ---------------------------------------------------------------------------------------------------------------
- * --locate, --composition, --quality, --runs / --masked-runs, --kmers, --orfs, --translate and --repeats write a table of their own
- * instead of an output type.  A mode is a row here -- what its refusals say, its options, its runner -- plus the checks that are
+ * --locate, --composition, --quality, --runs / --masked-runs, --kmers, --orfs, --translate, --repeats and --trim write a table of their own
+ * instead of an output type (--trim without --trim-table: the reads, in one of the sequence output types).  A mode is a row here -- what its refusals say, its options, its runner -- plus the checks that are
  * really its own; parse_command_line walks the rows once, in this order, and main runs the first one asked for (--orfs in front
  * of --translate: the one legal pair). */
 typedef struct { bool given, fits; const char *refusal; } satellite;        /* an option of a mode: given; given together with what it belongs to */
@@ -260,18 +299,23 @@ typedef struct table_mode {
     const char *strands;                            /* "NAME STRANDS: --revcomp [--rc-region] can't be used with it" */
     bool one_selection;                             /* at most one --records or one --region ID, as stored (not --translate: any selection) */
     bool type_first;                                /* the output type is refused in front of another mode, not behind it */
+    bool sequence_types;                            /* --fasta, --fastq, --seq and --sequences are its own output types: only the others are refused */
     satellite sat[7];                               /* refused without the mode, in this order; ends at the first without a refusal */
     void (*early)(void);                            /* what holds whether the mode was asked for or not, behind the satellites */
     void (*own)(const struct table_mode *);         /* the mode's own checks and defaults, behind the output type */
     const char *protein;                            /* main's refusal of protein and text archives (%s: which), NULL: none */
     void (*run)(bool has_ids, bool has_names);
 } table_mode;
-enum { M_LOCATE, M_COMPOSITION, M_QUALITY, M_RUNS, M_KMERS, M_ORFS, M_TRANSLATE, M_REPEATS, N_MODES };
+enum { M_LOCATE, M_COMPOSITION, M_QUALITY, M_RUNS, M_KMERS, M_ORFS, M_TRANSLATE, M_REPEATS, M_TRIM, N_MODES };
 static table_mode modes[N_MODES];
 static void run_locate(bool, bool), run_composition(bool, bool), run_quality(bool, bool), run_runs(bool, bool), run_kmers(bool, bool), run_orfs(bool, bool),
-            run_translate(bool, bool), run_repeats(bool, bool);
+            run_translate(bool, bool), run_repeats(bool, bool), run_trim(bool, bool);
 
-static void refuse_output_type(const table_mode *m) { if (out_type != UNDECIDED) die("%s writes %s: no output type can be given with it\n", m->name, m->writes); }
+static void refuse_output_type(const table_mode *m)
+{
+    if (m->sequence_types && (out_type == FASTA || out_type == FASTQ || out_type == SEQ || out_type == SEQUENCES)) return;
+    if (out_type != UNDECIDED) die("%s writes %s: no %soutput type can be given with it\n", m->name, m->writes, m->sequence_types ? "other " : "");
+}
 static void refuse_revcomp(const table_mode *m) { if (revcomp) die("%s %s: --revcomp can't be used with it\n", m->name, m->strands); }
 static void one_whole_selection(const table_mode *m)
 {
@@ -342,6 +386,11 @@ static void fill_modes(void)
     modes[M_REPEATS] = (table_mode){ .asked = repeats_text != NULL, .name = "--repeats", .writes = "a table", .strands = "lists the sequences as stored", .one_selection = true,
         .sat = { { min_repeat_given, repeats_text != NULL, "--min-repeat can be used only with --repeats\n" }, { whole_units, repeats_text != NULL, "--whole-units can be used only with --repeats\n" } },
         .protein = "tandem repeats cannot be listed in %s sequences\n", .run = run_repeats };
+    modes[M_TRIM] = (table_mode){ .asked = trim_text != NULL, .name = "--trim", .writes = trim_table ? "a table" : "reads as --fastq, --fasta, --sequences or --seq",
+        .strands = "writes the reads as stored", .one_selection = true, .type_first = true, .sequence_types = !trim_table,
+        .sat = { { min_length_given, trim_text != NULL, "--min-length can be used only with --trim\n" }, { max_ee_text != NULL, trim_text != NULL, "--max-ee can be used only with --trim\n" },
+                 { trim_table, trim_text != NULL, "--trim-table can be used only with --trim\n" } },
+        .run = run_trim };
 }
 static const table_mode *asked_mode(void)
 {
@@ -359,7 +408,7 @@ static void parse_command_line(int argc, char **argv)
         {"--fasta", FASTA}, {"--fastq", FASTQ}, {"--dna", DNA}, {"--masked-dna", MASKED_DNA}, {"--unmasked-dna", UNMASKED_DNA},
         {"--masked-fasta", MASKED_FASTA}, {"--unmasked-fasta", UNMASKED_FASTA} };
     /* the other options (unnaf/src/unnaf.c:282-353), as a table: one that takes a value is only recognised with an argument behind it */
-    enum { OP_LINE_LENGTH, OP_OUT, OP_NO_MASK, OP_IGNORED, OP_HELP, OP_VERBOSE, OP_VERSION, OP_STDOUT, OP_REGION, OP_RECORDS, OP_RC_REGION, OP_REVCOMP, OP_LOCATE, OP_STRAND, OP_MISMATCHES, OP_COMPOSITION, OP_WINDOW, OP_QUALITY, OP_CYCLES, OP_RUNS, OP_MASKED_RUNS, OP_MIN_RUN, OP_EACH, OP_KMERS, OP_CANONICAL, OP_PER_RECORD, OP_ORFS, OP_MIN_ORF, OP_STOPS, OP_STARTS, OP_STOP_TO_STOP, OP_CLOSED, OP_SPLIT_UNKNOWN, OP_TRANSLATE, OP_FRAME, OP_CODE, OP_CODE_TABLE, OP_REPEATS, OP_MIN_REPEAT, OP_WHOLE_UNITS };
+    enum { OP_LINE_LENGTH, OP_OUT, OP_NO_MASK, OP_IGNORED, OP_HELP, OP_VERBOSE, OP_VERSION, OP_STDOUT, OP_REGION, OP_RECORDS, OP_RC_REGION, OP_REVCOMP, OP_LOCATE, OP_STRAND, OP_MISMATCHES, OP_COMPOSITION, OP_WINDOW, OP_QUALITY, OP_CYCLES, OP_RUNS, OP_MASKED_RUNS, OP_MIN_RUN, OP_EACH, OP_KMERS, OP_CANONICAL, OP_PER_RECORD, OP_ORFS, OP_MIN_ORF, OP_STOPS, OP_STARTS, OP_STOP_TO_STOP, OP_CLOSED, OP_SPLIT_UNKNOWN, OP_TRANSLATE, OP_FRAME, OP_CODE, OP_CODE_TABLE, OP_REPEATS, OP_MIN_REPEAT, OP_WHOLE_UNITS, OP_TRIM, OP_MIN_LENGTH, OP_MAX_EE, OP_TRIM_TABLE };
     static const struct { const char *name; int op; bool value; } option_table[] = {
         { "--line-length", OP_LINE_LENGTH, true }, { "-o", OP_OUT, true }, { "--no-mask", OP_NO_MASK, false }, { "--binary-stdout", OP_IGNORED, false },
         { "--binary-stderr", OP_IGNORED, false }, { "--binary", OP_IGNORED, false }, { "--help", OP_HELP, false }, { "-h", OP_HELP, false },
@@ -372,7 +421,8 @@ static void parse_command_line(int argc, char **argv)
         { "--orfs", OP_ORFS, false }, { "--min-orf", OP_MIN_ORF, true }, { "--stops", OP_STOPS, true }, { "--starts", OP_STARTS, true }, { "--stop-to-stop", OP_STOP_TO_STOP, false },
         { "--closed", OP_CLOSED, false }, { "--split-unknown", OP_SPLIT_UNKNOWN, false },
         { "--translate", OP_TRANSLATE, false }, { "--frame", OP_FRAME, true }, { "--code", OP_CODE, true }, { "--code-table", OP_CODE_TABLE, true },
-        { "--repeats", OP_REPEATS, true }, { "--min-repeat", OP_MIN_REPEAT, true }, { "--whole-units", OP_WHOLE_UNITS, false } };
+        { "--repeats", OP_REPEATS, true }, { "--min-repeat", OP_MIN_REPEAT, true }, { "--whole-units", OP_WHOLE_UNITS, false },
+        { "--trim", OP_TRIM, true }, { "--min-length", OP_MIN_LENGTH, true }, { "--max-ee", OP_MAX_EE, true }, { "--trim-table", OP_TRIM_TABLE, false } };
     for (int i = 1; i < argc; i++) {
         char *arg = argv[i];
         if (arg[0] != '-') {
@@ -429,6 +479,10 @@ static void parse_command_line(int argc, char **argv)
         case OP_REPEATS: set_repeats(v); break;
         case OP_MIN_REPEAT: min_repeat = positive_number("--min-repeat", "bases", v); min_repeat_given = true; break;
         case OP_WHOLE_UNITS: whole_units = true; break;
+        case OP_TRIM: set_trim(v); break;
+        case OP_MIN_LENGTH: trim_opts.min_len = positive_number("--min-length", "bases", v); min_length_given = true; break;
+        case OP_MAX_EE: set_max_ee(v); break;
+        case OP_TRIM_TABLE: trim_table = true; break;
         }
     }
     if (print_version) {
@@ -613,15 +667,17 @@ static void *sel_buf = NULL; static size_t sel_cap = 0;
 static void emit_segments(const naf_gpu_unnaf_opts *o, const naf_gpu_segment *segs, const uint8_t *strand, size_t n)
 {
     /* a selection larger than the range buffer is produced in pieces of whole segments: halves until a piece fits (or is one segment) */
-    /* (--translate: the same segments as protein, naf_gpu_unnaf_translate) */
+    /* (--translate: the same segments as protein, naf_gpu_unnaf_translate; --trim: as reads, naf_gpu_unnaf_select_reads) */
     size_t need = 0;
     if (translate) GPU_TRY(naf_gpu_unnaf_translate_size(gpu, d_naf, naf_len, o, &genetic_code, segs, strand, n, &need));
+    else if (reads_selection) GPU_TRY(naf_gpu_unnaf_select_reads_size(gpu, d_naf, naf_len, o, segs, strand, n, &need));
     else GPU_TRY(naf_gpu_unnaf_select_stranded_size(gpu, d_naf, naf_len, o, segs, strand, n, &need));
     if (!need) return;
     if (need > range_bytes() && n > 1) { emit_segments(o, segs, strand, n / 2); emit_segments(o, segs + n / 2, strand ? strand + n / 2 : NULL, n - n / 2); return; }
     if (need > sel_cap) { if (sel_buf) naf_gpu_free(gpu, sel_buf); GPU_TRY(naf_gpu_malloc(gpu, need + 64, &sel_buf)); sel_cap = need; }
     size_t got = 0;
     if (translate) GPU_TRY(naf_gpu_unnaf_translate(gpu, d_naf, naf_len, o, &genetic_code, segs, strand, n, sel_buf, sel_cap, &got));
+    else if (reads_selection) GPU_TRY(naf_gpu_unnaf_select_reads(gpu, d_naf, naf_len, o, segs, strand, n, sel_buf, sel_cap, &got));
     else GPU_TRY(naf_gpu_unnaf_select_stranded(gpu, d_naf, naf_len, o, segs, strand, n, sel_buf, sel_cap, &got));
     if (got != need) die("can't decompress sequence\n");
     write_from_device(OUT, sel_buf, got);
@@ -913,6 +969,66 @@ static void run_repeats(bool has_ids, bool has_names)
     GPU_TRY(naf_gpu_unnaf_repeats_count(gpu, d_naf, naf_len, &repeats_spec, whole_units ? NAF_GPU_REPEATS_WHOLE_UNITS : 0, min_repeat, rng_first, rng_count, &n, NULL, NULL));
     phase("repeats: count");
     if (n) write_rows(&t, n, true, has_ids, has_names);
+}
+
+/* --trim: naf_gpu_unnaf_trim -- one sweep over the quality stream, a row per read.  --trim-table writes the rows as lines; without it a
+ * chunk's kept rows are the segments of a selection of reads (naf_gpu_unnaf_select_reads): the trimmed reads instead of the lines. */
+static uint64_t *trim_len;                                          /* the lengths of records rng_first .. (--trim-table's second column) */
+static uint64_t fill_trim(void *d, size_t cap)
+{
+    uint64_t got = 0;
+    GPU_TRY(naf_gpu_unnaf_trim(gpu, d_naf, naf_len, &trim_opts, rng_first, rng_count, (naf_gpu_trim_row *)d, cap, &got, NULL));
+    return got;
+}
+static void trim_lines(const void *rows, size_t m, uint64_t at, const char **name)
+{
+    for (size_t k = 0; k < m; k++) {
+        const naf_gpu_trim_row *x = (const naf_gpu_trim_row *)rows + k;
+        if (x->record != rng_first + at + k || x->end < x->begin || x->end > trim_len[at + k] || x->flags < 1 || x->flags > 6 || x->flags == 5) die("can't decompress quality\n");
+        fprintf(OUT, "%s\t%llu\t%llu\t%llu\t%.6f\t%s\n", name[x->record], (unsigned long long)trim_len[at + k], (unsigned long long)x->begin, (unsigned long long)x->end,
+                (double)x->ee / 4294967296.0, x->flags == NAF_GPU_TRIM_KEPT ? "kept" : x->flags == NAF_GPU_TRIM_SHORT ? "short" : x->flags == NAF_GPU_TRIM_ERRORS ? "errors" : "short,errors");
+    }
+}
+static void trim_reads(const void *rows, size_t m, uint64_t at, const char **name)
+{
+    (void)name;
+    const naf_gpu_trim_row *x = (const naf_gpu_trim_row *)rows;
+    naf_gpu_segment *segs = (naf_gpu_segment *)malloc((m + 1) * sizeof *segs); if (!segs) die("can't allocate memory\n");
+    size_t n = 0;
+    for (size_t k = 0; k < m; k++) {
+        if (x[k].record != rng_first + at + k || x[k].end < x[k].begin) die("can't decompress quality\n");
+        if (x[k].flags == NAF_GPU_TRIM_KEPT) segs[n++] = (naf_gpu_segment){ x[k].record, x[k].begin, x[k].end };
+    }
+    const int mode = out_type == FASTA ? NAF_OUT_FASTA : out_type == FASTQ ? NAF_OUT_FASTQ : out_type == SEQ ? NAF_OUT_SEQ : NAF_OUT_SEQUENCES;
+    naf_gpu_unnaf_opts o = { mode, mode != NAF_OUT_FASTQ && use_mask, line_length_is_specified ? requested_line_length : -1 };
+    fflush(OUT);
+    if (n) emit_segments(&o, segs, NULL, n);
+    free(segs);
+}
+static void run_trim(bool has_ids, bool has_names)
+{
+    static const row_table lines = { sizeof(naf_gpu_trim_row), 1 << 20, "quality", "trim: rows", "trim: download + lines", fill_trim, trim_lines },
+                           reads = { sizeof(naf_gpu_trim_row), 1 << 20, "quality", "trim: rows", "trim: download + reads", fill_trim, trim_reads };
+    if (!(H.flags & 1)) die("--trim reads the quality codes: the archive has no quality section\n");
+    table_range(has_ids);
+    const unsigned long long N = H.n_sequences;
+    if (rng_first > N) die("can't decompress quality\n");
+    const uint64_t n = rng_count == NAF_GPU_WHOLE ? N - rng_first : rng_count;
+    if (trim_table) {
+        fprintf(OUT, "#seq\tlength\tbegin\tend\tee\tstatus\n");
+        if (!n) return;
+        uint64_t *off = (uint64_t *)malloc((size_t)(n + 1) * sizeof *off); trim_len = (uint64_t *)malloc((size_t)n * sizeof *trim_len);
+        if (!off || !trim_len) die("can't allocate memory\n");
+        naf_gpu_unnaf_opts o = { NAF_OUT_SEQUENCES, 0, -1 };
+        GPU_TRY(naf_gpu_unnaf_record_table(gpu, d_naf, naf_len, &o, rng_first, n, trim_len, off));
+        free(off);
+        write_rows(&lines, n, true, has_ids, has_names);
+        free(trim_len); trim_len = NULL;
+        return;
+    }
+    reads_selection = true;
+    if (n) write_rows(&reads, n, false, has_ids, has_names);
+    if (sel_buf) { naf_gpu_free(gpu, sel_buf); sel_buf = NULL; sel_cap = 0; }
 }
 
 /* --orfs: naf_gpu_unnaf_orfs -- the stops, starts and record bounds of the packed stream as six lists, a stretch between two neighbours of one
