@@ -648,6 +648,61 @@ int  naf_gpu_unnaf_select_reads_size(naf_gpu_ctx *ctx, const void *d_naf, size_t
 int  naf_gpu_unnaf_select_reads(naf_gpu_ctx *ctx, const void *d_naf, size_t naf_len, const naf_gpu_unnaf_opts *opts,
                                 const naf_gpu_segment *segs, const uint8_t *strand, size_t n_segs, void *d_out, size_t out_cap, size_t *out_len);
 
+/* ---- unnaf: 3' adapters clipped from reads, decided in the packed sequence stream ---------------------------------------
+ * What cutadapt -a, fastp, Trimmomatic ILLUMINACLIP and BBDuk ktrim=r answer from the text -- where the sequencing adapter begins at the 3'
+ * end of every read, an adapter that the read's end cuts short included -- as a table of (record, begin, end, adapter, mismatches,
+ * overlap, flags) rows, made without expanding the codes.  Integers only: the same bytes on every run and for every piece size.
+ *   Adapters  1 .. NAF_GPU_CLIP_MAX_ADAPTERS of them, each m = 1 .. 32 letters of ACGTU RYSWKM BDHV N in either case, U = T, passed as
+ *             the locate calls pass patterns (zero-terminated strings one behind the other).  Square brackets, '-' and anything else are
+ *             rejected.  A longer adapter is rejected too: of a 3' adapter the first 32 letters decide the same clip points.  Forward
+ *             strand only.  The match rule is naf_gpu_unnaf_locate's: a stored code c matches a letter p iff c != 0 && (c & ~p) == 0, so
+ *             a stored N matches only an adapter's N and a stored gap matches nothing.  Case (the soft mask) plays no part.
+ *   Window    of record r: [begin_r, end_r) in bases of the record.  d_bounds == NULL: the whole record.  Otherwise d_bounds holds one
+ *             naf_gpu_trim_row per selected record (DEVICE memory of any alignment, exactly count rows, what naf_gpu_unnaf_trim wrote for
+ *             the same first / count) and the window is the row's (begin, end): quality trimming goes first, as in cutadapt, the adapter
+ *             is searched in the quality-trimmed stretch, and "the read's end" is end_r.
+ *   Candidate a start x, begin_r <= x < end_r, overlaps adapter k in L = min(m_k, end_r - x) letters; d of the adapter's first L letters
+ *             mismatch bases x .. x + L.  x is a candidate of k iff L >= min_overlap and d <= budget[k][L].
+ *   Budget    h_budget: 33 bytes per adapter, indexed by L.  For every L in min_overlap .. m_k the call requires budget[k][L] < L
+ *             (NAF_GPU_EARG otherwise: every place would be a hit).  naf_gpu_clip_budgets fills a table with floor(L * num / den) for
+ *             1 <= L <= m, at most L - 1, and 0 elsewhere: cutadapt's -e rate (default 1/10) as a rational (host only; den == 0 and m
+ *             outside 1 .. 32 are NAF_GPU_EARG).
+ *   Clip      the smallest candidate x over all adapters; at equal x the lowest adapter number.  A later candidate never wins, however
+ *             few mismatches it has.  The kept stretch is [begin_r, x); with no candidate [begin_r, end_r).
+ *   Rows      exactly one per selected record, ascending.  adapter: its number, or NAF_GPU_CLIP_NO_ADAPTER; mismatches and overlap (d
+ *             and L of the clip point) are 0 then.  flags: NAF_GPU_TRIM_SHORT iff end - begin < min_len; NAF_GPU_TRIM_ERRORS iff the
+ *             bounds row had it (never without bounds); NAF_GPU_TRIM_KEPT iff neither; NAF_GPU_CLIP_CLIPPED or-ed in iff an adapter was
+ *             found.  Expected errors only fall when a stretch gets shorter: a read within max_ee before the clip is within it after, so
+ *             nothing is recomputed (and a read that was outside stays dropped, as in cutadapt's order of steps).  d_rows is DEVICE memory
+ *             of any alignment; exactly 40 * n_records bytes are written and nothing else.  d_rows == NULL: the totals only.  With
+ *             row_cap too small the call returns NAF_GPU_ECAP, sets *n_records and writes nothing.
+ *   Total     h_total (HOST memory, may be NULL): reads, clipped (rows with NAF_GPU_CLIP_CLIPPED), kept (rows with NAF_GPU_TRIM_KEPT),
+ *             bases (the windows' bases), kept_bases (end - begin over the kept rows), removed_bases (window end - end over all rows),
+ *             n_short, n_errors.  per_adapter (HOST, n_adapters x 33, may be NULL): the clips by [adapter][overlap], the table cutadapt
+ *             prints.  All are integer sums.
+ *   Errors    NAF_GPU_EARG, last_error saying which: no adapters or more than 16; a letter that is no IUPAC code (with its position); an
+ *             adapter of 0 or more than 32 letters; min_overlap 0 or above 32; min_len 0; h_budget NULL or a budget that is no smaller
+ *             than its overlap; protein and text archives; first > n_sequences or a range past the last record, as for
+ *             naf_gpu_unnaf_locate; a bounds row whose record is not first + its number, whose begin > end or whose end > the record's
+ *             length (found on the device; nothing is written to d_rows then, *n_records and *h_total are 0).  An archive without
+ *             records gives 0 rows; one without a quality section is as good as any: only the sequence stream is read, and of it only
+ *             the zstd blocks behind the selected records when the frame allows it.
+ *   Pieces    more bases than NAF_GPU_CLIP_PIECE (default 2^31) are decoded and swept in pieces of whole records.
+ * A kept row's (record, begin, end) is what naf_gpu_unnaf_select_reads takes: the clipped read under its own header line.
+ * TRACE=1: "[clip] adapters A records R clipped C pieces P sequence bytes decoded X of Y" per call that reaches the records. */
+#define NAF_GPU_CLIP_MAX_ADAPTERS 16
+#define NAF_GPU_CLIP_NO_ADAPTER UINT32_MAX
+enum { NAF_GPU_CLIP_CLIPPED = 8 };                                  /* beside NAF_GPU_TRIM_KEPT, _SHORT, _ERRORS in naf_gpu_clip_row.flags */
+typedef struct { uint32_t min_overlap; uint64_t min_len; } naf_gpu_clip_opts;
+typedef struct { uint64_t record, begin, end; uint32_t adapter, mismatches, overlap, flags; } naf_gpu_clip_row;   /* 40 bytes */
+typedef struct { uint64_t reads, clipped, kept, bases, kept_bases, removed_bases, n_short, n_errors; } naf_gpu_clip_total;
+
+int  naf_gpu_clip_budgets(uint64_t num, uint64_t den, unsigned m, uint8_t out[33]);     /* host only, no device */
+int  naf_gpu_unnaf_clip(naf_gpu_ctx *ctx, const void *d_naf, size_t naf_len, const char *h_adapters, size_t adapters_bytes, size_t n_adapters,
+                        const uint8_t *h_budget /* n_adapters x 33 */, const naf_gpu_clip_opts *opts, uint64_t first, uint64_t count,
+                        const naf_gpu_trim_row *d_bounds /* or NULL */, naf_gpu_clip_row *d_rows, size_t row_cap, uint64_t *n_records,
+                        naf_gpu_clip_total *h_total, uint64_t *per_adapter /* n_adapters x 33, or NULL */);
+
 /* ---- ennaf ------------------------------------------------------------------------------------------ */
 typedef struct {
     int      format;            /* NAF_FMT_* (AUTO = sniff, process.c:547-583) */

@@ -40,6 +40,7 @@ EXPORTS = [
     "naf_gpu_unnaf_translate_size", "naf_gpu_unnaf_translate",
     "naf_gpu_parse_repeat_spec", "naf_gpu_repeat_class", "naf_gpu_unnaf_repeats_count", "naf_gpu_unnaf_repeats",
     "naf_gpu_trim_limit", "naf_gpu_unnaf_trim", "naf_gpu_unnaf_select_reads_size", "naf_gpu_unnaf_select_reads",
+    "naf_gpu_clip_budgets", "naf_gpu_unnaf_clip",
 ]
 WHOLE = 2 ** 64 - 1                     # NAF_GPU_WHOLE: (record, 0, WHOLE) is the record as stored
 MAX_SHARDS = 64
@@ -227,6 +228,28 @@ TRIM_KEPT, TRIM_SHORT, TRIM_ERRORS = 1, 2, 4
 TRIM_NONE = 2 ** 64 - 1
 
 
+class ClipOpts(C.Structure):
+    """naf_gpu_clip_opts: the letters of an adapter that must overlap the read, the bases a kept read needs."""
+    _fields_ = [("min_overlap", C.c_uint32), ("min_len", C.c_uint64)]
+
+
+class ClipTotal(C.Structure):
+    """naf_gpu_clip_total: the reads of a call, those an adapter was found in, those kept, the bases of their windows, the bases of the kept
+    stretches, the bases behind the clip points, the rows with TRIM_SHORT and with TRIM_ERRORS."""
+    _fields_ = [("reads", C.c_uint64), ("clipped", C.c_uint64), ("kept", C.c_uint64), ("bases", C.c_uint64), ("kept_bases", C.c_uint64),
+                ("removed_bases", C.c_uint64), ("n_short", C.c_uint64), ("n_errors", C.c_uint64)]
+
+
+# numpy's view of a table of naf_gpu_clip_row: bases [begin, end) of `record` are kept; adapter: the number of the adapter that begins at
+# `end` (CLIP_NO_ADAPTER: none) with `mismatches` among the `overlap` letters of it the window holds; flags: TRIM_KEPT, or TRIM_SHORT and /
+# or TRIM_ERRORS, and CLIP_CLIPPED
+CLIP_DTYPE = [("record", "<u8"), ("begin", "<u8"), ("end", "<u8"), ("adapter", "<u4"), ("mismatches", "<u4"), ("overlap", "<u4"), ("flags", "<u4")]
+CLIP_BYTES = 40
+CLIP_CLIPPED = 8
+CLIP_NO_ADAPTER = 2 ** 32 - 1
+CLIP_MAX_ADAPTERS = 16
+
+
 class NafGpuError(RuntimeError):
     def __init__(self, code, msg):
         super().__init__("naf_gpu error %d: %s" % (code, msg))
@@ -355,6 +378,8 @@ def load():
         L.naf_gpu_unnaf_repeats.argtypes = [vp, vp, sz, C.POINTER(RepeatSpec), i, C.c_uint64, C.c_uint64, C.c_uint64, vp, sz, u64p, u64p, u64p]
         L.naf_gpu_trim_limit.argtypes = [C.c_uint, u64p]
         L.naf_gpu_unnaf_trim.argtypes = [vp, vp, sz, C.POINTER(TrimOpts), C.c_uint64, C.c_uint64, vp, sz, u64p, C.POINTER(TrimTotal)]
+        L.naf_gpu_clip_budgets.argtypes = [C.c_uint64, C.c_uint64, C.c_uint, u8p]
+        L.naf_gpu_unnaf_clip.argtypes = [vp, vp, sz, C.c_char_p, sz, sz, u8p, C.POINTER(ClipOpts), C.c_uint64, C.c_uint64, vp, vp, sz, u64p, C.POINTER(ClipTotal), u64p]
         L.naf_gpu_unnaf_select_reads_size.argtypes = [vp, vp, sz, C.POINTER(UnnafOpts), C.POINTER(Segment), u8p, sz, C.POINTER(sz)]
         L.naf_gpu_unnaf_select_reads.argtypes = [vp, vp, sz, C.POINTER(UnnafOpts), C.POINTER(Segment), u8p, sz, vp, sz, C.POINTER(sz)]
         _lib = L
@@ -431,19 +456,25 @@ def trim_limit(q):
     return int(v.value)
 
 
-def ee_units(x):
-    """Expected errors as the trim calls take them: floor(x * 2^32) of an int, a Fraction, or a decimal text of digits with at most one
-    point that has 1 to 9 digits behind it ("2", "0.5", "1.999999999").  No floats: a float is not the number that was written."""
+def _decimal(x, what, plural):
+    """A number given as an int, a Fraction, or a decimal text of digits with at most one point that has 1 to 9 digits behind it, as a
+    Fraction.  No floats: a float is not the number that was written."""
     from fractions import Fraction
     if isinstance(x, bool) or isinstance(x, float):
-        raise ValueError("expected errors are given as text, int or Fraction, not as %r" % (x,))
+        raise ValueError("%s given as text, int or Fraction, not as %r" % (plural, x))
     if isinstance(x, (bytes, str)):
         t = x.decode("latin1") if isinstance(x, bytes) else x
         whole, point, frac = t.partition(".")
         if not (whole.isascii() and whole.isdigit() and ((not point) or (frac.isascii() and frac.isdigit() and 1 <= len(frac) <= 9))):
-            raise ValueError("not a number of expected errors (digits, or digits.digits with 1 to 9 behind the point): %r" % (x,))
-        x = Fraction(int(whole)) + (Fraction(int(frac), 10 ** len(frac)) if point else 0)
-    v = int(Fraction(x) * 2 ** 32)
+            raise ValueError("not %s (digits, or digits.digits with 1 to 9 behind the point): %r" % (what, x))
+        return Fraction(int(whole)) + (Fraction(int(frac), 10 ** len(frac)) if point else 0)
+    return Fraction(x)
+
+
+def ee_units(x):
+    """Expected errors as the trim calls take them: floor(x * 2^32) of an int, a Fraction, or a decimal text of digits with at most one
+    point that has 1 to 9 digits behind it ("2", "0.5", "1.999999999").  No floats: a float is not the number that was written."""
+    v = int(_decimal(x, "a number of expected errors", "expected errors are") * 2 ** 32)
     if not 0 <= v < 2 ** 64 - 1:
         raise ValueError("expected errors out of range: %r" % (x,))
     return v
@@ -452,6 +483,23 @@ def ee_units(x):
 def trim_to_segments(rows):
     """The (record, begin, end) tuples unnaf_select_reads takes: the kept rows of the table unnaf_trim returns, in its order."""
     return [(int(x["record"]), int(x["begin"]), int(x["end"])) for x in rows if int(x["flags"]) == TRIM_KEPT]
+
+
+def clip_budgets(rate, m):
+    """Host-only: the 33 budgets of an adapter of m letters at an error rate (naf_gpu_clip_budgets): floor(L * rate) mismatches in an
+    overlap of L <= m letters, at most L - 1, and 0 above m, as a list of ints.  rate: text ("0.1"), int or Fraction, never a float."""
+    r = _decimal(rate, "an error rate", "an error rate is")
+    if r < 0 or r.numerator >= 2 ** 64 or r.denominator >= 2 ** 64 or not 1 <= int(m) <= 32:
+        raise ValueError("not an error rate and an adapter length of 1 to 32: %r, %r" % (rate, m))
+    out = (C.c_uint8 * 33)()
+    if load().naf_gpu_clip_budgets(r.numerator, r.denominator, int(m), out):
+        raise ValueError("not an error rate and an adapter length of 1 to 32: %r, %r" % (rate, m))
+    return [int(v) for v in out]
+
+
+def clip_to_segments(rows):
+    """The (record, begin, end) tuples unnaf_select_reads takes: the kept rows of the table unnaf_clip returns, in its order."""
+    return [(int(x["record"]), int(x["begin"]), int(x["end"])) for x in rows if int(x["flags"]) & TRIM_KEPT]
 
 
 def parse_base_class(text):
@@ -1175,6 +1223,41 @@ class Context:
             return None, tot
         view = buf[:TRIM_BYTES * n.value]
         return (np.frombuffer(view.cpu().numpy().tobytes(), dtype=TRIM_DTYPE) if own else view), tot
+
+    def unnaf_clip(self, d_naf, adapters, rate="0.1", budgets=None, min_overlap=3, min_len=1, bounds=None, first=0, count=None, out=None):
+        """(rows, total, per_adapter): where a 3' adapter begins in every read of records [first, first + count) (naf_gpu_unnaf_clip) --
+        adapters: 1 to 16 IUPAC texts of 1 to 32 letters; rate: the mismatches allowed per overlapped letter (clip_budgets), or budgets:
+        one table of 33 ints per adapter; min_overlap: the letters of an adapter that must lie in the read; min_len: the bases a kept
+        read needs; bounds: a uint8 device tensor of trim rows for the same records (the view unnaf_trim(out=...) returned), whose
+        (begin, end) are searched instead of the whole reads -- as a structured numpy array (CLIP_DTYPE), one row per read, a ClipTotal
+        and the clips by [adapter][overlap] as lists of 33 ints.  out: a uint8 device tensor to take the table (40 bytes a row); then
+        `rows` is the torch view of its first 40 * n bytes and too small a tensor raises NafGpuError(E_CAP).  out=False: the totals only."""
+        import numpy as np
+        import torch
+        blob, na = self._patterns(adapters)
+        if budgets is None:
+            budgets = [clip_budgets(rate, min(max(len(a), 1), 32)) for a in adapters]
+        flat = [int(v) for b in budgets for v in b]
+        if len(flat) != 33 * na or any(not 0 <= v < 256 for v in flat):
+            raise ValueError("budgets: 33 values of 0 to 255 per adapter")
+        tab = (C.c_uint8 * max(len(flat), 1))(*flat)
+        o = ClipOpts(int(min_overlap), int(min_len))
+        n, tot, per = C.c_uint64(), ClipTotal(), (C.c_uint64 * max(33 * na, 1))()
+        cnt = WHOLE if count is None else int(count)
+        own = out is None
+        if own:
+            have = int(self.parse_header(d_naf).n_sequences)
+            rows = max(0, min(have - int(first), cnt)) if cnt != WHOLE else max(0, have - int(first))
+            out = torch.empty(max(CLIP_BYTES * rows, 1), dtype=torch.uint8, device=self.device)
+        buf = None if out is False else out
+        self._check(self.L.naf_gpu_unnaf_clip(self.h, _ptr(d_naf), d_naf.numel(), blob, len(blob), na, tab, C.byref(o), int(first), cnt,
+                                              _ptr(bounds) if bounds is not None else None, _ptr(buf) if buf is not None else None,
+                                              buf.numel() // CLIP_BYTES if buf is not None else 0, C.byref(n), C.byref(tot), per))
+        per_adapter = [[int(per[33 * k + L]) for L in range(33)] for k in range(na)]
+        if buf is None:
+            return None, tot, per_adapter
+        view = buf[:CLIP_BYTES * n.value]
+        return (np.frombuffer(view.cpu().numpy().tobytes(), dtype=CLIP_DTYPE) if own else view), tot, per_adapter
 
     @staticmethod
     def _run_class(cls, each, masked):

@@ -47,6 +47,11 @@ static const char *frame_text = NULL, *code_text = NULL, *code_table_text = NULL
  * the stretches (this implementation only) */
 static const char *trim_text = NULL, *max_ee_text = NULL; static naf_gpu_trim_opts trim_opts = { 0, 1, UINT64_MAX };
 static bool min_length_given = false, trim_table = false, reads_selection = false;      /* reads_selection: emit_segments writes reads (naf_gpu_unnaf_select_reads) */
+/* --adapter SEQ (up to 16) [--adapter-errors R] [--min-overlap N] [--min-length N] [--clip-table] [--trim Q|none [--max-ee X]]: the reads cut where
+ * a 3' adapter begins, behind the quality trimming when there is one, or the table of the clip points (this implementation only) */
+static const char *adapters[NAF_GPU_CLIP_MAX_ADAPTERS]; static size_t n_adapters = 0;
+static const char *adapter_errors_text = NULL; static unsigned long long adapter_num = 1, adapter_den = 10;
+static naf_gpu_clip_opts clip_opts = { 3, 1 }; static bool min_overlap_given = false, clip_table = false;
 
 static void done(int status, void *arg)
 {
@@ -156,6 +161,34 @@ static void set_max_ee(const char *v)
     for (size_t k = 0; k < nf; k++) pow10 *= 10;
     trim_opts.max_ee = (whole << 32) + (frac << 32) / pow10;                   /* frac < 10^9 < 2^30: no overflow */
     max_ee_text = v;
+}
+
+static void add_adapter(const char *v)
+{
+    uint8_t fwd[32], rev[32]; size_t len;
+    if (strlen(v) > 32) die("--adapter %s has more than 32 letters: of a 3' adapter the first 32 decide the same clip points, give those\n", v);
+    if (naf_gpu_compile_motif(v, fwd, rev, &len)) die("can't parse the value of --adapter parameter (1 to 32 IUPAC nucleotide letters)\n");
+    if (n_adapters == NAF_GPU_CLIP_MAX_ADAPTERS) die("at most %d --adapter sequences can be clipped at once\n", (int)NAF_GPU_CLIP_MAX_ADAPTERS);
+    adapters[n_adapters++] = v;
+}
+/* --adapter-errors R: 0, or 0.digits with 1 to 9 behind the point; kept as num / den */
+static void set_adapter_errors(const char *v)
+{
+    if (adapter_errors_text) die("only one --adapter-errors value can be given\n");
+    const char *dot = strchr(v, '.');
+    const size_t nw = dot ? (size_t)(dot - v) : strlen(v), nf = dot ? strlen(dot + 1) : 0;
+    unsigned long long whole = 0, frac = 0, pow10 = 1;
+    bool ok = !strchr(v, ',') && number_of(v, nw, &whole) && whole == 0 && (!dot || (nf >= 1 && nf <= 9 && number_of(dot + 1, nf, &frac)));
+    if (!ok) die("can't parse the value of --adapter-errors parameter (mismatches per overlapped letter, below 1: 0, or 0.digits with 1 to 9 behind the point)\n");
+    for (size_t k = 0; k < nf; k++) pow10 *= 10;
+    adapter_num = frac; adapter_den = pow10;
+    adapter_errors_text = v;
+}
+static void set_min_overlap(const char *v)
+{
+    const unsigned long long a = positive_number("--min-overlap", "adapter letters", v);
+    if (a > 32) die("can't parse the value of --min-overlap parameter (1 to 32 adapter letters)\n");
+    clip_opts.min_overlap = (uint32_t)a; min_overlap_given = true;
 }
 
 static void set_runs(const char *v)
@@ -280,6 +313,12 @@ static void show_help(void)
         "  --repeats SPEC  - Every perfect tandem repeat, as lines \"ID begin end PERIOD MOTIF COPIES CLASS\" (0-based half-open): SPEC is PERIOD-COPIES pairs, e.g. 1-10,2-6,3-5, periods 1 to 16; or misa\n"
         "  --min-repeat N  - With --repeats: only repeats of at least N bases (default 1)\n"
         "  --whole-units   - With --repeats: the end of a repeat is cut to a whole number of copies, as MISA and PERF print it\n"
+        "Options for clipping adapters (output: the kept reads, each cut where its 3' adapter begins, as --fastq, --fasta, --sequences or --seq; with at most one --records A-B or --region ID):\n"
+        "  --adapter SEQ   - Cut every read at the leftmost place where SEQ (1 to 32 IUPAC letters) begins, also one that the read's end cuts short; repeatable, up to 16 adapters.\n"
+        "                    With --trim Q (and --max-ee X) the reads are trimmed by quality first and the adapter is searched in what is left; --min-length N drops reads cut shorter than N\n"
+        "  --adapter-errors R - With --adapter: floor(R * L) mismatches are allowed where L letters of the adapter lie in the read (default 0.1)\n"
+        "  --min-overlap N - With --adapter: at least N letters of the adapter must lie in the read (default 3)\n"
+        "  --clip-table    - With --adapter: instead of the reads, a table \"#seq length begin end adapter mismatches overlap status\" of all reads (adapter: its number from 1, or .)\n"
         "Options for trimming reads by quality (output: the kept reads, each cut to its stretch, as --fastq (default), --fasta, --sequences or --seq; with at most one --records A-B or --region ID):\n"
         "  --trim Q        - Of every read the stretch of the largest sum of (error rate of Phred Q) - (error rate of the code), Q = 0 to 93: the Phred / Mott rule of seqtk and BBDuk; none = the whole read\n"
         "  --min-length N  - With --trim: drop reads whose stretch has fewer than N bases (default 1)\n"
@@ -288,7 +327,7 @@ static void show_help(void)
 }
 
 /* ---- the table modes ---------------------------------------------------------------------------------------------------------------
- * --locate, --composition, --quality, --runs / --masked-runs, --kmers, --orfs, --translate, --repeats and --trim write a table of their own
+ * --locate, --composition, --quality, --runs / --masked-runs, --kmers, --orfs, --translate, --repeats, --adapter and --trim write a table of their own
  * instead of an output type (--trim without --trim-table: the reads, in one of the sequence output types).  A mode is a row here -- what its refusals say, its options, its runner -- plus the checks that are
  * really its own; parse_command_line walks the rows once, in this order, and main runs the first one asked for (--orfs in front
  * of --translate: the one legal pair). */
@@ -306,10 +345,10 @@ typedef struct table_mode {
     const char *protein;                            /* main's refusal of protein and text archives (%s: which), NULL: none */
     void (*run)(bool has_ids, bool has_names);
 } table_mode;
-enum { M_LOCATE, M_COMPOSITION, M_QUALITY, M_RUNS, M_KMERS, M_ORFS, M_TRANSLATE, M_REPEATS, M_TRIM, N_MODES };
+enum { M_LOCATE, M_COMPOSITION, M_QUALITY, M_RUNS, M_KMERS, M_ORFS, M_TRANSLATE, M_REPEATS, M_CLIP, M_TRIM, N_MODES };
 static table_mode modes[N_MODES];
 static void run_locate(bool, bool), run_composition(bool, bool), run_quality(bool, bool), run_runs(bool, bool), run_kmers(bool, bool), run_orfs(bool, bool),
-            run_translate(bool, bool), run_repeats(bool, bool), run_trim(bool, bool);
+            run_translate(bool, bool), run_repeats(bool, bool), run_clip(bool, bool), run_trim(bool, bool);
 
 static void refuse_output_type(const table_mode *m)
 {
@@ -356,6 +395,12 @@ static void translate_own(const table_mode *m)
     if (!code_text && !code_table_text) naf_gpu_genetic_code_by_id(1, &genetic_code);
 }
 
+static void clip_own(const table_mode *m)
+{
+    (void)m;
+    if (trim_table) die("--trim-table can't be used with --adapter: --clip-table writes the table of the clipped reads\n");
+}
+
 /* the rows, from the options as they were given */
 static void fill_modes(void)
 {
@@ -386,9 +431,15 @@ static void fill_modes(void)
     modes[M_REPEATS] = (table_mode){ .asked = repeats_text != NULL, .name = "--repeats", .writes = "a table", .strands = "lists the sequences as stored", .one_selection = true,
         .sat = { { min_repeat_given, repeats_text != NULL, "--min-repeat can be used only with --repeats\n" }, { whole_units, repeats_text != NULL, "--whole-units can be used only with --repeats\n" } },
         .protein = "tandem repeats cannot be listed in %s sequences\n", .run = run_repeats };
+    /* --adapter stands in front of --trim, the one mode it can be used with: main then runs it, and it trims first */
+    modes[M_CLIP] = (table_mode){ .asked = n_adapters != 0, .name = "--adapter", .writes = clip_table ? "a table" : "reads as --fastq, --fasta, --sequences or --seq",
+        .strands = "clips the reads as stored", .one_selection = true, .type_first = true, .sequence_types = !clip_table,
+        .sat = { { adapter_errors_text != NULL, n_adapters != 0, "--adapter-errors can be used only with --adapter\n" }, { min_overlap_given, n_adapters != 0, "--min-overlap can be used only with --adapter\n" },
+                 { clip_table, n_adapters != 0, "--clip-table can be used only with --adapter\n" } },
+        .own = clip_own, .protein = "adapters cannot be clipped in %s sequences\n", .run = run_clip };
     modes[M_TRIM] = (table_mode){ .asked = trim_text != NULL, .name = "--trim", .writes = trim_table ? "a table" : "reads as --fastq, --fasta, --sequences or --seq",
         .strands = "writes the reads as stored", .one_selection = true, .type_first = true, .sequence_types = !trim_table,
-        .sat = { { min_length_given, trim_text != NULL, "--min-length can be used only with --trim\n" }, { max_ee_text != NULL, trim_text != NULL, "--max-ee can be used only with --trim\n" },
+        .sat = { { min_length_given, trim_text != NULL || n_adapters != 0, "--min-length can be used only with --trim or --adapter\n" }, { max_ee_text != NULL, trim_text != NULL, "--max-ee can be used only with --trim\n" },
                  { trim_table, trim_text != NULL, "--trim-table can be used only with --trim\n" } },
         .run = run_trim };
 }
@@ -408,7 +459,7 @@ static void parse_command_line(int argc, char **argv)
         {"--fasta", FASTA}, {"--fastq", FASTQ}, {"--dna", DNA}, {"--masked-dna", MASKED_DNA}, {"--unmasked-dna", UNMASKED_DNA},
         {"--masked-fasta", MASKED_FASTA}, {"--unmasked-fasta", UNMASKED_FASTA} };
     /* the other options (unnaf/src/unnaf.c:282-353), as a table: one that takes a value is only recognised with an argument behind it */
-    enum { OP_LINE_LENGTH, OP_OUT, OP_NO_MASK, OP_IGNORED, OP_HELP, OP_VERBOSE, OP_VERSION, OP_STDOUT, OP_REGION, OP_RECORDS, OP_RC_REGION, OP_REVCOMP, OP_LOCATE, OP_STRAND, OP_MISMATCHES, OP_COMPOSITION, OP_WINDOW, OP_QUALITY, OP_CYCLES, OP_RUNS, OP_MASKED_RUNS, OP_MIN_RUN, OP_EACH, OP_KMERS, OP_CANONICAL, OP_PER_RECORD, OP_ORFS, OP_MIN_ORF, OP_STOPS, OP_STARTS, OP_STOP_TO_STOP, OP_CLOSED, OP_SPLIT_UNKNOWN, OP_TRANSLATE, OP_FRAME, OP_CODE, OP_CODE_TABLE, OP_REPEATS, OP_MIN_REPEAT, OP_WHOLE_UNITS, OP_TRIM, OP_MIN_LENGTH, OP_MAX_EE, OP_TRIM_TABLE };
+    enum { OP_LINE_LENGTH, OP_OUT, OP_NO_MASK, OP_IGNORED, OP_HELP, OP_VERBOSE, OP_VERSION, OP_STDOUT, OP_REGION, OP_RECORDS, OP_RC_REGION, OP_REVCOMP, OP_LOCATE, OP_STRAND, OP_MISMATCHES, OP_COMPOSITION, OP_WINDOW, OP_QUALITY, OP_CYCLES, OP_RUNS, OP_MASKED_RUNS, OP_MIN_RUN, OP_EACH, OP_KMERS, OP_CANONICAL, OP_PER_RECORD, OP_ORFS, OP_MIN_ORF, OP_STOPS, OP_STARTS, OP_STOP_TO_STOP, OP_CLOSED, OP_SPLIT_UNKNOWN, OP_TRANSLATE, OP_FRAME, OP_CODE, OP_CODE_TABLE, OP_REPEATS, OP_MIN_REPEAT, OP_WHOLE_UNITS, OP_TRIM, OP_MIN_LENGTH, OP_MAX_EE, OP_TRIM_TABLE, OP_ADAPTER, OP_ADAPTER_ERRORS, OP_MIN_OVERLAP, OP_CLIP_TABLE };
     static const struct { const char *name; int op; bool value; } option_table[] = {
         { "--line-length", OP_LINE_LENGTH, true }, { "-o", OP_OUT, true }, { "--no-mask", OP_NO_MASK, false }, { "--binary-stdout", OP_IGNORED, false },
         { "--binary-stderr", OP_IGNORED, false }, { "--binary", OP_IGNORED, false }, { "--help", OP_HELP, false }, { "-h", OP_HELP, false },
@@ -422,7 +473,8 @@ static void parse_command_line(int argc, char **argv)
         { "--closed", OP_CLOSED, false }, { "--split-unknown", OP_SPLIT_UNKNOWN, false },
         { "--translate", OP_TRANSLATE, false }, { "--frame", OP_FRAME, true }, { "--code", OP_CODE, true }, { "--code-table", OP_CODE_TABLE, true },
         { "--repeats", OP_REPEATS, true }, { "--min-repeat", OP_MIN_REPEAT, true }, { "--whole-units", OP_WHOLE_UNITS, false },
-        { "--trim", OP_TRIM, true }, { "--min-length", OP_MIN_LENGTH, true }, { "--max-ee", OP_MAX_EE, true }, { "--trim-table", OP_TRIM_TABLE, false } };
+        { "--trim", OP_TRIM, true }, { "--min-length", OP_MIN_LENGTH, true }, { "--max-ee", OP_MAX_EE, true }, { "--trim-table", OP_TRIM_TABLE, false },
+        { "--adapter", OP_ADAPTER, true }, { "--adapter-errors", OP_ADAPTER_ERRORS, true }, { "--min-overlap", OP_MIN_OVERLAP, true }, { "--clip-table", OP_CLIP_TABLE, false } };
     for (int i = 1; i < argc; i++) {
         char *arg = argv[i];
         if (arg[0] != '-') {
@@ -483,6 +535,10 @@ static void parse_command_line(int argc, char **argv)
         case OP_MIN_LENGTH: trim_opts.min_len = positive_number("--min-length", "bases", v); min_length_given = true; break;
         case OP_MAX_EE: set_max_ee(v); break;
         case OP_TRIM_TABLE: trim_table = true; break;
+        case OP_ADAPTER: add_adapter(v); break;
+        case OP_ADAPTER_ERRORS: set_adapter_errors(v); break;
+        case OP_MIN_OVERLAP: set_min_overlap(v); break;
+        case OP_CLIP_TABLE: clip_table = true; break;
         }
     }
     if (print_version) {
@@ -499,7 +555,7 @@ static void parse_command_line(int argc, char **argv)
         if (!m->asked) continue;
         if (m->type_first) refuse_output_type(m);
         for (const table_mode *e = modes; e < m; e++)
-            if (e->asked && !(e == &modes[M_ORFS] && m == &modes[M_TRANSLATE])) die("%s and %s can't be used together\n", m->name, e->name);
+            if (e->asked && !(e == &modes[M_ORFS] && m == &modes[M_TRANSLATE]) && !(e == &modes[M_CLIP] && m == &modes[M_TRIM])) die("%s and %s can't be used together\n", m->name, e->name);
         refuse_output_type(m);
         if (m->own) m->own(m);
         if (m->one_selection) one_whole_selection(m);
@@ -989,6 +1045,14 @@ static void trim_lines(const void *rows, size_t m, uint64_t at, const char **nam
                 (double)x->ee / 4294967296.0, x->flags == NAF_GPU_TRIM_KEPT ? "kept" : x->flags == NAF_GPU_TRIM_SHORT ? "short" : x->flags == NAF_GPU_TRIM_ERRORS ? "errors" : "short,errors");
     }
 }
+/* the n kept stretches of a chunk as reads, in the output type asked for */
+static void emit_reads(const naf_gpu_segment *segs, size_t n)
+{
+    const int mode = out_type == FASTA ? NAF_OUT_FASTA : out_type == FASTQ ? NAF_OUT_FASTQ : out_type == SEQ ? NAF_OUT_SEQ : NAF_OUT_SEQUENCES;
+    naf_gpu_unnaf_opts o = { mode, mode != NAF_OUT_FASTQ && use_mask, line_length_is_specified ? requested_line_length : -1 };
+    fflush(OUT);
+    if (n) emit_segments(&o, segs, NULL, n);
+}
 static void trim_reads(const void *rows, size_t m, uint64_t at, const char **name)
 {
     (void)name;
@@ -999,10 +1063,7 @@ static void trim_reads(const void *rows, size_t m, uint64_t at, const char **nam
         if (x[k].record != rng_first + at + k || x[k].end < x[k].begin) die("can't decompress quality\n");
         if (x[k].flags == NAF_GPU_TRIM_KEPT) segs[n++] = (naf_gpu_segment){ x[k].record, x[k].begin, x[k].end };
     }
-    const int mode = out_type == FASTA ? NAF_OUT_FASTA : out_type == FASTQ ? NAF_OUT_FASTQ : out_type == SEQ ? NAF_OUT_SEQ : NAF_OUT_SEQUENCES;
-    naf_gpu_unnaf_opts o = { mode, mode != NAF_OUT_FASTQ && use_mask, line_length_is_specified ? requested_line_length : -1 };
-    fflush(OUT);
-    if (n) emit_segments(&o, segs, NULL, n);
+    emit_reads(segs, n);
     free(segs);
 }
 static void run_trim(bool has_ids, bool has_names)
@@ -1029,6 +1090,85 @@ static void run_trim(bool has_ids, bool has_names)
     reads_selection = true;
     if (n) write_rows(&reads, n, false, has_ids, has_names);
     if (sel_buf) { naf_gpu_free(gpu, sel_buf); sel_buf = NULL; sel_cap = 0; }
+}
+
+/* --adapter: naf_gpu_unnaf_clip -- one sweep over the packed stream, a row per read.  With --trim the trim rows of the same reads are made
+ * first (naf_gpu_unnaf_trim) and stay on the device: they are the clip call's bounds.  --clip-table writes the rows as lines; without it a
+ * chunk's kept rows are the segments of a selection of reads, as for --trim. */
+static struct { char *blob; size_t bytes; uint8_t budget[NAF_GPU_CLIP_MAX_ADAPTERS][33]; } clip;
+static uint64_t fill_clip(void *d, size_t cap)
+{
+    uint64_t got = 0; void *d_bounds = NULL;
+    if (trim_text) {
+        GPU_TRY(naf_gpu_malloc(gpu, cap * sizeof(naf_gpu_trim_row), &d_bounds));
+        GPU_TRY(naf_gpu_unnaf_trim(gpu, d_naf, naf_len, &trim_opts, rng_first, rng_count, (naf_gpu_trim_row *)d_bounds, cap, &got, NULL));
+        if (got != cap) die("can't decompress quality\n");
+        phase("clip: trim rows");
+    }
+    GPU_TRY(naf_gpu_unnaf_clip(gpu, d_naf, naf_len, clip.blob, clip.bytes, n_adapters, &clip.budget[0][0], &clip_opts, rng_first, rng_count,
+                               (const naf_gpu_trim_row *)d_bounds, (naf_gpu_clip_row *)d, cap, &got, NULL, NULL));
+    if (d_bounds) naf_gpu_free(gpu, d_bounds);
+    return got;
+}
+static void clip_lines(const void *rows, size_t m, uint64_t at, const char **name)
+{
+    for (size_t k = 0; k < m; k++) {
+        const naf_gpu_clip_row *x = (const naf_gpu_clip_row *)rows + k;
+        const uint32_t f = x->flags & 7u; const bool clipped = (x->flags & NAF_GPU_CLIP_CLIPPED) != 0;
+        if (x->record != rng_first + at + k || x->end < x->begin || x->end > trim_len[at + k] || x->flags > 15 || f < 1 || f > 6 || f == 5 || clipped != (x->adapter < n_adapters)) die("can't decompress sequence\n");
+        fprintf(OUT, "%s\t%llu\t%llu\t%llu\t", name[x->record], (unsigned long long)trim_len[at + k], (unsigned long long)x->begin, (unsigned long long)x->end);
+        if (clipped) fprintf(OUT, "%u", (unsigned)x->adapter + 1); else fputc('.', OUT);
+        fprintf(OUT, "\t%u\t%u\t%s\n", (unsigned)x->mismatches, (unsigned)x->overlap, f == NAF_GPU_TRIM_KEPT ? "kept" : f == NAF_GPU_TRIM_SHORT ? "short" : f == NAF_GPU_TRIM_ERRORS ? "errors" : "short,errors");
+    }
+}
+static void clip_reads(const void *rows, size_t m, uint64_t at, const char **name)
+{
+    (void)name;
+    const naf_gpu_clip_row *x = (const naf_gpu_clip_row *)rows;
+    naf_gpu_segment *segs = (naf_gpu_segment *)malloc((m + 1) * sizeof *segs); if (!segs) die("can't allocate memory\n");
+    size_t n = 0;
+    for (size_t k = 0; k < m; k++) {
+        if (x[k].record != rng_first + at + k || x[k].end < x[k].begin) die("can't decompress sequence\n");
+        if (x[k].flags & NAF_GPU_TRIM_KEPT) segs[n++] = (naf_gpu_segment){ x[k].record, x[k].begin, x[k].end };
+    }
+    emit_reads(segs, n);
+    free(segs);
+}
+static void run_clip(bool has_ids, bool has_names)
+{
+    static const row_table lines = { sizeof(naf_gpu_clip_row), 1 << 20, "sequence", "clip: rows", "clip: download + lines", fill_clip, clip_lines },
+                           reads = { sizeof(naf_gpu_clip_row), 1 << 20, "sequence", "clip: rows", "clip: download + reads", fill_clip, clip_reads };
+    if (trim_text && !(H.flags & 1)) die("--trim reads the quality codes: the archive has no quality section\n");
+    if (out_type == FASTQ && !(H.flags & 1)) die("FASTQ output requested, but input has no qualities\n");
+    table_range(has_ids);
+    const unsigned long long N = H.n_sequences;
+    if (rng_first > N) die("can't decompress sequence\n");
+    const uint64_t n = rng_count == NAF_GPU_WHOLE ? N - rng_first : rng_count;
+    clip.bytes = 0; for (size_t k = 0; k < n_adapters; k++) clip.bytes += strlen(adapters[k]) + 1;
+    clip.blob = (char *)malloc(clip.bytes + 1); if (!clip.blob) die("can't allocate memory\n");
+    for (size_t k = 0, at = 0; k < n_adapters; k++) {
+        const size_t l = strlen(adapters[k]);
+        memcpy(clip.blob + at, adapters[k], l + 1); at += l + 1;
+        if (naf_gpu_clip_budgets(adapter_num, adapter_den, (unsigned)l, clip.budget[k])) die("can't parse the value of --adapter parameter (1 to 32 IUPAC nucleotide letters)\n");
+    }
+    clip_opts.min_len = trim_opts.min_len;                           /* --min-length: one value for both steps */
+    if (clip_table) {
+        fprintf(OUT, "#seq\tlength\tbegin\tend\tadapter\tmismatches\toverlap\tstatus\n");
+        if (n) {
+            uint64_t *off = (uint64_t *)malloc((size_t)(n + 1) * sizeof *off); trim_len = (uint64_t *)malloc((size_t)n * sizeof *trim_len);
+            if (!off || !trim_len) die("can't allocate memory\n");
+            naf_gpu_unnaf_opts o = { NAF_OUT_SEQUENCES, 0, -1 };
+            GPU_TRY(naf_gpu_unnaf_record_table(gpu, d_naf, naf_len, &o, rng_first, n, trim_len, off));
+            free(off);
+            write_rows(&lines, n, true, has_ids, has_names);
+            free(trim_len); trim_len = NULL;
+        }
+    } else {
+        reads_selection = true;
+        if (n) write_rows(&reads, n, false, has_ids, has_names);
+        if (sel_buf) { naf_gpu_free(gpu, sel_buf); sel_buf = NULL; sel_cap = 0; }
+    }
+    free(clip.blob);
 }
 
 /* --orfs: naf_gpu_unnaf_orfs -- the stops, starts and record bounds of the packed stream as six lists, a stretch between two neighbours of one
