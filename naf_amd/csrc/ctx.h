@@ -5,6 +5,7 @@
 #include <hip/hip_runtime.h>
 #include <stdio.h>
 #include <stdarg.h>
+#include <string.h>
 #include <vector>
 #include <functional>
 #include <string>
@@ -93,6 +94,16 @@ static inline bool ctx_opt_is(const naf_gpu_ctx *c, const char *name, char v) { 
 bool ctx_tracing(const naf_gpu_ctx *c);
 void ctx_trace(naf_gpu_ctx *c, const char *fmt, ...);                  // a path's verdict, kept when TRACE is on
 #define HIP_TRY(c, call) do { hipError_t e_ = (call); if (e_ != hipSuccess) return ctx_fail((c), NAF_GPU_EHIP, "%s: %s (%s:%d)", #call, hipGetErrorString(e_), __FILE__, __LINE__); } while (0)
+// An error a worker left on its side context (or a text kept from one) becomes this context's.
+static inline void ctx_take_error(naf_gpu_ctx *c, const char (&text)[512]) { memcpy(c->err, text, sizeof c->err); }
+static inline void ctx_take_error(naf_gpu_ctx *c, const naf_gpu_ctx *from) { ctx_take_error(c, from->err); }
+// A side context's job and what it queued on its stream: both waited for.
+static inline hipError_t ctx_side_join(naf_gpu_ctx *x) { ctx_worker_join(x); return hipStreamSynchronize(x->stream); }
+// ... and what it returned as this context's error, in HIP_TRY's words (x: the side context as the caller names it)
+#define SIDE_SYNC_TRY(c, e, x) do { if ((e) != hipSuccess) return ctx_fail((c), NAF_GPU_EHIP, "%s: %s (%s:%d)", "hipStreamSynchronize(" #x "->stream)", hipGetErrorString(e), __FILE__, __LINE__); } while (0)
+// A job that captures its starter's locals is joined before they go, whatever the way out (x: nullptr when none was started); joining
+// twice is free, so the explicit join stays the normal path.
+struct CtxJoinGuard { naf_gpu_ctx *x; ~CtxJoinGuard() { if (x) ctx_worker_join(x); } };
 
 // Scratch arena: pointers stay valid until arena_reset.  Returns nullptr on allocation failure.
 void  arena_reset(naf_gpu_ctx *c);

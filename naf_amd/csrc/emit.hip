@@ -1649,269 +1649,719 @@ static int unnaf_prepare(naf_gpu_ctx *c, const u8 *d_naf, size_t naf_len, const 
     return 0;
 }
 
-// Lengths, ids, names and the prefix tables built from them (text offset / first base of every record).  `aux`: a context of its
-// own for ids + names (second host thread and stream); nullptr = everything on c, in order.
-template <typename Hook>
-static int unnaf_sections_main(naf_gpu_ctx *c, const u8 *d_naf, UnnafPlan &pl, naf_gpu_ctx *aux, Hook early, bool early_has_work, naf_gpu_ctx *aux_names)
+// ---- the side-stream chain: lengths, ids, names, mask and the tables built from them -------------------------------
+// What its phases share.  ids, names and lengths are k = 0, 1, 2 of sec / wanted / pre.
+struct SideCall {
+    const u8 *d_naf; UnnafPlan &pl; const naf_gpu_header &h; EmitP &P;
+    bool want_names = false;
+    int sec[3] = { S_IDS, S_NAMES, S_LEN }; bool wanted[3] = { false, false, true };
+    u8 *pre[3] = { nullptr, nullptr, nullptr };                   // a section the small batch has decoded already
+    u64 *rec_len = nullptr;
+    u64 tot[2] = { 0, 0 };                                        // bytes of text, bases of all records
+    // The mask stream of a call with a thread for ids and names and none for the mask: it goes FIRST on this context, right after that
+    // thread has been started -- this context would otherwise idle while it waits, and the mask decode (a few long Huffman streams) is
+    // pure latency.  Its error waits for its turn (mask_err: what it left in c->err).
+    bool mask_meanwhile = false, mask_ran = false; int rc_mask = 0; char mask_err[sizeof(naf_gpu_ctx::err)];
+};
+
+// The wanted, non-empty sections among ids, names and lengths as decode jobs with buffers from x's arena (k: which of the three).
+struct SectionJobs { const u8 *src[3]; size_t len[3], cap[3]; u8 *dst[3]; int k[3]; int m; };
+static int section_jobs(naf_gpu_ctx *x, const SideCall &S, SectionJobs &j)
 {
-    const naf_gpu_header &h = pl.h;
-    EmitP &P = pl.P;
-    int has_ids = (h.flags >> 5) & 1, has_names = (h.flags >> 4) & 1, has_len = (h.flags >> 3) & 1;
-    u64 N = h.n_sequences, T = h.orig_size[S_SEQ];
-    int rc;
-    if (P.mode == EM_SEQ) {
-        pl.total = pl.main_total = T;
-    } else {
-        if (!has_len) return ctx_fail(c, NAF_GPU_EFORMAT, "archive has no lengths");
-        // ids and names: on `aux` (its own host thread and stream) beside the lengths when there is one, else after them
-        P.has_ids = 0; P.has_names = 0;
-        const bool want_names = P.mode == EM_FASTA || P.mode == EM_FASTQ;
-        if (want_names) { P.has_ids = has_ids; P.has_names = has_names; }
-        // ids, names and lengths of an archive with few records are a few hundred bytes each: one launch decodes all three (the ones
-        // that are not small, or fail, take the ordinary path below, which also words the error)
-        u8 *pre[3] = { nullptr, nullptr, nullptr };
-        auto small3 = [&](naf_gpu_ctx *x) -> int {
-            const int sec[3] = { S_IDS, S_NAMES, S_LEN }; const bool wanted[3] = { want_names && has_ids != 0, want_names && has_names != 0, true };
-            const u8 *src[3]; size_t len[3], cap[3]; u8 *dst[3]; bool ok[3]; int idx[3], m = 0;
-            for (int k = 0; k < 3; k++) {
-                if (!wanted[k] || h.orig_size[sec[k]] == 0) continue;
-                u8 *b = (u8 *)arena_alloc(x, h.orig_size[sec[k]] + 32); if (!b) return NAF_GPU_ENOMEM;
-                src[m] = d_naf + h.payload_off[sec[k]]; len[m] = h.comp_size[sec[k]]; dst[m] = b; cap[m] = h.orig_size[sec[k]]; idx[m++] = k;
-            }
-            if (!m) return 0;
-            int r = zstd_small_batch(x, m, src, len, dst, cap, ok); if (r) return r;
-            for (int q = 0; q < m; q++) if (ok[q]) pre[idx[q]] = dst[q];
-            return 0;
-        };
-        // which = 1: ids, 2: names, 3: both (one after the other)
-        auto ids_names = [&](naf_gpu_ctx *x, int which = 3) -> int {
-            int r;
-            if ((which & 1) && want_names && has_ids) {
-                u8 *b = pre[0]; u64 *z = nullptr;
-                if (h.orig_size[S_IDS] == 0) return ctx_fail(x, NAF_GPU_EFORMAT, "corrupted ids - not 0-terminated\n");
-                if (!b && (r = load_section(x, d_naf, h, S_IDS, h.orig_size[S_IDS], "ids", &b, pl.frame_head[S_IDS]))) return r;
-                if ((r = zero_positions(x, b, h.orig_size[S_IDS], N, &z, false))) return r;
-                P.ids = b; P.idz = z;
-            }
-            if ((which & 2) && want_names && has_names) {
-                u8 *b = pre[1]; u64 *z = nullptr;
-                if (h.orig_size[S_NAMES] == 0) return ctx_fail(x, NAF_GPU_EFORMAT, "corrupted names - not 0-terminated\n");
-                if (!b && (r = load_section(x, d_naf, h, S_NAMES, h.orig_size[S_NAMES], "names", &b, pl.frame_head[S_NAMES]))) return r;
-                if ((r = zero_positions(x, b, h.orig_size[S_NAMES], N, &z, true))) return r;
-                P.names = b; P.nmz = z;
-            }
-            return 0;
-        };
-        u64 *rec_len = nullptr;
-        auto lengths = [&](naf_gpu_ctx *x) -> int {
-            int r;
-            u8 *lens = pre[2];
-            if (!lens && (r = load_section(x, d_naf, h, S_LEN, h.orig_size[S_LEN], "lengths", &lens, pl.frame_head[S_LEN]))) return r;
-            u64 n_len = h.orig_size[S_LEN] / 4;
-            u64 *flag = arena_new<u64>(x, n_len + 2); rec_len = arena_new<u64>(x, N + 1);
-            if (!flag || !rec_len) return NAF_GPU_ENOMEM;
-            HIP_TRY(x, hipMemsetAsync(rec_len, 0, (N + 1) * 8, x->stream));
-            if (n_len) LAUNCH(x, "unnaf_len_flags", k_len_flags, cdiv(n_len, 256), 256, 0, (const u32 *)lens, n_len, flag);
-            if ((r = scan_exclusive_u64(x, flag, n_len, flag + n_len + 1))) return r;
-            if (n_len) LAUNCH(x, "unnaf_len_acc", k_len_acc, cdiv(n_len, 256), 256, 0, (const u32 *)lens, n_len, (const u64 *)flag, rec_len, N);
-            u64 nrec = 0;
-            if ((r = ctx_readback(x, &nrec, flag + n_len + 1, 8))) return r;
-            if (nrec < N) return ctx_fail(x, NAF_GPU_EFORMAT, "corrupted lengths: %llu records described, %llu expected", (unsigned long long)nrec, (unsigned long long)N);
-            return 0;
-        };
-        // Few records, every one of the three streams a small frame: two launches and one read-back make all the tables (k_side_tables),
-        // on `aux` beside the mask stream when there is one (NAF_GPU_SIDE_FUSED=0: the long way below, which is also where a frame that
-        // turns out not to decode goes, for its message)
-        u64 tot[2] = { 0, 0 };
-        bool fused_done = false;
-        {
-            const char *sf = ctx_opt(c, "SIDE_FUSED");
-            const int sec[3] = { S_IDS, S_NAMES, S_LEN }; const bool wanted[3] = { want_names && has_ids != 0, want_names && has_names != 0, true };
-            bool fits = !(sf && sf[0] == '0') && N <= SIDE_FUSED_N && h.orig_size[S_LEN] % 4 == 0;
-            for (int k = 0; k < 3; k++) if (wanted[k] && !zstd_small_fits(h.comp_size[sec[k]], h.orig_size[sec[k]])) fits = false;
-            for (int k = 0; k < 3; k++) if (wanted[k] && h.orig_size[sec[k]] == 0) fits = false;
-            if (fits) {
-                u64 st[6] = { 0, 0, 0, 0, 0, 0 };
-                auto fused = [&](naf_gpu_ctx *x) -> int {
-                    const u8 *src[3]; size_t len[3], cap[3]; u8 *dst[3]; u8 *buf[3] = { nullptr, nullptr, nullptr }; int m = 0, r;
-                    SideJob J; memset(&J, 0, sizeof J);
-                    for (int k = 0; k < 3; k++) {
-                        if (!wanted[k]) continue;
-                        u8 *b = (u8 *)arena_alloc(x, h.orig_size[sec[k]] + 32); if (!b) return NAF_GPU_ENOMEM;
-                        src[m] = d_naf + h.payload_off[sec[k]]; len[m] = h.comp_size[sec[k]]; dst[m] = b; cap[m] = h.orig_size[sec[k]];
-                        J.cap[m] = (u32)cap[m]; J.len[m] = (u32)len[m]; buf[k] = b; m++;
-                    }
-                    u32 *d_res = nullptr;
-                    if ((r = zstd_small_launch(x, m, src, len, dst, cap, &d_res))) return r;
-                    J.res = d_res; J.n_jobs = (u32)m;
-                    J.ids = buf[0]; J.ids_n = h.orig_size[S_IDS]; J.names = buf[1]; J.names_n = h.orig_size[S_NAMES];
-                    J.lens = (const u32 *)buf[2]; J.n_len = h.orig_size[S_LEN] / 4;
-                    J.N = N; J.L = P.L; J.has_ids = P.has_ids; J.has_names = P.has_names; J.mode = P.mode;
-                    J.idz = P.has_ids ? arena_new<u64>(x, N + 1) : nullptr; J.nmz = P.has_names ? arena_new<u64>(x, N + 1) : nullptr;
-                    J.rec_len = arena_new<u64>(x, N + 1); J.hdr_len = arena_new<u32>(x, N + 1);
-                    J.rec_out = arena_new<u64>(x, N + 2); J.rec_base = arena_new<u64>(x, N + 2); J.status = arena_new<u64>(x, 8);
-                    if ((P.has_ids && !J.idz) || (P.has_names && !J.nmz) || !J.rec_len || !J.hdr_len || !J.rec_out || !J.rec_base || !J.status) return NAF_GPU_ENOMEM;
-                    LAUNCH(x, "unnaf_side_tables", k_side_tables, 1, 256, 0, J);
-                    if ((r = ctx_readback(x, st, J.status, sizeof st))) return r;
-                    if (st[0] != 1) return 0;
-                    P.ids = buf[0]; P.idz = J.idz; P.names = buf[1]; P.nmz = J.nmz;
-                    P.rec_len = J.rec_len; P.hdr_len = J.hdr_len; P.rec_out = J.rec_out; P.rec_base = J.rec_base;
-                    fused_done = true;
-                    return 0;
-                };
-                int rf = 0;
-                if (aux) { ctx_worker_start(aux, [&] { rf = fused(aux); }); early(); ctx_worker_join(aux); if (rf) memcpy(c->err, aux->err, sizeof c->err); }   // no return until it is joined
-                else rf = fused(c);
-                if (rf) return rf;
-                if (fused_done) {
-                    // the order (and the words) of the long way: lengths, ids, names
-                    if (st[3] < N) return ctx_fail(c, NAF_GPU_EFORMAT, "corrupted lengths: %llu records described, %llu expected", (unsigned long long)st[3], (unsigned long long)N);
-                    if (P.has_ids && st[1] < N) return ctx_fail(c, NAF_GPU_EFORMAT, "currupted ids - can't read id %llu\n", (unsigned long long)st[1]);
-                    if (P.has_names && st[2] < N) return ctx_fail(c, NAF_GPU_EFORMAT, "corrupted names - can't read name %llu\n", (unsigned long long)st[2]);
-                    tot[0] = st[4]; tot[1] = st[5];
-                }
-            }
-        }
-        if (fused_done) rec_len = (u64 *)P.rec_len;
-        else {
-        // With a second context: ids and names go there.  When this context also has the mask stream to decode (`early`), the
-        // lengths follow the names over there, so that the two chains (mask | ids, names, lengths) are about as long as each other.
-        const bool aux_run = aux && want_names && (has_ids || has_names);
-        int rc_aux = 0, rc_len = 0;
-        const bool len_on_aux = aux_run && early_has_work;
-        int rc_small = 0;
-        if (aux_run && !len_on_aux) rc_small = small3(c);                    // this context has nothing else to do meanwhile
-        // Ids and names of an archive of many records (a FASTQ's 12 M reads per 4 GB: two streams through the sequence executor, 3.9 and
-        // 1.1 ms one after the other, and the emit waits for both) go to a context each (NAF_GPU_NAMES_BESIDE=0: both on `aux`).
-        bool names_beside = aux_run && aux_names && !len_on_aux && has_ids && has_names && h.orig_size[S_IDS] >= (1u << 20) && h.orig_size[S_NAMES] >= (1u << 20);
-        { const char *nb = ctx_opt(c, "NAMES_BESIDE"); if (nb && nb[0] == '0') names_beside = false; }
-        int rc_names = 0;
-        if (names_beside) ctx_worker_start(aux_names, [&] { rc_names = ids_names(aux_names, 2); });               // pre[] is set by now (small3 ran on c above), no return until it is joined
-        if (aux_run) ctx_worker_start(aux, [&] { if (len_on_aux) rc_small = small3(aux); rc_aux = rc_small ? rc_small : ids_names(aux, names_beside ? 1 : 3); if (len_on_aux && !rc_small) rc_len = lengths(aux); });     // no return until it is joined
-        early();                                                                                         // work that needs none of this (the mask stream)
-        if (!aux_run) rc_small = small3(c);
-        if (!len_on_aux) rc_len = rc_small ? rc_small : lengths(c);
-        if (aux_run) { ctx_worker_join(aux); hipStreamSynchronize(aux->stream); }
-        if (names_beside) { ctx_worker_join(aux_names); hipStreamSynchronize(aux_names->stream); }
-        if (rc_len) { if (len_on_aux) memcpy(c->err, aux->err, sizeof c->err); return rc_len; }           // the order a sequential run reports in: lengths, ids, names
-        if (!aux_run) rc_aux = ids_names(c);
-        else if (rc_aux) memcpy(c->err, aux->err, sizeof c->err);
-        if (rc_aux) return rc_aux;
-        if (rc_names) { memcpy(c->err, aux_names->err, sizeof c->err); return rc_names; }                      // (ids, then names: the order a sequential run reports in)
-        P.rec_len = rec_len;
-        u32 *hdr_len = arena_new<u32>(c, N + 1);
-        u64 *rec_out = arena_new<u64>(c, N + 2), *rec_base = arena_new<u64>(c, N + 2);
-        if (!hdr_len || !rec_out || !rec_base) return NAF_GPU_ENOMEM;
-        LAUNCH(c, "unnaf_rec_sizes", k_rec_sizes, cdiv(N, 256), 256, 0, N, (const u64 *)rec_len, P.idz, P.nmz, P.has_ids, P.has_names, P.mode, P.L, hdr_len, rec_out, rec_base);
-        // exclusive scans; element N receives the total (scan over N+1 entries with a zero tail)
-        HIP_TRY(c, hipMemsetAsync(rec_out + N, 0, 8, c->stream));
-        HIP_TRY(c, hipMemsetAsync(rec_base + N, 0, 8, c->stream));
-        if ((rc = scan_exclusive_u64(c, rec_out, N + 1, (u64 *)nullptr))) return rc;
-        if ((rc = scan_exclusive_u64(c, rec_base, N + 1, (u64 *)nullptr))) return rc;
-        if ((rc = ctx_readback2(c, &tot[0], rec_out + N, 8, &tot[1], rec_base + N, 8))) return rc;
-        P.hdr_len = hdr_len; P.rec_out = rec_out; P.rec_base = rec_base;
-        }
-        if (tot[1] > T) return ctx_fail(c, NAF_GPU_EFORMAT, "sum of lengths (%llu) exceeds the stored sequence length (%llu)", (unsigned long long)tot[1], (unsigned long long)T);
-        // every base of a read needs its quality byte: a shorter quality stream would be read past its end by the emit kernels (the
-        // reference has no message for this -- print_quality_from_file, output-fastq.c:69-85, never returns on such an archive)
-        if (P.mode == EM_FASTQ && h.orig_size[S_QUAL] < tot[1])
-            return ctx_fail(c, NAF_GPU_EFORMAT, "corrupted quality: %llu quality codes stored for %llu bases\n", (unsigned long long)h.orig_size[S_QUAL], (unsigned long long)tot[1]);
-        if (P.mode == EM_SEQUENCES && T == 0) tot[0] = 0;                            // output-sequences.c:81: nothing printed
-        pl.total = pl.main_total = tot[0]; pl.surplus = 0; pl.sur_c = 0;
-        if (tot[1] < T && P.mode != EM_FASTQ) {
-            // more bases than the lengths account for.  FASTQ never prints them (output-fastq.c:100-149 stops after the N-th
-            // read); --sequences appends them raw (output-sequences.c:82-116); FASTA wraps them on from the last non-empty record's line
-            const u64 S = T - tot[1];
-            u64 tail = S;
-            if (P.mode == EM_FASTA) {
-                unsigned long long *d_last = arena_new<unsigned long long>(c, 2); if (!d_last) return NAF_GPU_ENOMEM;
-                HIP_TRY(c, hipMemsetAsync(d_last, 0, 16, c->stream));
-                LAUNCH(c, "unnaf_last_nonempty", k_last_nonempty, cdiv(N, 256), 256, 0, (const u64 *)rec_len, N, d_last);
-                u64 last1 = 0; if ((rc = ctx_readback(c, &last1, d_last, 8))) return rc;
-                if (last1 == 0) tail = 0;                                           // no record ever started a line of bases: nothing is printed
-                else {
-                    u64 len_last = 0; if ((rc = ctx_readback(c, &len_last, rec_len + (last1 - 1), 8))) return rc;
-                    const u64 L = P.L;
-                    const u64 cc = L ? ((len_last % L) ? L - len_last % L : 0) : 0;
-                    pl.sur_c = cc;
-                    if (L && S > cc) { const u64 R = S - cc; tail = cc + 1 + R + (R - 1) / L; }
-                }
-            }
-            pl.surplus = tail ? S : 0; pl.sur_base0 = tot[1];
-            pl.total = pl.main_total + tail;
-        }
+    const naf_gpu_header &h = S.h;
+    j.m = 0;
+    for (int k = 0; k < 3; k++) {
+        const int s = S.sec[k];
+        if (!S.wanted[k] || h.orig_size[s] == 0) continue;
+        u8 *b = (u8 *)arena_alloc(x, h.orig_size[s] + 32); if (!b) return NAF_GPU_ENOMEM;
+        j.src[j.m] = S.d_naf + h.payload_off[s]; j.len[j.m] = h.comp_size[s]; j.dst[j.m] = b; j.cap[j.m] = h.orig_size[s]; j.k[j.m++] = k;
     }
     return 0;
 }
 
-// The side streams (lengths, ids, names, mask) and the tables built from them.  Runs on whichever context it is given: the
-// archive's own for byte-range calls (aux = aux_mask = nullptr: sequential), the side context for whole-text calls, which also
-// hands over contexts for ids + names and for the mask.
-static int unnaf_sections(naf_gpu_ctx *c, const u8 *d_naf, UnnafPlan &pl, naf_gpu_ctx *aux = nullptr, naf_gpu_ctx *aux_mask = nullptr, naf_gpu_ctx *aux_names = nullptr)
+// ids, names and lengths of an archive with few records are a few hundred bytes each: one launch decodes all three (the ones that
+// are not small, or fail, take the ordinary path, which also words the error)
+static int side_small_batch(naf_gpu_ctx *x, SideCall &S)
 {
-    const naf_gpu_header &h = pl.h;
-    EmitP &P = pl.P;
-    // mask stream -> toggle table.  A handful of long Huffman streams: its decode is pure latency, so with `aux_mask` it runs on a
-    // context of its own from the start of the call
-    auto mask_part = [&](naf_gpu_ctx *x) -> int {
-        int r;
-        u8 *mu = nullptr; u64 n_mask = h.orig_size[S_MASK];
-        {
-            // a frame of a few KB for MBs of units: Raw / RLE blocks, one launch (NAF_GPU_MASK_RLE=0: never)
-            const char *mr = ctx_opt(c, "MASK_RLE");
-            const u64 cs = h.comp_size[S_MASK];
-            if (cs >= 4 && cs <= MASK_RLE_SRC && n_mask >= 2 * cs && !(mr && mr[0] == '0')) {
-                // Frame_Header (RFC 8878 3.1.1.1) of a frame without dictionary and checksum: descriptor, window byte, content size
-                const u8 fhd = pl.frame_head[S_MASK][0];
-                const u32 fcs_flag = fhd >> 6, single = (fhd >> 5) & 1;
-                struct { u32 hdr_size; bool ok; } fh;
-                fh.hdr_size = 1 + (single ? 0 : 1) + (fcs_flag == 0 ? single : (fcs_flag == 1 ? 2 : (fcs_flag == 2 ? 4 : 8)));
-                fh.ok = !(fhd & 0x0F);                               // no reserved bit, no checksum, no dictionary id
-                if (fh.ok && fh.hdr_size < cs) {
-                    u64 *tg = arena_new<u64>(x, MASK_RLE_TOG + 1), *d_res = arena_new<u64>(x, 4);
-                    if (!tg || !d_res) return NAF_GPU_ENOMEM;
-                    LAUNCH(x, "unnaf_mask_rle", k_mask_rle_frame, 1, 256, (u32)((cs + 15) & ~15ull), d_naf + h.payload_off[S_MASK], (u32)cs, fh.hdr_size, n_mask, tg, MASK_RLE_TOG, d_res);
-                    u64 res[3] = { 0, 0, 0 };
-                    if ((r = ctx_readback(x, res, d_res, 24))) return r;
-                    if (res[0] == 1) { P.toggles = tg; P.n_toggles = res[1]; return 0; }
-                }
-            }
-        }
-        if ((r = load_section(x, d_naf, h, S_MASK, n_mask, "mask", &mu, pl.frame_head[S_MASK]))) return r;
-        u64 tiles = (n_mask + MT_TILE - 1) / MT_TILE;
-        u64 *ts = arena_new<u64>(x, tiles + 2), *tc = arena_new<u64>(x, tiles + 2);
-        if (!ts || !tc) return NAF_GPU_ENOMEM;
-        if (tiles) LAUNCH(x, "unnaf_mask_count", k_mask_count, tiles, 256, 0, (const u8 *)mu, n_mask, ts, tc);
-        if ((r = scan_exclusive_u64(x, ts, tiles, (u64 *)nullptr))) return r;
-        if ((r = scan_exclusive_u64(x, tc, tiles, tc + tiles + 1))) return r;
-        u64 ntog = 0;
-        if ((r = ctx_readback(x, &ntog, tc + tiles + 1, 8))) return r;
-        u64 *tg = arena_new<u64>(x, ntog + 1);
-        if (!tg) return NAF_GPU_ENOMEM;
-        if (tiles) LAUNCH(x, "unnaf_mask_scatter", k_mask_scatter, tiles, 256, 0, (const u8 *)mu, n_mask, (const u64 *)ts, (const u64 *)tc, tg, ntog);
-        P.toggles = tg; P.n_toggles = ntog;
-        return 0;
-    };
-    int rc_mask = 0;
-    const bool mask_started = P.masking && aux_mask;
-    if (mask_started) ctx_worker_start(aux_mask, [&] { rc_mask = mask_part(aux_mask); });      // joined below: no return before
-    // Without a context of its own the mask goes FIRST on this one, right after the ids / names thread has been started: this
-    // context would otherwise idle while it waits for that thread, and the mask decode (a few long Huffman streams) is pure latency.
-    // Errors keep the order of a sequential run: lengths, ids, names, then mask.
-    bool mask_early = false; char mask_err[sizeof c->err];
-    auto early = [&]() {
-        if (P.masking && !mask_started && P.mode != EM_SEQ && aux) { mask_early = true; rc_mask = mask_part(c); if (rc_mask) memcpy(mask_err, c->err, sizeof c->err); }
-    };
-    int rc = unnaf_sections_main(c, d_naf, pl, aux, early, P.masking && !mask_started && P.mode != EM_SEQ && aux != nullptr, aux_names);
-    if (mask_started) { ctx_worker_join(aux_mask); hipStreamSynchronize(aux_mask->stream); }
-    if (rc) return rc;                                                                                     // the order a sequential run reports in
-    if (mask_started && rc_mask) { memcpy(c->err, aux_mask->err, sizeof c->err); return rc_mask; }
-    if (mask_early) { if (rc_mask) { memcpy(c->err, mask_err, sizeof c->err); return rc_mask; } }
-    else if (P.masking && !mask_started && (rc = mask_part(c))) return rc;
+    SectionJobs j; bool ok[3];
+    int r = section_jobs(x, S, j); if (r) return r;
+    if (!j.m) return 0;
+    if ((r = zstd_small_batch(x, j.m, j.src, j.len, j.dst, j.cap, ok))) return r;
+    for (int q = 0; q < j.m; q++) if (ok[q]) S.pre[j.k[q]] = j.dst[q];
     return 0;
 }
 
+// which = 1: ids, 2: names, 3: both (one after the other)
+static int side_ids_names(naf_gpu_ctx *x, SideCall &S, int which)
+{
+    const naf_gpu_header &h = S.h; EmitP &P = S.P;
+    const u64 N = h.n_sequences;
+    int r;
+    if ((which & 1) && S.wanted[0]) {
+        u8 *b = S.pre[0]; u64 *z = nullptr;
+        if (h.orig_size[S_IDS] == 0) return ctx_fail(x, NAF_GPU_EFORMAT, "corrupted ids - not 0-terminated\n");
+        if (!b && (r = load_section(x, S.d_naf, h, S_IDS, h.orig_size[S_IDS], "ids", &b, S.pl.frame_head[S_IDS]))) return r;
+        if ((r = zero_positions(x, b, h.orig_size[S_IDS], N, &z, false))) return r;
+        P.ids = b; P.idz = z;
+    }
+    if ((which & 2) && S.wanted[1]) {
+        u8 *b = S.pre[1]; u64 *z = nullptr;
+        if (h.orig_size[S_NAMES] == 0) return ctx_fail(x, NAF_GPU_EFORMAT, "corrupted names - not 0-terminated\n");
+        if (!b && (r = load_section(x, S.d_naf, h, S_NAMES, h.orig_size[S_NAMES], "names", &b, S.pl.frame_head[S_NAMES]))) return r;
+        if ((r = zero_positions(x, b, h.orig_size[S_NAMES], N, &z, true))) return r;
+        P.names = b; P.nmz = z;
+    }
+    return 0;
+}
+
+static int side_lengths(naf_gpu_ctx *x, SideCall &S)
+{
+    const naf_gpu_header &h = S.h;
+    const u64 N = h.n_sequences;
+    int r;
+    u8 *lens = S.pre[2];
+    if (!lens && (r = load_section(x, S.d_naf, h, S_LEN, h.orig_size[S_LEN], "lengths", &lens, S.pl.frame_head[S_LEN]))) return r;
+    u64 n_len = h.orig_size[S_LEN] / 4;
+    u64 *flag = arena_new<u64>(x, n_len + 2), *rec_len = S.rec_len = arena_new<u64>(x, N + 1);
+    if (!flag || !rec_len) return NAF_GPU_ENOMEM;
+    HIP_TRY(x, hipMemsetAsync(rec_len, 0, (N + 1) * 8, x->stream));
+    if (n_len) LAUNCH(x, "unnaf_len_flags", k_len_flags, cdiv(n_len, 256), 256, 0, (const u32 *)lens, n_len, flag);
+    if ((r = scan_exclusive_u64(x, flag, n_len, flag + n_len + 1))) return r;
+    if (n_len) LAUNCH(x, "unnaf_len_acc", k_len_acc, cdiv(n_len, 256), 256, 0, (const u32 *)lens, n_len, (const u64 *)flag, rec_len, N);
+    u64 nrec = 0;
+    if ((r = ctx_readback(x, &nrec, flag + n_len + 1, 8))) return r;
+    if (nrec < N) return ctx_fail(x, NAF_GPU_EFORMAT, "corrupted lengths: %llu records described, %llu expected", (unsigned long long)nrec, (unsigned long long)N);
+    return 0;
+}
+
+// mask stream -> toggle table, the shortcut: a frame of a few KB for MBs of units -- Raw / RLE blocks, one launch (NAF_GPU_MASK_RLE=0:
+// never).  *done: the table is made; else the frame is not of that kind and takes the decoder.
+static int mask_rle_frame(naf_gpu_ctx *x, SideCall &S, bool *done)
+{
+    const naf_gpu_header &h = S.h; EmitP &P = S.P;
+    const u64 cs = h.comp_size[S_MASK], n_mask = h.orig_size[S_MASK];
+    *done = false;
+    if (!(cs >= 4 && cs <= MASK_RLE_SRC && n_mask >= 2 * cs) || ctx_opt_is(x, "MASK_RLE", '0')) return 0;
+    // Frame_Header (RFC 8878 3.1.1.1) of a frame without dictionary and checksum: descriptor, window byte, content size
+    const u8 fhd = S.pl.frame_head[S_MASK][0];
+    const u32 fcs_flag = fhd >> 6, single = (fhd >> 5) & 1;
+    const u32 hdr_size = 1 + (single ? 0 : 1) + (fcs_flag == 0 ? single : (fcs_flag == 1 ? 2 : (fcs_flag == 2 ? 4 : 8)));
+    if ((fhd & 0x0F) || hdr_size >= cs) return 0;                 // a reserved bit, a checksum, a dictionary id
+    u64 *tg = arena_new<u64>(x, MASK_RLE_TOG + 1), *d_res = arena_new<u64>(x, 4);
+    if (!tg || !d_res) return NAF_GPU_ENOMEM;
+    LAUNCH(x, "unnaf_mask_rle", k_mask_rle_frame, 1, 256, (u32)((cs + 15) & ~15ull), S.d_naf + h.payload_off[S_MASK], (u32)cs, hdr_size, n_mask, tg, MASK_RLE_TOG, d_res);
+    u64 res[3] = { 0, 0, 0 };
+    int r = ctx_readback(x, res, d_res, 24); if (r) return r;
+    if (res[0] == 1) { P.toggles = tg; P.n_toggles = res[1]; *done = true; }
+    return 0;
+}
+
+// mask stream -> toggle table
+static int mask_toggles(naf_gpu_ctx *x, SideCall &S)
+{
+    const naf_gpu_header &h = S.h; EmitP &P = S.P;
+    int r; bool done;
+    u8 *mu = nullptr; const u64 n_mask = h.orig_size[S_MASK];
+    if ((r = mask_rle_frame(x, S, &done)) || done) return r;
+    if ((r = load_section(x, S.d_naf, h, S_MASK, n_mask, "mask", &mu, S.pl.frame_head[S_MASK]))) return r;
+    u64 tiles = (n_mask + MT_TILE - 1) / MT_TILE;
+    u64 *ts = arena_new<u64>(x, tiles + 2), *tc = arena_new<u64>(x, tiles + 2);
+    if (!ts || !tc) return NAF_GPU_ENOMEM;
+    if (tiles) LAUNCH(x, "unnaf_mask_count", k_mask_count, tiles, 256, 0, (const u8 *)mu, n_mask, ts, tc);
+    if ((r = scan_exclusive_u64(x, ts, tiles, (u64 *)nullptr))) return r;
+    if ((r = scan_exclusive_u64(x, tc, tiles, tc + tiles + 1))) return r;
+    u64 ntog = 0;
+    if ((r = ctx_readback(x, &ntog, tc + tiles + 1, 8))) return r;
+    u64 *tg = arena_new<u64>(x, ntog + 1);
+    if (!tg) return NAF_GPU_ENOMEM;
+    if (tiles) LAUNCH(x, "unnaf_mask_scatter", k_mask_scatter, tiles, 256, 0, (const u8 *)mu, n_mask, (const u64 *)ts, (const u64 *)tc, tg, ntog);
+    P.toggles = tg; P.n_toggles = ntog;
+    return 0;
+}
+
+// Called by whoever has just started the ids / names thread (see SideCall::mask_meanwhile).
+static void side_mask_meanwhile(naf_gpu_ctx *c, SideCall &S)
+{
+    if (!S.mask_meanwhile) return;
+    S.mask_ran = true; S.rc_mask = mask_toggles(c, S);
+    if (S.rc_mask) memcpy(S.mask_err, c->err, sizeof c->err);
+}
+
+// Few records, every one of the three streams a small frame: two launches and one read-back make all the tables (k_side_tables)
+static int side_fused_launch(naf_gpu_ctx *x, SideCall &S, u64 st[6], bool *done)
+{
+    const naf_gpu_header &h = S.h; EmitP &P = S.P;
+    const u64 N = h.n_sequences;
+    SectionJobs j; u8 *buf[3] = { nullptr, nullptr, nullptr };
+    int r = section_jobs(x, S, j); if (r) return r;
+    SideJob J; memset(&J, 0, sizeof J);
+    for (int q = 0; q < j.m; q++) { J.cap[q] = (u32)j.cap[q]; J.len[q] = (u32)j.len[q]; buf[j.k[q]] = j.dst[q]; }
+    u32 *d_res = nullptr;
+    if ((r = zstd_small_launch(x, j.m, j.src, j.len, j.dst, j.cap, &d_res))) return r;
+    J.res = d_res; J.n_jobs = (u32)j.m;
+    J.ids = buf[0]; J.ids_n = h.orig_size[S_IDS]; J.names = buf[1]; J.names_n = h.orig_size[S_NAMES];
+    J.lens = (const u32 *)buf[2]; J.n_len = h.orig_size[S_LEN] / 4;
+    J.N = N; J.L = P.L; J.has_ids = P.has_ids; J.has_names = P.has_names; J.mode = P.mode;
+    J.idz = P.has_ids ? arena_new<u64>(x, N + 1) : nullptr; J.nmz = P.has_names ? arena_new<u64>(x, N + 1) : nullptr;
+    J.rec_len = arena_new<u64>(x, N + 1); J.hdr_len = arena_new<u32>(x, N + 1);
+    J.rec_out = arena_new<u64>(x, N + 2); J.rec_base = arena_new<u64>(x, N + 2); J.status = arena_new<u64>(x, 8);
+    if ((P.has_ids && !J.idz) || (P.has_names && !J.nmz) || !J.rec_len || !J.hdr_len || !J.rec_out || !J.rec_base || !J.status) return NAF_GPU_ENOMEM;
+    LAUNCH(x, "unnaf_side_tables", k_side_tables, 1, 256, 0, J);
+    if ((r = ctx_readback(x, st, J.status, 6 * sizeof(u64)))) return r;
+    if (st[0] != 1) return 0;
+    P.ids = buf[0]; P.idz = J.idz; P.names = buf[1]; P.nmz = J.nmz;
+    P.rec_len = J.rec_len; P.hdr_len = J.hdr_len; P.rec_out = J.rec_out; P.rec_base = J.rec_base;
+    *done = true;
+    return 0;
+}
+
+// ... on `aux` beside the mask stream when there is one (NAF_GPU_SIDE_FUSED=0: the long way, which is also where a frame that turns
+// out not to decode goes, for its message).  *done: the tables are made.
+static int side_fused_tables(naf_gpu_ctx *c, SideCall &S, naf_gpu_ctx *aux, bool *done)
+{
+    const naf_gpu_header &h = S.h; EmitP &P = S.P;
+    const u64 N = h.n_sequences;
+    *done = false;
+    bool fits = !ctx_opt_is(c, "SIDE_FUSED", '0') && N <= SIDE_FUSED_N && h.orig_size[S_LEN] % 4 == 0;
+    for (int k = 0; k < 3; k++) if (S.wanted[k] && (!zstd_small_fits(h.comp_size[S.sec[k]], h.orig_size[S.sec[k]]) || h.orig_size[S.sec[k]] == 0)) fits = false;
+    if (!fits) return 0;
+    u64 st[6] = { 0, 0, 0, 0, 0, 0 };
+    int rf = 0;
+    if (aux) {
+        CtxJoinGuard joined{ aux };
+        ctx_worker_start(aux, [&] { rf = side_fused_launch(aux, S, st, done); });
+        side_mask_meanwhile(c, S);
+        ctx_worker_join(aux);
+        if (rf) ctx_take_error(c, aux);
+    } else rf = side_fused_launch(c, S, st, done);
+    if (rf || !*done) return rf;
+    // the order (and the words) of the long way: lengths, ids, names
+    if (st[3] < N) return ctx_fail(c, NAF_GPU_EFORMAT, "corrupted lengths: %llu records described, %llu expected", (unsigned long long)st[3], (unsigned long long)N);
+    if (P.has_ids && st[1] < N) return ctx_fail(c, NAF_GPU_EFORMAT, "currupted ids - can't read id %llu\n", (unsigned long long)st[1]);
+    if (P.has_names && st[2] < N) return ctx_fail(c, NAF_GPU_EFORMAT, "corrupted names - can't read name %llu\n", (unsigned long long)st[2]);
+    S.tot[0] = st[4]; S.tot[1] = st[5];
+    S.rec_len = (u64 *)P.rec_len;
+    return 0;
+}
+
+// Lengths, ids and names, a load_section each.  With a second context (`aux`: its own host thread and stream) ids and names go there.
+// When this context also has the mask stream to decode meanwhile, the lengths follow the names over there, so that the two chains
+// (mask | ids, names, lengths) are about as long as each other.
+static int side_long_way(naf_gpu_ctx *c, SideCall &S, naf_gpu_ctx *aux, naf_gpu_ctx *aux_names)
+{
+    const naf_gpu_header &h = S.h;
+    const bool aux_run = aux && (S.wanted[0] || S.wanted[1]);
+    const bool len_on_aux = aux_run && S.mask_meanwhile;
+    int rc_small = 0, rc_aux = 0, rc_len = 0, rc_names = 0;
+    if (aux_run && !len_on_aux) rc_small = side_small_batch(c, S);        // this context has nothing else to do meanwhile
+    // Ids and names of an archive of many records (a FASTQ's 12 M reads per 4 GB: two streams through the sequence executor, 3.9 and
+    // 1.1 ms one after the other, and the emit waits for both) go to a context each (NAF_GPU_NAMES_BESIDE=0: both on `aux`).
+    const bool names_beside = aux_run && aux_names && !len_on_aux && S.wanted[0] && S.wanted[1] && h.orig_size[S_IDS] >= (1u << 20) && h.orig_size[S_NAMES] >= (1u << 20) &&
+                              !ctx_opt_is(c, "NAMES_BESIDE", '0');
+    CtxJoinGuard names_joined{ names_beside ? aux_names : nullptr }, aux_joined{ aux_run ? aux : nullptr };
+    if (names_beside) ctx_worker_start(aux_names, [&] { rc_names = side_ids_names(aux_names, S, 2); });       // pre[] is set by now (the small batch ran on c above)
+    if (aux_run) ctx_worker_start(aux, [&] { if (len_on_aux) rc_small = side_small_batch(aux, S); rc_aux = rc_small ? rc_small : side_ids_names(aux, S, names_beside ? 1 : 3); if (len_on_aux && !rc_small) rc_len = side_lengths(aux, S); });
+    side_mask_meanwhile(c, S);
+    if (!aux_run) rc_small = side_small_batch(c, S);
+    if (!len_on_aux) rc_len = rc_small ? rc_small : side_lengths(c, S);
+    const hipError_t aux_synced = aux_run ? ctx_side_join(aux) : hipSuccess;
+    const hipError_t names_synced = names_beside ? ctx_side_join(aux_names) : hipSuccess;
+    // the order a sequential run reports in: lengths, ids, names; a stream that failed to synchronize, behind what ran on it
+    if (rc_len) { if (len_on_aux) ctx_take_error(c, aux); return rc_len; }
+    if (!aux_run) rc_aux = side_ids_names(c, S, 3);
+    else if (rc_aux) ctx_take_error(c, aux);
+    if (rc_aux) return rc_aux;
+    SIDE_SYNC_TRY(c, aux_synced, aux);
+    if (rc_names) { ctx_take_error(c, aux_names); return rc_names; }
+    SIDE_SYNC_TRY(c, names_synced, aux_names);
+    S.P.rec_len = S.rec_len;
+    return 0;
+}
+
+// text offset / first base of every record: a record's sizes, then two exclusive scans
+static int record_tables(naf_gpu_ctx *c, SideCall &S)
+{
+    EmitP &P = S.P;
+    const u64 N = S.h.n_sequences;
+    int rc;
+    u32 *hdr_len = arena_new<u32>(c, N + 1);
+    u64 *rec_out = arena_new<u64>(c, N + 2), *rec_base = arena_new<u64>(c, N + 2);
+    if (!hdr_len || !rec_out || !rec_base) return NAF_GPU_ENOMEM;
+    LAUNCH(c, "unnaf_rec_sizes", k_rec_sizes, cdiv(N, 256), 256, 0, N, (const u64 *)S.rec_len, P.idz, P.nmz, P.has_ids, P.has_names, P.mode, P.L, hdr_len, rec_out, rec_base);
+    // element N receives the total (scan over N+1 entries with a zero tail)
+    HIP_TRY(c, hipMemsetAsync(rec_out + N, 0, 8, c->stream));
+    HIP_TRY(c, hipMemsetAsync(rec_base + N, 0, 8, c->stream));
+    if ((rc = scan_exclusive_u64(c, rec_out, N + 1, (u64 *)nullptr))) return rc;
+    if ((rc = scan_exclusive_u64(c, rec_base, N + 1, (u64 *)nullptr))) return rc;
+    if ((rc = ctx_readback2(c, &S.tot[0], rec_out + N, 8, &S.tot[1], rec_base + N, 8))) return rc;
+    P.hdr_len = hdr_len; P.rec_out = rec_out; P.rec_base = rec_base;
+    return 0;
+}
+
+static int side_totals_and_surplus(naf_gpu_ctx *c, SideCall &S)
+{
+    const naf_gpu_header &h = S.h; EmitP &P = S.P; UnnafPlan &pl = S.pl;
+    const u64 N = h.n_sequences, T = h.orig_size[S_SEQ];
+    u64 *tot = S.tot;
+    int rc;
+    if (tot[1] > T) return ctx_fail(c, NAF_GPU_EFORMAT, "sum of lengths (%llu) exceeds the stored sequence length (%llu)", (unsigned long long)tot[1], (unsigned long long)T);
+    // every base of a read needs its quality byte: a shorter quality stream would be read past its end by the emit kernels (the
+    // reference has no message for this -- print_quality_from_file, output-fastq.c:69-85, never returns on such an archive)
+    if (P.mode == EM_FASTQ && h.orig_size[S_QUAL] < tot[1])
+        return ctx_fail(c, NAF_GPU_EFORMAT, "corrupted quality: %llu quality codes stored for %llu bases\n", (unsigned long long)h.orig_size[S_QUAL], (unsigned long long)tot[1]);
+    if (P.mode == EM_SEQUENCES && T == 0) tot[0] = 0;                            // output-sequences.c:81: nothing printed
+    pl.total = pl.main_total = tot[0]; pl.surplus = 0; pl.sur_c = 0;
+    if (tot[1] < T && P.mode != EM_FASTQ) {
+        // more bases than the lengths account for.  FASTQ never prints them (output-fastq.c:100-149 stops after the N-th
+        // read); --sequences appends them raw (output-sequences.c:82-116); FASTA wraps them on from the last non-empty record's line
+        const u64 sur = T - tot[1];
+        u64 tail = sur;
+        if (P.mode == EM_FASTA) {
+            unsigned long long *d_last = arena_new<unsigned long long>(c, 2); if (!d_last) return NAF_GPU_ENOMEM;
+            HIP_TRY(c, hipMemsetAsync(d_last, 0, 16, c->stream));
+            LAUNCH(c, "unnaf_last_nonempty", k_last_nonempty, cdiv(N, 256), 256, 0, (const u64 *)S.rec_len, N, d_last);
+            u64 last1 = 0; if ((rc = ctx_readback(c, &last1, d_last, 8))) return rc;
+            if (last1 == 0) tail = 0;                                           // no record ever started a line of bases: nothing is printed
+            else {
+                u64 len_last = 0; if ((rc = ctx_readback(c, &len_last, S.rec_len + (last1 - 1), 8))) return rc;
+                const u64 L = P.L;
+                const u64 cc = L ? ((len_last % L) ? L - len_last % L : 0) : 0;
+                pl.sur_c = cc;
+                if (L && sur > cc) { const u64 R = sur - cc; tail = cc + 1 + R + (R - 1) / L; }
+            }
+        }
+        pl.surplus = tail ? sur : 0; pl.sur_base0 = tot[1];
+        pl.total = pl.main_total + tail;
+    }
+    return 0;
+}
+
+// Lengths, ids, names and the prefix tables built from them.  `aux`: a context of its own for ids + names (second host thread and
+// stream); nullptr = everything on c, in order.
+static int unnaf_sections_main(naf_gpu_ctx *c, SideCall &S, naf_gpu_ctx *aux, naf_gpu_ctx *aux_names)
+{
+    const naf_gpu_header &h = S.h; EmitP &P = S.P;
+    const int has_ids = (h.flags >> 5) & 1, has_names = (h.flags >> 4) & 1, has_len = (h.flags >> 3) & 1;
+    if (P.mode == EM_SEQ) { S.pl.total = S.pl.main_total = h.orig_size[S_SEQ]; return 0; }
+    if (!has_len) return ctx_fail(c, NAF_GPU_EFORMAT, "archive has no lengths");
+    S.want_names = P.mode == EM_FASTA || P.mode == EM_FASTQ;
+    P.has_ids = S.want_names ? has_ids : 0; P.has_names = S.want_names ? has_names : 0;
+    S.wanted[0] = P.has_ids != 0; S.wanted[1] = P.has_names != 0;
+    int rc; bool fused = false;
+    if ((rc = side_fused_tables(c, S, aux, &fused))) return rc;
+    if (!fused) {
+        if ((rc = side_long_way(c, S, aux, aux_names))) return rc;
+        if ((rc = record_tables(c, S))) return rc;
+    }
+    return side_totals_and_surplus(c, S);
+}
+
+// The side streams and the tables built from them.  Runs on whichever context it is given: the archive's own for byte-range calls
+// (aux = aux_mask = nullptr: sequential), the side context for whole-text calls, which also hands over contexts for ids + names
+// (`aux`, `aux_names`).  A handful of long Huffman streams, the mask's decode is pure latency: with `aux_mask` it runs on a context of
+// its own from the start of the call.  Errors keep the order of a sequential run: lengths, ids, names, then mask.
+static int unnaf_sections(naf_gpu_ctx *c, const u8 *d_naf, UnnafPlan &pl, naf_gpu_ctx *aux = nullptr, naf_gpu_ctx *aux_mask = nullptr, naf_gpu_ctx *aux_names = nullptr)
+{
+    SideCall S{ d_naf, pl, pl.h, pl.P };
+    const EmitP &P = pl.P;
+    const bool mask_beside = P.masking && aux_mask;
+    S.mask_meanwhile = P.masking && !mask_beside && P.mode != EM_SEQ && aux;
+    CtxJoinGuard mask_joined{ mask_beside ? aux_mask : nullptr };
+    if (mask_beside) ctx_worker_start(aux_mask, [&] { S.rc_mask = mask_toggles(aux_mask, S); });
+    int rc = unnaf_sections_main(c, S, aux, aux_names);
+    const hipError_t mask_synced = mask_beside ? ctx_side_join(aux_mask) : hipSuccess;
+    if (rc) return rc;
+    if (mask_beside) { if (S.rc_mask) { ctx_take_error(c, aux_mask); return S.rc_mask; } SIDE_SYNC_TRY(c, mask_synced, aux_mask); return 0; }
+    if (S.mask_ran) { if (S.rc_mask) ctx_take_error(c, S.mask_err); return S.rc_mask; }
+    return P.masking ? mask_toggles(c, S) : 0;
+}
+
 #include "payload.h"
+
+// ---- the text driver: naf_gpu_unnaf, naf_gpu_unnaf_size, naf_gpu_unnaf_range -----------------------------------------
+// What its phases share.
+struct UnnafCall {
+    naf_gpu_ctx *c; const u8 *d_naf;
+    UnnafPlan pl;
+    // decode -> emit pipeline of the sequence stream (ctx.h: ZSplit); a flat frame the tile kernels read in place (ctx.h: ZFlat)
+    ZSplit split; ZFlat zflat;
+    bool whole, size_only; u64 out_begin, out_end; u8 *d_out; size_t out_cap, *out_len;      // the caller's range and output
+    bool ranged = false; u64 s_lo = 0, s_hi = 0, q_lo = 0, q_hi = 0;   // a byte-range call: the bytes of the two streams it needs
+    u64 rec0 = 0, rec1 = 0;                                       // records the byte range touches
+    bool has_main = false, has_tail = false;                      // text of records; bases behind the last record
+    bool payload_done = false;
+    // the switches
+    bool fuse_on, flat_fuse, emit_wave; const char *emit; int split_parts;
+    bool try_flat = false;
+    UnnafCall() { split.parts = 0; split.done = 0; split.status = nullptr; memset(&zflat, 0, sizeof zflat); }
+    ~UnnafCall() { zstd_flat_drop(&zflat); }                      // (a job the decoder left and nobody ran: an error on the way)
+};
+
+static void unnaf_switches(UnnafCall &U)
+{
+    const naf_gpu_ctx *c = U.c;
+    U.fuse_on = ctx_opt_is(c, "FUSE", '1');
+    U.flat_fuse = !ctx_opt_is(c, "FLAT_FUSE", '0');               // "0": always decode first (cross-check)
+    U.emit = ctx_opt(c, "EMIT");
+    U.emit_wave = !ctx_opt_is(c, "EMIT_WAVE", '0');               // wavefront-sized workgroups ("0": the workgroups of 256 everywhere)
+    const char *nsp = ctx_opt(c, "SPLIT");
+    U.split_parts = nsp ? atoi(nsp) : 4;
+}
+
+// sequence (and quality) payload: the dominant zstd streams
+static int payload_seq(UnnafCall &U)
+{
+    PayloadSpan sp;
+    int r = payload_range(U.c, U.d_naf, U.pl, S_SEQ, U.s_lo, U.s_hi, U.ranged ? PAYLOAD_RANGE : PAYLOAD_WHOLE, &sp);
+    if (!r) U.pl.P.seq = sp.base;
+    return r;
+}
+// qc: the context the quality stream is decoded on (the archive's own, or the second side context beside the sequence stream)
+static int payload_qual(UnnafCall &U, naf_gpu_ctx *qc)
+{
+    PayloadSpan sp;
+    int r = payload_range(qc, U.d_naf, U.pl, S_QUAL, U.q_lo, U.q_hi, U.ranged ? PAYLOAD_RANGE : PAYLOAD_WHOLE, &sp);
+    if (!r) U.pl.P.qual = sp.base;
+    return r;
+}
+
+// Whole-text call: the side streams (a chain of small launches and read-backs, mostly latency) are prepared by a second host thread
+// on the side context's stream while this thread decodes the payload; they meet before the emit.
+static int unnaf_fork_sides(UnnafCall &U)
+{
+    naf_gpu_ctx *c = U.c; UnnafPlan &pl = U.pl; const u8 *d_naf = U.d_naf;
+    arena_reset(c->side);
+    HIP_TRY(c, hipEventRecord(c->fork_ev, c->stream));
+    HIP_TRY(c, hipStreamWaitEvent(c->side->stream, c->fork_ev, 0));
+    int rc_side = 0, rc_q = 0;
+    const bool qpar = pl.need_qual && c->side2;
+    if (qpar) { arena_reset(c->side2); HIP_TRY(c, hipStreamWaitEvent(c->side2->stream, c->fork_ev, 0)); }
+    if (c->side3) { arena_reset(c->side3); HIP_TRY(c, hipStreamWaitEvent(c->side3->stream, c->fork_ev, 0)); }
+    if (c->side4) { arena_reset(c->side4); HIP_TRY(c, hipStreamWaitEvent(c->side4->stream, c->fork_ev, 0)); }
+    // no early return between here and the joins
+    ctx_worker_start(c->side, [&] { rc_side = unnaf_sections(c->side, d_naf, pl, c->side3, nullptr, c->side4); });   // the mask stays on this context: a thread of its own measured slower, with and without the split decode
+    if (qpar) ctx_worker_start(c->side2, [&] { rc_q = payload_qual(U, c->side2); });
+    // decode -> emit pipeline (ZSplit): the quality context is free when there is no quality stream
+    const int nparts = U.split_parts;
+    if (!pl.need_qual && c->side2 && nparts >= 2 && nparts <= ZSPLIT_MAX && pl.P.mode != -1) {
+        U.split.parts = nparts; U.split.done = 0;
+        for (int k = 0; k < nparts; k++) U.split.ev[k] = c->split_ev[k];
+        c->zsplit = &U.split;
+        arena_reset(c->side2);                                // (what the pipeline and the flat frame's job allocate there -- launch_lz_exec's arrays among it -- is this call's: ADVICE r05)
+    }
+    if (U.try_flat) { U.zflat.ready = false; U.zflat.aux = c->zsplit ? c->side2 : nullptr; c->zflat = &U.zflat; }
+    int rc = payload_seq(U);
+    c->zsplit = nullptr; c->zflat = nullptr;
+    if (!rc && pl.need_qual && !qpar) rc = payload_qual(U, c);
+    ctx_worker_join(c->side);
+    if (qpar) ctx_worker_join(c->side2);
+    // the order a sequential run reports errors in: the side sections, the sequence, the quality
+    if (rc_side) { ctx_take_error(c, c->side); return rc_side; }
+    if (rc) return rc;
+    if (rc_q) { ctx_take_error(c, c->side2); return rc_q; }
+    HIP_TRY(c, hipStreamSynchronize(c->side->stream));
+    if (qpar) HIP_TRY(c, hipStreamSynchronize(c->side2->stream));
+    U.payload_done = true;
+    return 0;
+}
+
+// The caller's range against the text's size.  *done: a size call, or nothing to write.
+static int unnaf_output_range(UnnafCall &U, bool *done)
+{
+    const UnnafPlan &pl = U.pl;
+    *done = true;
+    if (U.whole) { U.out_begin = 0; U.out_end = pl.total; }
+    if (U.out_end > pl.total) U.out_end = pl.total;
+    if (U.out_begin > U.out_end) U.out_begin = U.out_end;
+    *U.out_len = U.out_end - U.out_begin;
+    if (U.size_only) { *U.out_len = pl.total; return 0; }
+    if (*U.out_len > U.out_cap) return ctx_fail(U.c, NAF_GPU_ECAP, "unnaf output needs %llu bytes, capacity %zu", (unsigned long long)*U.out_len, U.out_cap);
+    if (*U.out_len == 0) return 0;
+    // the records' text is [0, main_total); bases behind the last record (SURVEY R7) follow it and go through k_emit_surplus
+    const u64 m_begin = U.out_begin < pl.main_total ? U.out_begin : pl.main_total, m_end = U.out_end < pl.main_total ? U.out_end : pl.main_total;
+    U.has_main = m_end > m_begin; U.has_tail = U.out_end > pl.main_total;
+    U.pl.P.out_begin = m_begin; U.pl.P.out_end = m_end;
+    U.rec0 = 0; U.rec1 = pl.P.N ? pl.P.N - 1 : 0;
+    *done = false;
+    return 0;
+}
+
+// Byte-range call (multi-GPU shard): find the bases this range touches, so that only the zstd blocks behind them are decoded.
+static int unnaf_range_streams(UnnafCall &U)
+{
+    naf_gpu_ctx *c = U.c; UnnafPlan &pl = U.pl;
+    int rc;
+    u64 g[4] = { pl.sur_base0, pl.sur_base0, U.rec1, U.rec1 };
+    if (U.has_main) {
+        u64 *d_g = arena_new<u64>(c, 4); if (!d_g) return NAF_GPU_ENOMEM;
+        LAUNCH(c, "unnaf_range_bases", k_range_bases, 1, 64, 0, pl.P, d_g);
+        if ((rc = ctx_readback(c, g, d_g, 32))) return rc;
+    }
+    U.rec0 = g[2]; U.rec1 = g[3];
+    if (g[1] < g[0]) g[1] = g[0];
+    if (U.has_tail) g[1] = pl.P.T;
+    U.s_lo = pl.fourbit ? g[0] / 2 : g[0]; U.s_hi = pl.fourbit ? (g[1] + 1) / 2 : g[1];
+    U.q_lo = g[0]; U.q_hi = g[1];
+    U.ranged = true;
+    return 0;
+}
+
+// Whole FASTA text of a 4-bit archive: decode and emit in one kernel when the frame is literal-only.
+// (Measured slower than decode + emit on MI355X for now: its per-lane 16-byte text stores are partial-line
+// writes from 600 k streams; kept behind NAF_GPU_FUSE=1 and under test until the text is staged through LDS.)
+// *done: the text is written; else the frame needs the two-pass path.
+static int unnaf_try_fused(UnnafCall &U, bool *done)
+{
+    naf_gpu_ctx *c = U.c; UnnafPlan &pl = U.pl; const naf_gpu_header &h = pl.h;
+    *done = false;
+    if (!(U.whole && pl.P.mode == EM_FASTA && pl.fourbit && (pl.P.L == 0 || pl.P.L >= 16) && !pl.P.force_slow && U.fuse_on && !pl.surplus)) return 0;
+    size_t n2 = 0;
+    int rc = zstd_decode_fused_fasta(c, U.d_naf + h.payload_off[S_SEQ], h.comp_size[S_SEQ], 0, &n2, &pl.P, U.d_out);
+    if (rc == -100) return 0;
+    if (rc) return rc;
+    if (n2 != pl.seq_bytes) return ctx_fail(c, NAF_GPU_EFORMAT, "can't decompress sequence\n");
+    *done = true;
+    return 0;
+}
+
+// The sequential decode of a call whose payload the fork has not decoded already.
+static int unnaf_payload(UnnafCall &U)
+{
+    naf_gpu_ctx *c = U.c;
+    if (U.try_flat) { U.zflat.ready = false; c->zflat = &U.zflat; }
+    int rc = payload_seq(U);
+    if (!rc && U.pl.need_qual) rc = payload_qual(U, c);
+    c->zflat = nullptr;
+    return rc;
+}
+
+static void use_flat_frame(UnnafCall &U)
+{
+    EmitP &P = U.pl.P; const ZFlat &zflat = U.zflat;
+    if (zflat.ready) { P.fsrc = zflat.src; P.fsi = zflat.si; P.fslots = zflat.nslots; P.fsym = zflat.sym; P.ftail = zflat.tail; P.ftail_q = zflat.tail_q; P.ftail_n = zflat.tail_n; P.fcls = zflat.cls; }
+}
+
+// kern<true> for an archive of 4-bit codes, kern<false> for one of bytes, in workgroups of 256 or 64 without LDS of their own
+#define LAUNCH_4BIT(fourbit, x, name, kern, grid, block, ...) do { if (fourbit) LAUNCH(x, name, kern<true>, grid, block, 0, __VA_ARGS__); else LAUNCH(x, name, kern<false>, grid, block, 0, __VA_ARGS__); } while (0)
+
+// --4bit: the stream itself
+static int emit_4bit_copy(UnnafCall &U)
+{
+    naf_gpu_ctx *c = U.c;
+    HIP_TRY(c, hipMemcpyAsync(U.d_out, U.pl.P.seq + U.out_begin, U.out_end - U.out_begin, hipMemcpyDeviceToDevice, c->stream));
+    return 0;
+}
+
+// whole FASTQ text: a group of lanes per read
+static int emit_fastq_records(UnnafCall &U)
+{
+    naf_gpu_ctx *c = U.c; UnnafPlan &pl = U.pl; u8 *d_out = U.d_out;
+    const u64 avg = pl.P.N ? (pl.P.out_end - pl.P.out_begin) / pl.P.N + 1 : 1;        // bytes of text per read
+    const u32 lanes = avg * 64 <= ER_STAGE * 7 / 8 ? 4u : avg * 32 <= ER_STAGE * 7 / 8 ? 8u : 16u;
+    const bool w1 = U.emit_wave;
+    const u32 wgt = w1 ? 64u : 256u, grid = (u32)cdiv(pl.P.N, wgt / lanes);
+#define ER_LAUNCH(FB, LN) do { if (w1) LAUNCH(c, "unnaf_emit_records", (k_emit_fastq_records<FB, LN, 64>), grid, 64, 0, pl.P, d_out); \
+                               else LAUNCH(c, "unnaf_emit_records", (k_emit_fastq_records<FB, LN, 256>), grid, 256, 0, pl.P, d_out); } while (0)
+    if (pl.fourbit) { if (lanes == 4) ER_LAUNCH(true, 4); else if (lanes == 8) ER_LAUNCH(true, 8); else ER_LAUNCH(true, 16); }
+    else { if (lanes == 4) ER_LAUNCH(false, 4); else if (lanes == 8) ER_LAUNCH(false, 8); else ER_LAUNCH(false, 16); }
+#undef ER_LAUNCH
+    return 0;
+}
+
+// short records (FASTQ reads, contigs, proteins): segment-composing kernel, behind a table of the header lines of the records touched
+static int emit_short_records(UnnafCall &U)
+{
+    naf_gpu_ctx *c = U.c; UnnafPlan &pl = U.pl; u8 *d_out = U.d_out;
+    const u64 rec0 = U.rec0, rec1 = U.rec1;
+    int rc;
+    if (pl.P.mode == EM_FASTA || pl.P.mode == EM_FASTQ) {
+        u64 nr = rec1 - rec0 + 1, htot = 0;
+        u64 *ho = arena_new<u64>(c, nr + 2); if (!ho) return NAF_GPU_ENOMEM;
+        LAUNCH(c, "unnaf_hdr_len64", k_hdr_len64, cdiv(nr, 256), 256, 0, pl.P.hdr_len, rec0, nr, ho);
+        if ((rc = scan_exclusive_u64(c, ho, nr, ho + nr + 1))) return rc;
+        if ((rc = ctx_readback(c, &htot, ho + nr + 1, 8))) return rc;
+        u8 *ht = (u8 *)arena_alloc(c, htot + 32); if (!ht) return NAF_GPU_ENOMEM;
+        LAUNCH(c, "unnaf_hdr_build", k_hdr_build, cdiv(nr, 32), 256, 0, pl.P, rec0, nr, (const u64 *)ho, ht);
+        pl.P.hdr_off = ho; pl.P.hdr_text = ht; pl.P.hdr_r0 = rec0;
+    }
+    u32 grid = cdiv(pl.P.out_end - pl.P.out_begin, ES_SPAN);
+    LAUNCH_4BIT(pl.fourbit, c, "unnaf_emit_short", k_emit_short, grid, 256, pl.P, d_out);
+    return 0;
+}
+
+// previous long-record kernel (kept as a cross-check)
+static int emit_span(UnnafCall &U)
+{
+    naf_gpu_ctx *c = U.c; UnnafPlan &pl = U.pl; u8 *d_out = U.d_out;
+    u32 grid = cdiv(pl.P.out_end - pl.P.out_begin, EMIT_SPAN);
+    LAUNCH_4BIT(pl.fourbit, c, "unnaf_emit", k_emit, grid, 256, pl.P, d_out);
+    return 0;
+}
+
+// ---- long records: the streaming kernels over tiles of 4096 bytes of text ----
+// What the sub-steps of emit_tiles share.  ic: the context the tile index is built on; xc: where the tiles with headers / record ends,
+// and those over decoded blocks of a mostly-flat frame, are emitted; t_done: tiles emitted behind the parts of a split decode.
+struct TileCall { u64 ntiles; TileIdx *ti; u64 *tr; u32 *list, *list2, *cnt; TileFlat *tsig; naf_gpu_ctx *ic, *xc; u64 t_done; };
+
+// tiles [t0, t1) of a decoded stream: k_emit_tile_wave, or k_emit_tile in workgroups of 256
+static void launch_tiles(UnnafCall &U, const TileCall &T, naf_gpu_ctx *x, u64 t0, u64 t1)
+{
+    const UnnafPlan &pl = U.pl; u8 *d_out = U.d_out; const TileIdx *ti = T.ti;
+    if (U.emit_wave && pl.fourbit) LAUNCH(x, "unnaf_emit", (k_emit_tile_wave<true, 2>), cdiv(t1 - t0, 2u), 64, 0, pl.P, (const TileIdx *)(ti + t0), d_out + t0 * 4096, (u64)(t1 - t0));
+    else if (U.emit_wave) LAUNCH(x, "unnaf_emit", (k_emit_tile_wave<false, 2>), cdiv(t1 - t0, 2u), 64, 0, pl.P, (const TileIdx *)(ti + t0), d_out + t0 * 4096, (u64)(t1 - t0));
+    else LAUNCH_4BIT(pl.fourbit, x, "unnaf_emit", k_emit_tile, (u32)(t1 - t0), 256, pl.P, (const TileIdx *)(ti + t0), d_out + t0 * 4096);
+}
+
+// The tile index, on the second stream when a split decode (ZSplit) is under way: the index and the tiles behind the finished parts
+// run there beside the decode of the next part; the caller's stream takes the tiles behind the last part, the boundary tiles, and
+// waits for the other.
+static int tile_index(UnnafCall &U, TileCall &T)
+{
+    naf_gpu_ctx *c = U.c; UnnafPlan &pl = U.pl; const ZFlat &zflat = U.zflat;
+    const u64 ntiles = T.ntiles = cdiv(pl.P.out_end - pl.P.out_begin, 4096);
+    TileIdx *ti = T.ti = arena_new<TileIdx>(c, ntiles + 2 + FLAT_TPW); u64 *tr = T.tr = arena_new<u64>(c, ntiles + 2);
+    u32 *list = T.list = arena_new<u32>(c, ntiles + 1), *cnt = T.cnt = arena_new<u32>(c, 2);
+    u32 *list2 = T.list2 = (zflat.ready && zflat.cls) ? arena_new<u32>(c, ntiles + 1) : list;      // tiles over decoded blocks of a mostly-flat frame
+    if (!ti || !tr || !list || !cnt || !list2) return NAF_GPU_ENOMEM;
+    // exact c / (L+1) for c < L + 1 + 4096 as mulhi(c, M), M = floor(2^32 / (L+1)) + 1, valid while c * (L+1) < 2^32
+    u64 Lp1 = pl.P.L + 1;
+    pl.P.Ldiv_magic = (Lp1 >= 2 && Lp1 < 32768) ? (u32)((1ull << 32) / Lp1 + 1) : 0;
+    naf_gpu_ctx *ic = T.ic = U.split.done ? c->side2 : c;
+    HIP_TRY(c, hipMemsetAsync(cnt, 0, 8, ic->stream));
+    TileFlat *tsig = T.tsig = nullptr;
+    if (zflat.ready) {
+        tsig = T.tsig = arena_new<TileFlat>(c, ntiles + 2 + FLAT_TPW); u32 *fpair = arena_new<u32>(c, 400); if (!tsig || !fpair) return NAF_GPU_ENOMEM;
+        LAUNCH(ic, "unnaf_flat_pair", k_flat_pair, 1, 256, 0, pl.P, fpair);
+        pl.P.fpair = fpair;
+    }
+    LAUNCH(ic, "unnaf_tile_index", k_tile_index, cdiv(ntiles + 1 + FLAT_TPW, TILE_WG), 256, 0, pl.P, ntiles, ti, tr, list, cnt, tsig, (u32)FLAT_TPW, list2);
+    // the spare stream of a flat frame starts behind the tile index: it takes the job (if any) and the tiles with headers / record ends, beside the bulk emit
+    T.xc = c; T.t_done = 0;
+    if (zflat.ready && zflat.aux) {
+        HIP_TRY(c, hipEventRecord(c->split_ev[0], c->stream));
+        if (!zflat.later) { HIP_TRY(c, hipStreamWaitEvent(zflat.aux->stream, c->split_ev[0], 0)); T.xc = zflat.aux; }
+    }
+    return 0;
+}
+
+static int tiles_behind_split_parts(UnnafCall &U, TileCall &T)
+{
+    naf_gpu_ctx *c = U.c, *ic = T.ic; const UnnafPlan &pl = U.pl; const ZSplit &split = U.split;
+    HIP_TRY(c, hipEventRecord(c->split_ev[ZSPLIT_MAX], ic->stream));
+    for (int k = 0; k + 1 < split.parts; k++) {
+        // a tile's bases all lie below its last text position, and a lane reads at most 32 packed bytes past its own
+        u64 bases_ready = split.out_end[k] * (pl.fourbit ? 2u : 1u);
+        u64 t_hi = bases_ready / 4096; t_hi = t_hi > 1 ? t_hi - 1 : 0;
+        if (t_hi > T.ntiles) t_hi = T.ntiles;
+        if (t_hi <= T.t_done) continue;
+        HIP_TRY(c, hipStreamWaitEvent(ic->stream, split.ev[k], 0));
+        launch_tiles(U, T, ic, T.t_done, t_hi);
+        T.t_done = t_hi;
+    }
+    HIP_TRY(c, hipEventRecord(c->split_ev[ZSPLIT_MAX + 1], ic->stream));
+    HIP_TRY(c, hipStreamWaitEvent(c->stream, c->split_ev[ZSPLIT_MAX], 0));         // the index
+    return 0;
+}
+
+// A flat frame, read in place: the flat emit in one of three shapes; the decode of a mostly-flat frame's other blocks, a job left for
+// now -- on the spare stream, beside the emit of the flat tiles; the tiles over those blocks, from their list.
+static int flat_tiles(UnnafCall &U, TileCall &T)
+{
+    naf_gpu_ctx *c = U.c; UnnafPlan &pl = U.pl; ZFlat &zflat = U.zflat; u8 *d_out = U.d_out;
+    const u64 ntiles = T.ntiles; const TileIdx *ti = T.ti; const TileFlat *tsig = T.tsig;
+    int rc;
+    const bool flat_job = zflat.later != nullptr;
+    // four tiles per workgroup (eight measured slower: DESIGN.md section 8), workgroups dealt to the XCDs in contiguous chunks
+    const u32 nwg = cdiv(ntiles, 4u), chunk = (nwg + 7) / 8;
+    // A wavefront per two tiles (per tile when there are many mask toggles to stage), in workgroups of 64 -- 3.17 -> 2.24 ms per
+    // 10 GB against four tiles per workgroup of 256 (k_emit_tile_flat_wave).  A mostly-flat frame whose decode job walks Huffman
+    // streams keeps the workgroups of 256: that walk is bound by latency, and beside the wavefront-per-tile emit it takes
+    // 1.9 instead of 1.1 ms (a realistic genome, 4 GB: 3.16 -> 3.41 ms); a job of flat literals and matches only (the reference's
+    // archive of random bases) is better off with it (4 GB: 2.45 -> 2.31 ms), its kernels in workgroups of 64 as well -- a
+    // workgroup of 256 waits for four wave slots of one CU to be free at once.  NAF_GPU_EMIT_WAVE=0: workgroups of 256 everywhere.
+    const bool mixed = flat_job || (zflat.cls && zflat.n_decoded);
+    const bool wave = U.emit_wave && (!mixed || zflat.n_walk == 0);
+    // (many: about a toggle per tile or more -- a soft-masked genome, not the odd lower-case stretch)
+    if (wave && pl.P.masking && pl.P.n_toggles >= ntiles) { const u32 ch = ((u32)ntiles + 7) / 8; LAUNCH(c, "unnaf_emit_flat", k_emit_tile_flat_wave<1>, ch * 8, 64, 0, pl.P, (const TileIdx *)ti, (const TileFlat *)tsig, d_out, (u64)ntiles, ch); }
+    else if (wave) { const u32 ch = (cdiv(ntiles, 2u) + 7) / 8; LAUNCH(c, "unnaf_emit_flat", k_emit_tile_flat_wave<2>, ch * 8, 64, 0, pl.P, (const TileIdx *)ti, (const TileFlat *)tsig, d_out, (u64)ntiles, ch); }
+    else LAUNCH(c, "unnaf_emit_flat", k_emit_tile_flat<4>, chunk * 8, 256, 0, pl.P, (const TileIdx *)ti, (const TileFlat *)tsig, d_out, (u64)ntiles, chunk);
+    if (flat_job) {                                                               // (queued behind the flat emit: the job waits for its tables on the host)
+        if ((rc = zstd_flat_later(c, &zflat))) return rc;
+        if (zflat.aux) T.xc = zflat.aux;
+    }
+    if (zflat.cls && zflat.n_decoded) {
+        // a tile costs this kernel about what it costs k_emit_tile: as many workgroups as there can be tiles over decoded blocks, up to a few waves of the device
+        const u64 est = (u64)zflat.n_decoded * 64 + 64;                           // (blocks of up to 128 KiB: 64 tiles each)
+        const u32 lgrid = (u32)(est < ntiles ? (est < 16384 ? est : 16384) : (ntiles < 16384 ? ntiles : 16384));
+        naf_gpu_ctx *xc = T.xc; const u32 *list2 = T.list2, *cnt = T.cnt;
+        if (wave) LAUNCH(xc, "unnaf_emit", k_emit_tile_list_wave<true>, lgrid, 64, 0, pl.P, (const TileIdx *)ti, (const u32 *)list2, (const u32 *)(cnt + 1), d_out);
+        else LAUNCH(xc, "unnaf_emit", k_emit_tile_list<true>, lgrid, 256, 0, pl.P, (const TileIdx *)ti, (const u32 *)list2, (const u32 *)(cnt + 1), d_out);
+    }
+    return 0;
+}
+
+// tiles holding a header or a record boundary (their number stays on the device)
+static void rest_tiles(UnnafCall &U, const TileCall &T)
+{
+    const UnnafPlan &pl = U.pl; u8 *d_out = U.d_out; naf_gpu_ctx *xc = T.xc;
+    const u64 ntiles = T.ntiles; const TileIdx *ti = T.ti; const u64 *tr = T.tr; const u32 *list = T.list, *cnt = T.cnt;
+    const u32 rest_grid = 4u * (u32)(ntiles < EMIT_REST_GRID ? ntiles : EMIT_REST_GRID);      // (quarter tiles: k_emit_rest)
+    LAUNCH_4BIT(pl.fourbit, xc, "unnaf_emit_rest", k_emit_rest, rest_grid, 64, pl.P, (const TileIdx *)ti, (const u64 *)tr, (const u32 *)list, (const u32 *)cnt, d_out);
+}
+
+static int emit_tiles(UnnafCall &U)
+{
+    naf_gpu_ctx *c = U.c; TileCall T;
+    int rc = tile_index(U, T); if (rc) return rc;
+    if (U.split.done && (rc = tiles_behind_split_parts(U, T))) return rc;
+    if (U.zflat.ready) { if ((rc = flat_tiles(U, T))) return rc; }
+    else if (T.t_done < T.ntiles) launch_tiles(U, T, c, T.t_done, T.ntiles);
+    rest_tiles(U, T);
+    if (T.xc != c) { HIP_TRY(c, hipEventRecord(c->split_ev[1], T.xc->stream)); HIP_TRY(c, hipStreamWaitEvent(c->stream, c->split_ev[1], 0)); }
+    if (U.split.done) HIP_TRY(c, hipStreamWaitEvent(c->stream, c->split_ev[ZSPLIT_MAX + 1], 0));
+    if (U.zflat.ready && ctx_tracing(c)) {          // tests: how the tiles were dealt
+        u32 hc[2] = { 0, 0 };
+        if (!ctx_readback(c, hc, T.cnt, 8)) ctx_trace(c, "[flat tiles] total %llu rest %u decoded %u\n", (unsigned long long)T.ntiles, hc[0], hc[1]);
+    }
+    return 0;
+}
+
+// the text of records: which kernels write it
+static int emit_records(UnnafCall &U)
+{
+    const UnnafPlan &pl = U.pl;
+    const char *ek = U.emit;
+    bool short_rec = pl.P.mode != EM_SEQ && pl.total / pl.P.N < 16384;
+    if (ek && !strcmp(ek, "short")) short_rec = pl.P.mode != EM_SEQ;
+    if (ek && !strcmp(ek, "long")) short_rec = false;
+    if (pl.P.force_slow) { short_rec = false; ek = "span"; }
+    if (U.whole && pl.P.mode == EM_FASTQ && !pl.P.force_slow && !(ek && ek[0])) return emit_fastq_records(U);
+    if (short_rec) return emit_short_records(U);
+    if (ek && !strcmp(ek, "span")) return emit_span(U);
+    return emit_tiles(U);
+}
+
+// bases behind the last record
+static void emit_surplus(UnnafCall &U)
+{
+    naf_gpu_ctx *c = U.c; const UnnafPlan &pl = U.pl;
+    const u64 lo = (U.out_begin > pl.main_total ? U.out_begin : pl.main_total) - pl.main_total, hi = U.out_end - pl.main_total;
+    u8 *dst = U.d_out + (pl.main_total + lo - U.out_begin);
+    const int wrap = pl.P.mode == EM_FASTA;
+    LAUNCH_4BIT(pl.fourbit, c, "unnaf_emit_surplus", k_emit_surplus, cdiv(hi - lo, 256), 256, pl.P, pl.sur_base0, pl.surplus, pl.sur_c, pl.P.L, wrap, lo, hi, dst);
+}
+#undef LAUNCH_4BIT
+
+// What the decoder left to be read after the emit was queued (no host wait between decode and emit): a split decode's status, a flat frame's.
+static int unnaf_final_status(UnnafCall &U)
+{
+    naf_gpu_ctx *c = U.c;
+    int rc;
+    HIP_TRY(c, hipGetLastError());
+    if ((rc = zstd_split_status(c, &U.split))) return rc;
+    if (U.zflat.ready) { ZSplit fs; fs.parts = 0; fs.done = 1; fs.status = U.zflat.status; if ((rc = zstd_split_status(c, &fs))) return rc; }
+    return 0;
+}
 
 static int unnaf_run(naf_gpu_ctx *c, const u8 *d_naf, size_t naf_len, const naf_gpu_unnaf_opts *o,
                      u64 out_begin, u64 out_end, bool whole, u8 *d_out, size_t out_cap, size_t *out_len, bool size_only)
@@ -1919,269 +2369,32 @@ static int unnaf_run(naf_gpu_ctx *c, const u8 *d_naf, size_t naf_len, const naf_
     if (!c || !d_naf || !o || !out_len) return NAF_GPU_EARG;
     arena_reset(c);
     if (whole && !size_only) { int rs = ctx_sides_ready(c); if (rs) return rs; }        // (a range or a size call stays on this context)
-    UnnafPlan pl;
+    UnnafCall U;
+    U.c = c; U.d_naf = d_naf; U.whole = whole; U.size_only = size_only;
+    U.out_begin = out_begin; U.out_end = out_end; U.d_out = d_out; U.out_cap = out_cap; U.out_len = out_len;
+    unnaf_switches(U);
+    UnnafPlan &pl = U.pl;
     int rc = unnaf_prepare(c, d_naf, naf_len, o, pl); if (rc) return rc;
     if (pl.empty) { *out_len = 0; return 0; }
-    const naf_gpu_header &h = pl.h;
-    bool ranged = false; u64 s_lo = 0, s_hi = 0, q_lo = 0, q_hi = 0;               // a byte-range call: the bytes of the two streams it needs
-    // sequence (and quality) payload: the dominant zstd streams
-    auto payload_seq = [&]() -> int {
-        PayloadSpan sp;
-        int r = payload_range(c, d_naf, pl, S_SEQ, s_lo, s_hi, ranged ? PAYLOAD_RANGE : PAYLOAD_WHOLE, &sp);
-        if (!r) pl.P.seq = sp.base;
-        return r;
-    };
-    // qc: the context the quality stream is decoded on (the archive's own, or the second side context beside the sequence stream)
-    auto payload_qual = [&](naf_gpu_ctx *qc) -> int {
-        PayloadSpan sp;
-        int r = payload_range(qc, d_naf, pl, S_QUAL, q_lo, q_hi, ranged ? PAYLOAD_RANGE : PAYLOAD_WHOLE, &sp);
-        if (!r) pl.P.qual = sp.base;
-        return r;
-    };
-    auto payload = [&]() -> int { int r = payload_seq(); if (r) return r; return pl.need_qual ? payload_qual(c) : 0; };
-    const char *fuse = ctx_opt(c, "FUSE");
-    const bool fuse_on = fuse && fuse[0] == '1';
-    // Whole-text call: the side streams (a chain of small launches and read-backs, mostly latency) are prepared by a second
-    // host thread on the side context's stream while this thread decodes the payload; they meet before the emit.
-    const bool par = whole && !size_only && pl.P.mode != -1 && c->side && !fuse_on;
-    bool payload_done = false;
-    ZSplit split; split.parts = 0; split.done = 0; split.status = nullptr;
     // A whole 4-bit text with long records goes through the tile kernels: if its sequence stream turns out to be a flat frame
-    // (ctx.h: ZFlat) those read it in place and nothing is decoded.  NAF_GPU_FLAT_FUSE=0: always decode first (cross-check).
-    ZFlat zflat; memset(&zflat, 0, sizeof zflat);
-    struct FlatGuard { ZFlat *z; ~FlatGuard() { zstd_flat_drop(z); } } flat_guard{ &zflat };      // (a job the decoder left and nobody ran: an error on the way)
-    const char *ff = ctx_opt(c, "FLAT_FUSE"), *ek0 = ctx_opt(c, "EMIT");
-    const bool try_flat = !size_only && pl.fourbit && !fuse_on && !pl.P.force_slow && !(ff && ff[0] == '0') && !(ek0 && ek0[0]) &&
-                          (pl.P.mode == EM_FASTA || pl.P.mode == EM_SEQ || pl.P.mode == EM_SEQUENCES) && pl.P.N && h.orig_size[S_SEQ] / pl.P.N >= 16384 &&
-                          (pl.P.mode != EM_FASTA || pl.P.L == 0 || pl.P.L >= 16);
-    if (par) {
-        arena_reset(c->side);
-        HIP_TRY(c, hipEventRecord(c->fork_ev, c->stream));
-        HIP_TRY(c, hipStreamWaitEvent(c->side->stream, c->fork_ev, 0));
-        int rc_side = 0, rc_q = 0;
-        const bool qpar = pl.need_qual && c->side2;
-        if (qpar) { arena_reset(c->side2); HIP_TRY(c, hipStreamWaitEvent(c->side2->stream, c->fork_ev, 0)); }
-        if (c->side3) { arena_reset(c->side3); HIP_TRY(c, hipStreamWaitEvent(c->side3->stream, c->fork_ev, 0)); }
-        if (c->side4) { arena_reset(c->side4); HIP_TRY(c, hipStreamWaitEvent(c->side4->stream, c->fork_ev, 0)); }
-        // no early return between here and the joins
-        ctx_worker_start(c->side, [&] { rc_side = unnaf_sections(c->side, d_naf, pl, c->side3, nullptr, c->side4); });   // the mask stays on this context: a thread of its own measured slower, with and without the split decode
-        if (qpar) ctx_worker_start(c->side2, [&] { rc_q = payload_qual(c->side2); });
-        // decode -> emit pipeline (ZSplit): the quality context is free when there is no quality stream
-        const char *nsp = ctx_opt(c, "SPLIT");
-        const int nparts = nsp ? atoi(nsp) : 4;
-        if (!pl.need_qual && c->side2 && nparts >= 2 && nparts <= ZSPLIT_MAX && pl.P.mode != -1) {
-            split.parts = nparts; split.done = 0;
-            for (int k = 0; k < nparts; k++) split.ev[k] = c->split_ev[k];
-            c->zsplit = &split;
-            arena_reset(c->side2);                                // (what the pipeline and the flat frame's job allocate there -- launch_lz_exec's arrays among it -- is this call's: ADVICE r05)
-        }
-        if (try_flat) { zflat.ready = false; zflat.aux = c->zsplit ? c->side2 : nullptr; c->zflat = &zflat; }
-        rc = payload_seq();
-        c->zsplit = nullptr; c->zflat = nullptr;
-        if (!rc && pl.need_qual && !qpar) rc = payload_qual(c);
-        ctx_worker_join(c->side);
-        if (qpar) ctx_worker_join(c->side2);
-        if (rc_side) { memcpy(c->err, c->side->err, sizeof c->err); return rc_side; }   // the order a sequential run reports errors in
-        if (rc) return rc;
-        if (rc_q) { memcpy(c->err, c->side2->err, sizeof c->err); return rc_q; }
-        HIP_TRY(c, hipStreamSynchronize(c->side->stream));
-        if (qpar) HIP_TRY(c, hipStreamSynchronize(c->side2->stream));
-        payload_done = true;
-    } else if (pl.P.mode != -1) {
-        if ((rc = unnaf_sections(c, d_naf, pl))) return rc;
-    }
-    if (whole) { out_begin = 0; out_end = pl.total; }
-    if (out_end > pl.total) out_end = pl.total;
-    if (out_begin > out_end) out_begin = out_end;
-    *out_len = out_end - out_begin;
-    if (size_only) { *out_len = pl.total; return 0; }
-    if (*out_len > out_cap) return ctx_fail(c, NAF_GPU_ECAP, "unnaf output needs %llu bytes, capacity %zu", (unsigned long long)*out_len, out_cap);
-    if (*out_len == 0) return 0;
-    // the records' text is [0, main_total); bases behind the last record (SURVEY R7) follow it and go through k_emit_surplus
-    const u64 m_begin = out_begin < pl.main_total ? out_begin : pl.main_total, m_end = out_end < pl.main_total ? out_end : pl.main_total;
-    const bool has_main = m_end > m_begin, has_tail = out_end > pl.main_total;
-    pl.P.out_begin = m_begin; pl.P.out_end = m_end;
-    // Byte-range call (multi-GPU shard): find the bases this range touches and decode only the zstd blocks behind them.
-    u64 rec0 = 0, rec1 = pl.P.N ? pl.P.N - 1 : 0;                                        // records the byte range touches
-    if (!whole && pl.P.mode != -1) {
-        u64 g[4] = { pl.sur_base0, pl.sur_base0, rec1, rec1 };
-        if (has_main) {
-            u64 *d_g = arena_new<u64>(c, 4); if (!d_g) return NAF_GPU_ENOMEM;
-            LAUNCH(c, "unnaf_range_bases", k_range_bases, 1, 64, 0, pl.P, d_g);
-            if ((rc = ctx_readback(c, g, d_g, 32))) return rc;
-        }
-        rec0 = g[2]; rec1 = g[3];
-        if (g[1] < g[0]) g[1] = g[0];
-        if (has_tail) g[1] = pl.P.T;
-        s_lo = pl.fourbit ? g[0] / 2 : g[0]; s_hi = pl.fourbit ? (g[1] + 1) / 2 : g[1];
-        q_lo = g[0]; q_hi = g[1];
-        ranged = true;
-    }
-    // Whole FASTA text of a 4-bit archive: decode and emit in one kernel when the frame is literal-only.
-    // (Measured slower than decode + emit on MI355X for now: its per-lane 16-byte text stores are partial-line
-    // writes from 600 k streams; kept behind NAF_GPU_FUSE=1 and under test until the text is staged through LDS.)
-    if (whole && pl.P.mode == EM_FASTA && pl.fourbit && (pl.P.L == 0 || pl.P.L >= 16) && !pl.P.force_slow && fuse_on && !pl.surplus) {
-        size_t n2 = 0;
-        rc = zstd_decode_fused_fasta(c, d_naf + h.payload_off[S_SEQ], h.comp_size[S_SEQ], 0, &n2, &pl.P, d_out);
-        if (rc == 0) {
-            if (n2 != pl.seq_bytes) return ctx_fail(c, NAF_GPU_EFORMAT, "can't decompress sequence\n");
-            return 0;
-        }
-        if (rc != -100) return rc;
-    }
-    if (!payload_done) {
-        if (try_flat) { zflat.ready = false; c->zflat = &zflat; }
-        rc = payload();
-        c->zflat = nullptr;
-        if (rc) return rc;
-    }
-    if (zflat.ready) { pl.P.fsrc = zflat.src; pl.P.fsi = zflat.si; pl.P.fslots = zflat.nslots; pl.P.fsym = zflat.sym; pl.P.ftail = zflat.tail; pl.P.ftail_q = zflat.tail_q; pl.P.ftail_n = zflat.tail_n; pl.P.fcls = zflat.cls; }
-    if (pl.P.mode == -1) {                                                             // --4bit: the stream itself
-        HIP_TRY(c, hipMemcpyAsync(d_out, pl.P.seq + out_begin, out_end - out_begin, hipMemcpyDeviceToDevice, c->stream));
-        return 0;
-    }
-    if (has_main) {
-        // short records (FASTQ reads, contigs, proteins): segment-composing kernel; long records: streaming kernel
-        const char *ek = ctx_opt(c, "EMIT");
-        bool short_rec = pl.P.mode != EM_SEQ && pl.total / pl.P.N < 16384;
-        if (ek && !strcmp(ek, "short")) short_rec = pl.P.mode != EM_SEQ;
-        if (ek && !strcmp(ek, "long")) short_rec = false;
-        if (pl.P.force_slow) { short_rec = false; ek = "span"; }
-        const bool emit_wave = !ctx_opt_is(c, "EMIT_WAVE", '0');      // wavefront-sized workgroups ("0": the workgroups of 256 everywhere)
-        if (whole && pl.P.mode == EM_FASTQ && !pl.P.force_slow && !(ek && ek[0])) {
-            {
-                const u64 avg = pl.P.N ? (pl.P.out_end - pl.P.out_begin) / pl.P.N + 1 : 1;        // bytes of text per read
-                const u32 lanes = avg * 64 <= ER_STAGE * 7 / 8 ? 4u : avg * 32 <= ER_STAGE * 7 / 8 ? 8u : 16u;
-                const bool w1 = emit_wave;
-                const u32 wgt = w1 ? 64u : 256u, grid = (u32)cdiv(pl.P.N, wgt / lanes);
-#define ER_LAUNCH(FB, LN) do { if (w1) LAUNCH(c, "unnaf_emit_records", (k_emit_fastq_records<FB, LN, 64>), grid, 64, 0, pl.P, d_out); \
-                               else LAUNCH(c, "unnaf_emit_records", (k_emit_fastq_records<FB, LN, 256>), grid, 256, 0, pl.P, d_out); } while (0)
-                if (pl.fourbit) { if (lanes == 4) ER_LAUNCH(true, 4); else if (lanes == 8) ER_LAUNCH(true, 8); else ER_LAUNCH(true, 16); }
-                else { if (lanes == 4) ER_LAUNCH(false, 4); else if (lanes == 8) ER_LAUNCH(false, 8); else ER_LAUNCH(false, 16); }
-#undef ER_LAUNCH
-            }
-        } else if (short_rec) {
-            if (pl.P.mode == EM_FASTA || pl.P.mode == EM_FASTQ) {
-                u64 nr = rec1 - rec0 + 1, htot = 0;
-                u64 *ho = arena_new<u64>(c, nr + 2); if (!ho) return NAF_GPU_ENOMEM;
-                LAUNCH(c, "unnaf_hdr_len64", k_hdr_len64, cdiv(nr, 256), 256, 0, pl.P.hdr_len, rec0, nr, ho);
-                if ((rc = scan_exclusive_u64(c, ho, nr, ho + nr + 1))) return rc;
-                if ((rc = ctx_readback(c, &htot, ho + nr + 1, 8))) return rc;
-                u8 *ht = (u8 *)arena_alloc(c, htot + 32); if (!ht) return NAF_GPU_ENOMEM;
-                LAUNCH(c, "unnaf_hdr_build", k_hdr_build, cdiv(nr, 32), 256, 0, pl.P, rec0, nr, (const u64 *)ho, ht);
-                pl.P.hdr_off = ho; pl.P.hdr_text = ht; pl.P.hdr_r0 = rec0;
-            }
-            u32 grid = cdiv(m_end - m_begin, ES_SPAN);
-            if (pl.fourbit) LAUNCH(c, "unnaf_emit_short", k_emit_short<true>, grid, 256, 0, pl.P, d_out);
-            else LAUNCH(c, "unnaf_emit_short", k_emit_short<false>, grid, 256, 0, pl.P, d_out);
-        } else if (ek && !strcmp(ek, "span")) {                                              // previous long-record kernel (kept as a cross-check)
-            u32 grid = cdiv(m_end - m_begin, EMIT_SPAN);
-            if (pl.fourbit) LAUNCH(c, "unnaf_emit", k_emit<true>, grid, 256, 0, pl.P, d_out);
-            else LAUNCH(c, "unnaf_emit", k_emit<false>, grid, 256, 0, pl.P, d_out);
-        } else {
-            u64 ntiles = cdiv(m_end - m_begin, 4096);
-            TileIdx *ti = arena_new<TileIdx>(c, ntiles + 2 + FLAT_TPW); u64 *tr = arena_new<u64>(c, ntiles + 2);
-            u32 *list = arena_new<u32>(c, ntiles + 1), *cnt = arena_new<u32>(c, 2);
-            u32 *list2 = (zflat.ready && zflat.cls) ? arena_new<u32>(c, ntiles + 1) : list;      // tiles over decoded blocks of a mostly-flat frame
-            if (!ti || !tr || !list || !cnt || !list2) return NAF_GPU_ENOMEM;
-            if (!split.done) HIP_TRY(c, hipMemsetAsync(cnt, 0, 8, c->stream));
-            // exact c / (L+1) for c < L + 1 + 4096 as mulhi(c, M), M = floor(2^32 / (L+1)) + 1, valid while c * (L+1) < 2^32
-            u64 Lp1 = pl.P.L + 1;
-            pl.P.Ldiv_magic = (Lp1 >= 2 && Lp1 < 32768) ? (u32)((1ull << 32) / Lp1 + 1) : 0;
-            // With a split decode (ZSplit) the index and the tiles behind the finished parts run on the second stream beside the
-            // decode of the next part; this stream takes the tiles behind the last part, the boundary tiles, and waits for the other.
-            naf_gpu_ctx *ic = split.done ? c->side2 : c;                                     // context the tile index is built on
-            // tiles [t0, t1) of a decoded stream: k_emit_tile_wave, or k_emit_tile in workgroups of 256
-            auto emit_tiles = [&](naf_gpu_ctx *x, u64 t0, u64 t1) {
-                if (emit_wave && pl.fourbit) LAUNCH(x, "unnaf_emit", (k_emit_tile_wave<true, 2>), cdiv(t1 - t0, 2u), 64, 0, pl.P, (const TileIdx *)(ti + t0), d_out + t0 * 4096, (u64)(t1 - t0));
-                else if (emit_wave) LAUNCH(x, "unnaf_emit", (k_emit_tile_wave<false, 2>), cdiv(t1 - t0, 2u), 64, 0, pl.P, (const TileIdx *)(ti + t0), d_out + t0 * 4096, (u64)(t1 - t0));
-                else if (pl.fourbit) LAUNCH(x, "unnaf_emit", k_emit_tile<true>, (u32)(t1 - t0), 256, 0, pl.P, (const TileIdx *)(ti + t0), d_out + t0 * 4096);
-                else LAUNCH(x, "unnaf_emit", k_emit_tile<false>, (u32)(t1 - t0), 256, 0, pl.P, (const TileIdx *)(ti + t0), d_out + t0 * 4096);
-            };
-            if (split.done) HIP_TRY(c, hipMemsetAsync(cnt, 0, 8, ic->stream));
-            TileFlat *tsig = nullptr;
-            if (zflat.ready) {
-                tsig = arena_new<TileFlat>(c, ntiles + 2 + FLAT_TPW); u32 *fpair = arena_new<u32>(c, 400); if (!tsig || !fpair) return NAF_GPU_ENOMEM;
-                LAUNCH(ic, "unnaf_flat_pair", k_flat_pair, 1, 256, 0, pl.P, fpair);
-                pl.P.fpair = fpair;
-            }
-            LAUNCH(ic, "unnaf_tile_index", k_tile_index, cdiv(ntiles + 1 + FLAT_TPW, TILE_WG), 256, 0, pl.P, ntiles, ti, tr, list, cnt, tsig, (u32)FLAT_TPW, list2);
-            // a mostly-flat frame: the blocks that are not flat are decoded now -- on the spare stream, beside the emit of the flat tiles
-            naf_gpu_ctx *xc = c;                                                              // where the tiles over decoded blocks are emitted
-            const bool flat_job = zflat.ready && zflat.later;
-            // the spare stream starts behind the tile index: it takes the job (if any) and the tiles with headers / record ends, beside the bulk emit
-            if (zflat.ready && zflat.aux) {
-                HIP_TRY(c, hipEventRecord(c->split_ev[0], c->stream));
-                if (!flat_job) { HIP_TRY(c, hipStreamWaitEvent(zflat.aux->stream, c->split_ev[0], 0)); xc = zflat.aux; }
-            }
-            u64 t_done = 0;
-            if (split.done) {
-                HIP_TRY(c, hipEventRecord(c->split_ev[ZSPLIT_MAX], ic->stream));
-                for (int k = 0; k + 1 < split.parts; k++) {
-                    // a tile's bases all lie below its last text position, and a lane reads at most 32 packed bytes past its own
-                    u64 bases_ready = split.out_end[k] * (pl.fourbit ? 2u : 1u);
-                    u64 t_hi = bases_ready / 4096; t_hi = t_hi > 1 ? t_hi - 1 : 0;
-                    if (t_hi > ntiles) t_hi = ntiles;
-                    if (t_hi <= t_done) continue;
-                    HIP_TRY(c, hipStreamWaitEvent(ic->stream, split.ev[k], 0));
-                    emit_tiles(ic, t_done, t_hi);
-                    t_done = t_hi;
-                }
-                HIP_TRY(c, hipEventRecord(c->split_ev[ZSPLIT_MAX + 1], ic->stream));
-                HIP_TRY(c, hipStreamWaitEvent(c->stream, c->split_ev[ZSPLIT_MAX], 0));         // the index
-            }
-            if (zflat.ready) {
-                // four tiles per workgroup (eight measured slower: DESIGN.md section 8), workgroups dealt to the XCDs in contiguous chunks
-                const u32 nwg = cdiv(ntiles, 4u), chunk = (nwg + 7) / 8;
-                // A wavefront per two tiles (per tile when there are many mask toggles to stage), in workgroups of 64 -- 3.17 -> 2.24 ms per
-                // 10 GB against four tiles per workgroup of 256 (k_emit_tile_flat_wave).  A mostly-flat frame whose decode job walks Huffman
-                // streams keeps the workgroups of 256: that walk is bound by latency, and beside the wavefront-per-tile emit it takes
-                // 1.9 instead of 1.1 ms (a realistic genome, 4 GB: 3.16 -> 3.41 ms); a job of flat literals and matches only (the reference's
-                // archive of random bases) is better off with it (4 GB: 2.45 -> 2.31 ms), its kernels in workgroups of 64 as well -- a
-                // workgroup of 256 waits for four wave slots of one CU to be free at once.  NAF_GPU_EMIT_WAVE=0: workgroups of 256 everywhere.
-                const bool mixed = flat_job || (zflat.cls && zflat.n_decoded);
-                const bool wave = emit_wave && (!mixed || zflat.n_walk == 0);
-                // (many: about a toggle per tile or more -- a soft-masked genome, not the odd lower-case stretch)
-                if (wave && pl.P.masking && pl.P.n_toggles >= ntiles) { const u32 ch = ((u32)ntiles + 7) / 8; LAUNCH(c, "unnaf_emit_flat", k_emit_tile_flat_wave<1>, ch * 8, 64, 0, pl.P, (const TileIdx *)ti, (const TileFlat *)tsig, d_out, (u64)ntiles, ch); }
-                else if (wave) { const u32 ch = (cdiv(ntiles, 2u) + 7) / 8; LAUNCH(c, "unnaf_emit_flat", k_emit_tile_flat_wave<2>, ch * 8, 64, 0, pl.P, (const TileIdx *)ti, (const TileFlat *)tsig, d_out, (u64)ntiles, ch); }
-                else
-                LAUNCH(c, "unnaf_emit_flat", k_emit_tile_flat<4>, chunk * 8, 256, 0, pl.P, (const TileIdx *)ti, (const TileFlat *)tsig, d_out, (u64)ntiles, chunk);
-                if (flat_job) {                                                               // (queued behind the flat emit: the job waits for its tables on the host)
-                    if ((rc = zstd_flat_later(c, &zflat))) return rc;
-                    if (zflat.aux) xc = zflat.aux;
-                }
-                if (zflat.cls && zflat.n_decoded) {
-                    // a tile costs this kernel about what it costs k_emit_tile: as many workgroups as there can be tiles over decoded blocks, up to a few waves of the device
-                    const u64 est = (u64)zflat.n_decoded * 64 + 64;                           // (blocks of up to 128 KiB: 64 tiles each)
-                    const u32 lgrid = (u32)(est < ntiles ? (est < 16384 ? est : 16384) : (ntiles < 16384 ? ntiles : 16384));
-                    if (wave) LAUNCH(xc, "unnaf_emit", k_emit_tile_list_wave<true>, lgrid, 64, 0, pl.P, (const TileIdx *)ti, (const u32 *)list2, (const u32 *)(cnt + 1), d_out);
-                    else LAUNCH(xc, "unnaf_emit", k_emit_tile_list<true>, lgrid, 256, 0, pl.P, (const TileIdx *)ti, (const u32 *)list2, (const u32 *)(cnt + 1), d_out);
-                }
-            }
-            else if (t_done < ntiles) emit_tiles(c, t_done, ntiles);
-            // tiles holding a header or a record boundary (their number stays on the device)
-            const u32 rest_grid = 4u * (u32)(ntiles < EMIT_REST_GRID ? ntiles : EMIT_REST_GRID);      // (quarter tiles: k_emit_rest)
-            if (pl.fourbit) LAUNCH(xc, "unnaf_emit_rest", k_emit_rest<true>, rest_grid, 64, 0, pl.P, (const TileIdx *)ti, (const u64 *)tr, (const u32 *)list, (const u32 *)cnt, d_out);
-            else LAUNCH(xc, "unnaf_emit_rest", k_emit_rest<false>, rest_grid, 64, 0, pl.P, (const TileIdx *)ti, (const u64 *)tr, (const u32 *)list, (const u32 *)cnt, d_out);
-            if (xc != c) { HIP_TRY(c, hipEventRecord(c->split_ev[1], xc->stream)); HIP_TRY(c, hipStreamWaitEvent(c->stream, c->split_ev[1], 0)); }
-            if (split.done) HIP_TRY(c, hipStreamWaitEvent(c->stream, c->split_ev[ZSPLIT_MAX + 1], 0));
-            if (zflat.ready && ctx_tracing(c)) {          // tests: how the tiles were dealt
-                u32 hc[2] = { 0, 0 };
-                if (!ctx_readback(c, hc, cnt, 8)) ctx_trace(c, "[flat tiles] total %llu rest %u decoded %u\n", (unsigned long long)ntiles, hc[0], hc[1]);
-            }
-        }
-    }
-    if (has_tail) {
-        const u64 lo = (out_begin > pl.main_total ? out_begin : pl.main_total) - pl.main_total, hi = out_end - pl.main_total;
-        u8 *dst = d_out + (pl.main_total + lo - out_begin);
-        const int wrap = pl.P.mode == EM_FASTA;
-        if (pl.fourbit) LAUNCH(c, "unnaf_emit_surplus", k_emit_surplus<true>, cdiv(hi - lo, 256), 256, 0, pl.P, pl.sur_base0, pl.surplus, pl.sur_c, pl.P.L, wrap, lo, hi, dst);
-        else LAUNCH(c, "unnaf_emit_surplus", k_emit_surplus<false>, cdiv(hi - lo, 256), 256, 0, pl.P, pl.sur_base0, pl.surplus, pl.sur_c, pl.P.L, wrap, lo, hi, dst);
-    }
-    HIP_TRY(c, hipGetLastError());
-    if ((rc = zstd_split_status(c, &split))) return rc;           // a split decode left its status for after the emit was queued
-    if (zflat.ready) { ZSplit fs; fs.parts = 0; fs.done = 1; fs.status = zflat.status; if ((rc = zstd_split_status(c, &fs))) return rc; }
-    return 0;
+    // (ctx.h: ZFlat) those read it in place and nothing is decoded.
+    U.try_flat = !size_only && pl.fourbit && !U.fuse_on && !pl.P.force_slow && U.flat_fuse && !(U.emit && U.emit[0]) &&
+                 (pl.P.mode == EM_FASTA || pl.P.mode == EM_SEQ || pl.P.mode == EM_SEQUENCES) && pl.P.N && pl.h.orig_size[S_SEQ] / pl.P.N >= 16384 &&
+                 (pl.P.mode != EM_FASTA || pl.P.L == 0 || pl.P.L >= 16);
+    const bool text = pl.P.mode != -1;                             // (-1: --4bit, no section but the sequence)
+    bool done = false;
+    if (whole && !size_only && text && c->side && !U.fuse_on) rc = unnaf_fork_sides(U);
+    else if (text) rc = unnaf_sections(c, d_naf, pl);
+    if (rc) return rc;
+    if ((rc = unnaf_output_range(U, &done)) || done) return rc;
+    if (!whole && text && (rc = unnaf_range_streams(U))) return rc;
+    if ((rc = unnaf_try_fused(U, &done)) || done) return rc;
+    if (!U.payload_done && (rc = unnaf_payload(U))) return rc;
+    use_flat_frame(U);
+    if (!text) return emit_4bit_copy(U);
+    if (U.has_main && (rc = emit_records(U))) return rc;
+    if (U.has_tail) emit_surplus(U);
+    return unnaf_final_status(U);
 }
 
 extern "C" int naf_gpu_unnaf_size(naf_gpu_ctx *c, const void *d_naf, size_t naf_len, const naf_gpu_unnaf_opts *o, size_t *out_len)

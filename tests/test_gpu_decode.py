@@ -1197,3 +1197,128 @@ def test_reference_archives_of_structured_texts_at_every_level(gpu, oracle):
             assert got == want, (len(text), fmt, flags)
             b, e = len(want) // 5, len(want) // 5 + 300_001
             assert host(gpu.unnaf_range(d_naf, b, min(e, len(want)))) == want[b:e], (len(text), fmt, flags, "range")
+
+
+# ---- the order in which errors of several damaged sections are reported -------------------------------------------------------------
+_ORDER = (2, 0, 1, 3, 4, 5)                                                    # lengths, ids, names, mask, sequence, quality (section numbers)
+_SECTION = ("ids", "names", "lengths", "mask", "sequence", "quality")
+
+
+def _frame_header_size(fhd):
+    """RFC 8878 3.1.1.1: bytes of the Frame_Header in front of the first Block_Header."""
+    single, fcs, did = (fhd >> 5) & 1, fhd >> 6, fhd & 3
+    return 1 + (0 if single else 1) + (0, 1, 2, 4)[did] + ((1 if single else 0), 2, 4, 8)[fcs]
+
+
+def _undecodable(naf, h, sec, kind):
+    """The archive with section `sec` made undecodable.  kind 0: the reserved bit of its Frame_Header_Descriptor (sections are stored
+    without magic, so that is the first byte of the payload); kind 1: Block_Type 3 in its first Block_Header."""
+    bad = bytearray(naf)
+    o = h.payload_off[sec]
+    if kind == 0:
+        bad[o] |= 8
+    else:
+        bad[o + _frame_header_size(naf[o])] |= 6
+    return bytes(bad)
+
+
+def _reached(mode, shape, capi):
+    """Sections a call decodes: FASTQ takes no mask, --sequences no ids and names, --seq mask and sequence only; a size call stops
+    in front of the sequence and the quality."""
+    s = {capi.OUT_FASTA: {2, 0, 1, 3, 4}, capi.OUT_FASTQ: {2, 0, 1, 4, 5}, capi.OUT_SEQUENCES: {2, 3, 4}, capi.OUT_SEQ: {3, 4}}[mode]
+    return s - {4, 5} if shape == "size" else s
+
+
+@pytest.mark.parametrize("name", ["mixed_60", "fastq_4k", "ids_and_names_above_1_mib"])
+def test_errors_of_damaged_sections_come_in_the_order_of_a_sequential_run(gpu, oracle, name):
+    """Sections are decoded by up to five host threads (emit.hip: unnaf_sections, unnaf_run); whichever of them fail, the error a call
+    returns is that of the section a sequential run meets first: lengths, ids, names, mask, sequence, quality.  Every section an archive
+    has, and every pair of them, is made undecodable (the oracle's decoder refuses each damaged frame: checked here); each such archive
+    goes through a whole call, a size call and a range call over the middle third of the text, in every mode, under default switches
+    and with NAF_GPU_SIDE_FUSED=0.  A call that reaches none of the damaged sections gives the undamaged archive's text.
+
+    As found: an undecodable frame is reported in the decoder's words (NAF_GPU_EZSTD, "zstd frame unsupported feature (frame header)"),
+    which name no section -- "can't decompress <section>" is the message of a frame that decodes to another size.  So the section is told
+    from the damage: the two sections of a pair get the two kinds of damage, either way round, and the error has to be the one the first
+    section's damage gives when it is the only one -- the two differ in every cell that reaches both sections, which is asserted.  Either
+    kind of damage alone gives NAF_GPU_EZSTD; a text that does name a section has to name that one."""
+    from itertools import combinations
+    from naf_amd import capi, synth
+    from naf_amd.capi import NafGpuError
+    import torch
+    if name == "ids_and_names_above_1_mib":                                    # test_names_decoded_beside_ids: names on a context of their own
+        naf = host(gpu.ennaf(gpu.to_device(synth.fastq_reads(200_000, 100, seed=5, var_len=True)))[0])
+    else:
+        naf = golden_bytes("naf", name + ".naf")
+    h = oracle.parse_naf(naf)
+    have = [s for s in _ORDER if h.payload_off[s] is not None and h.comp[s] >= 8]
+    assert {2, 4} <= set(have) and (0 in have or 1 in have) and (3 in have or 5 in have), have
+    for s in have:                                                             # a condition on the inputs: each damage alone is refused
+        for kind in (0, 1):
+            bad = _undecodable(naf, h, s, kind)
+            with pytest.raises(ValueError):
+                oracle.zstd_decompress(oracle.parse_naf(bad).frame(bad, s), h.orig[s] + 64)
+    modes = [capi.OUT_FASTA, capi.OUT_SEQUENCES, capi.OUT_SEQ] + ([capi.OUT_FASTQ] if 5 in have else [])
+    d_clean = gpu.to_device(naf)
+    clean = {m: host(gpu.unnaf(d_clean, m)) for m in modes}
+    out = torch.empty(max(len(t) for t in clean.values()) + 1, dtype=torch.uint8, device=gpu.device)
+
+    def call(d, mode, shape):
+        n = len(clean[mode])
+        try:
+            if shape == "size":
+                return ("ok", gpu.unnaf_size(d, mode))
+            if shape == "whole":
+                return ("ok", sha(host(gpu.unnaf(d, mode, out=out))))
+            return ("ok", sha(host(gpu.unnaf_range(d, n // 3, 2 * n // 3, mode, out=out))))
+        except NafGpuError as e:
+            return ("error", e.code, e.msg)
+
+    def want_clean(mode, shape):
+        n = len(clean[mode])
+        return ("ok", n if shape == "size" else sha(clean[mode]) if shape == "whole" else sha(clean[mode][n // 3:2 * n // 3]))
+
+    cells = [(m, shape, fused) for m in modes for shape in ("whole", "size", "range") for fused in (None, "0")]
+
+    def run(d):
+        res = {}
+        for fused in (None, "0"):
+            if fused is not None:
+                os.environ["NAF_GPU_SIDE_FUSED"] = fused
+            try:
+                for m in modes:
+                    for shape in ("whole", "size", "range"):
+                        res[(m, shape, fused)] = call(d, m, shape)
+            finally:
+                os.environ.pop("NAF_GPU_SIDE_FUSED", None)
+        return res
+
+    alone = {(s, kind): run(gpu.to_device(_undecodable(naf, h, s, kind))) for s in have for kind in (0, 1)}
+    wrong = []
+    for (s, kind), res in alone.items():
+        for cell in cells:
+            got = res[cell]
+            if s not in _reached(cell[0], cell[1], capi):
+                ok = got == want_clean(cell[0], cell[1])
+            else:                                                              # NAF_GPU_EZSTD for either kind of damage, and no other section's name
+                named = [x for x in _SECTION if got[0] == "error" and any(w + x in got[2] for w in ("decompress ", "rrupted "))]
+                ok = got[0] == "error" and got[1] == -5 and named in ([], [_SECTION[s]])
+            if not ok:
+                wrong.append((_SECTION[s], kind, cell, got))
+    n_both = n_told = 0
+    for a, b in combinations(have, 2):                                         # a comes before b in the order
+        for ka, kb in ((0, 1), (1, 0)):
+            bad = _undecodable(_undecodable(naf, h, a, ka), h, b, kb)
+            res = run(gpu.to_device(bad))
+            for cell in cells:
+                hit = [(s, k) for s, k in ((a, ka), (b, kb)) if s in _reached(cell[0], cell[1], capi)]
+                want = alone[hit[0]][cell] if hit else want_clean(cell[0], cell[1])
+                n_both += len(hit) == 2
+                n_told += len(hit) == 2 and alone[hit[0]][cell] != alone[hit[1]][cell]
+                if res[cell] != want:
+                    wrong.append((_SECTION[a], ka, _SECTION[b], kb, cell, res[cell], want))
+    for w in wrong:
+        print(w)
+    assert not wrong, "%d cells, the first: %r" % (len(wrong), wrong[0])
+    print("cells with both damaged sections reached: %d, told apart: %d" % (n_both, n_told))
+    assert n_both >= len(cells) and n_told == n_both, (n_both, n_told)         # the two kinds of damage give different errors in every such cell
