@@ -46,7 +46,8 @@ enum {
     NAF_GPU_EZSTD = -5,      /* corrupt / unsupported zstd frame */
     NAF_GPU_ECAP = -6,       /* output capacity too small; required size is reported */
     NAF_GPU_EINPUT = -7,     /* input text rejected (reference die() messages of process.c) */
-    NAF_GPU_EARG = -8
+    NAF_GPU_EARG = -8,
+    NAF_GPU_EINTERNAL = -9   /* a state the library's own reasoning rules out (text in last_error) */
 };
 
 /* sequence types (NAF header byte; ennaf.c:52, unnaf.c:27) and text formats (ennaf.c:47) */
@@ -702,6 +703,64 @@ int  naf_gpu_unnaf_clip(naf_gpu_ctx *ctx, const void *d_naf, size_t naf_len, con
                         const uint8_t *h_budget /* n_adapters x 33 */, const naf_gpu_clip_opts *opts, uint64_t first, uint64_t count,
                         const naf_gpu_trim_row *d_bounds /* or NULL */, naf_gpu_clip_row *d_rows, size_t row_cap, uint64_t *n_records,
                         naf_gpu_clip_total *h_total, uint64_t *per_adapter /* n_adapters x 33, or NULL */);
+
+/* ---- unnaf: exact duplicates among reads collapsed, decided in the packed sequence stream -------------------------------
+ * What seqkit rmdup -s, fastp --dedup, clumpify dedupe, fastx_collapser and vsearch --derep_fulllength answer from the text -- which reads
+ * are copies of an earlier read, and how often every sequence occurs (FastQC's duplication levels) -- as a table of (record, begin, end,
+ * first, copies, flags, strand) rows, made without expanding the codes.  Integers only: the table is a function of the codes alone, the
+ * same bytes on every run, for every value of NAF_GPU_DEDUP_HASH_BITS and whichever order the kernels meet the records in.
+ *   Window    of record r: [begin_r, end_r) in bases of the record.  d_bounds == NULL: the whole record.  Otherwise d_bounds holds exactly
+ *             count rows of 40 bytes (DEVICE memory of any alignment), the rows naf_gpu_unnaf_trim (bounds_kind NAF_GPU_DEDUP_BOUNDS_TRIM)
+ *             or naf_gpu_unnaf_clip (NAF_GPU_DEDUP_BOUNDS_CLIP: that is where the flags word lies) wrote for the same first / count, and the
+ *             window is the row's (begin, end).  A record whose bounds row lacks NAF_GPU_TRIM_KEPT takes NO part: in its row first is its
+ *             own number, copies is 0, strand 0, and flags, begin and end are the bounds row's as they came.
+ *   Class     two records that take part are in one class iff their windows have the same number of bases and the same stored 4-bit code
+ *             at every place.  Case (the mask), qualities, ids and names play no part.  Codes are compared literally: a stored N equals
+ *             only a stored N, a gap only a gap; U and T are one code.  Empty windows are equal to each other.  With
+ *             NAF_GPU_DEDUP_BOTH_STRANDS in opts.flags two records are also in one class when one window is the reverse complement of the
+ *             other: the order reversed and every code complemented by reversing its four bits (T=1 <-> A=8, G=2 <-> C=4).
+ *   Rows      exactly one per selected record, ascending.  first: the smallest record number of its class; copies: the records in the
+ *             class, the same value in every row of it; strand: 0 when the window equals the first's window as stored, 1 when it equals
+ *             only its reverse complement (a window equal both ways has 0, the first itself 0, without the flag always 0).  flags of a
+ *             record that takes part: NAF_GPU_TRIM_KEPT if it is its class's first, else NAF_GPU_DEDUP_DUPLICATE; the bounds row's
+ *             NAF_GPU_CLIP_CLIPPED is carried.  d_rows is DEVICE memory of any alignment; exactly 48 * n_records bytes are written and
+ *             nothing else.  d_rows == NULL: the totals only.  With row_cap too small the call returns NAF_GPU_ECAP, sets *n_records and
+ *             writes nothing.
+ *   Total     h_total (HOST memory, may be NULL): reads (the selected records), considered (those that take part), classes (rows with
+ *             NAF_GPU_TRIM_KEPT), duplicates (considered - classes), singletons (classes of one), largest (the largest copies), bases
+ *             (the bases of the windows that take part), kept_bases (those of the firsts' windows).
+ *   Levels    h_levels (HOST, NAF_GPU_DEDUP_LEVELS counters, may be NULL): the classes by their copies in FastQC's bins -- 1 to 9 each,
+ *             then 10-49, 50-99, 100-499, 500-999, 1000-4999, 5000-9999 and 10000 or more.  naf_gpu_dedup_level gives the bin of a count
+ *             (host only; copies == 0 is NAF_GPU_EARG).
+ *   Errors    NAF_GPU_EARG, last_error saying which: an unknown flag or bounds_kind; NAF_GPU_DEDUP_HASH_BITS above 64; protein and text
+ *             archives ("duplicates cannot be collapsed in %s sequences"); first > n_sequences or a range past the last record, as for
+ *             naf_gpu_unnaf_clip; a bounds row whose record is not first + its number, whose begin > end or whose end > the record's
+ *             length (found on the device; nothing is written to d_rows then, *n_records, *h_total and h_levels are 0).  An archive
+ *             without records gives 0 rows; one without a quality section is as good as any other.
+ *   No pieces a comparison needs both records resident: the packed bytes behind the selected records are decoded as ONE range and held
+ *             for the call (only the zstd blocks behind them where the frame allows it).  The call needs, beside them, per selected
+ *             record 16 bytes of hashes, 16 of window, 8 of first, 8 of copies, 6 of flags and, with d_rows, 48 of row; a table of
+ *             8-byte slots, the power of two that is at least 2 * considered (64 at the least); and 96 bytes per 4096 bases.  What does
+ *             not fit is NAF_GPU_ENOMEM: there is no piece size to set.
+ *   Hashes    a window's 128-bit polynomial hash only FINDS candidates: every duplicate is confirmed by comparing the windows' codes,
+ *             and records that share a hash without being equal are resolved in further rounds.  NAF_GPU_DEDUP_HASH_BITS=b (0 to 64)
+ *             cuts every 64-bit word of the hash to its low b bits, so that different sequences truly share one: the cross-check lever
+ *             of the tests; the table does not change by a byte.  A round that resolves nothing is NAF_GPU_EINTERNAL (never seen).
+ * A row with NAF_GPU_TRIM_KEPT gives the (record, begin, end) naf_gpu_unnaf_select_reads takes: every distinct read once.
+ * TRACE=1: "[dedup] records R considered C classes U rounds J verified V sequence bytes decoded X of Y" per call that reaches the
+ * records (J: rounds of insert + compare; V: pairs of windows whose codes were compared). */
+enum { NAF_GPU_DEDUP_DUPLICATE = 16 };            /* beside NAF_GPU_TRIM_KEPT, _SHORT, _ERRORS, NAF_GPU_CLIP_CLIPPED in naf_gpu_dedup_row.flags */
+enum { NAF_GPU_DEDUP_BOTH_STRANDS = 1 };          /* opts.flags */
+enum { NAF_GPU_DEDUP_BOUNDS_TRIM = 0, NAF_GPU_DEDUP_BOUNDS_CLIP = 1 };
+#define NAF_GPU_DEDUP_LEVELS 16
+typedef struct { uint32_t flags, bounds_kind; } naf_gpu_dedup_opts;
+typedef struct { uint64_t record, begin, end, first, copies; uint32_t flags, strand; } naf_gpu_dedup_row;   /* 48 bytes */
+typedef struct { uint64_t reads, considered, classes, duplicates, singletons, largest, bases, kept_bases; } naf_gpu_dedup_total;
+
+int  naf_gpu_dedup_level(uint64_t copies, unsigned *level);    /* host only, no device */
+int  naf_gpu_unnaf_dedup(naf_gpu_ctx *ctx, const void *d_naf, size_t naf_len, const naf_gpu_dedup_opts *opts, uint64_t first, uint64_t count,
+                         const void *d_bounds /* or NULL */, naf_gpu_dedup_row *d_rows, size_t row_cap, uint64_t *n_records,
+                         naf_gpu_dedup_total *h_total, uint64_t *h_levels /* NAF_GPU_DEDUP_LEVELS, or NULL */);
 
 /* ---- ennaf ------------------------------------------------------------------------------------------ */
 typedef struct {

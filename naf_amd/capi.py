@@ -41,6 +41,7 @@ EXPORTS = [
     "naf_gpu_parse_repeat_spec", "naf_gpu_repeat_class", "naf_gpu_unnaf_repeats_count", "naf_gpu_unnaf_repeats",
     "naf_gpu_trim_limit", "naf_gpu_unnaf_trim", "naf_gpu_unnaf_select_reads_size", "naf_gpu_unnaf_select_reads",
     "naf_gpu_clip_budgets", "naf_gpu_unnaf_clip",
+    "naf_gpu_dedup_level", "naf_gpu_unnaf_dedup",
 ]
 WHOLE = 2 ** 64 - 1                     # NAF_GPU_WHOLE: (record, 0, WHOLE) is the record as stored
 MAX_SHARDS = 64
@@ -250,6 +251,29 @@ CLIP_NO_ADAPTER = 2 ** 32 - 1
 CLIP_MAX_ADAPTERS = 16
 
 
+class DedupOpts(C.Structure):
+    """naf_gpu_dedup_opts: DEDUP_BOTH_STRANDS or 0; which call wrote the bounds rows (DEDUP_BOUNDS_TRIM, DEDUP_BOUNDS_CLIP)."""
+    _fields_ = [("flags", C.c_uint32), ("bounds_kind", C.c_uint32)]
+
+
+class DedupTotal(C.Structure):
+    """naf_gpu_dedup_total: the reads of a call, those that take part, their classes, the copies among them, the classes of one, the largest
+    class, the bases of the windows that take part and of the firsts' windows."""
+    _fields_ = [("reads", C.c_uint64), ("considered", C.c_uint64), ("classes", C.c_uint64), ("duplicates", C.c_uint64), ("singletons", C.c_uint64),
+                ("largest", C.c_uint64), ("bases", C.c_uint64), ("kept_bases", C.c_uint64)]
+
+
+# numpy's view of a table of naf_gpu_dedup_row: bases [begin, end) of `record` are its window; first: the smallest record of its class;
+# copies: the records in the class; flags: TRIM_KEPT (the class's first) or DEDUP_DUPLICATE, and CLIP_CLIPPED carried -- of a record that
+# takes no part the bounds row's flags; strand: 1 when the window equals only the reverse complement of the first's
+DEDUP_DTYPE = [("record", "<u8"), ("begin", "<u8"), ("end", "<u8"), ("first", "<u8"), ("copies", "<u8"), ("flags", "<u4"), ("strand", "<u4")]
+DEDUP_BYTES = 48
+DEDUP_DUPLICATE = 16
+DEDUP_BOTH_STRANDS = 1
+DEDUP_BOUNDS_TRIM, DEDUP_BOUNDS_CLIP = 0, 1
+DEDUP_LEVELS = 16
+
+
 class NafGpuError(RuntimeError):
     def __init__(self, code, msg):
         super().__init__("naf_gpu error %d: %s" % (code, msg))
@@ -380,6 +404,8 @@ def load():
         L.naf_gpu_unnaf_trim.argtypes = [vp, vp, sz, C.POINTER(TrimOpts), C.c_uint64, C.c_uint64, vp, sz, u64p, C.POINTER(TrimTotal)]
         L.naf_gpu_clip_budgets.argtypes = [C.c_uint64, C.c_uint64, C.c_uint, u8p]
         L.naf_gpu_unnaf_clip.argtypes = [vp, vp, sz, C.c_char_p, sz, sz, u8p, C.POINTER(ClipOpts), C.c_uint64, C.c_uint64, vp, vp, sz, u64p, C.POINTER(ClipTotal), u64p]
+        L.naf_gpu_dedup_level.argtypes = [C.c_uint64, C.POINTER(C.c_uint)]
+        L.naf_gpu_unnaf_dedup.argtypes = [vp, vp, sz, C.POINTER(DedupOpts), C.c_uint64, C.c_uint64, vp, vp, sz, u64p, C.POINTER(DedupTotal), u64p]
         L.naf_gpu_unnaf_select_reads_size.argtypes = [vp, vp, sz, C.POINTER(UnnafOpts), C.POINTER(Segment), u8p, sz, C.POINTER(sz)]
         L.naf_gpu_unnaf_select_reads.argtypes = [vp, vp, sz, C.POINTER(UnnafOpts), C.POINTER(Segment), u8p, sz, vp, sz, C.POINTER(sz)]
         _lib = L
@@ -499,6 +525,20 @@ def clip_budgets(rate, m):
 
 def clip_to_segments(rows):
     """The (record, begin, end) tuples unnaf_select_reads takes: the kept rows of the table unnaf_clip returns, in its order."""
+    return [(int(x["record"]), int(x["begin"]), int(x["end"])) for x in rows if int(x["flags"]) & TRIM_KEPT]
+
+
+def dedup_level(copies):
+    """Host-only: FastQC's duplication-level bin of a class of `copies` reads (naf_gpu_dedup_level): 0 to 8 for 1 to 9 copies, then 10-49,
+    50-99, 100-499, 500-999, 1000-4999, 5000-9999 and 10000 or more as 9 to 15.  ValueError for 0."""
+    v = C.c_uint()
+    if not 0 < int(copies) < 2 ** 64 or load().naf_gpu_dedup_level(int(copies), C.byref(v)):
+        raise ValueError("not a number of copies (1 or more): %r" % (copies,))
+    return int(v.value)
+
+
+def dedup_to_segments(rows):
+    """The (record, begin, end) tuples unnaf_select_reads takes: the firsts of the table unnaf_dedup returns, in its order."""
     return [(int(x["record"]), int(x["begin"]), int(x["end"])) for x in rows if int(x["flags"]) & TRIM_KEPT]
 
 
@@ -1258,6 +1298,36 @@ class Context:
             return None, tot, per_adapter
         view = buf[:CLIP_BYTES * n.value]
         return (np.frombuffer(view.cpu().numpy().tobytes(), dtype=CLIP_DTYPE) if own else view), tot, per_adapter
+
+    def unnaf_dedup(self, d_naf, both_strands=False, bounds=None, bounds_kind="trim", first=0, count=None, out=None):
+        """(rows, total, levels): the classes of equal reads among records [first, first + count) (naf_gpu_unnaf_dedup) -- both_strands: a
+        read and its reverse complement are one class; bounds: a uint8 device tensor of the rows unnaf_trim (bounds_kind "trim") or
+        unnaf_clip ("clip") wrote for the same records, whose (begin, end) are compared instead of the whole reads and whose rows
+        without TRIM_KEPT take no part -- as a structured numpy array (DEDUP_DTYPE), one row per read, a DedupTotal and the classes by
+        FastQC's duplication level as a list of DEDUP_LEVELS ints.  out: a uint8 device tensor to take the table (48 bytes a row); then
+        `rows` is the torch view of its first 48 * n bytes and too small a tensor raises NafGpuError(E_CAP).  out=False: the totals only."""
+        import numpy as np
+        import torch
+        kinds = {"trim": DEDUP_BOUNDS_TRIM, "clip": DEDUP_BOUNDS_CLIP}
+        if bounds_kind not in kinds and not isinstance(bounds_kind, int):
+            raise ValueError("bounds_kind: 'trim' or 'clip', not %r" % (bounds_kind,))
+        o = DedupOpts(DEDUP_BOTH_STRANDS if both_strands is True else int(both_strands), kinds.get(bounds_kind, bounds_kind))
+        n, tot, lev = C.c_uint64(), DedupTotal(), (C.c_uint64 * DEDUP_LEVELS)()
+        cnt = WHOLE if count is None else int(count)
+        own = out is None
+        if own:
+            have = int(self.parse_header(d_naf).n_sequences)
+            rows = max(0, min(have - int(first), cnt)) if cnt != WHOLE else max(0, have - int(first))
+            out = torch.empty(max(DEDUP_BYTES * rows, 1), dtype=torch.uint8, device=self.device)
+        buf = None if out is False else out
+        self._check(self.L.naf_gpu_unnaf_dedup(self.h, _ptr(d_naf), d_naf.numel(), C.byref(o), int(first), cnt, _ptr(bounds) if bounds is not None else None,
+                                               _ptr(buf) if buf is not None else None, buf.numel() // DEDUP_BYTES if buf is not None else 0,
+                                               C.byref(n), C.byref(tot), lev))
+        levels = [int(v) for v in lev]
+        if buf is None:
+            return None, tot, levels
+        view = buf[:DEDUP_BYTES * n.value]
+        return (np.frombuffer(view.cpu().numpy().tobytes(), dtype=DEDUP_DTYPE) if own else view), tot, levels
 
     @staticmethod
     def _run_class(cls, each, masked):

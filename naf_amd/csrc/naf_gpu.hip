@@ -28,6 +28,7 @@ extern "C" const char *naf_gpu_strerror(int code)
     case NAF_GPU_ECAP: return "output buffer too small";
     case NAF_GPU_EINPUT: return "invalid input text";
     case NAF_GPU_EARG: return "invalid argument";
+    case NAF_GPU_EINTERNAL: return "internal error";
     default: return "unknown error";
     }
 }

@@ -52,6 +52,9 @@ static bool min_length_given = false, trim_table = false, reads_selection = fals
 static const char *adapters[NAF_GPU_CLIP_MAX_ADAPTERS]; static size_t n_adapters = 0;
 static const char *adapter_errors_text = NULL; static unsigned long long adapter_num = 1, adapter_den = 10;
 static naf_gpu_clip_opts clip_opts = { 3, 1 }; static bool min_overlap_given = false, clip_table = false;
+/* --dedup [--either-strand] [--dedup-table] [--trim Q|none ...] [--adapter SEQ ...]: every distinct read once -- the first of its copies --, behind
+ * the quality trimming and the adapter clipping when there are any, or the table of the classes (this implementation only) */
+static bool dedup = false, either_strand = false, dedup_table = false;
 
 static void done(int status, void *arg)
 {
@@ -313,6 +316,11 @@ static void show_help(void)
         "  --repeats SPEC  - Every perfect tandem repeat, as lines \"ID begin end PERIOD MOTIF COPIES CLASS\" (0-based half-open): SPEC is PERIOD-COPIES pairs, e.g. 1-10,2-6,3-5, periods 1 to 16; or misa\n"
         "  --min-repeat N  - With --repeats: only repeats of at least N bases (default 1)\n"
         "  --whole-units   - With --repeats: the end of a repeat is cut to a whole number of copies, as MISA and PERF print it\n"
+        "Options for collapsing duplicate reads (output: every distinct read once, the first of its copies, as --fastq, --fasta, --sequences or --seq; with at most one --records A-B or --region ID):\n"
+        "  --dedup         - Drop every read whose bases are exactly those of an earlier read; case, qualities and names play no part, N equals only N.\n"
+        "                    With --trim Q and / or --adapter SEQ the reads are trimmed and clipped first, and what is left of them is compared and written\n"
+        "  --either-strand - With --dedup: a read that is the reverse complement of an earlier read is a copy of it too\n"
+        "  --dedup-table   - With --dedup: instead of the reads, a table \"#seq length begin end first copies strand status\" of all reads (first: the read it copies; status first, duplicate, or short / errors)\n"
         "Options for clipping adapters (output: the kept reads, each cut where its 3' adapter begins, as --fastq, --fasta, --sequences or --seq; with at most one --records A-B or --region ID):\n"
         "  --adapter SEQ   - Cut every read at the leftmost place where SEQ (1 to 32 IUPAC letters) begins, also one that the read's end cuts short; repeatable, up to 16 adapters.\n"
         "                    With --trim Q (and --max-ee X) the reads are trimmed by quality first and the adapter is searched in what is left; --min-length N drops reads cut shorter than N\n"
@@ -327,7 +335,7 @@ static void show_help(void)
 }
 
 /* ---- the table modes ---------------------------------------------------------------------------------------------------------------
- * --locate, --composition, --quality, --runs / --masked-runs, --kmers, --orfs, --translate, --repeats, --adapter and --trim write a table of their own
+ * --locate, --composition, --quality, --runs / --masked-runs, --kmers, --orfs, --translate, --repeats, --dedup, --adapter and --trim write a table of their own
  * instead of an output type (--trim without --trim-table: the reads, in one of the sequence output types).  A mode is a row here -- what its refusals say, its options, its runner -- plus the checks that are
  * really its own; parse_command_line walks the rows once, in this order, and main runs the first one asked for (--orfs in front
  * of --translate: the one legal pair). */
@@ -345,10 +353,10 @@ typedef struct table_mode {
     const char *protein;                            /* main's refusal of protein and text archives (%s: which), NULL: none */
     void (*run)(bool has_ids, bool has_names);
 } table_mode;
-enum { M_LOCATE, M_COMPOSITION, M_QUALITY, M_RUNS, M_KMERS, M_ORFS, M_TRANSLATE, M_REPEATS, M_CLIP, M_TRIM, N_MODES };
+enum { M_LOCATE, M_COMPOSITION, M_QUALITY, M_RUNS, M_KMERS, M_ORFS, M_TRANSLATE, M_REPEATS, M_DEDUP, M_CLIP, M_TRIM, N_MODES };
 static table_mode modes[N_MODES];
 static void run_locate(bool, bool), run_composition(bool, bool), run_quality(bool, bool), run_runs(bool, bool), run_kmers(bool, bool), run_orfs(bool, bool),
-            run_translate(bool, bool), run_repeats(bool, bool), run_clip(bool, bool), run_trim(bool, bool);
+            run_translate(bool, bool), run_repeats(bool, bool), run_dedup(bool, bool), run_clip(bool, bool), run_trim(bool, bool);
 
 static void refuse_output_type(const table_mode *m)
 {
@@ -401,6 +409,13 @@ static void clip_own(const table_mode *m)
     if (trim_table) die("--trim-table can't be used with --adapter: --clip-table writes the table of the clipped reads\n");
 }
 
+static void dedup_own(const table_mode *m)
+{
+    (void)m;
+    if (trim_table) die("--trim-table can't be used with --dedup: --dedup-table writes the table of the collapsed reads\n");
+    if (clip_table) die("--clip-table can't be used with --dedup: --dedup-table writes the table of the collapsed reads\n");
+}
+
 /* the rows, from the options as they were given */
 static void fill_modes(void)
 {
@@ -431,6 +446,11 @@ static void fill_modes(void)
     modes[M_REPEATS] = (table_mode){ .asked = repeats_text != NULL, .name = "--repeats", .writes = "a table", .strands = "lists the sequences as stored", .one_selection = true,
         .sat = { { min_repeat_given, repeats_text != NULL, "--min-repeat can be used only with --repeats\n" }, { whole_units, repeats_text != NULL, "--whole-units can be used only with --repeats\n" } },
         .protein = "tandem repeats cannot be listed in %s sequences\n", .run = run_repeats };
+    /* --dedup stands in front of --adapter and --trim, the two modes it can be used with: main then runs it, and it trims and clips first */
+    modes[M_DEDUP] = (table_mode){ .asked = dedup, .name = "--dedup", .writes = dedup_table ? "a table" : "reads as --fastq, --fasta, --sequences or --seq",
+        .strands = "writes the reads as stored", .one_selection = true, .type_first = true, .sequence_types = !dedup_table,
+        .sat = { { either_strand, dedup, "--either-strand can be used only with --dedup\n" }, { dedup_table, dedup, "--dedup-table can be used only with --dedup\n" } },
+        .own = dedup_own, .protein = "duplicates cannot be collapsed in %s sequences\n", .run = run_dedup };
     /* --adapter stands in front of --trim, the one mode it can be used with: main then runs it, and it trims first */
     modes[M_CLIP] = (table_mode){ .asked = n_adapters != 0, .name = "--adapter", .writes = clip_table ? "a table" : "reads as --fastq, --fasta, --sequences or --seq",
         .strands = "clips the reads as stored", .one_selection = true, .type_first = true, .sequence_types = !clip_table,
@@ -459,7 +479,7 @@ static void parse_command_line(int argc, char **argv)
         {"--fasta", FASTA}, {"--fastq", FASTQ}, {"--dna", DNA}, {"--masked-dna", MASKED_DNA}, {"--unmasked-dna", UNMASKED_DNA},
         {"--masked-fasta", MASKED_FASTA}, {"--unmasked-fasta", UNMASKED_FASTA} };
     /* the other options (unnaf/src/unnaf.c:282-353), as a table: one that takes a value is only recognised with an argument behind it */
-    enum { OP_LINE_LENGTH, OP_OUT, OP_NO_MASK, OP_IGNORED, OP_HELP, OP_VERBOSE, OP_VERSION, OP_STDOUT, OP_REGION, OP_RECORDS, OP_RC_REGION, OP_REVCOMP, OP_LOCATE, OP_STRAND, OP_MISMATCHES, OP_COMPOSITION, OP_WINDOW, OP_QUALITY, OP_CYCLES, OP_RUNS, OP_MASKED_RUNS, OP_MIN_RUN, OP_EACH, OP_KMERS, OP_CANONICAL, OP_PER_RECORD, OP_ORFS, OP_MIN_ORF, OP_STOPS, OP_STARTS, OP_STOP_TO_STOP, OP_CLOSED, OP_SPLIT_UNKNOWN, OP_TRANSLATE, OP_FRAME, OP_CODE, OP_CODE_TABLE, OP_REPEATS, OP_MIN_REPEAT, OP_WHOLE_UNITS, OP_TRIM, OP_MIN_LENGTH, OP_MAX_EE, OP_TRIM_TABLE, OP_ADAPTER, OP_ADAPTER_ERRORS, OP_MIN_OVERLAP, OP_CLIP_TABLE };
+    enum { OP_LINE_LENGTH, OP_OUT, OP_NO_MASK, OP_IGNORED, OP_HELP, OP_VERBOSE, OP_VERSION, OP_STDOUT, OP_REGION, OP_RECORDS, OP_RC_REGION, OP_REVCOMP, OP_LOCATE, OP_STRAND, OP_MISMATCHES, OP_COMPOSITION, OP_WINDOW, OP_QUALITY, OP_CYCLES, OP_RUNS, OP_MASKED_RUNS, OP_MIN_RUN, OP_EACH, OP_KMERS, OP_CANONICAL, OP_PER_RECORD, OP_ORFS, OP_MIN_ORF, OP_STOPS, OP_STARTS, OP_STOP_TO_STOP, OP_CLOSED, OP_SPLIT_UNKNOWN, OP_TRANSLATE, OP_FRAME, OP_CODE, OP_CODE_TABLE, OP_REPEATS, OP_MIN_REPEAT, OP_WHOLE_UNITS, OP_TRIM, OP_MIN_LENGTH, OP_MAX_EE, OP_TRIM_TABLE, OP_ADAPTER, OP_ADAPTER_ERRORS, OP_MIN_OVERLAP, OP_CLIP_TABLE, OP_DEDUP, OP_EITHER_STRAND, OP_DEDUP_TABLE };
     static const struct { const char *name; int op; bool value; } option_table[] = {
         { "--line-length", OP_LINE_LENGTH, true }, { "-o", OP_OUT, true }, { "--no-mask", OP_NO_MASK, false }, { "--binary-stdout", OP_IGNORED, false },
         { "--binary-stderr", OP_IGNORED, false }, { "--binary", OP_IGNORED, false }, { "--help", OP_HELP, false }, { "-h", OP_HELP, false },
@@ -474,7 +494,8 @@ static void parse_command_line(int argc, char **argv)
         { "--translate", OP_TRANSLATE, false }, { "--frame", OP_FRAME, true }, { "--code", OP_CODE, true }, { "--code-table", OP_CODE_TABLE, true },
         { "--repeats", OP_REPEATS, true }, { "--min-repeat", OP_MIN_REPEAT, true }, { "--whole-units", OP_WHOLE_UNITS, false },
         { "--trim", OP_TRIM, true }, { "--min-length", OP_MIN_LENGTH, true }, { "--max-ee", OP_MAX_EE, true }, { "--trim-table", OP_TRIM_TABLE, false },
-        { "--adapter", OP_ADAPTER, true }, { "--adapter-errors", OP_ADAPTER_ERRORS, true }, { "--min-overlap", OP_MIN_OVERLAP, true }, { "--clip-table", OP_CLIP_TABLE, false } };
+        { "--adapter", OP_ADAPTER, true }, { "--adapter-errors", OP_ADAPTER_ERRORS, true }, { "--min-overlap", OP_MIN_OVERLAP, true }, { "--clip-table", OP_CLIP_TABLE, false },
+        { "--dedup", OP_DEDUP, false }, { "--either-strand", OP_EITHER_STRAND, false }, { "--dedup-table", OP_DEDUP_TABLE, false } };
     for (int i = 1; i < argc; i++) {
         char *arg = argv[i];
         if (arg[0] != '-') {
@@ -539,6 +560,9 @@ static void parse_command_line(int argc, char **argv)
         case OP_ADAPTER_ERRORS: set_adapter_errors(v); break;
         case OP_MIN_OVERLAP: set_min_overlap(v); break;
         case OP_CLIP_TABLE: clip_table = true; break;
+        case OP_DEDUP: dedup = true; break;
+        case OP_EITHER_STRAND: either_strand = true; break;
+        case OP_DEDUP_TABLE: dedup_table = true; break;
         }
     }
     if (print_version) {
@@ -555,7 +579,8 @@ static void parse_command_line(int argc, char **argv)
         if (!m->asked) continue;
         if (m->type_first) refuse_output_type(m);
         for (const table_mode *e = modes; e < m; e++)
-            if (e->asked && !(e == &modes[M_ORFS] && m == &modes[M_TRANSLATE]) && !(e == &modes[M_CLIP] && m == &modes[M_TRIM])) die("%s and %s can't be used together\n", m->name, e->name);
+            if (e->asked && !(e == &modes[M_ORFS] && m == &modes[M_TRANSLATE]) && !(e == &modes[M_CLIP] && m == &modes[M_TRIM]) &&
+                !(e == &modes[M_DEDUP] && (m == &modes[M_CLIP] || m == &modes[M_TRIM]))) die("%s and %s can't be used together\n", m->name, e->name);
         refuse_output_type(m);
         if (m->own) m->own(m);
         if (m->one_selection) one_whole_selection(m);
@@ -1134,6 +1159,18 @@ static void clip_reads(const void *rows, size_t m, uint64_t at, const char **nam
     emit_reads(segs, n);
     free(segs);
 }
+/* the adapters and their budgets as the clip call takes them (the caller frees clip.blob) */
+static void clip_prepare(void)
+{
+    clip.bytes = 0; for (size_t k = 0; k < n_adapters; k++) clip.bytes += strlen(adapters[k]) + 1;
+    clip.blob = (char *)malloc(clip.bytes + 1); if (!clip.blob) die("can't allocate memory\n");
+    for (size_t k = 0, at = 0; k < n_adapters; k++) {
+        const size_t l = strlen(adapters[k]);
+        memcpy(clip.blob + at, adapters[k], l + 1); at += l + 1;
+        if (naf_gpu_clip_budgets(adapter_num, adapter_den, (unsigned)l, clip.budget[k])) die("can't parse the value of --adapter parameter (1 to 32 IUPAC nucleotide letters)\n");
+    }
+    clip_opts.min_len = trim_opts.min_len;                           /* --min-length: one value for both steps */
+}
 static void run_clip(bool has_ids, bool has_names)
 {
     static const row_table lines = { sizeof(naf_gpu_clip_row), 1 << 20, "sequence", "clip: rows", "clip: download + lines", fill_clip, clip_lines },
@@ -1144,14 +1181,7 @@ static void run_clip(bool has_ids, bool has_names)
     const unsigned long long N = H.n_sequences;
     if (rng_first > N) die("can't decompress sequence\n");
     const uint64_t n = rng_count == NAF_GPU_WHOLE ? N - rng_first : rng_count;
-    clip.bytes = 0; for (size_t k = 0; k < n_adapters; k++) clip.bytes += strlen(adapters[k]) + 1;
-    clip.blob = (char *)malloc(clip.bytes + 1); if (!clip.blob) die("can't allocate memory\n");
-    for (size_t k = 0, at = 0; k < n_adapters; k++) {
-        const size_t l = strlen(adapters[k]);
-        memcpy(clip.blob + at, adapters[k], l + 1); at += l + 1;
-        if (naf_gpu_clip_budgets(adapter_num, adapter_den, (unsigned)l, clip.budget[k])) die("can't parse the value of --adapter parameter (1 to 32 IUPAC nucleotide letters)\n");
-    }
-    clip_opts.min_len = trim_opts.min_len;                           /* --min-length: one value for both steps */
+    clip_prepare();
     if (clip_table) {
         fprintf(OUT, "#seq\tlength\tbegin\tend\tadapter\tmismatches\toverlap\tstatus\n");
         if (n) {
@@ -1169,6 +1199,88 @@ static void run_clip(bool has_ids, bool has_names)
         if (sel_buf) { naf_gpu_free(gpu, sel_buf); sel_buf = NULL; sel_cap = 0; }
     }
     free(clip.blob);
+}
+
+/* --dedup: naf_gpu_unnaf_dedup -- the windows of all selected reads hashed in one sweep over the packed stream and compared, a row per read.
+ * With --trim and / or --adapter the trim rows and then the clip rows of the same reads are made first and stay on the device: the last
+ * of them are the dedup call's bounds, as in run_clip.  --dedup-table writes the rows as lines; without it a chunk's firsts are the
+ * segments of a selection of reads, as for --trim. */
+static uint64_t fill_dedup(void *d, size_t cap)
+{
+    uint64_t got = 0; void *d_trim = NULL, *d_clip = NULL;
+    if (trim_text) {
+        GPU_TRY(naf_gpu_malloc(gpu, cap * sizeof(naf_gpu_trim_row), &d_trim));
+        GPU_TRY(naf_gpu_unnaf_trim(gpu, d_naf, naf_len, &trim_opts, rng_first, rng_count, (naf_gpu_trim_row *)d_trim, cap, &got, NULL));
+        if (got != cap) die("can't decompress quality\n");
+        phase("dedup: trim rows");
+    }
+    if (n_adapters) {
+        GPU_TRY(naf_gpu_malloc(gpu, cap * sizeof(naf_gpu_clip_row), &d_clip));
+        GPU_TRY(naf_gpu_unnaf_clip(gpu, d_naf, naf_len, clip.blob, clip.bytes, n_adapters, &clip.budget[0][0], &clip_opts, rng_first, rng_count,
+                                   (const naf_gpu_trim_row *)d_trim, (naf_gpu_clip_row *)d_clip, cap, &got, NULL, NULL));
+        if (got != cap) die("can't decompress sequence\n");
+        phase("dedup: clip rows");
+    }
+    const naf_gpu_dedup_opts o = { either_strand ? NAF_GPU_DEDUP_BOTH_STRANDS : 0, d_clip ? NAF_GPU_DEDUP_BOUNDS_CLIP : NAF_GPU_DEDUP_BOUNDS_TRIM };
+    GPU_TRY(naf_gpu_unnaf_dedup(gpu, d_naf, naf_len, &o, rng_first, rng_count, d_clip ? d_clip : d_trim, (naf_gpu_dedup_row *)d, cap, &got, NULL, NULL));
+    if (d_trim) naf_gpu_free(gpu, d_trim);
+    if (d_clip) naf_gpu_free(gpu, d_clip);
+    return got;
+}
+static void dedup_lines(const void *rows, size_t m, uint64_t at, const char **name)
+{
+    for (size_t k = 0; k < m; k++) {
+        const naf_gpu_dedup_row *x = (const naf_gpu_dedup_row *)rows + k;
+        const uint32_t f = x->flags & 7u; const bool dup = (x->flags & NAF_GPU_DEDUP_DUPLICATE) != 0;
+        if (x->record != rng_first + at + k || x->end < x->begin || x->end > trim_len[at + k] || x->first > x->record || x->first < rng_first || x->strand > 1 || x->flags > 31 ||
+            (dup ? f != 0 : f < 1 || f > 6 || f == 5) || (x->copies == 0) != (!dup && f != NAF_GPU_TRIM_KEPT)) die("can't decompress sequence\n");
+        fprintf(OUT, "%s\t%llu\t%llu\t%llu\t%s\t%llu\t%c\t%s\n", name[x->record], (unsigned long long)trim_len[at + k], (unsigned long long)x->begin, (unsigned long long)x->end,
+                name[x->first], (unsigned long long)x->copies, x->strand ? '-' : '+',
+                dup ? "duplicate" : f == NAF_GPU_TRIM_KEPT ? "first" : f == NAF_GPU_TRIM_SHORT ? "short" : f == NAF_GPU_TRIM_ERRORS ? "errors" : "short,errors");
+    }
+}
+static void dedup_reads(const void *rows, size_t m, uint64_t at, const char **name)
+{
+    (void)name;
+    const naf_gpu_dedup_row *x = (const naf_gpu_dedup_row *)rows;
+    naf_gpu_segment *segs = (naf_gpu_segment *)malloc((m + 1) * sizeof *segs); if (!segs) die("can't allocate memory\n");
+    const bool bounds = trim_text || n_adapters;                    /* without them a first is its whole record, an empty one too */
+    size_t n = 0;
+    for (size_t k = 0; k < m; k++) {
+        if (x[k].record != rng_first + at + k || x[k].end < x[k].begin) die("can't decompress sequence\n");
+        if (x[k].flags & NAF_GPU_TRIM_KEPT) segs[n++] = bounds ? (naf_gpu_segment){ x[k].record, x[k].begin, x[k].end } : (naf_gpu_segment){ x[k].record, 0, NAF_GPU_WHOLE };
+    }
+    emit_reads(segs, n);
+    free(segs);
+}
+static void run_dedup(bool has_ids, bool has_names)
+{
+    static const row_table lines = { sizeof(naf_gpu_dedup_row), 1 << 20, "sequence", "dedup: rows", "dedup: download + lines", fill_dedup, dedup_lines },
+                           reads = { sizeof(naf_gpu_dedup_row), 1 << 20, "sequence", "dedup: rows", "dedup: download + reads", fill_dedup, dedup_reads };
+    if (trim_text && !(H.flags & 1)) die("--trim reads the quality codes: the archive has no quality section\n");
+    if (!dedup_table && out_type == FASTQ && !(H.flags & 1)) die("FASTQ output requested, but input has no qualities\n");
+    table_range(has_ids);
+    const unsigned long long N = H.n_sequences;
+    if (rng_first > N) die("can't decompress sequence\n");
+    const uint64_t n = rng_count == NAF_GPU_WHOLE ? N - rng_first : rng_count;
+    if (n_adapters) clip_prepare();
+    if (dedup_table) {
+        fprintf(OUT, "#seq\tlength\tbegin\tend\tfirst\tcopies\tstrand\tstatus\n");
+        if (n) {
+            uint64_t *off = (uint64_t *)malloc((size_t)(n + 1) * sizeof *off); trim_len = (uint64_t *)malloc((size_t)n * sizeof *trim_len);
+            if (!off || !trim_len) die("can't allocate memory\n");
+            naf_gpu_unnaf_opts o = { NAF_OUT_SEQUENCES, 0, -1 };
+            GPU_TRY(naf_gpu_unnaf_record_table(gpu, d_naf, naf_len, &o, rng_first, n, trim_len, off));
+            free(off);
+            write_rows(&lines, n, true, has_ids, has_names);
+            free(trim_len); trim_len = NULL;
+        }
+    } else {
+        reads_selection = true;
+        if (n) write_rows(&reads, n, false, has_ids, has_names);
+        if (sel_buf) { naf_gpu_free(gpu, sel_buf); sel_buf = NULL; sel_cap = 0; }
+    }
+    if (n_adapters) free(clip.blob);
 }
 
 /* --orfs: naf_gpu_unnaf_orfs -- the stops, starts and record bounds of the packed stream as six lists, a stretch between two neighbours of one
