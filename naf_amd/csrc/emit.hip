@@ -124,44 +124,64 @@ __global__ __launch_bounds__(256) void k_mask_scatter(const u8 *units, u64 n, co
     for (u32 i = 0; i < valid; i++) { u32 u = (w[i >> 2] >> (8 * (i & 3))) & 0xFF; pos += u; if (u != 255) toggles[k++] = pos; }
 }
 
-// The mask of a text without (or almost without) lower case is a few KB of RLE blocks that regenerate tens of MB of 0xFF units, and the
-// general zstd pipeline -- index, parse, tables, copies, then k_mask_count / scans / k_mask_scatter: some 45 dependent launches and four
-// read-backs -- was what the tile index of a 10 GB decode waited for.  One workgroup takes the whole frame through LDS instead: a run
-// of n units of 255 moves the base position by 255 n, every other unit is a toggle.  Frames with a compressed block, more than `cap`
-// toggles or anything unexpected are left to the general path (res[0] = 0).  res: ok, toggles, units.
-#define MASK_RLE_SRC (48u * 1024u)
+// The mask of a text without (or almost without) lower case is a few KB (tens of KB at 100 GB) of RLE blocks that regenerate tens or
+// hundreds of MB of 0xFF units, and the general zstd pipeline -- index, parse, tables, copies, then k_mask_count / scans /
+// k_mask_scatter: some 45 dependent launches and four read-backs, and a pass of writing and one of reading over the units -- was what
+// the tile index of a 10 GB decode waited for.  One workgroup walks the frame where it lies in global memory instead, whatever its
+// size: a run of n units of 255 moves the base position by 255 n, every other unit is a toggle.  The walk is a loop of two steps:
+//   - a run of four-byte RLE blocks of 0xFF units (not the frame's last block), MASK_RLE_RUN headers per thread and round, all at
+//     once: the first header that is not of that kind ends the run, a sum over the ones in front of it gives the units;
+//   - ONE other block, every thread on the same one: an RLE block of another value (or the last one), or a Raw block, which goes
+//     through LDS in pieces of MASK_RLE_STAGE bytes.
+// so that the thousands of 0xFF blocks behind a lower-case island are taken like the ones in front of it.  At most MASK_RLE_OTHER
+// blocks of the second kind: a frame of a million empty or one-unit blocks would be a serial walk at raised priority, and is the
+// decoder's.  Frames with a compressed block, a reserved block type, a size that runs over `len`, no last block, another number of
+// units than the header promises, more than `cap` toggles -- anything unexpected -- are left to the general path (res[0] = 0), which
+// also words the errors.  res: ok, toggles, units.
 #define MASK_RLE_TOG 8192u
+#define MASK_RLE_RUN 8u
+#define MASK_RLE_STAGE (16u * 1024u)
+#define MASK_RLE_OTHER 2048u
 __global__ __launch_bounds__(256) void k_mask_rle_frame(const u8 *src, u32 len, u32 hdr, u64 expect_units, u64 *toggles, u32 cap, u64 *res)
 {
     __builtin_amdgcn_s_setprio(3);                           // a serial chain: first in line for the SIMD's issue slots beside the bulk kernels of the other streams
-    extern __shared__ __attribute__((aligned(16))) u8 mbuf[];
-    __shared__ u64 lds[4]; __shared__ u32 s_first;
+    __shared__ __attribute__((aligned(16))) u8 stage[MASK_RLE_STAGE];
+    __shared__ u64 lds[4]; __shared__ u32 s_first[2];
     const u32 t = threadIdx.x;
-    for (u32 i = t; i < len; i += 256) mbuf[i] = src[i];
-    if (t == 0) s_first = 0xFFFFFFFFu;
-    __syncthreads();
-    // the leading RLE blocks of 0xFF units, four bytes each: all of them at once
-    const u32 nA = len > hdr ? (len - hdr) / 4 : 0;
-    for (u32 i = t; i < nA; i += 256) {
-        const u32 p = hdr + 4 * i, h = (u32)mbuf[p] | ((u32)mbuf[p + 1] << 8) | ((u32)mbuf[p + 2] << 16);
-        if (!(((h >> 1) & 3) == 1 && !(h & 1) && mbuf[p + 3] == 255)) { atomicMin(&s_first, i); break; }   // (a thread's later blocks lie behind this one)
-    }
-    __syncthreads();
-    const u32 F = s_first < nA ? s_first : nA;
-    u64 mine = 0;
-    for (u32 i = t; i < F; i += 256) { const u32 p = hdr + 4 * i; mine += ((u32)mbuf[p] | ((u32)mbuf[p + 1] << 8) | ((u32)mbuf[p + 2] << 16)) >> 3; }
-    u64 units = 0;
-    wg_scan_inclusive<u64, OpAdd>(mine, &units, lds);
-    u64 base = 255ull * units;
-    // what follows (any RLE block, Raw blocks), block after block, every thread on the same block
-    u32 pos = hdr + 4 * F, nt = 0; bool ok = true, done = false;
+    const u64 g = (u64)src;
+    u32 pos = hdr, nt = 0, other = 0, round = 0; u64 units = 0, base = 0; bool ok = true, done = false;   // (all of them the same in every thread; pos <= len)
     while (ok && !done) {
-        if (pos + 3 > len) { ok = false; break; }
-        const u32 h = (u32)mbuf[pos] | ((u32)mbuf[pos + 1] << 8) | ((u32)mbuf[pos + 2] << 16);
+        // RLE blocks of 0xFF units from pos on: the headers start at `hdr`, so they are words of any alignment
+        u64 mine = 0;
+        for (;;) {
+            const u32 left = (len - pos) / 4, n = left < 256 * MASK_RLE_RUN ? left : 256 * MASK_RLE_RUN;
+            u32 *first = &s_first[round++ & 1];              // (two slots: a round's readers and the next round's writer)
+            if (t == 0) *first = n;
+            __syncthreads();
+            u32 h[MASK_RLE_RUN], bad = n;
+#pragma unroll
+            for (u32 j = 0; j < MASK_RLE_RUN; j++) { const u32 i = j * 256 + t; h[j] = i < n ? ldg_at_unaligned<u32>(g + pos + 4 * i) : 0u; }
+#pragma unroll
+            for (u32 j = MASK_RLE_RUN; j-- > 0; ) { const u32 i = j * 256 + t; if (i < n && (h[j] & 0xFF000007u) != 0xFF000002u) bad = i; }   // value 255, RLE, not last
+            if (bad < n) atomicMin(first, bad);
+            __syncthreads();
+            const u32 F = *first;
+#pragma unroll
+            for (u32 j = 0; j < MASK_RLE_RUN; j++) if (j * 256 + t < F) mine += (h[j] & 0xFFFFFFu) >> 3;
+            pos += 4 * F;
+            if (F < 256 * MASK_RLE_RUN) break;
+        }
+        u64 run = 0;
+        wg_scan_inclusive<u64, OpAdd>(mine, &run, lds);
+        units += run; base += 255ull * run;
+        // the block that ended the run
+        if (len - pos < 3 || other == MASK_RLE_OTHER) { ok = false; break; }
+        other++;
+        const u32 h = (u32)src[pos] | ((u32)src[pos + 1] << 8) | ((u32)src[pos + 2] << 16);
         const u32 last = h & 1, type = (h >> 1) & 3, size = h >> 3;
         if (type == 1) {
-            if (pos + 4 > len) { ok = false; break; }
-            const u32 v = mbuf[pos + 3];
+            if (len - pos < 4) { ok = false; break; }
+            const u32 v = src[pos + 3];
             if (v != 255) {
                 if ((u64)nt + size > cap) { ok = false; break; }
                 for (u32 k = t; k < size; k += 256) toggles[nt + k] = base + (u64)v * (k + 1);
@@ -169,18 +189,28 @@ __global__ __launch_bounds__(256) void k_mask_rle_frame(const u8 *src, u32 len, 
             }
             base += (u64)v * size; units += size; pos += 4;
         } else if (type == 0) {
-            if ((u64)pos + 3 + size > len) { ok = false; break; }
-            const u8 *rb = mbuf + pos + 3;
-            const u32 per = (size + 255) / 256, lo = t * per < size ? t * per : size, hi = lo + per < size ? lo + per : size;
-            u64 sm = 0, cn = 0;
-            for (u32 k = lo; k < hi; k++) { const u32 u = rb[k]; sm += u; cn += u != 255; }
-            u64 tot_s, tot_c;
-            const u64 is = wg_scan_inclusive<u64, OpAdd>(sm, &tot_s, lds);
-            const u64 ic = wg_scan_inclusive<u64, OpAdd>(cn, &tot_c, lds);
-            if (nt + tot_c > cap) { ok = false; break; }
-            u64 at = base + is - sm; u32 idx = nt + (u32)(ic - cn);
-            for (u32 k = lo; k < hi; k++) { const u32 u = rb[k]; at += u; if (u != 255) toggles[idx++] = at; }
-            base += tot_s; nt += (u32)tot_c; units += size; pos += 3 + size;
+            if (len - pos - 3 < size) { ok = false; break; }
+            const u32 rb = pos + 3;
+            for (u32 o = 0; o < size && ok; o += MASK_RLE_STAGE) {
+                const u32 n = size - o < MASK_RLE_STAGE ? size - o : MASK_RLE_STAGE;
+                __syncthreads();                             // (the piece before this one has been read)
+                for (u32 i = 8 * t; i < n; i += 8 * 256) {
+                    if (i + 8 <= n) *(u64 *)(stage + i) = ldg_at_unaligned<u64>(g + rb + o + i);
+                    else for (u32 k = i; k < n; k++) stage[k] = src[rb + o + k];
+                }
+                __syncthreads();
+                const u32 per = (n + 255) / 256, lo = t * per < n ? t * per : n, hi = lo + per < n ? lo + per : n;
+                u64 sm = 0, cn = 0;
+                for (u32 k = lo; k < hi; k++) { const u32 u = stage[k]; sm += u; cn += u != 255; }
+                u64 tot_s, tot_c;
+                const u64 is = wg_scan_inclusive<u64, OpAdd>(sm, &tot_s, lds);
+                const u64 ic = wg_scan_inclusive<u64, OpAdd>(cn, &tot_c, lds);
+                if (nt + tot_c > cap) { ok = false; break; }
+                u64 at = base + is - sm; u32 idx = nt + (u32)(ic - cn);
+                for (u32 k = lo; k < hi; k++) { const u32 u = stage[k]; at += u; if (u != 255) toggles[idx++] = at; }
+                base += tot_s; nt += (u32)tot_c;
+            }
+            units += size; pos += 3 + size;
         } else ok = false;
         if (last) done = true;
     }
@@ -859,22 +889,35 @@ __global__ __launch_bounds__(256) void k_tile_index(EmitP P, u64 ntiles, TileIdx
     TileFlat f; f.q0 = f.A = f.q1 = f.A1 = f.q2 = f.qf = 0;
     u64 r = ~0ull; u32 cbits = 1;
     const bool inside = t < ntiles && p < P.out_end;              // (t == ntiles and the spare entries: the record of "behind the text")
+    // The record of the workgroup's FIRST tile and its table entries, looked up once per workgroup: everything here depends on
+    // blockIdx alone, so the search and the five loads are scalar.  A tile whose byte lies below the next record's start is in that
+    // record too -- one compare against a scalar; only the tiles behind a record boundary search, and from there on.  (Every thread
+    // ran the seven dependent vector loads of the search and four more for the entries, and they queue behind the kernel's own
+    // 2 GB of stores: profiles/tile_index_ablation.txt, 0.79 -> 0.43 ms at 100 GB without them.)
+    u64 r0 = 0, r0_out = 0, r0_next = 0, r0_hl = 0, r0_len = 0, r0_base = 0;
+    if (P.mode != EM_SEQ && P.N) {
+        r0 = upper_bound_u64(P.rec_out, 0, P.N + 1, P.out_begin + (u64)blockIdx.x * TILE_WG * 4096) - 1;
+        if (r0 >= P.N) r0 = P.N - 1;                                 // (workgroups behind the text)
+        r0_out = P.rec_out[r0]; r0_next = P.rec_out[r0 + 1]; r0_hl = P.hdr_len[r0]; r0_len = P.rec_len[r0]; r0_base = P.rec_base[r0];
+    }
     if (inside) {
         u64 g;
         if (P.mode == EM_SEQ) { r = 0; x.col = 0; g = p; x.gline = p; }
         else {
-            r = upper_bound_u64(P.rec_out, 0, P.N + 1, p) - 1;
-            u64 off = p - P.rec_out[r], hl = P.hdr_len[r], len = P.rec_len[r], j = 0;
+            const bool same = p < r0_next;
+            r = same ? r0 : upper_bound_u64(P.rec_out, r0 + 1, P.N + 1, p) - 1;
+            const u64 rbase = same ? r0_base : P.rec_base[r];
+            u64 off = p - (same ? r0_out : P.rec_out[r]), hl = same ? r0_hl : P.hdr_len[r], len = same ? r0_len : P.rec_len[r], j = 0;
             if (off >= hl) {
                 u64 q = off - hl;
                 if (P.mode == EM_FASTA && P.L) {
                     u64 line = q / (P.L + 1), col = q - line * (P.L + 1);
                     j = line * P.L + (col < P.L ? col : P.L);
-                    if (P.L < 0xFFFFFFF0ull) { x.gline = P.rec_base[r] + line * P.L; x.col = (u32)col; }
-                } else if (P.mode != EM_FASTQ) { j = q; x.col = 0; x.gline = P.rec_base[r] + q; }
+                    if (P.L < 0xFFFFFFF0ull) { x.gline = rbase + line * P.L; x.col = (u32)col; }
+                } else if (P.mode != EM_FASTQ) { j = q; x.col = 0; x.gline = rbase + q; }
                 if (j > len) j = len;
             }
-            g = P.rec_base[r] + j;
+            g = rbase + j;
         }
         x.k = P.masking ? upper_bound_u64(P.toggles, 0, P.n_toggles, g) : 0;
         if (tsig) {                                              // slot of the stream that holds the tile's first packed byte
@@ -1734,14 +1777,16 @@ static int side_lengths(naf_gpu_ctx *x, SideCall &S)
     return 0;
 }
 
-// mask stream -> toggle table, the shortcut: a frame of a few KB for MBs of units -- Raw / RLE blocks, one launch (NAF_GPU_MASK_RLE=0:
-// never).  *done: the table is made; else the frame is not of that kind and takes the decoder.
+// mask stream -> toggle table, the shortcut: a frame of a few KB or tens of KB for MBs of units -- Raw / RLE blocks of any number and
+// size, one launch and one read-back of 24 bytes (NAF_GPU_MASK_RLE=0: never).  The frame is read where it lies, so its size is bounded
+// only by the kernel's 32-bit positions; what bounds the work is the ratio (units at least twice the frame) and the kernel's own
+// count of blocks that are not 0xFF runs.  *done: the table is made; else the frame is not of that kind and takes the decoder.
 static int mask_rle_frame(naf_gpu_ctx *x, SideCall &S, bool *done)
 {
     const naf_gpu_header &h = S.h; EmitP &P = S.P;
     const u64 cs = h.comp_size[S_MASK], n_mask = h.orig_size[S_MASK];
     *done = false;
-    if (!(cs >= 4 && cs <= MASK_RLE_SRC && n_mask >= 2 * cs) || ctx_opt_is(x, "MASK_RLE", '0')) return 0;
+    if (!(cs >= 4 && cs <= 0x7FFFFFFFull && n_mask >= 2 * cs) || ctx_opt_is(x, "MASK_RLE", '0')) return 0;
     // Frame_Header (RFC 8878 3.1.1.1) of a frame without dictionary and checksum: descriptor, window byte, content size
     const u8 fhd = S.pl.frame_head[S_MASK][0];
     const u32 fcs_flag = fhd >> 6, single = (fhd >> 5) & 1;
@@ -1749,7 +1794,7 @@ static int mask_rle_frame(naf_gpu_ctx *x, SideCall &S, bool *done)
     if ((fhd & 0x0F) || hdr_size >= cs) return 0;                 // a reserved bit, a checksum, a dictionary id
     u64 *tg = arena_new<u64>(x, MASK_RLE_TOG + 1), *d_res = arena_new<u64>(x, 4);
     if (!tg || !d_res) return NAF_GPU_ENOMEM;
-    LAUNCH(x, "unnaf_mask_rle", k_mask_rle_frame, 1, 256, (u32)((cs + 15) & ~15ull), S.d_naf + h.payload_off[S_MASK], (u32)cs, hdr_size, n_mask, tg, MASK_RLE_TOG, d_res);
+    LAUNCH(x, "unnaf_mask_rle", k_mask_rle_frame, 1, 256, 0, S.d_naf + h.payload_off[S_MASK], (u32)cs, hdr_size, n_mask, tg, MASK_RLE_TOG, d_res);
     u64 res[3] = { 0, 0, 0 };
     int r = ctx_readback(x, res, d_res, 24); if (r) return r;
     if (res[0] == 1) { P.toggles = tg; P.n_toggles = res[1]; *done = true; }
