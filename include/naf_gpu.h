@@ -762,6 +762,73 @@ int  naf_gpu_unnaf_dedup(naf_gpu_ctx *ctx, const void *d_naf, size_t naf_len, co
                          const void *d_bounds /* or NULL */, naf_gpu_dedup_row *d_rows, size_t row_cap, uint64_t *n_records,
                          naf_gpu_dedup_total *h_total, uint64_t *h_levels /* NAF_GPU_DEDUP_LEVELS, or NULL */);
 
+/* ---- unnaf: reads screened against the k-mers of a reference archive, decided in the packed sequence stream -------------
+ * What bbduk.sh ref=phix.fa k=27, bbduk outm=, bbsplit and fastq_screen answer from the text -- which reads share k-mers with a contaminant
+ * (PhiX spike-in, rRNA, host, vector) or, mirrored, with a target -- as a table of (record, begin, end, hits, flags) rows, made without
+ * expanding the codes of either archive.  Integers only: the same bytes on every run, for every piece size and for every value of the
+ * two levers below.
+ *   K         opts.k, 1 to 31.  The key of a k-mer is naf_gpu_kmer_index's index in 64 bits: A = 0, C = 1, G = 2, T/U = 3, two bits a base,
+ *             the first base the most significant.  A key never reaches 2^62.
+ *   Valid     a k-mer is what naf_gpu_unnaf_kmers counts: K consecutive bases of ONE record, each stored as exactly A, C, G or T/U.  Any
+ *             other stored code invalidates every k-mer that covers it; case plays no part (no mask is decoded); bases behind the last
+ *             record of a malformed archive and the padding nibble of an odd stream are in no k-mer.
+ *   Set       the keys of all valid k-mers of ALL records of the archive at d_ref (DEVICE memory, ref_len bytes; FASTA or FASTQ, DNA or
+ *             RNA, U is T), each as min(key, key of its reverse complement) unless NAF_GPU_SCREEN_FORWARD_ONLY is in opts.flags: then as
+ *             stored.  A k-mer that would span two reference records is not in the set.  A reference without a valid k-mer -- or
+ *             without records -- is legal: no read matches.
+ *   Window    of read r: [begin_r, end_r) in bases of the record.  d_bounds == NULL: the whole record.  Otherwise d_bounds holds exactly
+ *             count rows (DEVICE memory of any alignment) written for the same first / count, opts.bounds_kind naming their layout:
+ *             NAF_GPU_SCREEN_BOUNDS_TRIM (40 bytes, the flags at byte 32: naf_gpu_unnaf_trim's rows, and this call's own),
+ *             NAF_GPU_SCREEN_BOUNDS_CLIP (40 bytes, flags at byte 36: naf_gpu_unnaf_clip's) or NAF_GPU_SCREEN_BOUNDS_DEDUP (48 bytes, flags
+ *             at byte 40: naf_gpu_unnaf_dedup's).  A record whose bounds row lacks NAF_GPU_TRIM_KEPT takes NO part: its row has hits = 0,
+ *             and flags, begin and end are the bounds row's as they came.
+ *   Hits      hits_r: the start positions x in [begin_r, end_r - K] whose k-mer is valid and whose key -- the canonical one unless
+ *             FORWARD_ONLY -- is in the set.  Every position counts; a k-mer equal to its own reverse complement counts once.
+ *   Verdict   a read is matched iff hits_r >= opts.min_hits (at least 1).  A matched read is dropped -- the filter --; with
+ *             NAF_GPU_SCREEN_KEEP_MATCHED an unmatched one is dropped instead.
+ *   Rows      exactly one per selected record, ascending: a naf_gpu_trim_row with hits where ee stands, so naf_gpu_unnaf_dedup takes
+ *             them as NAF_GPU_DEDUP_BOUNDS_TRIM and the chain trim, clip, screen, dedup never leaves the device.  reserved is 0.  flags
+ *             of a read that takes part: NAF_GPU_SCREEN_MATCHED iff it matched, NAF_GPU_TRIM_KEPT iff it is kept under the verdict; the
+ *             bounds row's NAF_GPU_CLIP_CLIPPED is carried.  d_rows is DEVICE memory of any alignment; exactly 40 * n_records bytes
+ *             are written and nothing else.  d_rows == NULL: the totals only.  With row_cap too small the call returns NAF_GPU_ECAP,
+ *             sets *n_records and writes nothing.
+ *   Total     h_total (HOST memory, may be NULL), integer sums all: reads (the selected records), considered (those that take part),
+ *             matched, kept (rows of reads that take part with NAF_GPU_TRIM_KEPT), bases (of the windows that take part), kept_bases,
+ *             kmers (the valid start positions in the windows that take part), hit_kmers (those of them that hit); ref_records and
+ *             ref_bases (the reference's records and their bases), ref_positions (its valid start positions), ref_kmers (the distinct
+ *             keys in the set).
+ *   Errors    NAF_GPU_EARG, last_error saying which: k outside 1 to 31; min_hits 0; unknown flag bits; an unknown bounds_kind; a lever
+ *             with a value it does not have; a protein or text archive on either side ("reads cannot be screened in %s sequences");
+ *             either archive without a sequence section; first > n_sequences or a range past the last record, as for
+ *             naf_gpu_unnaf_clip; a bounds row whose record is not first + its number, whose begin > end or whose end > the record's
+ *             length (found on the device; nothing is written to d_rows then, *n_records and *h_total are 0).  A reads archive without
+ *             records gives 0 rows.
+ *   Pieces    both archives are decoded and swept in pieces of whole records of at most NAF_GPU_SCREEN_PIECE bases (default 2^31): of
+ *             the reads only the zstd blocks behind the selected records where the frame allows it, the reference whole.  The set lives
+ *             in the context's scratch for the call: a table of 8-byte slots, the power of two that is at least 2 * ref_bases (64 at the
+ *             least).  When that cannot be had the call returns NAF_GPU_ENOMEM and last_error names the table.
+ *   Levers    NAF_GPU_SCREEN_HASH_BITS=b (0 to 64) cuts the hash that chooses a key's slot to its low b bits, so that different keys
+ *             truly share probe chains; NAF_GPU_SCREEN_FILTER_BITS=n sets the bits of the prefilter -- a bitmap with one bit per key of
+ *             the set, copied into LDS, that answers "not in the set" for most positions of a clean read without a look at the table --
+ *             to n, 0 or a power of two from 64 to 2^19 (default 2^18); 0 switches it off and every valid position probes the table.  Left at its default the bitmap is
+ *             only used while the set has at most half as many keys as it has bits: a fuller one lets most positions through.
+ *             Neither changes the rows or the totals by a byte.
+ * A kept row's (record, begin, end) is what naf_gpu_unnaf_select_reads takes.
+ * TRACE=1: "[screen] k K ref records R ref kmers U of V slots S filter bits F reads N considered C matched M filtered Q probed P sequence
+ * bytes decoded X of Y" per call that reaches the sweeps (U distinct keys of V valid reference positions; Q and P: the valid read
+ * positions the prefilter rejected and let through to the table -- the bitmap is a function of the set, so both are the same on every
+ * run; X of Y: of the reads' sequence stream). */
+enum { NAF_GPU_SCREEN_MATCHED = 32 };             /* beside NAF_GPU_TRIM_KEPT and NAF_GPU_CLIP_CLIPPED in naf_gpu_screen_row.flags */
+enum { NAF_GPU_SCREEN_KEEP_MATCHED = 1, NAF_GPU_SCREEN_FORWARD_ONLY = 2 };     /* opts.flags */
+enum { NAF_GPU_SCREEN_BOUNDS_TRIM = 0, NAF_GPU_SCREEN_BOUNDS_CLIP = 1, NAF_GPU_SCREEN_BOUNDS_DEDUP = 2 };
+typedef struct { uint32_t k, flags, bounds_kind; uint64_t min_hits; } naf_gpu_screen_opts;
+typedef struct { uint64_t record, begin, end, hits; uint32_t flags, reserved; } naf_gpu_screen_row;   /* 40 bytes */
+typedef struct { uint64_t reads, considered, matched, kept, bases, kept_bases, kmers, hit_kmers, ref_records, ref_bases, ref_positions, ref_kmers; } naf_gpu_screen_total;
+
+int  naf_gpu_unnaf_screen(naf_gpu_ctx *ctx, const void *d_naf, size_t naf_len, const void *d_ref, size_t ref_len, const naf_gpu_screen_opts *opts,
+                          uint64_t first, uint64_t count, const void *d_bounds /* or NULL */, naf_gpu_screen_row *d_rows, size_t row_cap,
+                          uint64_t *n_records, naf_gpu_screen_total *h_total);
+
 /* ---- ennaf ------------------------------------------------------------------------------------------ */
 typedef struct {
     int      format;            /* NAF_FMT_* (AUTO = sniff, process.c:547-583) */

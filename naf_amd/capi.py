@@ -42,6 +42,7 @@ EXPORTS = [
     "naf_gpu_trim_limit", "naf_gpu_unnaf_trim", "naf_gpu_unnaf_select_reads_size", "naf_gpu_unnaf_select_reads",
     "naf_gpu_clip_budgets", "naf_gpu_unnaf_clip",
     "naf_gpu_dedup_level", "naf_gpu_unnaf_dedup",
+    "naf_gpu_unnaf_screen",
 ]
 WHOLE = 2 ** 64 - 1                     # NAF_GPU_WHOLE: (record, 0, WHOLE) is the record as stored
 MAX_SHARDS = 64
@@ -274,6 +275,32 @@ DEDUP_BOUNDS_TRIM, DEDUP_BOUNDS_CLIP = 0, 1
 DEDUP_LEVELS = 16
 
 
+class ScreenOpts(C.Structure):
+    """naf_gpu_screen_opts: K (1 to 31); SCREEN_KEEP_MATCHED | SCREEN_FORWARD_ONLY or 0; which call wrote the bounds rows (SCREEN_BOUNDS_TRIM,
+    _CLIP, _DEDUP); the hits that make a read matched (1 or more)."""
+    _fields_ = [("k", C.c_uint32), ("flags", C.c_uint32), ("bounds_kind", C.c_uint32), ("min_hits", C.c_uint64)]
+
+
+class ScreenTotal(C.Structure):
+    """naf_gpu_screen_total: the reads of a call, those that take part, those matched, those kept, the bases of the windows that take part
+    and of the kept ones, the valid k-mer positions in those windows and the ones that hit; the reference's records, bases, valid positions
+    and distinct keys."""
+    _fields_ = [("reads", C.c_uint64), ("considered", C.c_uint64), ("matched", C.c_uint64), ("kept", C.c_uint64), ("bases", C.c_uint64),
+                ("kept_bases", C.c_uint64), ("kmers", C.c_uint64), ("hit_kmers", C.c_uint64), ("ref_records", C.c_uint64), ("ref_bases", C.c_uint64),
+                ("ref_positions", C.c_uint64), ("ref_kmers", C.c_uint64)]
+
+
+# numpy's view of a table of naf_gpu_screen_row: bases [begin, end) of `record` are its window, `hits` of its k-mers are in the reference's
+# set; flags: SCREEN_MATCHED, TRIM_KEPT (kept under the verdict) and CLIP_CLIPPED carried -- of a record that takes no part the bounds
+# row's flags.  A trim row with hits where ee stands: unnaf_dedup takes the table as bounds_kind "trim".
+SCREEN_DTYPE = [("record", "<u8"), ("begin", "<u8"), ("end", "<u8"), ("hits", "<u8"), ("flags", "<u4"), ("reserved", "<u4")]
+SCREEN_BYTES = 40
+SCREEN_MATCHED = 32
+SCREEN_KEEP_MATCHED, SCREEN_FORWARD_ONLY = 1, 2
+SCREEN_BOUNDS_TRIM, SCREEN_BOUNDS_CLIP, SCREEN_BOUNDS_DEDUP = 0, 1, 2
+SCREEN_MAX_K = 31
+
+
 class NafGpuError(RuntimeError):
     def __init__(self, code, msg):
         super().__init__("naf_gpu error %d: %s" % (code, msg))
@@ -406,6 +433,7 @@ def load():
         L.naf_gpu_unnaf_clip.argtypes = [vp, vp, sz, C.c_char_p, sz, sz, u8p, C.POINTER(ClipOpts), C.c_uint64, C.c_uint64, vp, vp, sz, u64p, C.POINTER(ClipTotal), u64p]
         L.naf_gpu_dedup_level.argtypes = [C.c_uint64, C.POINTER(C.c_uint)]
         L.naf_gpu_unnaf_dedup.argtypes = [vp, vp, sz, C.POINTER(DedupOpts), C.c_uint64, C.c_uint64, vp, vp, sz, u64p, C.POINTER(DedupTotal), u64p]
+        L.naf_gpu_unnaf_screen.argtypes = [vp, vp, sz, vp, sz, C.POINTER(ScreenOpts), C.c_uint64, C.c_uint64, vp, vp, sz, u64p, C.POINTER(ScreenTotal)]
         L.naf_gpu_unnaf_select_reads_size.argtypes = [vp, vp, sz, C.POINTER(UnnafOpts), C.POINTER(Segment), u8p, sz, C.POINTER(sz)]
         L.naf_gpu_unnaf_select_reads.argtypes = [vp, vp, sz, C.POINTER(UnnafOpts), C.POINTER(Segment), u8p, sz, vp, sz, C.POINTER(sz)]
         _lib = L
@@ -539,6 +567,11 @@ def dedup_level(copies):
 
 def dedup_to_segments(rows):
     """The (record, begin, end) tuples unnaf_select_reads takes: the firsts of the table unnaf_dedup returns, in its order."""
+    return [(int(x["record"]), int(x["begin"]), int(x["end"])) for x in rows if int(x["flags"]) & TRIM_KEPT]
+
+
+def screen_to_segments(rows):
+    """The (record, begin, end) tuples unnaf_select_reads takes: the kept reads of the table unnaf_screen returns, in its order."""
     return [(int(x["record"]), int(x["begin"]), int(x["end"])) for x in rows if int(x["flags"]) & TRIM_KEPT]
 
 
@@ -1328,6 +1361,37 @@ class Context:
             return None, tot, levels
         view = buf[:DEDUP_BYTES * n.value]
         return (np.frombuffer(view.cpu().numpy().tobytes(), dtype=DEDUP_DTYPE) if own else view), tot, levels
+
+    def unnaf_screen(self, d_naf, d_ref, k=27, min_hits=1, keep_matched=False, forward_only=False, bounds=None, bounds_kind="trim", first=0, count=None, out=None):
+        """(rows, total): records [first, first + count) of the archive d_naf screened against the k-mers of ALL records of the archive d_ref
+        (naf_gpu_unnaf_screen; both uint8 device tensors) -- k: 1 to 31; a read with min_hits or more k-mers in the reference's set is
+        matched, and dropped unless keep_matched, which drops the others; forward_only: the k-mers as stored, not the smaller of a k-mer
+        and its reverse complement; bounds: a uint8 device tensor of the rows unnaf_trim or unnaf_screen (bounds_kind "trim"), unnaf_clip
+        ("clip") or unnaf_dedup ("dedup") wrote for the same records, whose (begin, end) are screened instead of the whole reads and whose
+        rows without TRIM_KEPT take no part -- as a structured numpy array (SCREEN_DTYPE), one row per read, and a ScreenTotal.  out: a
+        uint8 device tensor to take the table (40 bytes a row); then `rows` is the torch view of its first 40 * n bytes and too small a
+        tensor raises NafGpuError(E_CAP).  out=False: the totals only."""
+        import numpy as np
+        import torch
+        kinds = {"trim": SCREEN_BOUNDS_TRIM, "clip": SCREEN_BOUNDS_CLIP, "dedup": SCREEN_BOUNDS_DEDUP}
+        if bounds_kind not in kinds and not isinstance(bounds_kind, int):
+            raise ValueError("bounds_kind: 'trim', 'clip' or 'dedup', not %r" % (bounds_kind,))
+        o = ScreenOpts(int(k), (SCREEN_KEEP_MATCHED if keep_matched else 0) | (SCREEN_FORWARD_ONLY if forward_only else 0), kinds.get(bounds_kind, bounds_kind), int(min_hits))
+        n, tot = C.c_uint64(), ScreenTotal()
+        cnt = WHOLE if count is None else int(count)
+        own = out is None
+        if own:
+            have = int(self.parse_header(d_naf).n_sequences)
+            rows = max(0, min(have - int(first), cnt)) if cnt != WHOLE else max(0, have - int(first))
+            out = torch.empty(max(SCREEN_BYTES * rows, 1), dtype=torch.uint8, device=self.device)
+        buf = None if out is False else out
+        self._check(self.L.naf_gpu_unnaf_screen(self.h, _ptr(d_naf), d_naf.numel(), _ptr(d_ref), d_ref.numel(), C.byref(o), int(first), cnt,
+                                                _ptr(bounds) if bounds is not None else None, _ptr(buf) if buf is not None else None,
+                                                buf.numel() // SCREEN_BYTES if buf is not None else 0, C.byref(n), C.byref(tot)))
+        if buf is None:
+            return None, tot
+        view = buf[:SCREEN_BYTES * n.value]
+        return (np.frombuffer(view.cpu().numpy().tobytes(), dtype=SCREEN_DTYPE) if own else view), tot
 
     @staticmethod
     def _run_class(cls, each, masked):

@@ -2474,6 +2474,7 @@ extern "C" int naf_gpu_unnaf_range(naf_gpu_ctx *c, const void *d_naf, size_t naf
 #include "trim.h"
 #include "clip.h"
 #include "dedup.h"
+#include "screen.h"
 
 // ---- byte histogram (unnaf --charcount, output.c:515-605) ------------------------------------------------------------------
 __global__ __launch_bounds__(256) void k_histogram(const u8 *p, u64 n, unsigned long long *counts)

@@ -58,11 +58,13 @@ static int payload_range(naf_gpu_ctx *c, const u8 *d_naf, const UnnafPlan &pl, i
 // arena_reset, the record tables of --sequences (lengths only, no ids; the mask with FRONT_MASK) and the checks of first / count.
 // who: the caller's name in the messages; cannot: what it cannot do "in protein sequences" when it needs FRONT_4BIT.  FRONT_QUALITY: a
 // quality section, and a sequence section of any type for its lengths.  *count comes back resolved (NAF_GPU_WHOLE = to the last
-// record); 0 = nothing to do, and the side sections were then not made.
+// record); 0 = nothing to do, and the side sections were then not made.  reset = false: the front of a call's SECOND archive, whose
+// tables go behind the first's.
 enum { FRONT_4BIT = 1, FRONT_MASK = 2, FRONT_QUALITY = 4 };
-static int records_front(naf_gpu_ctx *c, const u8 *d_naf, size_t naf_len, int needs, const char *who, const char *cannot, u64 first, u64 *count, UnnafPlan &pl)
+static int records_front(naf_gpu_ctx *c, const u8 *d_naf, size_t naf_len, int needs, const char *who, const char *cannot, u64 first, u64 *count, UnnafPlan &pl,
+                         bool reset = true)
 {
-    arena_reset(c);
+    if (reset) arena_reset(c);
     naf_gpu_unnaf_opts o = { NAF_OUT_SEQUENCES, needs & FRONT_MASK ? 1 : 0, -1 };
     int rc = unnaf_prepare(c, d_naf, naf_len, &o, pl); if (rc) return rc;
     const naf_gpu_header &h = pl.h;

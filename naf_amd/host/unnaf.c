@@ -55,6 +55,11 @@ static naf_gpu_clip_opts clip_opts = { 3, 1 }; static bool min_overlap_given = f
 /* --dedup [--either-strand] [--dedup-table] [--trim Q|none ...] [--adapter SEQ ...]: every distinct read once -- the first of its copies --, behind
  * the quality trimming and the adapter clipping when there are any, or the table of the classes (this implementation only) */
 static bool dedup = false, either_strand = false, dedup_table = false;
+/* --screen REF.naf [--screen-k K] [--min-hits N] [--keep-matched] [--forward-only] [--screen-table] [--trim ...] [--adapter ...] [--dedup ...]: the reads
+ * that share no k-mer with the archive REF.naf (with --keep-matched: those that do), behind the quality trimming and the adapter clipping and in
+ * front of the duplicate collapsing when there are any, or the table of the hits (this implementation only) */
+static const char *screen_ref = NULL; static naf_gpu_screen_opts screen_opts = { 27, 0, 0, 1 };
+static bool screen_k_given = false, min_hits_given = false, keep_matched = false, forward_only = false, screen_table = false;
 
 static void done(int status, void *arg)
 {
@@ -208,6 +213,19 @@ static void set_repeats(const char *v)
     repeats_text = v;
 }
 
+static void set_screen(const char *v)
+{
+    if (screen_ref) die("only one --screen reference can be given\n");
+    if (!*v) die("empty --screen parameter\n");
+    screen_ref = v;
+}
+static void set_screen_k(const char *v)
+{
+    unsigned long long a = 0;
+    if (!number_of(v, strlen(v), &a) || a < 1 || a > 31) die("can't parse the value of --screen-k parameter (a k-mer length of 1 to 31)\n");
+    screen_opts.k = (uint32_t)a; screen_k_given = true;
+}
+
 static void set_kmers(const char *v)
 {
     if (kmers_k) die("only one --kmers length can be counted at a time\n");
@@ -316,6 +334,14 @@ static void show_help(void)
         "  --repeats SPEC  - Every perfect tandem repeat, as lines \"ID begin end PERIOD MOTIF COPIES CLASS\" (0-based half-open): SPEC is PERIOD-COPIES pairs, e.g. 1-10,2-6,3-5, periods 1 to 16; or misa\n"
         "  --min-repeat N  - With --repeats: only repeats of at least N bases (default 1)\n"
         "  --whole-units   - With --repeats: the end of a repeat is cut to a whole number of copies, as MISA and PERF print it\n"
+        "Options for screening reads against a reference (output: the reads that share no k-mer with it, as --fastq, --fasta, --sequences or --seq; with at most one --records A-B or --region ID):\n"
+        "  --screen REF.naf - Drop every read that has a k-mer of the archive REF.naf (FASTA or FASTQ, DNA or RNA; make it with ennaf), on either strand; k-mers are made of A, C, G, T/U only\n"
+        "                    and never run across a sequence's end. With --trim Q and / or --adapter SEQ the reads are trimmed and clipped first; with --dedup the kept reads are collapsed afterwards\n"
+        "  --screen-k K    - With --screen: the k-mer length, 1 to 31 (default 27)\n"
+        "  --min-hits N    - With --screen: a read matches when N of its k-mers are in the reference (default 1)\n"
+        "  --keep-matched  - With --screen: keep the reads that match and drop the others\n"
+        "  --forward-only  - With --screen: compare the k-mers as stored, not also their reverse complements\n"
+        "  --screen-table  - With --screen: instead of the reads, a table \"#seq length begin end hits status\" of all reads (status clean, matched, or short / errors / duplicate)\n"
         "Options for collapsing duplicate reads (output: every distinct read once, the first of its copies, as --fastq, --fasta, --sequences or --seq; with at most one --records A-B or --region ID):\n"
         "  --dedup         - Drop every read whose bases are exactly those of an earlier read; case, qualities and names play no part, N equals only N.\n"
         "                    With --trim Q and / or --adapter SEQ the reads are trimmed and clipped first, and what is left of them is compared and written\n"
@@ -335,7 +361,7 @@ static void show_help(void)
 }
 
 /* ---- the table modes ---------------------------------------------------------------------------------------------------------------
- * --locate, --composition, --quality, --runs / --masked-runs, --kmers, --orfs, --translate, --repeats, --dedup, --adapter and --trim write a table of their own
+ * --locate, --composition, --quality, --runs / --masked-runs, --kmers, --orfs, --translate, --repeats, --screen, --dedup, --adapter and --trim write a table of their own
  * instead of an output type (--trim without --trim-table: the reads, in one of the sequence output types).  A mode is a row here -- what its refusals say, its options, its runner -- plus the checks that are
  * really its own; parse_command_line walks the rows once, in this order, and main runs the first one asked for (--orfs in front
  * of --translate: the one legal pair). */
@@ -353,10 +379,10 @@ typedef struct table_mode {
     const char *protein;                            /* main's refusal of protein and text archives (%s: which), NULL: none */
     void (*run)(bool has_ids, bool has_names);
 } table_mode;
-enum { M_LOCATE, M_COMPOSITION, M_QUALITY, M_RUNS, M_KMERS, M_ORFS, M_TRANSLATE, M_REPEATS, M_DEDUP, M_CLIP, M_TRIM, N_MODES };
+enum { M_LOCATE, M_COMPOSITION, M_QUALITY, M_RUNS, M_KMERS, M_ORFS, M_TRANSLATE, M_REPEATS, M_SCREEN, M_DEDUP, M_CLIP, M_TRIM, N_MODES };
 static table_mode modes[N_MODES];
 static void run_locate(bool, bool), run_composition(bool, bool), run_quality(bool, bool), run_runs(bool, bool), run_kmers(bool, bool), run_orfs(bool, bool),
-            run_translate(bool, bool), run_repeats(bool, bool), run_dedup(bool, bool), run_clip(bool, bool), run_trim(bool, bool);
+            run_translate(bool, bool), run_repeats(bool, bool), run_screen(bool, bool), run_dedup(bool, bool), run_clip(bool, bool), run_trim(bool, bool);
 
 static void refuse_output_type(const table_mode *m)
 {
@@ -416,6 +442,14 @@ static void dedup_own(const table_mode *m)
     if (clip_table) die("--clip-table can't be used with --dedup: --dedup-table writes the table of the collapsed reads\n");
 }
 
+static void screen_own(const table_mode *m)
+{
+    (void)m;
+    if (trim_table) die("--trim-table can't be used with --screen: --screen-table writes the table of the screened reads\n");
+    if (clip_table) die("--clip-table can't be used with --screen: --screen-table writes the table of the screened reads\n");
+    if (dedup_table) die("--dedup-table can't be used with --screen: --screen-table writes the table of the screened reads\n");
+}
+
 /* the rows, from the options as they were given */
 static void fill_modes(void)
 {
@@ -446,6 +480,13 @@ static void fill_modes(void)
     modes[M_REPEATS] = (table_mode){ .asked = repeats_text != NULL, .name = "--repeats", .writes = "a table", .strands = "lists the sequences as stored", .one_selection = true,
         .sat = { { min_repeat_given, repeats_text != NULL, "--min-repeat can be used only with --repeats\n" }, { whole_units, repeats_text != NULL, "--whole-units can be used only with --repeats\n" } },
         .protein = "tandem repeats cannot be listed in %s sequences\n", .run = run_repeats };
+    /* --screen stands in front of --dedup, --adapter and --trim, the three modes it can be used with: main then runs it; it trims and clips first and collapses last */
+    modes[M_SCREEN] = (table_mode){ .asked = screen_ref != NULL, .name = "--screen", .writes = screen_table ? "a table" : "reads as --fastq, --fasta, --sequences or --seq",
+        .strands = "writes the reads as stored", .one_selection = true, .type_first = true, .sequence_types = !screen_table,
+        .sat = { { screen_k_given, screen_ref != NULL, "--screen-k can be used only with --screen\n" }, { min_hits_given, screen_ref != NULL, "--min-hits can be used only with --screen\n" },
+                 { keep_matched, screen_ref != NULL, "--keep-matched can be used only with --screen\n" }, { forward_only, screen_ref != NULL, "--forward-only can be used only with --screen\n" },
+                 { screen_table, screen_ref != NULL, "--screen-table can be used only with --screen\n" } },
+        .own = screen_own, .protein = "reads cannot be screened in %s sequences\n", .run = run_screen };
     /* --dedup stands in front of --adapter and --trim, the two modes it can be used with: main then runs it, and it trims and clips first */
     modes[M_DEDUP] = (table_mode){ .asked = dedup, .name = "--dedup", .writes = dedup_table ? "a table" : "reads as --fastq, --fasta, --sequences or --seq",
         .strands = "writes the reads as stored", .one_selection = true, .type_first = true, .sequence_types = !dedup_table,
@@ -479,7 +520,7 @@ static void parse_command_line(int argc, char **argv)
         {"--fasta", FASTA}, {"--fastq", FASTQ}, {"--dna", DNA}, {"--masked-dna", MASKED_DNA}, {"--unmasked-dna", UNMASKED_DNA},
         {"--masked-fasta", MASKED_FASTA}, {"--unmasked-fasta", UNMASKED_FASTA} };
     /* the other options (unnaf/src/unnaf.c:282-353), as a table: one that takes a value is only recognised with an argument behind it */
-    enum { OP_LINE_LENGTH, OP_OUT, OP_NO_MASK, OP_IGNORED, OP_HELP, OP_VERBOSE, OP_VERSION, OP_STDOUT, OP_REGION, OP_RECORDS, OP_RC_REGION, OP_REVCOMP, OP_LOCATE, OP_STRAND, OP_MISMATCHES, OP_COMPOSITION, OP_WINDOW, OP_QUALITY, OP_CYCLES, OP_RUNS, OP_MASKED_RUNS, OP_MIN_RUN, OP_EACH, OP_KMERS, OP_CANONICAL, OP_PER_RECORD, OP_ORFS, OP_MIN_ORF, OP_STOPS, OP_STARTS, OP_STOP_TO_STOP, OP_CLOSED, OP_SPLIT_UNKNOWN, OP_TRANSLATE, OP_FRAME, OP_CODE, OP_CODE_TABLE, OP_REPEATS, OP_MIN_REPEAT, OP_WHOLE_UNITS, OP_TRIM, OP_MIN_LENGTH, OP_MAX_EE, OP_TRIM_TABLE, OP_ADAPTER, OP_ADAPTER_ERRORS, OP_MIN_OVERLAP, OP_CLIP_TABLE, OP_DEDUP, OP_EITHER_STRAND, OP_DEDUP_TABLE };
+    enum { OP_LINE_LENGTH, OP_OUT, OP_NO_MASK, OP_IGNORED, OP_HELP, OP_VERBOSE, OP_VERSION, OP_STDOUT, OP_REGION, OP_RECORDS, OP_RC_REGION, OP_REVCOMP, OP_LOCATE, OP_STRAND, OP_MISMATCHES, OP_COMPOSITION, OP_WINDOW, OP_QUALITY, OP_CYCLES, OP_RUNS, OP_MASKED_RUNS, OP_MIN_RUN, OP_EACH, OP_KMERS, OP_CANONICAL, OP_PER_RECORD, OP_ORFS, OP_MIN_ORF, OP_STOPS, OP_STARTS, OP_STOP_TO_STOP, OP_CLOSED, OP_SPLIT_UNKNOWN, OP_TRANSLATE, OP_FRAME, OP_CODE, OP_CODE_TABLE, OP_REPEATS, OP_MIN_REPEAT, OP_WHOLE_UNITS, OP_TRIM, OP_MIN_LENGTH, OP_MAX_EE, OP_TRIM_TABLE, OP_ADAPTER, OP_ADAPTER_ERRORS, OP_MIN_OVERLAP, OP_CLIP_TABLE, OP_DEDUP, OP_EITHER_STRAND, OP_DEDUP_TABLE, OP_SCREEN, OP_SCREEN_K, OP_MIN_HITS, OP_KEEP_MATCHED, OP_FORWARD_ONLY, OP_SCREEN_TABLE };
     static const struct { const char *name; int op; bool value; } option_table[] = {
         { "--line-length", OP_LINE_LENGTH, true }, { "-o", OP_OUT, true }, { "--no-mask", OP_NO_MASK, false }, { "--binary-stdout", OP_IGNORED, false },
         { "--binary-stderr", OP_IGNORED, false }, { "--binary", OP_IGNORED, false }, { "--help", OP_HELP, false }, { "-h", OP_HELP, false },
@@ -495,7 +536,9 @@ static void parse_command_line(int argc, char **argv)
         { "--repeats", OP_REPEATS, true }, { "--min-repeat", OP_MIN_REPEAT, true }, { "--whole-units", OP_WHOLE_UNITS, false },
         { "--trim", OP_TRIM, true }, { "--min-length", OP_MIN_LENGTH, true }, { "--max-ee", OP_MAX_EE, true }, { "--trim-table", OP_TRIM_TABLE, false },
         { "--adapter", OP_ADAPTER, true }, { "--adapter-errors", OP_ADAPTER_ERRORS, true }, { "--min-overlap", OP_MIN_OVERLAP, true }, { "--clip-table", OP_CLIP_TABLE, false },
-        { "--dedup", OP_DEDUP, false }, { "--either-strand", OP_EITHER_STRAND, false }, { "--dedup-table", OP_DEDUP_TABLE, false } };
+        { "--dedup", OP_DEDUP, false }, { "--either-strand", OP_EITHER_STRAND, false }, { "--dedup-table", OP_DEDUP_TABLE, false },
+        { "--screen", OP_SCREEN, true }, { "--screen-k", OP_SCREEN_K, true }, { "--min-hits", OP_MIN_HITS, true }, { "--keep-matched", OP_KEEP_MATCHED, false },
+        { "--forward-only", OP_FORWARD_ONLY, false }, { "--screen-table", OP_SCREEN_TABLE, false } };
     for (int i = 1; i < argc; i++) {
         char *arg = argv[i];
         if (arg[0] != '-') {
@@ -563,6 +606,12 @@ static void parse_command_line(int argc, char **argv)
         case OP_DEDUP: dedup = true; break;
         case OP_EITHER_STRAND: either_strand = true; break;
         case OP_DEDUP_TABLE: dedup_table = true; break;
+        case OP_SCREEN: set_screen(v); break;
+        case OP_SCREEN_K: set_screen_k(v); break;
+        case OP_MIN_HITS: screen_opts.min_hits = positive_number("--min-hits", "k-mers", v); min_hits_given = true; break;
+        case OP_KEEP_MATCHED: keep_matched = true; break;
+        case OP_FORWARD_ONLY: forward_only = true; break;
+        case OP_SCREEN_TABLE: screen_table = true; break;
         }
     }
     if (print_version) {
@@ -580,7 +629,8 @@ static void parse_command_line(int argc, char **argv)
         if (m->type_first) refuse_output_type(m);
         for (const table_mode *e = modes; e < m; e++)
             if (e->asked && !(e == &modes[M_ORFS] && m == &modes[M_TRANSLATE]) && !(e == &modes[M_CLIP] && m == &modes[M_TRIM]) &&
-                !(e == &modes[M_DEDUP] && (m == &modes[M_CLIP] || m == &modes[M_TRIM]))) die("%s and %s can't be used together\n", m->name, e->name);
+                !(e == &modes[M_DEDUP] && (m == &modes[M_CLIP] || m == &modes[M_TRIM])) &&
+                !(e == &modes[M_SCREEN] && (m == &modes[M_DEDUP] || m == &modes[M_CLIP] || m == &modes[M_TRIM]))) die("%s and %s can't be used together\n", m->name, e->name);
         refuse_output_type(m);
         if (m->own) m->own(m);
         if (m->one_selection) one_whole_selection(m);
@@ -1281,6 +1331,127 @@ static void run_dedup(bool has_ids, bool has_names)
         if (sel_buf) { naf_gpu_free(gpu, sel_buf); sel_buf = NULL; sel_cap = 0; }
     }
     if (n_adapters) free(clip.blob);
+}
+
+/* --screen: naf_gpu_unnaf_screen -- the reference's k-mers in a table on the device, the windows of all selected reads probed in one sweep over
+ * the packed stream, a row per read.  With --trim and / or --adapter the trim rows and then the clip rows are made first and are the screen
+ * call's bounds; with --dedup the screen rows are the dedup call's, as trim rows, and the table written is dedup's.  Nothing but the last
+ * table leaves the device -- and, for --screen-table with --dedup, the screen rows, whose hits the lines carry. */
+static void *d_screen_ref = NULL; static size_t screen_ref_len = 0;
+static naf_gpu_screen_row *screen_host = NULL;                      /* --screen-table with --dedup: the screen rows of records rng_first .. */
+static uint64_t fill_screen(void *d, size_t cap)
+{
+    uint64_t got = 0; void *d_trim = NULL, *d_clip = NULL, *d_scr = d;
+    if (trim_text) {
+        GPU_TRY(naf_gpu_malloc(gpu, cap * sizeof(naf_gpu_trim_row), &d_trim));
+        GPU_TRY(naf_gpu_unnaf_trim(gpu, d_naf, naf_len, &trim_opts, rng_first, rng_count, (naf_gpu_trim_row *)d_trim, cap, &got, NULL));
+        if (got != cap) die("can't decompress quality\n");
+        phase("screen: trim rows");
+    }
+    if (n_adapters) {
+        GPU_TRY(naf_gpu_malloc(gpu, cap * sizeof(naf_gpu_clip_row), &d_clip));
+        GPU_TRY(naf_gpu_unnaf_clip(gpu, d_naf, naf_len, clip.blob, clip.bytes, n_adapters, &clip.budget[0][0], &clip_opts, rng_first, rng_count,
+                                   (const naf_gpu_trim_row *)d_trim, (naf_gpu_clip_row *)d_clip, cap, &got, NULL, NULL));
+        if (got != cap) die("can't decompress sequence\n");
+        phase("screen: clip rows");
+    }
+    if (dedup) GPU_TRY(naf_gpu_malloc(gpu, cap * sizeof(naf_gpu_screen_row), &d_scr));
+    naf_gpu_screen_opts o = screen_opts;
+    o.flags = (keep_matched ? NAF_GPU_SCREEN_KEEP_MATCHED : 0) | (forward_only ? NAF_GPU_SCREEN_FORWARD_ONLY : 0);
+    o.bounds_kind = d_clip ? NAF_GPU_SCREEN_BOUNDS_CLIP : NAF_GPU_SCREEN_BOUNDS_TRIM;
+    GPU_TRY(naf_gpu_unnaf_screen(gpu, d_naf, naf_len, d_screen_ref, screen_ref_len, &o, rng_first, rng_count, d_clip ? d_clip : d_trim, (naf_gpu_screen_row *)d_scr, cap, &got, NULL));
+    if (d_trim) naf_gpu_free(gpu, d_trim);
+    if (d_clip) naf_gpu_free(gpu, d_clip);
+    if (dedup) {
+        if (got != cap) die("can't decompress sequence\n");
+        phase("screen: screen rows");
+        if (screen_table) {
+            screen_host = (naf_gpu_screen_row *)malloc((cap + 1) * sizeof *screen_host); if (!screen_host) die("can't allocate memory\n");
+            GPU_TRY(naf_gpu_download(gpu, screen_host, d_scr, cap * sizeof *screen_host));
+        }
+        const naf_gpu_dedup_opts od = { either_strand ? NAF_GPU_DEDUP_BOTH_STRANDS : 0, NAF_GPU_DEDUP_BOUNDS_TRIM };
+        GPU_TRY(naf_gpu_unnaf_dedup(gpu, d_naf, naf_len, &od, rng_first, rng_count, d_scr, (naf_gpu_dedup_row *)d, cap, &got, NULL, NULL));
+        naf_gpu_free(gpu, d_scr);
+    }
+    return got;
+}
+static void screen_line(const char **name, uint64_t k, uint64_t record, uint64_t begin, uint64_t end, uint64_t hits, uint32_t flags, bool dup)
+{
+    const uint32_t f = flags & 6u;
+    if (record != rng_first + k || end < begin || end > trim_len[k]) die("can't decompress sequence\n");
+    fprintf(OUT, "%s\t%llu\t%llu\t%llu\t%llu\t%s\n", name[record], (unsigned long long)trim_len[k], (unsigned long long)begin, (unsigned long long)end, (unsigned long long)hits,
+            f == NAF_GPU_TRIM_SHORT ? "short" : f == NAF_GPU_TRIM_ERRORS ? "errors" : f ? "short,errors" : dup ? "duplicate" : flags & NAF_GPU_SCREEN_MATCHED ? "matched" : "clean");
+}
+static void screen_lines(const void *rows, size_t m, uint64_t at, const char **name)
+{
+    for (size_t k = 0; k < m; k++) {
+        const naf_gpu_screen_row *x = (const naf_gpu_screen_row *)rows + k;
+        screen_line(name, at + k, x->record, x->begin, x->end, x->hits, x->flags, false);
+    }
+}
+static void screen_dedup_lines(const void *rows, size_t m, uint64_t at, const char **name)
+{
+    for (size_t k = 0; k < m; k++) {
+        const naf_gpu_dedup_row *x = (const naf_gpu_dedup_row *)rows + k; const naf_gpu_screen_row *s = screen_host + at + k;
+        if (s->record != x->record || s->begin != x->begin || s->end != x->end) die("can't decompress sequence\n");
+        screen_line(name, at + k, x->record, x->begin, x->end, s->hits, s->flags, (x->flags & NAF_GPU_DEDUP_DUPLICATE) != 0);
+    }
+}
+static void screen_reads(const void *rows, size_t m, uint64_t at, const char **name)
+{
+    (void)name;
+    const naf_gpu_screen_row *x = (const naf_gpu_screen_row *)rows;
+    naf_gpu_segment *segs = (naf_gpu_segment *)malloc((m + 1) * sizeof *segs); if (!segs) die("can't allocate memory\n");
+    const bool bounds = trim_text || n_adapters;                    /* without them a kept read is its whole record, an empty one too */
+    size_t n = 0;
+    for (size_t k = 0; k < m; k++) {
+        if (x[k].record != rng_first + at + k || x[k].end < x[k].begin) die("can't decompress sequence\n");
+        if (x[k].flags & NAF_GPU_TRIM_KEPT) segs[n++] = bounds ? (naf_gpu_segment){ x[k].record, x[k].begin, x[k].end } : (naf_gpu_segment){ x[k].record, 0, NAF_GPU_WHOLE };
+    }
+    emit_reads(segs, n);
+    free(segs);
+}
+static void run_screen(bool has_ids, bool has_names)
+{
+    static const row_table lines = { sizeof(naf_gpu_screen_row), 1 << 20, "sequence", "screen: rows", "screen: download + lines", fill_screen, screen_lines },
+                           dlines = { sizeof(naf_gpu_dedup_row), 1 << 20, "sequence", "screen: rows", "screen: download + lines", fill_screen, screen_dedup_lines },
+                           reads = { sizeof(naf_gpu_screen_row), 1 << 20, "sequence", "screen: rows", "screen: download + reads", fill_screen, screen_reads },
+                           dreads = { sizeof(naf_gpu_dedup_row), 1 << 20, "sequence", "screen: rows", "screen: download + reads", fill_screen, dedup_reads };     /* (the firsts among the kept reads: dedup's rows) */
+    if (trim_text && !(H.flags & 1)) die("--trim reads the quality codes: the archive has no quality section\n");
+    if (!screen_table && out_type == FASTQ && !(H.flags & 1)) die("FASTQ output requested, but input has no qualities\n");
+    FILE *R = fopen(screen_ref, "rb");
+    if (!R) die("can't open the --screen reference file\n");
+    unsigned char *ref = read_all(R, &screen_ref_len); fclose(R);
+    naf_gpu_header RH; char eb[128] = "";
+    if (naf_gpu_parse_header_host(ref, screen_ref_len, &RH, eb)) die("--screen reference: %s", eb);
+    if (RH.seq_type >= NAF_SEQ_PROTEIN) die("reads cannot be screened in %s sequences\n", RH.seq_type == NAF_SEQ_PROTEIN ? "protein" : "text");
+    table_range(has_ids);
+    const unsigned long long N = H.n_sequences;
+    if (rng_first > N) die("can't decompress sequence\n");
+    const uint64_t n = rng_count == NAF_GPU_WHOLE ? N - rng_first : rng_count;
+    GPU_TRY(naf_gpu_malloc(gpu, screen_ref_len + 64, &d_screen_ref));
+    GPU_TRY(naf_gpu_upload(gpu, d_screen_ref, ref, screen_ref_len)); GPU_TRY(naf_gpu_synchronize(gpu));
+    free(ref);
+    phase("screen: reference upload");
+    if (n_adapters) clip_prepare();
+    if (screen_table) {
+        fprintf(OUT, "#seq\tlength\tbegin\tend\thits\tstatus\n");
+        if (n) {
+            uint64_t *off = (uint64_t *)malloc((size_t)(n + 1) * sizeof *off); trim_len = (uint64_t *)malloc((size_t)n * sizeof *trim_len);
+            if (!off || !trim_len) die("can't allocate memory\n");
+            naf_gpu_unnaf_opts o = { NAF_OUT_SEQUENCES, 0, -1 };
+            GPU_TRY(naf_gpu_unnaf_record_table(gpu, d_naf, naf_len, &o, rng_first, n, trim_len, off));
+            free(off);
+            write_rows(dedup ? &dlines : &lines, n, true, has_ids, has_names);
+            free(trim_len); trim_len = NULL; free(screen_host); screen_host = NULL;
+        }
+    } else {
+        reads_selection = true;
+        if (n) write_rows(dedup ? &dreads : &reads, n, false, has_ids, has_names);
+        if (sel_buf) { naf_gpu_free(gpu, sel_buf); sel_buf = NULL; sel_cap = 0; }
+    }
+    if (n_adapters) free(clip.blob);
+    naf_gpu_free(gpu, d_screen_ref); d_screen_ref = NULL;
 }
 
 /* --orfs: naf_gpu_unnaf_orfs -- the stops, starts and record bounds of the packed stream as six lists, a stretch between two neighbours of one
