@@ -2,15 +2,14 @@
 // emit.hip (included by it, behind trim.h): the window, its masks and the rule "c matches p  <=>  c != 0 && (c & ~p) == 0" are locate.h's,
 // the collapse of the mismatch word to one bit a letter locate_near.h's, the front of the call, the pieces and the decode of a piece's
 // bytes payload.h's (records_front, piece_plan, PieceSweep), the walk over the blob of adapters locate.h's (motif_walk).  This file holds
-// the four kernels and their launches.  The contract is include/naf_gpu.h's.
+// the two kernels and the launches.  The contract is include/naf_gpu.h's.
 //
 // A start x of record r (window [begin_r, end_r) of it) overlaps adapter k in L = min(m_k, end_r - x) letters; it is a candidate when
 // L >= min_overlap and at most budget[k][L] of the adapter's first L letters mismatch.  The clip point is the smallest candidate of the
 // record, the lowest adapter number at equal x.
 //
-// k_clip_stage: a lane per selected record.  The caller's bounds rows (any alignment) -- or, without them, the whole records -- become an
-// aligned table of (begin, end) and one of the flags that are carried; a row that is none leaves its number and what is wrong with it in
-// ONE word (the smallest wins), and its window is cut to the record, so that no kernel behind it depends on the caller's numbers.
+// The stage: k_bounds_stage (reads.h) with the flags cut to NAF_GPU_TRIM_ERRORS, the one a clip row carries on.  Its verdict on the bounds
+// rows is looked at once, at the end of the call; until then the row copy holds back (k_row_copy's guard).
 // k_clip_mark: k_locate_near's skeleton -- a wavefront per tile of 4096 bases, 64 positions a lane, the 32-base window loaded once and
 // moved on by the nibble funnel shift, the record walk by rec_base.  What is new: `room` is min(32, end_r - x) of the record's WINDOW, the
 // collapsed mismatch word is cut to its lowest `room` letters before the popcount, the budget is looked up by the overlap (for a full
@@ -20,9 +19,8 @@
 // lane's first base.  The candidates of one record are combined by a 64-bit atomicMin on a key per record of the piece,
 // preset to all ones:  key = x << 16 | adapter << 8 | mismatches.  A minimum does not depend on the order, so the table is the same on
 // every run; at most one atomic a lane and record with a candidate.
-// k_clip_finish: a lane per record of the piece turns key and window into the row (5 u64, in the arena) and adds the totals and the
-// [adapter][overlap] histogram: lanes, then the workgroup in LDS, then one atomic per non-zero cell and workgroup.
-// k_clip_copy: the arena's rows to the caller's table of any alignment -- unless the stage left a bad bounds row: then nothing is written.
+// k_clip_finish: a lane per record of the piece turns key and window into the row (5 u64, in the arena) and adds the totals (wg_sums)
+// and the [adapter][overlap] histogram: lanes, then the workgroup in LDS, then one atomic per non-zero cell and workgroup.
 #pragma once
 
 #define CLIP_TILE 4096u
@@ -37,27 +35,6 @@
 #define CLIP_NEVER (-1)
 struct ClipPats { LocCombo c[CLIP_MAX_ADAPTERS]; u32 len[CLIP_MAX_ADAPTERS]; int full[CLIP_MAX_ADAPTERS]; u8 budget[CLIP_CELLS]; u32 n, min_overlap; };
 static_assert(sizeof(ClipPats) + 16 * 8 <= 4096, "k_clip_mark takes its adapters by value: they and its other arguments stay within the 4 KiB of kernel arguments");
-
-// bounds: the caller's rows (40 bytes each, any alignment), null: the whole records.  win[2k], win[2k + 1]: the window of record
-// first + k, inside the record whatever the row said; wflags[k]: NAF_GPU_TRIM_ERRORS where the row had it.  *bad (preset to all ones):
-// k << 2 | what of the first row that is none (1: its record, 2: begin > end, 3: end > the record's length).
-__global__ __launch_bounds__(256) void k_clip_stage(const u8 *bounds, const u64 *rec_base, u64 first, u64 count, u64 *win, u32 *wflags, unsigned long long *bad)
-{
-    const u64 k = (u64)blockIdx.x * 256 + threadIdx.x;
-    if (k >= count) return;
-    const u64 n = rec_base[first + k + 1] - rec_base[first + k];
-    u64 b = 0, e = n; u32 f = 0;
-    if (bounds) {
-        const u8 *p = bounds + 40 * k;
-        const u64 rec = ld64(p);
-        b = ld64(p + 8); e = ld64(p + 16); f = ld32(p + 32) & NAF_GPU_TRIM_ERRORS;
-        const u32 what = rec != first + k ? 1u : b > e ? 2u : e > n ? 3u : 0u;
-        if (what) atomicMin(bad, (unsigned long long)(k << 2 | what));
-        if (e > n) e = n;
-        if (b > e) b = e;
-    }
-    win[2 * k] = b; win[2 * k + 1] = e; wflags[k] = f;
-}
 
 // LONG: an adapter is longer than 16 letters (the upper half of the window takes part).
 // seq: pointer to packed byte 0 of the stream; bytes [.., b_end) of it may be read (the lanes at the range's end load byte by byte).
@@ -157,7 +134,7 @@ __global__ __launch_bounds__(256) void k_clip_finish(ClipFinP P)
 {
     __shared__ unsigned long long tsum[CLIP_TOTALS];
     __shared__ u32 hist[CLIP_CELLS];
-    const u32 tid = threadIdx.x, lane = tid & 63u;
+    const u32 tid = threadIdx.x;
     if (tid < CLIP_TOTALS) tsum[tid] = 0;
     for (u32 k = tid; k < CLIP_CELLS; k += 256) hist[k] = 0;
     __syncthreads();
@@ -179,22 +156,8 @@ __global__ __launch_bounds__(256) void k_clip_finish(ClipFinP P)
         T[0] = 1; T[1] = clipped; T[3] = wend - begin; T[5] = wend - end; T[6] = is_short; T[7] = errors;
         if (flags & NAF_GPU_TRIM_KEPT) { T[2] = 1; T[4] = end - begin; }
     }
-#pragma unroll
-    for (u32 k = 0; k < CLIP_TOTALS; k++) {
-        u64 v = T[k];
-        for (int d = 32; d; d >>= 1) v += shfl_u64(v, (int)(lane ^ (u32)d));
-        if (lane == 0 && v) atomicAdd(&tsum[k], (unsigned long long)v);
-    }
-    __syncthreads();
-    if (tid < CLIP_TOTALS && tsum[tid]) atomicAdd(&P.total[tid], tsum[tid]);
+    wg_sums(T, tsum, P.total);                                                    // (its barrier stands behind the histogram's atomics too)
     for (u32 k = tid; k < CLIP_CELLS; k += 256) if (hist[k]) atomicAdd(&P.cells[k], (unsigned long long)hist[k]);
-}
-
-// n u64 from the arena to a table of any alignment, unless a bounds row was none (*bad is then no longer all ones)
-__global__ __launch_bounds__(256) void k_clip_copy(const u64 *src, u8 *dst, u64 n, const unsigned long long *bad)
-{
-    const u64 i = (u64)blockIdx.x * 256 + threadIdx.x;
-    if (i < n && *bad == CLIP_NO_KEY) st64(dst + 8 * i, src[i]);
 }
 
 // ---- host side -----------------------------------------------------------------------------------------------------------------
@@ -267,7 +230,7 @@ extern "C" int naf_gpu_unnaf_clip(naf_gpu_ctx *c, const void *d_naf_, size_t naf
         if (!win || !wflags) return NAF_GPU_ENOMEM;
         HIP_TRY(c, hipMemsetAsync(d_total, 0, (CLIP_TOTALS + CLIP_CELLS) * 8, c->stream));
         HIP_TRY(c, hipMemsetAsync(d_bad, 0xFF, 8, c->stream));
-        LAUNCH(c, "unnaf_clip_stage", k_clip_stage, (u32)((count + 255) / 256), 256, 0, d_bounds, P.rec_base, first, count, win, wflags, d_bad);
+        LAUNCH(c, "unnaf_clip_stage", k_bounds_stage, (u32)((count + 255) / 256), 256, 0, d_bounds, 40u, 32u, (u32)NAF_GPU_TRIM_ERRORS, P.rec_base, first, count, win, wflags, (u8 *)nullptr, d_bad);
         PieceSweep sw(c, d_naf, pl, who);                                             // (behind the tables of the whole call: they stay when a piece is released)
         for (const RecPiece &pc : pieces) {
             const u64 nr = pc.r_hi - pc.r_lo;
@@ -283,9 +246,9 @@ extern "C" int naf_gpu_unnaf_clip(naf_gpu_ctx *c, const void *d_naf_, size_t naf
             F.rec_base = P.rec_base; F.win = win + 2 * (pc.r_lo - first); F.wflags = wflags + (pc.r_lo - first); F.keys = keys;
             F.r_lo = pc.r_lo; F.r_hi = pc.r_hi; F.min_len = o->min_len; F.total = d_total; F.cells = d_cells;
             memcpy(F.len, Q.len, sizeof F.len);
-            if (d_rows) { F.rows = arena_new<u64>(c, nr * CLIP_ROW_U64); if (!F.rows) return NAF_GPU_ENOMEM; }
+            if (d_rows && (rc = rows_out(c, &F.rows, nr, CLIP_ROW_U64))) return rc;
             LAUNCH(c, "unnaf_clip_finish", k_clip_finish, (u32)((nr + 255) / 256), 256, 0, F);
-            if (d_rows) LAUNCH(c, "unnaf_clip_copy", k_clip_copy, (u32)((nr * CLIP_ROW_U64 + 255) / 256), 256, 0, (const u64 *)F.rows, d_rows + 40 * (pc.r_lo - first), nr * CLIP_ROW_U64, (const unsigned long long *)d_bad);
+            if (d_rows) rows_copy(c, "unnaf_clip_copy", F.rows, d_rows + 40 * (pc.r_lo - first), nr, CLIP_ROW_U64, d_bad);
             HIP_TRY(c, hipGetLastError());
             HIP_TRY(c, hipStreamSynchronize(c->stream));
             sw.release();
@@ -293,12 +256,7 @@ extern "C" int naf_gpu_unnaf_clip(naf_gpu_ctx *c, const void *d_naf_, size_t naf
         std::vector<u64> sum(CLIP_TOTALS + CLIP_CELLS + 1);
         if ((rc = ctx_readback(c, sum.data(), d_total, sum.size() * 8))) return rc;
         const u64 bad = sum[CLIP_TOTALS + CLIP_CELLS];
-        if (bad != CLIP_NO_KEY) {
-            const u64 k = bad >> 2; const u32 what = (u32)(bad & 3);
-            *n_records = 0;
-            return ctx_fail(c, NAF_GPU_EARG, "%s: bounds row %llu: %s", who, (unsigned long long)k,
-                            what == 1 ? "its record is not first + its number (one row per selected record, ascending)" : what == 2 ? "begin > end" : "end is behind the record's last base");
-        }
+        if (bad != BOUNDS_OK) { *n_records = 0; return bounds_row_fail(c, who, bad); }
         if (h_total) { h_total->reads = sum[0]; h_total->clipped = sum[1]; h_total->kept = sum[2]; h_total->bases = sum[3]; h_total->kept_bases = sum[4];
                        h_total->removed_bases = sum[5]; h_total->n_short = sum[6]; h_total->n_errors = sum[7]; }
         if (per_adapter) for (size_t k = 0; k < 33 * n_adapters; k++) per_adapter[k] = sum[CLIP_TOTALS + k];

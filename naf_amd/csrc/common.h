@@ -114,6 +114,9 @@ NAF_HD u32 bitf_peek(const BitF &b, u32 n)
 }
 
 #if defined(__HIPCC__)
+// lane + d's v (a lane without one gets its own)
+__device__ __forceinline__ u64 shfl_down_u64(u64 v, int d) { return ((u64)(u32)__shfl_down((int)(v >> 32), d) << 32) | (u32)__shfl_down((int)(u32)v, d); }
+
 // Workgroups are dealt to the eight XCDs in turn (workgroup b runs on XCD b % 8: MI355X_MICROARCH.md), each XCD with an L2 of its own.
 // xcd_block() renumbers a launch's workgroups so that every XCD walks ONE contiguous eighth of the grid: neighbouring units of work --
 // tiles of a text, blocks of a frame -- whose outputs share cache lines (unaligned stream pieces, eight-byte table entries) then meet in

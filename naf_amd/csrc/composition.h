@@ -209,8 +209,7 @@ __global__ __launch_bounds__(256) void k_comp_total(const u64 *acc, u64 nrows, u
     }
 #pragma unroll
     for (int q = 0; q < 18; q++) {
-        u64 v = s[q];
-        for (int d = 32; d; d >>= 1) v += shfl_u64(v, (int)((threadIdx.x & 63) ^ d));
+        const u64 v = wave_sum_u64(s[q]);
         if ((threadIdx.x & 63) == 0 && v) atomicAdd(&total[q], (unsigned long long)v);
     }
 }
@@ -276,7 +275,7 @@ static int composition_run(naf_gpu_ctx *c, const u8 *d_naf, size_t naf_len, u64 
         if (bases) LAUNCH(c, "unnaf_comp_count", k_comp_count, (u32)tl.ntiles, 64, 0, tl.seq, tl.b_hi, P.rec_base, (const u64 *)row_base, first, pc.r_lo, pc.r_hi, pc.p_lo, pc.p_hi, tl.t0, W, R0, acc,
                           tracing ? (unsigned long long *)d_sum + 18 : (unsigned long long *)nullptr);
         if (h_total) { const u64 nb = (nr + 255) / 256; LAUNCH(c, "unnaf_comp_total", k_comp_total, (u32)(nb < 2048 ? nb : 2048), 256, 0, (const u64 *)acc, nr, (unsigned long long *)d_sum); }
-        if (!in_place) LAUNCH(c, "unnaf_row_copy", k_row_copy, (u32)((nr * COMP_ROW_U64 + 255) / 256), 256, 0, (const u64 *)acc, d_rows + 168 * R0, nr * COMP_ROW_U64);
+        if (!in_place) rows_copy(c, "unnaf_row_copy", acc, d_rows + 168 * R0, nr, COMP_ROW_U64);
         HIP_TRY(c, hipGetLastError());
         HIP_TRY(c, hipStreamSynchronize(c->stream));
         sw.release();

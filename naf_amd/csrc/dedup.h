@@ -1,7 +1,7 @@
 // dedup.h -- exact duplicates among reads, decided in the packed 4-bit stream (naf_gpu_dedup_level, naf_gpu_unnaf_dedup).  Part of emit.hip
 // (included by it, behind clip.h): the front of the call and the decode of the bytes are payload.h's (records_front, PieceSweep -- ONE
-// piece: a comparison needs both records resident), the loads packed.h's, the stage of the bounds rows k_clip_stage's shape, the parts of
-// records that cross a lane or a tile trim.h's two-slot scheme.  The contract is include/naf_gpu.h's.
+// piece: a comparison needs both records resident), the loads packed.h's, the stage of the bounds rows, the walk of a lane's parts and the
+// carry of a record's parts across lanes and tiles reads.h's.  The contract is include/naf_gpu.h's.
 //
 // A window's SUMMARY is an element of a monoid: a polynomial hash of its codes carried with the power of its length, (h, p), h = sum of
 // (code_i + 1) B^(n - 1 - i), p = B^n, two polynomials of 64 bits each (arithmetic modulo 2^64, odd bases below 2^32: a step is one
@@ -13,13 +13,12 @@
 // both strands the smaller of (h0, h1) and (rev0, rev1), so a read and its reverse complement share it; every word is then cut to the
 // low NAF_GPU_DEDUP_HASH_BITS bits (the lever that makes different sequences share an H on purpose).
 //
-// k_dedup_stage:  a lane per record.  Windows, "takes part" and the carried flags from the bounds rows; the first bad row by atomicMin.
+// k_dedup_preset: a lane per record, behind k_bounds_stage: a record that takes no part is its own first, the others are pending; the
+//                 records that take part are counted (wg_sums).
 // k_dedup_hash:   a wavefront per tile of 4096 bases, 64 bases a lane, loaded once into a row of LDS; the lane walks its bases part by
-//                 part (a part: its bases of one record, the record walk by rec_base).  Whole records finish in the lane; a record that
-//                 goes on in the next lane is the lane's X, one that came from the lane in front its A; A moves one lane down, the X of
-//                 one record are combined in lane order by a segmented shuffle reduction; a record that crosses the tile leaves slot 0
-//                 (it began in front of the tile) or slot 1 (it ends behind it).
-// k_dedup_join:   a lane per record: empty records get the identity, records of several tiles combine their slots in tile order.
+//                 part (lane_parts).  Whole records finish in the lane, the others go through seam_carry; a record that crosses the tile
+//                 leaves slot 0 (it began in front of the tile) or slot 1 (it ends behind it).
+// k_dedup_join:   a lane per record: empty records get the identity, records of several tiles their summary from seam_join.
 // k_dedup_insert: a lane per pending record into an open-addressing table of record numbers (load <= 1/2, preset to all ones): an empty
 //                 slot is claimed by CAS, a slot whose occupant has the same H takes atomicMin(slot, r), any other means the next slot.
 //                 A slot never changes hands to another H and a minimum does not depend on the order: every H ends with the smallest
@@ -32,8 +31,8 @@
 // Rounds:         insert + verify with a fresh table until nothing is pending, one read-back a round.  The smallest pending record of
 //                 every H is a first, so every round resolves at least one class; one that resolves nothing is NAF_GPU_EINTERNAL.
 // k_dedup_count:  atomicAdd of one onto copies[first] per record that takes part (integers: no order).
-// k_dedup_finish: a lane per record writes the row (6 u64, in the arena; k_row_copy takes them to the caller's alignment) and adds the
-//                 totals and the levels: lanes, then the workgroup in LDS, then one atomic per counter.
+// k_dedup_finish: a lane per record writes the row (6 u64, in the arena; rows_copy takes them to the caller's alignment) and adds the
+//                 totals (wg_sums, the largest class as its one maximum) and the levels (a ballot a level).
 #pragma once
 
 #define DEDUP_TILE 4096u
@@ -66,21 +65,16 @@ __device__ __forceinline__ DedupSum dedup_combine(const DedupSum &L, const Dedup
     if (BOTH) { o.r0 = R.r0 * L.p0 + L.r0; o.r1 = R.r1 * L.p1 + L.r1; } else { o.r0 = o.r1 = 0; }
     return o;
 }
-__device__ __forceinline__ u64 dedup_down(u64 v, int d) { return ((u64)(u32)__shfl_down((int)(v >> 32), d) << 32) | (u32)__shfl_down((int)(u32)v, d); }
 template <bool BOTH>
 __device__ __forceinline__ DedupSum dedup_sum_down(const DedupSum &S, int d)
 {
     DedupSum o;
-    o.h0 = dedup_down(S.h0, d); o.h1 = dedup_down(S.h1, d); o.p0 = dedup_down(S.p0, d); o.p1 = dedup_down(S.p1, d);
-    if (BOTH) { o.r0 = dedup_down(S.r0, d); o.r1 = dedup_down(S.r1, d); } else { o.r0 = o.r1 = 0; }
+    o.h0 = shfl_down_u64(S.h0, d); o.h1 = shfl_down_u64(S.h1, d); o.p0 = shfl_down_u64(S.p0, d); o.p1 = shfl_down_u64(S.p1, d);
+    if (BOTH) { o.r0 = shfl_down_u64(S.r0, d); o.r1 = shfl_down_u64(S.r1, d); } else { o.r0 = o.r1 = 0; }
     return o;
 }
 
-struct DedupP {
-    const u8 *seq; u64 b_end;                  // pointer to packed byte 0 of the stream; bytes [.., b_end) of it may be read
-    const u64 *rec_base;                       // records [r_lo, r_hi): rec_base[r_lo] = p_lo, rec_base[r_hi] = p_hi
-    u64 r_lo, r_hi, p_lo, p_hi;
-    u64 t0, ntiles;                            // first base of tile 0 (even, <= p_lo), tiles that reach p_hi
+struct DedupP : ReadsPiece {
     const u64 *win;                            // win[2k], win[2k + 1]: the window of record r_lo + k
     u64 *hash;                                 // hash[2k], hash[2k + 1]: its H
     DedupSum *open;                            // two slots a tile
@@ -96,32 +90,16 @@ __device__ __forceinline__ void dedup_done(const DedupP &P, u64 r, const DedupSu
     P.hash[2 * (r - P.r_lo)] = a & P.cut; P.hash[2 * (r - P.r_lo) + 1] = b & P.cut;
 }
 
-// bounds: the caller's rows (40 bytes each, any alignment; their flags word at byte flags_at), null: the whole records.  win: the window
-// of record first + k, inside the record whatever the row said; wflags[k]: the row's flags as they came; part[k]: it takes part.
-// ctr[0] (preset to all ones): k << 2 | what of the first row that is none (k_clip_stage's); ctr[1]: the records that take part.
-__global__ __launch_bounds__(256) void k_dedup_stage(const u8 *bounds, u32 flags_at, const u64 *rec_base, u64 first, u64 count, u64 *win, u32 *wflags, u8 *part,
-                                                     u64 *first_of, unsigned long long *ctr)
+// first_of[k]: k for a record that takes no part, DEDUP_NONE (pending) for the others; *considered += the others
+__global__ __launch_bounds__(256) void k_dedup_preset(const u8 *part, u64 count, u64 *first_of, unsigned long long *considered)
 {
+    __shared__ unsigned long long tsum[1];
+    if (threadIdx.x == 0) tsum[0] = 0;
+    __syncthreads();
+    u64 T[1] = { 0 };
     const u64 k = (u64)blockIdx.x * 256 + threadIdx.x;
-    bool takes = false;
-    if (k < count) {
-        const u64 n = rec_base[first + k + 1] - rec_base[first + k];
-        u64 b = 0, e = n; u32 f = NAF_GPU_TRIM_KEPT;
-        if (bounds) {
-            const u8 *p = bounds + 40 * k;
-            const u64 rec = ld64(p);
-            b = ld64(p + 8); e = ld64(p + 16); f = ld32(p + flags_at);
-            const u32 what = rec != first + k ? 1u : b > e ? 2u : e > n ? 3u : 0u;
-            if (what) atomicMin(&ctr[0], (unsigned long long)(k << 2 | what));
-            if (e > n) e = n;
-            if (b > e) b = e;
-        }
-        takes = (f & NAF_GPU_TRIM_KEPT) != 0;
-        win[2 * k] = b; win[2 * k + 1] = e; wflags[k] = f; part[k] = takes;
-        first_of[k] = takes ? DEDUP_NONE : k;
-    }
-    const u64 m = __ballot(takes);
-    if ((threadIdx.x & 63u) == 0 && m) atomicAdd(&ctr[1], (unsigned long long)__popcll(m));
+    if (k < count) { T[0] = part[k] != 0; first_of[k] = T[0] ? DEDUP_NONE : k; }
+    wg_sums(T, tsum, considered);
 }
 
 template <bool BOTH>
@@ -142,11 +120,7 @@ __global__ __launch_bounds__(64) void k_dedup_hash(DedupP P)
         packed_load64(P.seq, P.b_end, g, x);
 #pragma unroll
         for (u32 i = 0; i < 8; i++) st[i] = x[i];                                 // (read by the lane that wrote them: no barrier)
-        u64 r = upper_bound_u64(P.rec_base, P.r_lo, P.r_hi + 1, lo) - 1;          // rec_base[r] <= lo < rec_base[r + 1]
-        u64 rbase = P.rec_base[r], rend = P.rec_base[r + 1];
-        u64 pos = lo;
-        for (;;) {
-            const u64 at = pos, stop = rend < hi ? rend : hi;                     // the part: bases [at, stop) of the stream
+        lane_parts(P.rec_base, P.r_lo, P.r_hi, lo, hi, [&](u64 r, u64 rbase, u64 rend, u64 at, u64 stop) {      // the part: bases [at, stop) of the stream
             const u64 wb = rbase + P.win[2 * (r - P.r_lo)], we = rbase + P.win[2 * (r - P.r_lo) + 1];
             const u64 ua = at > wb ? at : wb, ub = stop < we ? stop : we;         // its bases inside the record's window
             DedupSum S = dedup_identity();
@@ -168,36 +142,18 @@ __global__ __launch_bounds__(64) void k_dedup_hash(DedupP P)
                 }
                 S.h0 = h0; S.h1 = h1; S.r0 = r0; S.r1 = r1; S.p0 = dedup_pow.v[0][b - a]; S.p1 = dedup_pow.v[1][b - a];
             }
-            pos = stop;
             const bool from_front = rbase < at, goes_on = rend > stop;
             if (!from_front && !goes_on) dedup_done(P, r, S);
             else if (!goes_on) { A = S; has_a = true; }
             else { X = S; pend = true; thru = from_front; xr = r; xbase = rbase; xend = rend; }
-            if (stop >= hi) break;
-            do { r++; rbase = rend; rend = P.rec_base[r + 1]; } while (rend <= pos);      // the next record that has bases (pos < hi <= p_hi: there is one)
-        }
+        });
     }
-    if (__ballot(pend || has_a)) {
-        // the part that ends a record joins the X of the lane in front; lane 0's came from the tile in front: the record's bases in this
-        // tile are that part
-        const DedupSum N = dedup_sum_down<BOTH>(A, 1);
-        const bool na = __shfl_down((int)has_a, 1) != 0 && lane < 63;
-        if (na && pend) X = dedup_combine<BOTH>(X, N);
-        if (lane == 0 && has_a) P.open[2 * tile] = A;
-        // lanes of one record: its first lane here, then through-parts
-        const bool head = pend && (!thru || lane == 0);
-        const u64 cut = __ballot(head || !pend);
-        const u64 above = lane == 63 ? 0ull : cut >> (lane + 1);
-        const int len = above ? __ffsll((long long)above) : 64 - (int)lane;      // lanes [lane, lane + len) are this lane's segment
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) {
-            const DedupSum Y = dedup_sum_down<BOTH>(X, d);
-            if (pend && d < len) X = dedup_combine<BOTH>(X, Y);
-        }
-        if (head) {
-            if (xbase >= T0 && xend <= T0 + DEDUP_TILE) dedup_done(P, xr, X);
-            else P.open[2 * tile + (xbase < T0 ? 0 : 1)] = X;
-        }
+    const bool head = seam_carry(lane, has_a, A, pend, thru, X, [](const DedupSum &S, int d) { return dedup_sum_down<BOTH>(S, d); },
+                                 [](const DedupSum &L, const DedupSum &R) { return dedup_combine<BOTH>(L, R); });
+    if (lane == 0 && has_a) P.open[2 * tile] = A;                                 // it came from the tile in front: the record's bases in this tile are that part
+    if (head) {
+        if (xbase >= T0 && xend <= T0 + DEDUP_TILE) dedup_done(P, xr, X);
+        else P.open[2 * tile + (xbase < T0 ? 0 : 1)] = X;
     }
 }
 
@@ -207,11 +163,10 @@ __global__ __launch_bounds__(256) void k_dedup_join(DedupP P)
     if (r >= P.r_hi) return;
     const u64 rbase = P.rec_base[r], rend = P.rec_base[r + 1];
     if (rend == rbase) { dedup_done(P, r, dedup_identity()); return; }
-    const u64 a = (rbase - P.t0) / DEDUP_TILE, b = (rend - 1 - P.t0) / DEDUP_TILE;
-    if (b == a) return;
-    DedupSum S = P.open[2 * a + 1];
-    for (u64 t = a + 1; t <= b; t++) S = P.both ? dedup_combine<true>(S, P.open[2 * t]) : dedup_combine<false>(S, P.open[2 * t]);
-    dedup_done(P, r, S);
+    DedupSum S;
+    const u64 tiles = P.both ? seam_join(P.open, P.t0, DEDUP_TILE, rbase, rend, S, [](const DedupSum &L, const DedupSum &R) { return dedup_combine<true>(L, R); })
+                             : seam_join(P.open, P.t0, DEDUP_TILE, rbase, rend, S, [](const DedupSum &L, const DedupSum &R) { return dedup_combine<false>(L, R); });
+    if (tiles > 1) dedup_done(P, r, S);
 }
 
 __device__ __forceinline__ u64 dedup_mix(u64 a, u64 b)
@@ -302,7 +257,7 @@ __global__ __launch_bounds__(256) void k_dedup_verify(DedupV V)
     // the longer ones, one after the other, by all lanes of the wavefront
     u64 longs = __ballot(cmp && n > DEDUP_LANE_MAX);
     while (longs) {
-        const int src = __ffsll((long long)longs) - 1;
+        const int src = __builtin_ctzll(longs);
         longs &= longs - 1;
         const u64 qa = shfl_u64(pa, src), qb = shfl_u64(pb, src), qn = shfl_u64(n, src);
         int s = __ballot(!dedup_same(V.seq, V.b_end, qa, qb, qn, false, lane, 64)) == 0 ? 0 : -1;
@@ -354,18 +309,12 @@ __global__ __launch_bounds__(256) void k_dedup_finish(DedupFinP P)
         }
         if (P.rows) { u64 *o = P.rows + k * DEDUP_ROW_U64; o[0] = P.r_lo + k; o[1] = begin; o[2] = end; o[3] = P.r_lo + f; o[4] = copies; o[5] = (u64)flags | (u64)strand << 32; }
     }
-#pragma unroll
-    for (u32 i = 0; i < 8; i++) {
-        u64 v = T[i];
-        for (int d = 32; d; d >>= 1) { const u64 o = shfl_u64(v, (int)(lane ^ (u32)d)); v = i == 5 ? (o > v ? o : v) : v + o; }
-        if (lane == 0 && v) { if (i == 5) atomicMax(&tsum[i], (unsigned long long)v); else atomicAdd(&tsum[i], (unsigned long long)v); }
-    }
     for (u32 l = 0; l < NAF_GPU_DEDUP_LEVELS; l++) {
         const u64 m = __ballot(level == l);
         if (lane == 0 && m) atomicAdd(&tsum[8 + l], (unsigned long long)__popcll(m));
     }
-    __syncthreads();
-    if (tid < DEDUP_SUMS && tsum[tid]) { if (tid == 5) atomicMax(&P.sums[tid], tsum[tid]); else atomicAdd(&P.sums[tid], tsum[tid]); }
+    wg_sums<8, 1u << 5>(T, tsum, P.sums);                                         // [5], the largest class, is a maximum (its barrier stands behind the levels' atomics too)
+    if (tid >= 8 && tid < DEDUP_SUMS && tsum[tid]) atomicAdd(&P.sums[tid], tsum[tid]);
 }
 
 // ---- host side -----------------------------------------------------------------------------------------------------------------
@@ -389,11 +338,8 @@ extern "C" int naf_gpu_unnaf_dedup(naf_gpu_ctx *c, const void *d_naf_, size_t na
     if (o->flags & ~(uint32_t)NAF_GPU_DEDUP_BOTH_STRANDS) return ctx_fail(c, NAF_GPU_EARG, "%s: flags %u (NAF_GPU_DEDUP_BOTH_STRANDS or 0)", who, (unsigned)o->flags);
     if (o->bounds_kind != NAF_GPU_DEDUP_BOUNDS_TRIM && o->bounds_kind != NAF_GPU_DEDUP_BOUNDS_CLIP)
         return ctx_fail(c, NAF_GPU_EARG, "%s: bounds_kind %u (NAF_GPU_DEDUP_BOUNDS_TRIM or NAF_GPU_DEDUP_BOUNDS_CLIP)", who, (unsigned)o->bounds_kind);
-    u32 bits = 64;
-    { const char *e = ctx_opt(c, "DEDUP_HASH_BITS");
-      if (e && e[0]) { char *end = nullptr; const unsigned long long v = strtoull(e, &end, 10);
-                       if (*end || v > 64) return ctx_fail(c, NAF_GPU_EARG, "%s: NAF_GPU_DEDUP_HASH_BITS %s (0 to 64)", who, e);
-                       bits = (u32)v; } }
+    u64 bits = 64;
+    if (!lever_u64(c, "DEDUP_HASH_BITS", 64, nullptr, &bits)) return ctx_fail(c, NAF_GPU_EARG, "%s: NAF_GPU_DEDUP_HASH_BITS %s (0 to 64)", who, ctx_opt(c, "DEDUP_HASH_BITS"));
     const bool both = (o->flags & NAF_GPU_DEDUP_BOTH_STRANDS) != 0;
     UnnafPlan pl;
     int rc = records_front(c, d_naf, naf_len, FRONT_4BIT, who, "duplicates cannot be collapsed", first, &count, pl);
@@ -415,28 +361,22 @@ extern "C" int naf_gpu_unnaf_dedup(naf_gpu_ctx *c, const void *d_naf_, size_t na
         HIP_TRY(c, hipMemsetAsync(ctr, 0xFF, 8, c->stream));
         HIP_TRY(c, hipMemsetAsync(copies, 0, count * 8, c->stream));
         HIP_TRY(c, hipMemsetAsync(strand, 0, count, c->stream));
-        LAUNCH(c, "unnaf_dedup_stage", k_dedup_stage, grid, 256, 0, d_bounds, o->bounds_kind == NAF_GPU_DEDUP_BOUNDS_CLIP ? 36u : 32u, P.rec_base, first, count, win, wflags, part,
-               first_of, ctr);
+        LAUNCH(c, "unnaf_dedup_stage", k_bounds_stage, grid, 256, 0, d_bounds, 40u, o->bounds_kind == NAF_GPU_DEDUP_BOUNDS_CLIP ? 36u : 32u, ~0u, P.rec_base, first, count, win, wflags, part, ctr);
+        LAUNCH(c, "unnaf_dedup_preset", k_dedup_preset, grid, 256, 0, (const u8 *)part, count, first_of, ctr + 1);
         u64 head[2], ends[2];
         const void *src[3] = { ctr, P.rec_base + first, P.rec_base + first + count }; void *dst[3] = { head, &ends[0], &ends[1] }; const size_t nb[3] = { 16, 8, 8 };
         if ((rc = ctx_readbackv(c, 3, dst, src, nb))) return rc;
-        if (head[0] != DEDUP_NONE) {
-            const u64 k = head[0] >> 2; const u32 what = (u32)(head[0] & 3);
-            *n_records = 0;
-            return ctx_fail(c, NAF_GPU_EARG, "%s: bounds row %llu: %s", who, (unsigned long long)k,
-                            what == 1 ? "its record is not first + its number (one row per selected record, ascending)" : what == 2 ? "begin > end" : "end is behind the record's last base");
-        }
+        if (head[0] != BOUNDS_OK) { *n_records = 0; return bounds_row_fail(c, who, head[0]); }
         const u64 considered = head[1];
         // the bases of all selected records as ONE piece, held for the call
         const RecPiece pc = { first, first + count, ends[0], ends[1] };
         PieceSweep sw(c, d_naf, pl, who);
+        PieceSweep::Tiles tl = { nullptr, 0, 0, 0 };
+        if (pc.p_hi > pc.p_lo && (rc = sw.seq_for(pc, DEDUP_TILE, &tl))) return rc;
         DedupP Q; memset(&Q, 0, sizeof Q);
-        Q.rec_base = P.rec_base; Q.r_lo = pc.r_lo; Q.r_hi = pc.r_hi; Q.p_lo = pc.p_lo; Q.p_hi = pc.p_hi; Q.win = win; Q.hash = hash;
-        Q.cut = bits >= 64 ? ~0ull : (1ull << bits) - 1; Q.both = both;
-        if (pc.p_hi > pc.p_lo) {
-            PieceSweep::Tiles tl;
-            if ((rc = sw.seq_for(pc, DEDUP_TILE, &tl))) return rc;
-            Q.seq = tl.seq; Q.b_end = tl.b_hi; Q.t0 = tl.t0; Q.ntiles = tl.ntiles;
+        (ReadsPiece &)Q = ReadsPiece(P, pc, tl);
+        Q.win = win; Q.hash = hash; Q.cut = bits >= 64 ? ~0ull : (1ull << bits) - 1; Q.both = both;
+        if (Q.ntiles) {
             Q.open = arena_new<DedupSum>(c, 2 * Q.ntiles); if (!Q.open) return NAF_GPU_ENOMEM;
             if (both) LAUNCH(c, "unnaf_dedup_hash", (k_dedup_hash<true>), (u32)Q.ntiles, 64, 0, Q);
             else LAUNCH(c, "unnaf_dedup_hash", (k_dedup_hash<false>), (u32)Q.ntiles, 64, 0, Q);
@@ -465,9 +405,9 @@ extern "C" int naf_gpu_unnaf_dedup(naf_gpu_ctx *c, const void *d_naf_, size_t na
         LAUNCH(c, "unnaf_dedup_count", k_dedup_count, grid, 256, 0, (const u8 *)part, (const u64 *)first_of, count, copies);
         DedupFinP F; memset(&F, 0, sizeof F);
         F.win = win; F.wflags = wflags; F.part = part; F.strand = strand; F.first_of = first_of; F.copies = copies; F.r_lo = first; F.count = count; F.sums = ctr + 8;
-        if (d_rows) { F.rows = arena_new<u64>(c, count * DEDUP_ROW_U64); if (!F.rows) return NAF_GPU_ENOMEM; }
+        if (d_rows && (rc = rows_out(c, &F.rows, count, DEDUP_ROW_U64))) return rc;
         LAUNCH(c, "unnaf_dedup_finish", k_dedup_finish, grid, 256, 0, F);
-        if (d_rows) LAUNCH(c, "unnaf_row_copy", k_row_copy, (u32)((count * DEDUP_ROW_U64 + 255) / 256), 256, 0, (const u64 *)F.rows, d_rows, count * DEDUP_ROW_U64);
+        if (d_rows) rows_copy(c, "unnaf_row_copy", F.rows, d_rows, count, DEDUP_ROW_U64);
         HIP_TRY(c, hipGetLastError());
         u64 sum[DEDUP_SUMS];
         if ((rc = ctx_readback(c, sum, ctr + 8, sizeof sum))) return rc;

@@ -2465,6 +2465,7 @@ extern "C" int naf_gpu_unnaf_range(naf_gpu_ctx *c, const void *d_naf, size_t naf
 #include "locate.h"
 #include "locate_near.h"
 #include "composition.h"
+#include "reads.h"
 #include "quality.h"
 #include "runs.h"
 #include "kmers.h"

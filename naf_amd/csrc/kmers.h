@@ -246,7 +246,7 @@ __global__ __launch_bounds__(256) void k_kmer_rows(const u64 *rec_base, u64 firs
         if (rows) { u8 *o = rows + 40 * i; st64(o, first + i); st64(o + 8, 0); st64(o + 16, len); st64(o + 24, pos); st64(o + 32, cnt); }
         sp += pos; sc += cnt;
     }
-    for (int d = 32; d; d >>= 1) { sp += shfl_u64(sp, (int)((threadIdx.x & 63) ^ d)); sc += shfl_u64(sc, (int)((threadIdx.x & 63) ^ d)); }
+    sp = wave_sum_u64(sp); sc = wave_sum_u64(sc);
     if ((threadIdx.x & 63) == 0) { part[0][threadIdx.x >> 6] = sp; part[1][threadIdx.x >> 6] = sc; }
     __syncthreads();
     if (threadIdx.x < 2) {

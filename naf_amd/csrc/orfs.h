@@ -213,8 +213,7 @@ __global__ __launch_bounds__(256) void k_orfs_keep(const u64 *ent, const u64 *of
     }
 #pragma unroll
     for (int q = 0; q < 9; q++) {
-        u64 v = acc[q];
-        for (int d = 32; d; d >>= 1) v += shfl_u64(v, (int)((threadIdx.x & 63) ^ d));
+        const u64 v = wave_sum_u64(acc[q]);
         if ((threadIdx.x & 63) == 0) part[q][threadIdx.x >> 6] = v;
     }
     __syncthreads();

@@ -69,9 +69,10 @@ __device__ __forceinline__ void nib_products(u32 y, u32 (&lo)[4], u32 (&hi)[4])
     hi[0] = q2 & q3; hi[1] = p2 & q3; hi[2] = q2 & p3; hi[3] = p2 & p3;
 }
 
-// n u64 from the arena (8-byte aligned) to a table of any alignment
-__global__ __launch_bounds__(256) void k_row_copy(const u64 *src, u8 *dst, u64 n)
+// n u64 from the arena (8-byte aligned) to a table of any alignment.  bad (may be null): nothing is written unless *bad is all ones (a
+// call that looks at its bounds rows' verdict only at its end: reads.h)
+__global__ __launch_bounds__(256) void k_row_copy(const u64 *src, u8 *dst, u64 n, const unsigned long long *bad)
 {
     const u64 i = (u64)blockIdx.x * 256 + threadIdx.x;
-    if (i < n) st64(dst + 8 * i, src[i]);
+    if (i < n && (!bad || *bad == ~0ull)) st64(dst + 8 * i, src[i]);
 }

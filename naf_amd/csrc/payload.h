@@ -4,6 +4,8 @@
 //   records_front      the front of a call that addresses records [first, first + count) of an archive
 //   piece_plan         those records cut into pieces of whole records
 //   PieceSweep         a piece's part of a stream (its bytes; the packed one's tile geometry); the arena is given back piece by piece
+//   rows_out, rows_copy  a call's rows in the arena and their copy to the caller's table
+//   lever_u64          a strict whole-number lever
 //   count_then_write   the sweeps of a call that lists what it finds: too small a capacity is found before anything is written
 #pragma once
 #include <algorithm>
@@ -147,6 +149,28 @@ struct PieceSweep {
     }
     void release() { arena_release(c, mark); }
 };
+
+// The table of a call's rows in the arena (n rows of `per` u64, 8-byte aligned, written by the kernels), and its copy to the caller's
+// table of any alignment under the launch name given; bad: k_row_copy's
+static int rows_out(naf_gpu_ctx *c, u64 **rows, u64 n, u32 per) { *rows = arena_new<u64>(c, n * per); return *rows ? 0 : NAF_GPU_ENOMEM; }
+static void rows_copy(naf_gpu_ctx *c, const char *name, const u64 *rows, u8 *d_rows, u64 n, u32 per, const unsigned long long *bad = nullptr)
+{
+    LAUNCH(c, name, k_row_copy, cdiv(n * per, 256), 256, 0, rows, d_rows, n * per, bad);
+}
+
+// A lever NAF_GPU_<name> that is a whole number from 0 to max: *value when it is given, and *set (may be null) says whether.  Returns
+// false when what is given is none (the caller has the message: it knows the range's words)
+static bool lever_u64(naf_gpu_ctx *c, const char *name, u64 max, bool *set, u64 *value)
+{
+    const char *e = ctx_opt(c, name);
+    if (set) *set = false;
+    if (!e || !e[0]) return true;
+    char *end = nullptr; const unsigned long long v = strtoull(e, &end, 10);
+    if (*end || v > max) return false;
+    if (set) *set = true;
+    *value = v;
+    return true;
+}
 
 static int cap_fail(naf_gpu_ctx *c, const char *who, const char *things, u64 n, size_t cap) { return ctx_fail(c, NAF_GPU_ECAP, "%s: %llu %s, capacity %zu", who, (unsigned long long)n, things, cap); }
 

@@ -135,9 +135,7 @@ __device__ __forceinline__ bool qual_seg_reduce(bool pend, u64 key, QStat &S)
     const u64 pk = shfl_u64(key, lane ? lane - 1 : 0);
     const bool pp = __shfl((int)pend, lane ? lane - 1 : 0) != 0;
     const bool head = pend && (lane == 0 || !pp || pk != key);
-    const u64 cut = __ballot(head || !pend);                                      // lanes that are no continuation of the lane in front of them
-    const u64 above = lane == 63 ? 0ull : cut >> (lane + 1);
-    const int len = above ? __ffsll((long long)above) : 64 - lane;                // lanes [lane, lane + len) are this lane's segment
+    const int len = seg_len(lane, head || !pend);                                 // (a segment begins at every lane that is no continuation of the lane in front of it)
 #pragma unroll
     for (int d = 1; d < 64; d <<= 1) {
         const u32 n = qual_down(S.n, d), sum = qual_down(S.sum, d), q20 = qual_down(S.q20, d), q30 = qual_down(S.q30, d), mn = qual_down(S.mn, d), mx = qual_down(S.mx, d);
@@ -316,7 +314,7 @@ __global__ __launch_bounds__(256) void k_qual_maxlen(const u64 *len, u64 n, unsi
 {
     u64 m = 0;
     for (u64 i = (u64)blockIdx.x * 256 + threadIdx.x; i < n; i += (u64)gridDim.x * 256) m = len[i] > m ? len[i] : m;
-    for (int d = 32; d; d >>= 1) { const u64 o = shfl_u64(m, (int)((threadIdx.x & 63) ^ d)); m = o > m ? o : m; }
+    m = wave_max_u64(m);
     if ((threadIdx.x & 63) == 0 && m) atomicMax(out, (unsigned long long)m);
 }
 // ---- host side -----------------------------------------------------------------------------------------------------------------
@@ -418,12 +416,12 @@ static int quality_run(naf_gpu_ctx *c, const u8 *d_naf, size_t naf_len, u64 W, u
             const u64 wgs = (Q.ntiles + 3) / 4;
             LAUNCH(c, "unnaf_qual_count", k_qual_count, (u32)(wgs < max_grid ? wgs : max_grid), 256, 0, Q);
         }
-        if (want_rec) LAUNCH(c, "unnaf_row_copy", k_row_copy, (u32)((nr * QUAL_ROW_U64 + 255) / 256), 256, 0, (const u64 *)acc, d_rec + 56 * (pc.r_lo - first), nr * QUAL_ROW_U64);
+        if (want_rec) rows_copy(c, "unnaf_row_copy", acc, d_rec + 56 * (pc.r_lo - first), nr, QUAL_ROW_U64);
         HIP_TRY(c, hipGetLastError());
         HIP_TRY(c, hipStreamSynchronize(c->stream));
         sw.release();
     }
-    if (d_cyc_acc) LAUNCH(c, "unnaf_row_copy", k_row_copy, (u32)((C * QUAL_ROW_U64 + 255) / 256), 256, 0, (const u64 *)d_cyc_acc, d_cyc, C * QUAL_ROW_U64);
+    if (d_cyc_acc) rows_copy(c, "unnaf_row_copy", d_cyc_acc, d_cyc, C, QUAL_ROW_U64);
     HIP_TRY(c, hipGetLastError());
     u64 sum[8 + 256];
     if ((rc = ctx_readback(c, sum, d_sum, sizeof sum))) return rc;                // (waits for the copy too)

@@ -235,8 +235,7 @@ __global__ __launch_bounds__(256) void k_repeats_keep(const u64 *ent, const u64 
     }
 #pragma unroll
     for (int q = 0; q < 2; q++) {
-        u64 v = acc[q];
-        for (int d = 32; d; d >>= 1) v += shfl_u64(v, (int)((threadIdx.x & 63) ^ d));
+        const u64 v = wave_sum_u64(acc[q]);
         if ((threadIdx.x & 63) == 0) part[q][threadIdx.x >> 6] = v;
     }
     __syncthreads();

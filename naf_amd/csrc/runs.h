@@ -147,7 +147,7 @@ __global__ __launch_bounds__(256) void k_runs_pair(const u64 *starts, const u64 
         if (!bad && e - s >= min_len) kept = e - s;
     }
     if (k <= n) flag[k] = kept ? 1 : 0;
-    for (int d = 32; d; d >>= 1) kept += shfl_u64(kept, (int)((threadIdx.x & 63) ^ d));
+    kept = wave_sum_u64(kept);
     if ((threadIdx.x & 63) == 0 && kept) atomicAdd(&sum[0], (unsigned long long)kept);
     if (bad) atomicAdd(&sum[1], 1ull);
 }

@@ -1,8 +1,8 @@
 // screen.h -- reads screened against the k-mers of a second archive, decided in the packed 4-bit stream (naf_gpu_unnaf_screen).  Part of
 // emit.hip (included by it, behind dedup.h): the front of the call, the pieces and the decode of a piece's bytes are payload.h's
 // (records_front, piece_plan, PieceSweep), the loads packed.h's, the bit planes, the spread and the reversal of the 2-bit groups kmers.h's
-// (kmer_planes, kmer_spread, kmer_reverse_pairs), the record walk of a wavefront per 4096 bases and the stage of the bounds rows
-// dedup.h's and clip.h's.  The contract is include/naf_gpu.h's.
+// (kmer_planes, kmer_spread, kmer_reverse_pairs), the walk of a lane's parts (k_screen_insert), the stage of the bounds rows and the totals
+// reads.h's (lane_parts, k_bounds_stage, wg_sums).  The contract is include/naf_gpu.h's.
 //
 // A k-mer's KEY is naf_gpu_kmer_index's index in 64 bits: two bits a base, the first base the most significant, K <= 31, so a key stays
 // below 2^62 and all ones is the empty slot.  A lane holds its 64 bases and the 30 behind them (the neighbour lane's first four dwords by
@@ -15,12 +15,11 @@
 //                  holds the key is done, anything else means the next slot.  A claim adds one to ref_kmers and sets the key's bit of the
 //                  prefilter bitmap by atomicOr.  Which slot a key ends in depends on the order; WHICH keys the table holds, and which
 //                  bits are set, does not.
-// k_screen_stage:  a lane per selected record: k_dedup_stage with a row stride (a dedup row has 48 bytes).
 // k_screen_mark:   the reads.  A workgroup of four wavefronts copies the bitmap into LDS once and then walks a chunk of tiles, a wavefront
 //                  per tile.  A start whose bit is clear is no hit and touches no HBM; one whose bit is set probes the table.  The hits of
 //                  a lane's part of a record go to hits[record] by ONE atomicAdd (none when there are none: integer adds have no order).
-// k_screen_finish: a lane per record writes the row (5 u64, in the arena; k_row_copy takes them to the caller's alignment) and adds the
-//                  totals: lanes, then the workgroup in LDS, then one atomic per counter.
+// k_screen_finish: a lane per record writes the row (5 u64, in the arena; rows_copy takes them to the caller's alignment) and adds the
+//                  totals (wg_sums), the records that take part among them.
 #pragma once
 
 #define SCREEN_TILE 4096u
@@ -89,11 +88,7 @@ __device__ __forceinline__ void screen_behind(const u8 *seq, u64 b_end, u64 g, b
 }
 // ---- end of the bits of a lane -----------------------------------------------------------------------------------------------------
 
-struct ScreenP {
-    const u8 *seq; u64 b_end;                  // pointer to packed byte 0 of the stream; bytes [.., b_end) of it may be read
-    const u64 *rec_base;                       // records [r_lo, r_hi): rec_base[r_lo] = p_lo, rec_base[r_hi] = p_hi
-    u64 r_lo, r_hi, p_lo, p_hi;
-    u64 t0, ntiles;                            // first base of tile 0 (even, <= p_lo), tiles that reach p_hi
+struct ScreenP : ReadsPiece {
     u64 first;                                 // win, part and hits: [0] is record first's (the reads; not looked at by k_screen_insert)
     const u64 *win; const u8 *part;
     unsigned long long *hits;
@@ -119,10 +114,7 @@ __global__ __launch_bounds__(64) void k_screen_insert(ScreenP P)
         ScreenLane S;
         k_screen_keys(x, y, K, S);
         if (S.e) {
-            u64 r = upper_bound_u64(P.rec_base, P.r_lo, P.r_hi + 1, lo) - 1;      // rec_base[r] <= lo < rec_base[r + 1]
-            u64 rend = P.rec_base[r + 1], pos = lo;
-            for (;;) {
-                const u64 stop = rend < hi ? rend : hi;                           // the part: bases [pos, stop) of record r
+            lane_parts(P.rec_base, P.r_lo, P.r_hi, lo, hi, [&](u64, u64, u64 rend, u64 pos, u64 stop) {     // the part: bases [pos, stop) of a record
                 const u64 lim = rend + 1 > K ? rend + 1 - K : 0, ub = lim < stop ? lim : stop;     // no k-mer over the record's end
                 if (pos < ub) {
                     const u64 m = S.e & kmer_bits((u32)(pos - g), (u32)(ub - g));
@@ -145,39 +137,12 @@ __global__ __launch_bounds__(64) void k_screen_insert(ScreenP P)
                         }
                     }
                 }
-                pos = stop;
-                if (stop >= hi) break;
-                do { r++; rend = P.rec_base[r + 1]; } while (rend <= pos);        // the next record that has bases (pos < hi <= p_hi: there is one)
-            }
+            });
         }
     }
     const u32 sv = wave_sum_u32(n_valid), sc = wave_sum_u32(n_claims);
     if (lane == 0 && sv) atomicAdd(&P.ctr[0], (unsigned long long)sv);
     if (lane == 0 && sc) atomicAdd(&P.ctr[1], (unsigned long long)sc);
-}
-
-// bounds: the caller's rows (`stride` bytes each, any alignment; their flags word at byte flags_at), null: the whole records.  win: the
-// window of record first + k, inside the record whatever the row said; wflags[k]: the row's flags as they came; part[k]: it takes part.
-// *bad (preset to all ones): k << 2 | what of the first row that is none (k_clip_stage's).  (The records that take part are counted by
-// k_screen_finish: with one atomic a wavefront on a single counter this kernel took 7.2 ms for 38 M records, without it 0.20 ms.)
-__global__ __launch_bounds__(256) void k_screen_stage(const u8 *bounds, u32 stride, u32 flags_at, const u64 *rec_base, u64 first, u64 count, u64 *win, u32 *wflags,
-                                                      u8 *part, unsigned long long *bad)
-{
-    const u64 k = (u64)blockIdx.x * 256 + threadIdx.x;
-    if (k < count) {
-        const u64 n = rec_base[first + k + 1] - rec_base[first + k];
-        u64 b = 0, e = n; u32 f = NAF_GPU_TRIM_KEPT;
-        if (bounds) {
-            const u8 *p = bounds + (u64)stride * k;
-            const u64 rec = ld64(p);
-            b = ld64(p + 8); e = ld64(p + 16); f = ld32(p + flags_at);
-            const u32 what = rec != first + k ? 1u : b > e ? 2u : e > n ? 3u : 0u;
-            if (what) atomicMin(bad, (unsigned long long)(k << 2 | what));
-            if (e > n) e = n;
-            if (b > e) b = e;
-        }
-        win[2 * k] = b; win[2 * k + 1] = e; wflags[k] = f; part[k] = (f & NAF_GPU_TRIM_KEPT) != 0;
-    }
 }
 
 // chunk: tiles a wavefront walks; the launch has fbits / 8 bytes of dynamic LDS
@@ -203,6 +168,7 @@ __global__ __launch_bounds__(64 * SCREEN_WAVES) void k_screen_mark(ScreenP P, u3
         ScreenLane S;
         k_screen_keys(x, y, K, S);
         if (!S.e) continue;                                                       // no valid start in the lane: no walk
+        // (lane_parts' walk, written out: through the helper this kernel took 1.3 to 3 % longer)
         u64 r = upper_bound_u64(P.rec_base, P.r_lo, P.r_hi + 1, lo) - 1;          // rec_base[r] <= lo < rec_base[r + 1]
         u64 rbase = P.rec_base[r], rend = P.rec_base[r + 1], pos = lo;
         for (;;) {
@@ -256,7 +222,7 @@ struct ScreenFinP {
 __global__ __launch_bounds__(256) void k_screen_finish(ScreenFinP P)
 {
     __shared__ unsigned long long tsum[SCREEN_SUMS];
-    const u32 tid = threadIdx.x, lane = tid & 63u;
+    const u32 tid = threadIdx.x;
     if (tid < SCREEN_SUMS) tsum[tid] = 0;
     __syncthreads();
     u64 T[SCREEN_SUMS]; for (u32 i = 0; i < SCREEN_SUMS; i++) T[i] = 0;
@@ -273,27 +239,10 @@ __global__ __launch_bounds__(256) void k_screen_finish(ScreenFinP P)
         }
         if (P.rows) { u64 *o = P.rows + k * SCREEN_ROW_U64; o[0] = P.first + k; o[1] = begin; o[2] = end; o[3] = hits; o[4] = (u64)flags; }
     }
-#pragma unroll
-    for (u32 i = 0; i < SCREEN_SUMS; i++) {
-        u64 v = T[i];
-        for (int d = 32; d; d >>= 1) v += shfl_u64(v, (int)(lane ^ (u32)d));
-        if (lane == 0 && v) atomicAdd(&tsum[i], (unsigned long long)v);
-    }
-    __syncthreads();
-    if (tid < SCREEN_SUMS && tsum[tid]) atomicAdd(&P.sums[tid], tsum[tid]);
+    wg_sums(T, tsum, P.sums);
 }
 
 // ---- host side -----------------------------------------------------------------------------------------------------------------
-// the value of a lever that is a whole number; -1: not set
-static long long screen_opt(naf_gpu_ctx *c, const char *name, bool *bad)
-{
-    const char *e = ctx_opt(c, name);
-    if (!e || !e[0]) return -1;
-    char *end = nullptr; const unsigned long long v = strtoull(e, &end, 10);
-    if (*end || v > (1ull << 40)) { *bad = true; return -1; }
-    return (long long)v;
-}
-
 extern "C" int naf_gpu_unnaf_screen(naf_gpu_ctx *c, const void *d_naf_, size_t naf_len, const void *d_ref_, size_t ref_len, const naf_gpu_screen_opts *o,
                                     uint64_t first, uint64_t count, const void *d_bounds_, naf_gpu_screen_row *d_rows_, size_t row_cap, uint64_t *n_records,
                                     naf_gpu_screen_total *h_total)
@@ -309,14 +258,11 @@ extern "C" int naf_gpu_unnaf_screen(naf_gpu_ctx *c, const void *d_naf_, size_t n
     if (o->flags & ~(uint32_t)SCREEN_FLAGS) return ctx_fail(c, NAF_GPU_EARG, "%s: flags %u (NAF_GPU_SCREEN_KEEP_MATCHED, NAF_GPU_SCREEN_FORWARD_ONLY or 0)", who, (unsigned)o->flags);
     if (o->bounds_kind > NAF_GPU_SCREEN_BOUNDS_DEDUP)
         return ctx_fail(c, NAF_GPU_EARG, "%s: bounds_kind %u (NAF_GPU_SCREEN_BOUNDS_TRIM, NAF_GPU_SCREEN_BOUNDS_CLIP or NAF_GPU_SCREEN_BOUNDS_DEDUP)", who, (unsigned)o->bounds_kind);
-    u32 bits = 64, fbits = SCREEN_FILTER_DEFAULT; bool fbits_set = false;
-    { bool bad = false; long long v = screen_opt(c, "SCREEN_HASH_BITS", &bad);
-      if (bad || v > 64) return ctx_fail(c, NAF_GPU_EARG, "%s: NAF_GPU_SCREEN_HASH_BITS %s (0 to 64)", who, ctx_opt(c, "SCREEN_HASH_BITS"));
-      if (v >= 0) bits = (u32)v;
-      v = screen_opt(c, "SCREEN_FILTER_BITS", &bad);
-      if (bad || (v > 0 && (v < 64 || v > SCREEN_FILTER_MAX || (v & (v - 1)))))
-          return ctx_fail(c, NAF_GPU_EARG, "%s: NAF_GPU_SCREEN_FILTER_BITS %s (0, or a power of two from 64 to %u)", who, ctx_opt(c, "SCREEN_FILTER_BITS"), SCREEN_FILTER_MAX);
-      if (v >= 0) { fbits = (u32)v; fbits_set = true; } }
+    u64 bits = 64, fbits64 = SCREEN_FILTER_DEFAULT; bool fbits_set = false;
+    if (!lever_u64(c, "SCREEN_HASH_BITS", 64, nullptr, &bits)) return ctx_fail(c, NAF_GPU_EARG, "%s: NAF_GPU_SCREEN_HASH_BITS %s (0 to 64)", who, ctx_opt(c, "SCREEN_HASH_BITS"));
+    if (!lever_u64(c, "SCREEN_FILTER_BITS", SCREEN_FILTER_MAX, &fbits_set, &fbits64) || (fbits64 > 0 && (fbits64 < 64 || (fbits64 & (fbits64 - 1)))))
+        return ctx_fail(c, NAF_GPU_EARG, "%s: NAF_GPU_SCREEN_FILTER_BITS %s (0, or a power of two from 64 to %u)", who, ctx_opt(c, "SCREEN_FILTER_BITS"), SCREEN_FILTER_MAX);
+    u32 fbits = (u32)fbits64;
     const u32 stride = o->bounds_kind == NAF_GPU_SCREEN_BOUNDS_DEDUP ? 48u : 40u;
     const u32 flags_at = o->bounds_kind == NAF_GPU_SCREEN_BOUNDS_DEDUP ? 40u : o->bounds_kind == NAF_GPU_SCREEN_BOUNDS_CLIP ? 36u : 32u;
     UnnafPlan pl, rp;
@@ -339,15 +285,10 @@ extern "C" int naf_gpu_unnaf_screen(naf_gpu_ctx *c, const void *d_naf_, size_t n
             win = arena_new<u64>(c, 2 * count); wflags = arena_new<u32>(c, count); part = arena_new<u8>(c, count); hits = arena_new<unsigned long long>(c, count);
             if (!win || !wflags || !part || !hits) return NAF_GPU_ENOMEM;
             HIP_TRY(c, hipMemsetAsync(hits, 0, count * 8, c->stream));
-            LAUNCH(c, "unnaf_screen_stage", k_screen_stage, grid, 256, 0, d_bounds, stride, flags_at, P.rec_base, first, count, win, wflags, part, ctr);
+            LAUNCH(c, "unnaf_screen_stage", k_bounds_stage, grid, 256, 0, d_bounds, stride, flags_at, ~0u, P.rec_base, first, count, win, wflags, part, ctr);
             u64 bad = 0;
             if ((rc = ctx_readback(c, &bad, ctr, 8))) return rc;
-            if (bad != SCREEN_EMPTY) {
-                const u64 k = bad >> 2; const u32 what = (u32)(bad & 3);
-                *n_records = 0;
-                return ctx_fail(c, NAF_GPU_EARG, "%s: bounds row %llu: %s", who, (unsigned long long)k,
-                                what == 1 ? "its record is not first + its number (one row per selected record, ascending)" : what == 2 ? "begin > end" : "end is behind the record's last base");
-            }
+            if (bad != BOUNDS_OK) { *n_records = 0; return bounds_row_fail(c, who, bad); }
         }
         // the set: the table and the bitmap stay for the call, the reference's bytes go piece by piece
         std::vector<RecPiece> ref_pieces;
@@ -368,12 +309,12 @@ extern "C" int naf_gpu_unnaf_screen(naf_gpu_ctx *c, const void *d_naf_, size_t n
         u64 decoded = 0;
         {
             PieceSweep sw(c, d_ref, rp, who_ref);
-            Q.rec_base = R.rec_base; Q.ctr = ctr + 2;
+            Q.ctr = ctr + 2;
             for (const RecPiece &pc : ref_pieces) {
                 if (pc.p_hi == pc.p_lo) continue;
                 PieceSweep::Tiles tl;
                 if ((rc = sw.seq_for(pc, SCREEN_TILE, &tl))) return rc;
-                Q.seq = tl.seq; Q.b_end = tl.b_hi; Q.t0 = tl.t0; Q.ntiles = tl.ntiles; Q.r_lo = pc.r_lo; Q.r_hi = pc.r_hi; Q.p_lo = pc.p_lo; Q.p_hi = pc.p_hi;
+                (ReadsPiece &)Q = ReadsPiece(R, pc, tl);
                 LAUNCH(c, "unnaf_screen_insert", k_screen_insert, (u32)tl.ntiles, 64, 0, Q);
                 HIP_TRY(c, hipGetLastError());
                 HIP_TRY(c, hipStreamSynchronize(c->stream));
@@ -393,12 +334,12 @@ extern "C" int naf_gpu_unnaf_screen(naf_gpu_ctx *c, const void *d_naf_, size_t n
             std::vector<RecPiece> pieces;
             if ((rc = piece_plan(c, P, first, count, "SCREEN_PIECE", SCREEN_PIECE_DEFAULT, pieces))) return rc;
             PieceSweep sw(c, d_naf, pl, who);
-            Q.rec_base = P.rec_base; Q.ctr = ctr + 2; Q.first = first; Q.win = win; Q.part = part; Q.hits = hits;
+            Q.ctr = ctr + 2; Q.first = first; Q.win = win; Q.part = part; Q.hits = hits;
             for (const RecPiece &pc : pieces) {
                 if (pc.p_hi == pc.p_lo) continue;
                 PieceSweep::Tiles tl;
                 if ((rc = sw.seq_for(pc, SCREEN_TILE, &tl))) return rc;
-                Q.seq = tl.seq; Q.b_end = tl.b_hi; Q.t0 = tl.t0; Q.ntiles = tl.ntiles; Q.r_lo = pc.r_lo; Q.r_hi = pc.r_hi; Q.p_lo = pc.p_lo; Q.p_hi = pc.p_hi;
+                (ReadsPiece &)Q = ReadsPiece(P, pc, tl);
                 const u64 per = (u64)SCREEN_CHUNK * SCREEN_WAVES;
                 LAUNCH(c, "unnaf_screen_mark", k_screen_mark, (u32)((tl.ntiles + per - 1) / per), 64 * SCREEN_WAVES, fbits / 8, Q, SCREEN_CHUNK);
                 HIP_TRY(c, hipGetLastError());
@@ -409,9 +350,9 @@ extern "C" int naf_gpu_unnaf_screen(naf_gpu_ctx *c, const void *d_naf_, size_t n
             ScreenFinP F; memset(&F, 0, sizeof F);
             F.win = win; F.wflags = wflags; F.part = part; F.hits = hits; F.first = first; F.count = count; F.min_hits = o->min_hits;
             F.keep_matched = (o->flags & NAF_GPU_SCREEN_KEEP_MATCHED) ? 1u : 0u; F.sums = ctr + 8;
-            if (d_rows) { F.rows = arena_new<u64>(c, count * SCREEN_ROW_U64); if (!F.rows) return NAF_GPU_ENOMEM; }
+            if (d_rows && (rc = rows_out(c, &F.rows, count, SCREEN_ROW_U64))) return rc;
             LAUNCH(c, "unnaf_screen_finish", k_screen_finish, grid, 256, 0, F);
-            if (d_rows) LAUNCH(c, "unnaf_row_copy", k_row_copy, (u32)((count * SCREEN_ROW_U64 + 255) / 256), 256, 0, (const u64 *)F.rows, d_rows, count * SCREEN_ROW_U64);
+            if (d_rows) rows_copy(c, "unnaf_row_copy", F.rows, d_rows, count, SCREEN_ROW_U64);
             HIP_TRY(c, hipGetLastError());
         }
         u64 sum[8 + SCREEN_SUMS];

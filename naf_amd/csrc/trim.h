@@ -13,23 +13,17 @@
 // k_trim_mark: a workgroup of four wavefronts, a wavefront per tile of 4096 quality bytes, 64 bytes a lane as four 16-byte loads; tiles
 // start where the ADDRESS is a multiple of 16, as in k_qual_count, and lanes whose 64 bytes do not lie inside the decoded range load byte
 // by byte.  A lane puts its bytes into a row of its own in LDS (17 dwords a lane: the lanes' byte reads fall into different banks) and
-// walks them ONCE, part by part (a part: the lane's bytes of one record; the first record from one upper_bound in rec_base, the others by
-// walking on), one read of the 256-entry score table a byte.  A part that is a whole record writes its row.  A part whose record goes on
-// in the next lane is the lane's X, one whose record came from the lane in front its A; a lane inside a long record is X alone (a
-// through-part).  Every A moves one lane down into the X in front of it, and the X of one record -- its first lane, then through-parts --
-// are combined in lane order by a segmented reduction (shuffles, qual_seg_reduce's shape with the combine in place of the adds).  The
-// first lane of a segment then holds the summary of all bytes the record has in the tile: a record that lies inside the tile gets its
-// row, one that began in front of the tile leaves the summary in slot 0 of the tile, one that begins in it and ends behind it in slot 1
-// (open[2 * ntiles]).  Which slot a record's bytes of a tile went to follows from rec_base and the tile's number alone, so no slot needs
-// a mark: k_trim_join reads exactly the slots that were written.
+// walks them ONCE, part by part (lane_parts), one read of the 256-entry score table a byte.  A part that is a whole record writes its row;
+// the others go through seam_carry, and the first lane of a record then holds the summary of all bytes the record has in the tile: a
+// record that lies inside the tile gets its row, one that began in front of the tile leaves the summary in slot 0 of the tile, one that
+// begins in it and ends behind it in slot 1 (open[2 * ntiles]).
 //
 // k_trim_join: a lane per record of the piece.  An empty record writes its row (never kept: an empty stretch is short); a record whose
-// bytes touch more than one tile combines slot 1 of its first tile with slot 0 of every later one, in tile order, and writes its row; the
-// others return.  One step a tile: a record of 2^31 bytes costs its lane 2^19 steps.
+// bytes touch more than one tile gets its summary from seam_join and writes its row; the others return.  A record of 2^31 bytes costs
+// its lane 2^19 steps.
 //
-// Every row is written by exactly one lane, into a table in the arena (5 u64 a row) that k_row_copy takes to the caller's, whatever its
-// alignment.  The totals are sums of integers -- lanes, then the wavefront, then the workgroup in LDS, then one atomic add per counter
-// and workgroup -- so they do not depend on the order.  Nothing depends on the tile origin or on the piece size.
+// Every row is written by exactly one lane, into a table in the arena (5 u64 a row) that rows_copy takes to the caller's, whatever its
+// alignment.  The totals go through wg_sums.  Nothing depends on the tile origin or on the piece size.
 #pragma once
 
 #define TRIM_TILE 4096u
@@ -71,11 +65,10 @@ __device__ __forceinline__ TrimSum<POS> trim_combine(const TrimSum<POS> &L, cons
     if (cs > 0 && (cs > o.best || (cs == o.best && (L.suf_begin < o.b || (L.suf_begin == o.b && R.pre_end > o.e))))) { o.best = cs; o.b = L.suf_begin; o.e = R.pre_end; }
     return o;
 }
-__device__ __forceinline__ i64 trim_down(i64 v, int d) { return (i64)(((u64)(u32)__shfl_down((int)((u64)v >> 32), d) << 32) | (u32)__shfl_down((int)(u32)(u64)v, d)); }
 __device__ __forceinline__ TrimSum32 trim_sum_down(const TrimSum32 &S, int d)
 {
     TrimSum32 o;
-    o.tot = trim_down(S.tot, d); o.pre = trim_down(S.pre, d); o.suf = trim_down(S.suf, d); o.best = trim_down(S.best, d);
+    o.tot = (i64)shfl_down_u64((u64)S.tot, d); o.pre = (i64)shfl_down_u64((u64)S.pre, d); o.suf = (i64)shfl_down_u64((u64)S.suf, d); o.best = (i64)shfl_down_u64((u64)S.best, d);
     o.pre_end = (u32)__shfl_down((int)S.pre_end, d); o.suf_begin = (u32)__shfl_down((int)S.suf_begin, d); o.b = (u32)__shfl_down((int)S.b, d); o.e = (u32)__shfl_down((int)S.e, d);
     return o;
 }
@@ -97,7 +90,7 @@ struct TrimP {
     TrimOpen *open;                            // two slots a tile
     unsigned long long *total;                 // TRIM_TOTALS counters
 };
-struct TrimTot { u64 v[TRIM_TOTALS]; };
+typedef u64 TrimTot[TRIM_TOTALS];
 
 // The row of record r = bytes [rbase, rend) of the stream, from the summary of all its bytes (positions: stream byte indices), and its
 // share of the totals.
@@ -110,23 +103,9 @@ __device__ __forceinline__ void trim_row(const TrimP &P, u64 r, u64 rbase, u64 r
     const bool is_short = end - begin < P.min_len, errors = ee > P.max_ee;
     const u32 flags = is_short || errors ? (is_short ? NAF_GPU_TRIM_SHORT : 0u) | (errors ? NAF_GPU_TRIM_ERRORS : 0u) : NAF_GPU_TRIM_KEPT;
     if (P.rows) { u64 *o = P.rows + (r - P.r_lo) * TRIM_ROW_U64; o[0] = r; o[1] = begin; o[2] = end; o[3] = ee; o[4] = flags; }
-    T.v[0]++; T.v[2] += n;
-    if (flags == NAF_GPU_TRIM_KEPT) { T.v[1]++; T.v[3] += end - begin; T.v[4] += ee; }
-    T.v[5] += is_short; T.v[6] += errors;
-}
-// the lanes' shares: summed across the wavefront, then across the workgroup in `sum` (zeroed behind a barrier), then added to the counters.
-// Every lane of the workgroup calls it.
-__device__ __forceinline__ void trim_totals(TrimTot &T, unsigned long long *sum, unsigned long long *total)
-{
-    const u32 lane = threadIdx.x & 63u;
-#pragma unroll
-    for (u32 k = 0; k < TRIM_TOTALS; k++) {
-        u64 v = T.v[k];
-        for (int d = 32; d; d >>= 1) v += shfl_u64(v, (int)(lane ^ (u32)d));
-        if (lane == 0 && v) atomicAdd(&sum[k], (unsigned long long)v);
-    }
-    __syncthreads();
-    if (threadIdx.x < TRIM_TOTALS && sum[threadIdx.x]) atomicAdd(&total[threadIdx.x], sum[threadIdx.x]);
+    T[0]++; T[2] += n;
+    if (flags == NAF_GPU_TRIM_KEPT) { T[1]++; T[3] += end - begin; T[4] += ee; }
+    T[5] += is_short; T[6] += errors;
 }
 
 __global__ __launch_bounds__(256) void k_trim_mark(TrimP P)
@@ -138,7 +117,7 @@ __global__ __launch_bounds__(256) void k_trim_mark(TrimP P)
     stab[tid] = (i64)P.limit - (i64)qual_err_of(qual_err_33_dev, tid);
     if (tid < TRIM_TOTALS) tsum[tid] = 0;
     __syncthreads();
-    TrimTot T; for (u32 k = 0; k < TRIM_TOTALS; k++) T.v[k] = 0;
+    TrimTot T; for (u32 k = 0; k < TRIM_TOTALS; k++) T[k] = 0;
     const u64 tile = (u64)xcd_block() * 4 + wave;
     if (tile < P.ntiles) {                                                        // (the same for all lanes of a wave)
         const u64 T0 = P.t0 + tile * TRIM_TILE, g = T0 + lane * 64;               // the tile's and the lane's first byte
@@ -160,48 +139,28 @@ __global__ __launch_bounds__(256) void k_trim_mark(TrimP P)
                 }
             }
             const u8 *sb = (const u8 *)st;                                        // (read by the lane that wrote them: no barrier)
-            u64 r = upper_bound_u64(P.rec_base, P.r_lo, P.r_hi + 1, lo) - 1;      // rec_base[r] <= lo < rec_base[r + 1]
-            u64 rbase = P.rec_base[r], rend = P.rec_base[r + 1];
-            const u32 g32 = lane * 64, hi32 = (u32)(hi - T0);
-            u32 pos = (u32)(lo - T0);
-            for (;;) {
-                const u32 at = pos, stop = rend < hi ? (u32)(rend - T0) : hi32;   // the part: bytes [at, stop) of the tile
+            const u32 g32 = lane * 64;
+            lane_parts(P.rec_base, P.r_lo, P.r_hi, lo, hi, [&](u64 r, u64 rbase, u64 rend, u64 at64, u64 stop64) {
+                const u32 at = (u32)(at64 - T0), stop = (u32)(stop64 - T0);         // the part: bytes [at, stop) of the tile
                 i64 tot = 0, pre = 0, suf = 0, best = 0; u32 pre_end = at, suf_begin = at, bb = 0, last = 0;
 #pragma unroll 1
-                for (; pos < stop; pos++) trim_append(tot, pre, suf, best, pre_end, suf_begin, bb, last, pos, stab[sb[pos - g32]]);
+                for (u32 pos = at; pos < stop; pos++) trim_append(tot, pre, suf, best, pre_end, suf_begin, bb, last, pos, stab[sb[pos - g32]]);
                 TrimSum32 S; S.tot = tot; S.pre = pre; S.suf = suf; S.best = best; S.pre_end = pre_end; S.suf_begin = suf_begin; S.b = bb; S.e = best > 0 ? last + 1 : 0;
-                const bool from_front = rbase < T0 + at, goes_on = rend > T0 + stop;
+                const bool from_front = rbase < at64, goes_on = rend > stop64;
                 if (!from_front && !goes_on) trim_row(P, r, rbase, rend, S.tot, S.best, T0 + S.b, T0 + S.e, T);
                 else if (!goes_on) { A = S; has_a = true; }
                 else { X = S; pend = true; thru = from_front; xr = r; xbase = rbase; xend = rend; }
-                if (stop >= hi32) break;
-                do { r++; rbase = rend; rend = P.rec_base[r + 1]; } while (rend <= T0 + pos);     // the next record that has bytes (pos < hi <= p_hi: there is one)
-            }
+            });
         }
-        if (__ballot(pend || has_a)) {
-            // the part that ends a record joins the X of the lane in front (the byte in front of it is that lane's last and the same record's);
-            // lane 0's came from the tile in front: the record's bytes in this tile are that part
-            const TrimSum32 N = trim_sum_down(A, 1);
-            const bool na = __shfl_down((int)has_a, 1) != 0 && lane < 63;
-            if (na && pend) X = trim_combine(X, N);
-            if (lane == 0 && has_a) P.open[2 * tile] = trim_open_of(A, T0);
-            // lanes of one record: its first lane here, then through-parts
-            const bool head = pend && (!thru || lane == 0);
-            const u64 cut = __ballot(head || !pend);
-            const u64 above = lane == 63 ? 0ull : cut >> (lane + 1);
-            const int len = above ? __ffsll((long long)above) : 64 - (int)lane;  // lanes [lane, lane + len) are this lane's segment
-#pragma unroll
-            for (int d = 1; d < 64; d <<= 1) {
-                const TrimSum32 Y = trim_sum_down(X, d);
-                if (pend && d < len) X = trim_combine(X, Y);
-            }
-            if (head) {
-                if (xbase >= T0 && xend <= T0 + TRIM_TILE) trim_row(P, xr, xbase, xend, X.tot, X.best, T0 + X.b, T0 + X.e, T);
-                else P.open[2 * tile + (xbase < T0 ? 0 : 1)] = trim_open_of(X, T0);
-            }
+        const bool head = seam_carry(lane, has_a, A, pend, thru, X, [](const TrimSum32 &S, int d) { return trim_sum_down(S, d); },
+                                     [](const TrimSum32 &L, const TrimSum32 &R) { return trim_combine(L, R); });
+        if (lane == 0 && has_a) P.open[2 * tile] = trim_open_of(A, T0);          // it came from the tile in front: the record's bytes in this tile are that part
+        if (head) {
+            if (xbase >= T0 && xend <= T0 + TRIM_TILE) trim_row(P, xr, xbase, xend, X.tot, X.best, T0 + X.b, T0 + X.e, T);
+            else P.open[2 * tile + (xbase < T0 ? 0 : 1)] = trim_open_of(X, T0);
         }
     }
-    trim_totals(T, tsum, P.total);
+    wg_sums(T, tsum, P.total);
 }
 
 __global__ __launch_bounds__(256) void k_trim_join(TrimP P)
@@ -209,22 +168,18 @@ __global__ __launch_bounds__(256) void k_trim_join(TrimP P)
     __shared__ unsigned long long tsum[TRIM_TOTALS];
     if (threadIdx.x < TRIM_TOTALS) tsum[threadIdx.x] = 0;
     __syncthreads();
-    TrimTot T; for (u32 k = 0; k < TRIM_TOTALS; k++) T.v[k] = 0;
+    TrimTot T; for (u32 k = 0; k < TRIM_TOTALS; k++) T[k] = 0;
     const u64 r = P.r_lo + (u64)blockIdx.x * 256 + threadIdx.x;
     if (r < P.r_hi) {
         const u64 rbase = P.rec_base[r], rend = P.rec_base[r + 1];
         if (rend == rbase) trim_row(P, r, rbase, rend, 0, 0, 0, 0, T);
         else {
-            const u64 a = (rbase - P.t0) / TRIM_TILE, b = (rend - 1 - P.t0) / TRIM_TILE;
-            if (b > a) {
-                TrimOpen S = P.open[2 * a + 1];
-                for (u64 t = a + 1; t <= b; t++) S = trim_combine(S, P.open[2 * t]);
-                trim_row(P, r, rbase, rend, S.tot, S.best, S.b, S.e, T);
-                T.v[7] += b - a + 1;
-            }
+            TrimOpen S;
+            const u64 tiles = seam_join(P.open, P.t0, TRIM_TILE, rbase, rend, S, [](const TrimOpen &L, const TrimOpen &R) { return trim_combine(L, R); });
+            if (tiles > 1) { trim_row(P, r, rbase, rend, S.tot, S.best, S.b, S.e, T); T[7] += tiles; }
         }
     }
-    trim_totals(T, tsum, P.total);
+    wg_sums(T, tsum, P.total);
 }
 
 // ---- host side -----------------------------------------------------------------------------------------------------------------
@@ -275,13 +230,13 @@ extern "C" int naf_gpu_unnaf_trim(naf_gpu_ctx *c, const void *d_naf_, size_t naf
                 Q.ntiles = (pc.p_hi - Q.t0 + TRIM_TILE - 1) / TRIM_TILE;
                 if (Q.ntiles > 0x7FFFFFFFull) return ctx_fail(c, NAF_GPU_EARG, "trim: a piece of %llu quality bytes is too long for one launch", (unsigned long long)(pc.p_hi - pc.p_lo));
             }
-            if (d_rows) { Q.rows = arena_new<u64>(c, nr * TRIM_ROW_U64); if (!Q.rows) return NAF_GPU_ENOMEM; }
+            if (d_rows && (rc = rows_out(c, &Q.rows, nr, TRIM_ROW_U64))) return rc;
             if (Q.ntiles) {
                 Q.open = arena_new<TrimOpen>(c, 2 * Q.ntiles); if (!Q.open) return NAF_GPU_ENOMEM;
                 LAUNCH(c, "unnaf_trim_mark", k_trim_mark, (u32)((Q.ntiles + 3) / 4), 256, 0, Q);
             }
             LAUNCH(c, "unnaf_trim_join", k_trim_join, (u32)((nr + 255) / 256), 256, 0, Q);
-            if (d_rows) LAUNCH(c, "unnaf_row_copy", k_row_copy, (u32)((nr * TRIM_ROW_U64 + 255) / 256), 256, 0, (const u64 *)Q.rows, d_rows + 40 * (pc.r_lo - first), nr * TRIM_ROW_U64);
+            if (d_rows) rows_copy(c, "unnaf_row_copy", Q.rows, d_rows + 40 * (pc.r_lo - first), nr, TRIM_ROW_U64);
             HIP_TRY(c, hipGetLastError());
             HIP_TRY(c, hipStreamSynchronize(c->stream));
             sw.release();

@@ -92,6 +92,10 @@ __device__ __forceinline__ T wg_scan_inclusive(T v, T *total, T *lds /* 4 entrie
 
 // One u32 per lane of a wavefront of 64: the sum in every lane, and the exclusive prefix sum.
 __device__ __forceinline__ u32 wave_sum_u32(u32 v) { for (int d = 32; d; d >>= 1) v += (u32)__shfl_xor((int)v, d); return v; }
+// One u64 per lane: the sum and the maximum in every lane.  (lane ^ d's v)
+__device__ __forceinline__ u64 shfl_xor_u64(u64 v, int d) { const int o = (int)(threadIdx.x & 63u) ^ d; return ((u64)(u32)__shfl((int)(v >> 32), o) << 32) | (u32)__shfl((int)(u32)v, o); }
+__device__ __forceinline__ u64 wave_sum_u64(u64 v) { for (int d = 32; d; d >>= 1) v += shfl_xor_u64(v, d); return v; }
+__device__ __forceinline__ u64 wave_max_u64(u64 v) { for (int d = 32; d; d >>= 1) { const u64 o = shfl_xor_u64(v, d); v = o > v ? o : v; } return v; }
 __device__ __forceinline__ u32 wave_prefix_u32(u32 v, u32 lane)                 // exclusive
 {
     u32 s = v;

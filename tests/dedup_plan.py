@@ -559,3 +559,21 @@ def random_reads(seed, n=400):
         else:
             out.append(LP._random(rng, int(rng.integers(0, 12 if k % 4 == 0 else 90)), CODES if k % 2 else "ACGTN"))
     return out
+
+
+# ---- who takes part ------------------------------------------------------------------------------------------------------------------
+PART_N = (1, 63, 64, 65, 255, 256, 257, 513)                                            # the wave and workgroup seams of a launch of 256 lanes, a lane per record
+
+
+def part_sets(N):
+    """(name, per record: it takes part) -- exactly the first n records, exactly the last n, every n-th, for every n of PART_N"""
+    for n in PART_N:
+        yield "the first %d" % n, [k < n for k in range(N)]
+        yield "the last %d" % n, [k >= N - n for k in range(N)]
+        yield "every %d-th" % n, [k % n == 0 for k in range(N)]
+
+
+def part_bounds(lens, takes):
+    """trim-kind bounds of reads of at least 3 bases: windows that differ from read to read; NAF_GPU_TRIM_KEPT where the read takes part,
+    one of the three other states of a trim row where it does not"""
+    return [(k % 3, n - k % 2, KEPT if on else (SHORT, ERRORS, SHORT | ERRORS)[k % 3]) for k, (n, on) in enumerate(zip(lens, takes))]

@@ -430,3 +430,28 @@ def test_cli_dedup_writes_the_reads_and_the_table(gpu, planned):
     for args in (["--dedup", "--region", "nosuch"], ["--dedup", "--records", "1-99999"]):
         p = unnaf_cli(args, A.naf)
         assert p.returncode == 1 and p.stdout == b"" and p.stderr.startswith(b"unnaf error: "), args
+
+
+# ---- 13. who takes part, at the wave and workgroup seams of a launch with a lane per record ------------------------------------------------
+def test_considered_and_who_takes_part_at_the_seams_of_a_launch(oracle, gpu):
+    """513 reads of 8 to 12 bases, a third of them copies; the bounds rows carry NAF_GPU_TRIM_KEPT for exactly the first n, the last n and
+    every n-th record, n at 1, the wavefront's 64 and the workgroup's 256 and beside them, and 513.  `considered` is the number of set
+    bits, and a read that takes no part has its row as it went in."""
+    B = DP.Builder(7300 + SEED)
+    for k in range(513):
+        B.add(B.reads[int(B.rng.integers(0, k))] if k % 3 == 2 else B.bg(int(B.rng.integers(8, 13))))
+    c = DP.Case("short", B, lower=False)
+    A = Archive(oracle, gpu, oracle.ennaf(c.text, c.seq_type), c)
+    assert A.N == 513 and A.records == c.records and min(A.lens) >= 8 and max(A.lens) <= 12
+    for k, (name, takes) in enumerate(DP.part_sets(A.N)):
+        bounds = DP.part_bounds(A.lens, takes)
+        both = bool(k % 2)
+        want, total_w, levels_w = DP.model(A.records, both, bounds)
+        rows, total, levels = gpu.unnaf_dedup(A.d_naf, both, bounds=gpu.to_device(DP.bounds_rows(bounds, "trim")), bounds_kind="trim")
+        differ("rows", rows, want, name)
+        print(name, "considered", int(total.considered), "of", sum(takes))
+        assert total_tuple(total) == total_w and levels == levels_w, name
+        assert int(total.considered) == sum(takes), name
+        out = [r for r, on in enumerate(takes) if not on]
+        assert [(int(x["begin"]), int(x["end"]), int(x["flags"])) for x in rows[out]] == [bounds[r] for r in out], name
+        assert (rows["first"][out] == out).all() and not rows["copies"][out].any() and not rows["strand"][out].any(), name

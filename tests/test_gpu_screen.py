@@ -598,3 +598,32 @@ def test_cli_screen_writes_the_reads_and_the_table(gpu, planned, tmp_path):
     open(ref_path, "wb").write(b"not an archive")
     p = unnaf_cli(S, A.naf)
     assert p.returncode == 1 and p.stdout == b"" and p.stderr.startswith(b"unnaf error: --screen reference: ")
+
+
+# ---- 13. who takes part, at the wave and workgroup seams of a launch with a lane per record ------------------------------------------------
+def test_considered_and_who_takes_part_at_the_seams_of_a_launch(oracle, gpu):
+    """513 reads of 8 to 12 bases, every other one cut out of the reference; the bounds rows carry NAF_GPU_TRIM_KEPT for exactly the first
+    n, the last n and every n-th record (dedup_plan.part_sets).  `considered` is the number of set bits, and a read that takes no part has
+    no hits and its row as it went in."""
+    K = 4
+    rng = np.random.default_rng(9950 + SEED)
+    ref = SP.Ref("short", ["", SP.capped(rng, 80), SP.capped(rng, 30)])
+    B = SP.Builder(9960 + SEED, K, ref)
+    for k in range(513):
+        n = int(B.rng.integers(8, 13))
+        i = B.source(n)
+        B.add(B.big[i:i + n] if k % 2 else B.bg(n))
+    c = SP.Case("short", B, ref, (K,), lower=False)
+    A, R = archives(oracle, gpu, c.text, 0, "fasta", c.records)["oracle"], archives(oracle, gpu, ref.text, 0, "fasta", ref.records)["oracle"]
+    assert A.N == 513 and min(A.lens) >= 8 and max(A.lens) <= 12
+    for k, (name, takes) in enumerate(DP.part_sets(A.N)):
+        bounds = DP.part_bounds(A.lens, takes)
+        kw = dict(keep_matched=bool(k % 2), forward_only=bool(k % 4 >= 2))
+        want, total_w = SP.model(A.stream, R.stream, K, bounds=bounds, **kw)
+        rows, total = gpu.unnaf_screen(A.d_naf, R.d_naf, k=K, bounds=gpu.to_device(SP.bounds_rows(bounds, "trim")), bounds_kind="trim", **kw)
+        differ("rows", rows, want, name)
+        print(name, "considered", int(total.considered), "of", sum(takes))
+        assert total_tuple(total) == total_w, (name, total_tuple(total), total_w)
+        assert int(total.considered) == sum(takes), name
+        out = [r for r, on in enumerate(takes) if not on]
+        assert [(int(x["begin"]), int(x["end"]), int(x["flags"])) for x in rows[out]] == [bounds[r] for r in out] and not rows["hits"][out].any(), name

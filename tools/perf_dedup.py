@@ -23,7 +23,7 @@ from naf_amd import capi, synth  # noqa: E402
 from perf_trim import long_reads  # noqa: E402
 
 A13 = "AGATCGGAAGAGC"
-KERNELS = ("unnaf_dedup_stage", "unnaf_dedup_hash", "unnaf_dedup_join", "unnaf_dedup_insert", "unnaf_dedup_verify", "unnaf_dedup_count", "unnaf_dedup_finish", "unnaf_row_copy")
+KERNELS = ("unnaf_dedup_stage", "unnaf_dedup_preset", "unnaf_dedup_hash", "unnaf_dedup_join", "unnaf_dedup_insert", "unnaf_dedup_verify", "unnaf_dedup_count", "unnaf_dedup_finish", "unnaf_row_copy")
 SHARE, REVERSED = 4, 10                         # one read in SHARE is a copy, one copy in REVERSED its reverse complement
 
 
