@@ -3415,6 +3415,12 @@ static size_t naf_header_bytes(const naf_gpu_ennaf_opts *o, bool store_mask, boo
 // One stream -> its frame, or its part of a frame (flags: ZENC_PART*; 0 = a whole frame without the magic number).  `tail` bytes at
 // the end are coded as a part of their own, i.e. end up in a Raw block behind the others.  With `place` the frame goes where the hook
 // says once its size is known (zstd_encode): the tail part is coded first, into scratch, so that the hook hears the size of the whole.
+// The flags of the two parts of such a stream.  The head part begins the frame where the stream does and is coded as the stream is; the
+// tail part ends the frame where the stream does and carries `coding`.
+static int stream_head_flags(int flags) { return ZENC_PART | ((!(flags & ZENC_PART) || (flags & ZENC_PART_FIRST)) ? ZENC_PART_FIRST : 0) | (flags & (ZENC_PREFER_RAW | ZENC_PREFER_FLAT | ZENC_SHORT_CODES | ZENC_FRAME_TREE)); }
+static int stream_tail_flags(int flags, int coding) { return ZENC_PART | ((!(flags & ZENC_PART) || (flags & ZENC_PART_LAST)) ? ZENC_PART_LAST : 0) | coding; }
+// like_head: a ragged block of some size is coded like the blocks in front of it (a stream that is not placed, a shard's part); a placed stream's tail is not
+static int stream_tail_coding(int flags, u32 tail, bool like_head) { return (flags & ZENC_LONG_LAST) | ((like_head && tail >= 2048) ? (flags & (ZENC_PREFER_FLAT | ZENC_SHORT_CODES)) : 0); }
 struct PlaceTail { const ZencPlace *outer; size_t tail_len; u8 *at; };
 static u8 *place_before_tail(void *ud, size_t len) { PlaceTail *t = (PlaceTail *)ud; return t->at = t->outer->fn(t->outer->ud, len + t->tail_len); }
 // the two halves of a placed stream (zstd_encode_begin / _finish): what the caller queues between them runs beside the planning
@@ -3423,9 +3429,8 @@ static int encode_stream_begin(naf_gpu_ctx *c, const u8 *d_stream, u64 len, int 
 {
     J->main = nullptr; J->d_stream = d_stream; J->len = len; J->level = level; J->flags = flags; J->tail = (tail && len > tail) ? tail : 0;
     J->sized = false; J->tail_tmp = nullptr; J->tail_len = 0; J->tail_flags = 0;
-    int f1 = flags;
-    if (J->tail) f1 = ZENC_PART | ((!(flags & ZENC_PART) || (flags & ZENC_PART_FIRST)) ? ZENC_PART_FIRST : 0) | (flags & (ZENC_PREFER_RAW | ZENC_PREFER_FLAT | ZENC_SHORT_CODES | ZENC_FRAME_TREE));
-    J->tail_flags = flags & ZENC_LONG_LAST;
+    const int f1 = J->tail ? stream_head_flags(flags) : flags;
+    J->tail_flags = stream_tail_coding(flags, tail, false);
     if (direct && (lz || len - J->tail != (u64)nd << 15)) return ctx_fail(c, NAF_GPU_EARG, "direct blocks need a stream of whole blocks and no match finder");
     int rc = zstd_encode_begin(c, d_stream, len - J->tail, level, f1, lz, block_log, window_log, &J->main, direct, nd, dloc);
     if (rc) { zstd_encode_drop(J->main); J->main = nullptr; }
@@ -3436,7 +3441,7 @@ static int encode_stream_begin(naf_gpu_ctx *c, const u8 *d_stream, u64 len, int 
 static int encode_stream_size(naf_gpu_ctx *c, StreamJob *J, size_t *clen)
 {
     if (J->tail && !J->sized) {
-        const int f2 = ZENC_PART | ((!(J->flags & ZENC_PART) || (J->flags & ZENC_PART_LAST)) ? ZENC_PART_LAST : 0) | J->tail_flags;
+        const int f2 = stream_tail_flags(J->flags, J->tail_flags);
         const size_t tb = naf_gpu_zstd_compress_bound(J->tail);
         u8 *tmp = (u8 *)arena_alloc(c, tb); if (!tmp) return NAF_GPU_ENOMEM;
         size_t b = 0;
@@ -3453,7 +3458,7 @@ static int encode_stream_finish(naf_gpu_ctx *c, StreamJob *J, size_t *clen, cons
 {
     ZencJob *mj = J->main; J->main = nullptr;
     if (!J->tail) return zstd_encode_finish(c, mj, nullptr, 0, clen, place);
-    const int f2 = ZENC_PART | ((!(J->flags & ZENC_PART) || (J->flags & ZENC_PART_LAST)) ? ZENC_PART_LAST : 0) | J->tail_flags;
+    const int f2 = stream_tail_flags(J->flags, J->tail_flags);
     size_t a = 0, b = J->tail_len;
     u8 *tmp = J->tail_tmp;
     int rc = 0;
@@ -3476,9 +3481,7 @@ static int encode_stream(naf_gpu_ctx *c, const u8 *d_stream, u64 len, int level,
         return encode_stream_finish(c, &J, clen, place);
     }
     if (!tail || len <= tail) return zstd_encode(c, d_stream, len, level, dst, cap, clen, flags, lz, block_log, window_log);
-    const bool part = (flags & ZENC_PART) != 0;
-    const int f1 = ZENC_PART | ((!part || (flags & ZENC_PART_FIRST)) ? ZENC_PART_FIRST : 0) | (flags & (ZENC_PREFER_RAW | ZENC_PREFER_FLAT | ZENC_SHORT_CODES | ZENC_FRAME_TREE));
-    const int f2 = ZENC_PART | ((!part || (flags & ZENC_PART_LAST)) ? ZENC_PART_LAST : 0) | (flags & ZENC_LONG_LAST) | (tail >= 2048 ? (flags & (ZENC_PREFER_FLAT | ZENC_SHORT_CODES)) : 0);   // (a ragged block of some size is coded like the blocks in front of it)
+    const int f1 = stream_head_flags(flags), f2 = stream_tail_flags(flags, stream_tail_coding(flags, tail, true));
     size_t a = 0, b = 0;
     int rc = zstd_encode(c, d_stream, len - tail, level, dst, cap, &a, f1, lz, block_log, window_log); if (rc) return rc;
     rc = zstd_encode(c, d_stream + (len - tail), tail, level, dst + a, cap - a, &b, f2, 0, 0, 0); if (rc) return rc;
@@ -3953,7 +3956,7 @@ extern "C" int naf_gpu_ennaf_shard_finish(naf_gpu_ctx *c, const naf_gpu_ennaf_op
             const int flags = ZENC_PART | (V.first[i] ? ZENC_PART_FIRST : 0) | (V.last[i] ? ZENC_PART_LAST : 0) | X.flags[i];
             const u32 tail = part_tail(i);
             if ((rc = encode_stream_begin(w, X.ptr[i], X.len[i], o->level, flags, X.lz[i], X.block_log[i], X.window_log[i], tail, &job[i]))) { if (w != c) ctx_fail(c, rc, "%s", w->err); break; }
-            job[i].tail_flags = (flags & ZENC_LONG_LAST) | (tail >= 2048 ? (flags & (ZENC_PREFER_FLAT | ZENC_SHORT_CODES)) : 0);    // (a ragged block of some size is coded like the blocks in front of it: encode_stream)
+            job[i].tail_flags = stream_tail_coding(flags, tail, true);    // (as encode_stream codes it)
             begun[i] = true;
         }
         struct Fixed { u8 *at; size_t len; };

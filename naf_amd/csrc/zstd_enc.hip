@@ -1227,7 +1227,7 @@ __device__ __forceinline__ void zenc_flat4_stream(u8 *out, const u8 *s, u32 n, c
 // LZ-coded blocks (mode[b] != 0) take their literals from L.lits with the plan / codes / tree of those literals (plan1 ...)
 // and append the Sequences_Section made by k_lz_seqenc; all other blocks are coded from src as literal-only blocks.
 struct ZWriteLz { const u8 *mode; const ZEncPlan *plan1; const u16 *codes1; const u8 *trees1; LzBufs B; u32 not_last; u32 wave_general; u32 frame_split; };   // frame_split: the blocks coded with the frame's code are k_zenc_write<true>'s   // wave_general: blocks of general Huffman codes are k_zenc_write_wave's   // not_last: the frame continues behind these blocks (a shard's part of a frame)
-struct ZencJob { const u8 *src; size_t n; u32 nblk, frame_wlog; ZEncPlan *plan; u16 *codes; u8 *trees; u64 *offs; u64 hdr; int with_magic, empty; ZWriteLz L; bool direct; u32 block_bytes; ZencLoc dloc; u64 known_total; int have_total; };   // have_total: the blocks' bytes were read back already (zstd_encode_size)   // dloc.loc != nullptr: the direct blocks' codes are tile-local (k_zenc_write_direct_loc)
+struct ZencJob { const u8 *src; size_t n; u32 nblk, frame_wlog; ZEncPlan *plan; u16 *codes; u8 *trees; u64 *offs; u64 hdr; int with_magic, empty; ZWriteLz L; bool direct; u32 block_bytes; ZencLoc dloc; u64 known_total; int have_total, own_sync; };   // own_sync: ... by a read-back on this job's OWN stream (zstd_encode_size alone: its planning has finished, zenc_beside)   // have_total: the blocks' bytes were read back already (zstd_encode_size, zstd_encode_set_total)   // dloc.loc != nullptr: the direct blocks' codes are tile-local (k_zenc_write_direct_loc)
 // FRAME: the blocks coded with the FRAME's code only (ZENC_FRAME_TREE: nearly every block of a FASTQ's quality and sequence frames) -- one
 // table for the workgroup instead of sixteen, 5.6 KiB of LDS instead of 13: twice the wavefronts per CU for a kernel whose lanes each walk
 // a stream of 8 K symbols.  The plain instantiation then leaves those blocks alone (L.frame_split).
@@ -1578,204 +1578,356 @@ extern "C" size_t naf_gpu_zstd_compress_bound(size_t n)
     return n + 3 * (n / 1024 + 2) + 64;                            // blocks are never smaller than 1 KiB (a 2^10 window)
 }
 
+// ---- the frame driver ---------------------------------------------------------------------------------------------
+// zstd_encode_begin and zenc_finish are lists of phases.  What the phases of a frame being planned share is one plain struct, ZencFrame;
+// what the writers need of it afterwards is the ZencJob.
+// The options of a frame, decoded ONCE (zenc_options): nothing behind it looks at the flags, the level or a lever.
+struct ZencOpts {
+    bool part, part_first, part_last;             // a shard's part of a frame: blocks only
+    int with_magic;                               // 1: the magic number in front (never for a part)
+    int window_log;                               // as the caller gave it
+    u32 min_gain, maxbits, prefer_flat, long_last, try_fse;
+    u32 block_log;                                // of a frame without a window (zenc_geometry has the last word)
+    bool use_lz;
+    bool frame_tree_allowed, frame_quick, lz_lines, tree_defer, frame_write;    // levers, true unless NAF_GPU_<NAME>=0
+};
+struct ZencFrame {
+    naf_gpu_ctx *c; const u8 *src; size_t n; ZencJob *J;
+    ZencOpts O;
+    const u8 *direct; u32 nd; const ZencLoc *dloc;
+    // geometry
+    u32 block_log, window_log, frame_wlog, nblk, lz_buf; u64 bs, hdr; bool use_lz, lzx, lz_on;     // lz_on: the match finder runs (a stream of 64 bytes at least)
+    // the plan of the blocks, and what settles blocks in front of the planner
+    ZEncPlan *plan; u16 *codes; u8 *trees; u64 *offs; ZTreeCache *cache; u32 sample_stride;
+    u8 *done;                                     // zenc_done_map
+    bool frame_tree; u32 *fhist; ZEncPlan *fplan; u16 *fcodes; u8 *ftree;
+    LzBufs B; u8 *lz_fallback, *wt_defer;
+};
+#define ZENC_EMPTY_PART 1                         // zenc_geometry: the job is complete, nothing to plan
+
 // block_log: log2 of the target block size (clamped to 17 = the format maximum of 128 KiB)
 // with_magic: 1 = whole frame with its magic number, 0 = whole frame without it (as stored in a .naf section),
 //   ZENC_PART | ZENC_PART_FIRST | ZENC_PART_LAST = a shard's part of a frame: blocks only, behind the 2-byte frame header when
 //   FIRST, ending the frame when LAST (an empty part that is not LAST is zero bytes; an empty LAST part is one empty Raw block).
+static void zenc_options(const naf_gpu_ctx *c, int level, int with_magic, int lz, int block_log_hint, int window_log, ZencOpts &O)
+{
+    O.part = (with_magic & ZENC_PART) != 0; O.part_first = (with_magic & ZENC_PART_FIRST) != 0; O.part_last = (with_magic & ZENC_PART_LAST) != 0;
+    O.min_gain = (with_magic & ZENC_PREFER_RAW) ? 32u : 0u;
+    // (the same streams -- the mask -- keep their codes to 9 bits: this build's decoder then walks them with its single-level table)
+    O.maxbits = (with_magic & ZENC_PREFER_RAW) ? 9u : (with_magic & ZENC_SHORT_CODES) ? 7u : (u32)ZENC_HUF_MAXBITS;
+    // ZENC_PREFER_FLAT: blocks of 2^k distinct symbols take k-bit codes unless Huffman coding saves a sixteenth of the block
+    // (NAF_GPU_PREFER_FLAT=0: never; =d: the threshold 1/d)
+    O.prefer_flat = (with_magic & ZENC_PREFER_FLAT) ? 16u : 0u;
+    const char *pf = ctx_opt(c, "PREFER_FLAT");
+    if (O.prefer_flat && pf && pf[0]) O.prefer_flat = (u32)atoi(pf);
+    O.long_last = ((with_magic & ZENC_LONG_LAST) && (!O.part || O.part_last)) ? 1u : 0u;
+    O.with_magic = O.part ? 0 : with_magic & ~(ZENC_PREFER_RAW | ZENC_PREFER_FLAT | ZENC_SHORT_CODES | ZENC_FRAME_TREE | ZENC_LONG_LAST);
+    O.window_log = window_log;
+    O.block_log = 15;                                            // 32 KiB: 4 streams of 8 KiB; more streams = more decode parallelism
+    if (block_log_hint >= 10 && block_log_hint <= 17) O.block_log = (u32)block_log_hint;
+    const char *e = ctx_opt(c, "BLOCK_LOG");
+    if (e) { int v = atoi(e); if (v >= 10 && v <= 17) O.block_log = (u32)v; }
+    const char *el = ctx_opt(c, "LZ");                       // "0": never, "all": every stream (tests)
+    O.use_lz = lz || level >= 2;
+    if (el && !strcmp(el, "0")) O.use_lz = false;
+    if (el && !strcmp(el, "all")) O.use_lz = true;
+    // LZ-coded streams: 8 KiB blocks.  The decoder decodes and executes the sequences of a block serially -- a lane, then a wavefront per
+    // block whose LDS buffer is the block's size -- so smaller blocks are more lanes, more workgroups per CU and shorter chains; matches in
+    // ids / names / lengths are a few dozen bytes back anyway (a FASTQ's read names: the archive is no larger than with 16 KiB blocks).
+    if (O.use_lz && !e) O.block_log = (lz && block_log_hint >= 10 && block_log_hint <= 15) ? (u32)block_log_hint : 13u;   // (the hint of a caller that asked for the match finder itself: ennaf's comments and lengths of many records)
+    if (O.use_lz && O.block_log > 15) O.block_log = 15;          // LZ lengths and distances are kept in 16 bits
+    // level 1 writes Huffman weights directly where the format allows it (up to 128 of them): FSE-coding them saves about a
+    // dozen bytes per block and costs one lane a serial pass per block
+    O.try_fse = level >= 2;
+    // the frame's tree (k_zenc_plan): level 1 without the match finder, frames of enough blocks to sample; NAF_GPU_FRAME_TREE=0: a tree per block
+    const char *eft = ctx_opt(c, "FRAME_TREE");
+    O.frame_tree_allowed = level <= 1 && (with_magic & ZENC_FRAME_TREE) != 0 && !(eft && eft[0] == '0');
+    const char *fq = ctx_opt(c, "FRAME_QUICK");
+    O.frame_quick = !(fq && fq[0] == '0');
+    const char *ll = ctx_opt(c, "LZ_LINES");
+    O.lz_lines = !(ll && ll[0] == '0');
+    const char *td = ctx_opt(c, "TREE_DEFER");
+    O.tree_defer = !(td && td[0] == '0');
+    const char *fs = ctx_opt(c, "FRAME_WRITE");              // (NAF_GPU_FRAME_WRITE=0: every block by the sixteen-table writer)
+    O.frame_write = !(fs && fs[0] == '0');
+}
+
+// Blocks, window and header of the frame; ZENC_EMPTY_PART for an empty part that does not end its frame.
+static int zenc_geometry(ZencFrame &F)
+{
+    naf_gpu_ctx *c = F.c; const ZencOpts &O = F.O; const size_t n = F.n;
+    if (O.part && n == 0 && !O.part_last) {
+        F.J->empty = 1; F.J->hdr = O.part_first ? 2 : 0; F.J->frame_wlog = (u32)(O.window_log >= 10 ? O.window_log : 19);
+        return ZENC_EMPTY_PART;
+    }
+    F.use_lz = O.use_lz; F.lz_on = F.use_lz && n >= 64;
+    // cross-block matching (window_log >= 10; the host maps level / --long to it): 64 KiB blocks -- fewer block and table headers,
+    // and a repeat is cut less often; lengths still fit 16 bits (k_lzx_parse clamps a match at 65535)
+    F.lzx = F.lz_on && O.window_log >= 10;
+    F.window_log = (u32)(O.window_log > 31 ? 31 : O.window_log);
+    F.block_log = O.block_log;
+    if (F.lzx) F.block_log = F.window_log < 16 ? F.window_log : 16u;            // Block_Maximum_Size is the smaller of Window_Size and 128 KiB (3.1.1.2.4)
+    // The window announced in the frame header follows from the OPTIONS alone, not from this part's size: the header is written by the
+    // first part of a sharded / chunked frame, and a first part of a few bytes (the ids of a slice that is one chromosome) says
+    // nothing about the offsets the later parts use -- the reference's streaming decoder sizes its history from this field
+    F.frame_wlog = (F.use_lz && O.window_log >= 10) ? F.window_log : 19u;
+    F.bs = 1ull << F.block_log;
+    const u64 nblk64 = n ? (n + F.bs - 1) / F.bs : 1;
+    if (nblk64 > 0x7FFFFFFFull) return ctx_fail(c, NAF_GPU_EARG, "stream too large");
+    F.nblk = (u32)nblk64;
+    F.hdr = O.with_magic ? 6 : (O.part && !O.part_first) ? 0 : 2;
+    F.lz_buf = (u32)((F.bs + 1 + 320 + 15) & ~15ull);             // a block of the even split holds at most bs bytes
+    if (F.direct && (F.use_lz || F.block_log != 15 || F.nblk != F.nd || n != (size_t)F.nd << 15 || O.prefer_flat < 2 || !zenc_flat16().tb))
+        return ctx_fail(c, NAF_GPU_EARG, "direct blocks: the stream must be %u blocks of 32 KiB coded without the match finder", F.nd);
+    return 0;
+}
+
+// ---- launches the phases share
+// k_zenc_plan, whoever asks: what its four callers differ in, by name; what a caller does not set is null or zero.
+struct PlanCall {
+    const char *name; u32 grid;
+    const u8 *src; u64 n; u32 nblk; ZEncPlan *plan; u16 *codes; u8 *trees; u64 *csize;
+    const u32 *blk_len; u64 slot;                 // blocks of their own lengths, `slot` bytes apart (k_zenc_plan)
+    ZTreeCache *cache; u32 sample_stride;
+    u32 min_gain, prefer_flat;
+    const u8 *done; u8 *wt_defer;
+    u32 *fhist; const ZEncPlan *fplan; const u16 *fcodes; const u32 *fratio;
+    u32 long_last;
+};
+static PlanCall plan_call(const char *name, u32 grid) { PlanCall p; memset(&p, 0, sizeof p); p.name = name; p.grid = grid; return p; }
+// ... over the frame's own blocks
+static PlanCall plan_call_blocks(const ZencFrame &F, const char *name, u32 grid)
+{
+    PlanCall p = plan_call(name, grid);
+    p.src = F.src; p.n = (u64)F.n; p.nblk = F.nblk; p.plan = F.plan; p.codes = F.codes; p.trees = F.trees; p.csize = F.offs;
+    p.min_gain = F.O.min_gain; p.prefer_flat = F.O.prefer_flat; p.done = F.done;
+    return p;
+}
+static void launch_plan(const ZencFrame &F, const PlanCall &p)
+{
+    LAUNCH(F.c, p.name, k_zenc_plan, p.grid, 256, 0, p.src, p.n, p.nblk, p.plan, p.codes, p.trees, p.csize, p.blk_len, p.slot, p.cache, p.sample_stride, F.O.try_fse, p.min_gain, F.O.maxbits, p.prefer_flat,
+           p.done, p.wt_defer, p.fhist, p.fplan, p.fcodes, p.fratio, p.long_last);
+}
+// the tree descriptions a k_zenc_plan left in `wt_defer`, a lane each
+static void launch_tree(naf_gpu_ctx *c, u32 nblk, ZEncPlan *plan, u8 *trees, u64 *csize, const u8 *wt_defer, u32 min_gain)
+{
+    LAUNCH(c, "zenc_tree", k_zenc_tree, cdiv(nblk, 64), 64, 64 * sizeof(ZTreeLane), nblk, plan, trees, csize, wt_defer, min_gain);
+}
+// The map of the blocks that are settled in front of the planner: made by the first phase that needs it.  `zeroed`: a fresh map is
+// cleared (the flat scan writes every byte of its own).
+static int zenc_done_map(ZencFrame &F, bool zeroed)
+{
+    if (F.done) return 0;
+    F.done = (u8 *)arena_alloc(F.c, F.nblk); if (!F.done) return NAF_GPU_ENOMEM;
+    if (zeroed) HIP_TRY(F.c, hipMemsetAsync(F.done, 0, F.nblk, F.c->stream));
+    return 0;
+}
+
+// ---- the phases of zstd_encode_begin, in order
+static int plan_buffers(ZencFrame &F)
+{
+    naf_gpu_ctx *c = F.c; const u32 nblk = F.nblk;
+    F.plan = arena_new<ZEncPlan>(c, nblk);
+    F.codes = arena_new<u16>(c, (size_t)nblk * 256); F.trees = (u8 *)arena_alloc(c, (size_t)nblk * ZENC_TREE_SLOT);
+    F.offs = arena_new<u64>(c, (size_t)nblk + 2);
+    // tree descriptions of ZENC_CACHE_ENTRIES evenly spaced blocks first (worth a launch from a few thousand blocks up)
+    F.sample_stride = nblk >= 16 * ZENC_CACHE_ENTRIES ? nblk / ZENC_CACHE_ENTRIES : 0;
+    F.cache = F.sample_stride ? arena_new<ZTreeCache>(c, 1) : nullptr;
+    if (!F.plan || !F.codes || !F.trees || !F.offs || (F.sample_stride && !F.cache)) return NAF_GPU_ENOMEM;
+    if (F.cache) HIP_TRY(c, hipMemsetAsync(F.cache, 0, sizeof(ZTreeCache), c->stream));
+    return 0;
+}
+
+// the packed 4-bit stream: blocks of pure A C G T near four bits of entropy are settled by a wave each, without the planner
+static int flat_blocks(ZencFrame &F)
+{
+    naf_gpu_ctx *c = F.c; const u32 nblk = F.nblk; const u8 *direct = F.direct;
+    if (!(F.O.prefer_flat >= 2 && F.n >= 2048 && zenc_flat16().tb)) return 0;
+    int rc = zenc_done_map(F, false); if (rc) return rc;
+    bool dplans = false;
+    if (direct) {
+        // what k_zenc_flat_scan makes of a direct block, once, on the host
+        ZEncPlan pd; memset(&pd, 0, sizeof pd);
+        const u32 bn = 32768, perq = bn / 4;
+        pd.n = bn; pd.kind = ZK_RAW; pd.csize = 3 + bn;
+        for (u32 k = 0; k < 4; k++) pd.ssz[k] = (perq * 4 + 8) >> 3;
+        zenc_plan_finish(pd, bn, 4, zenc_flat16().tb, F.O.min_gain);
+        if (pd.kind == ZK_HUF) {
+            pd.pad = 2; dplans = true;
+            LAUNCH(c, "zenc_direct_plans", k_zenc_direct_plans, cdiv(nblk, 256), 256, 0, direct, nblk, pd, zenc_flat16(), F.plan, F.trees, F.offs, F.done);
+        }
+    }
+    LAUNCH(c, "zenc_flat_scan", k_zenc_flat_scan, (dplans && cdiv(nblk, ZENC_FLATSCAN_WAVES) > 16384u) ? 16384u : cdiv(nblk, ZENC_FLATSCAN_WAVES), 64 * ZENC_FLATSCAN_WAVES, 0, F.src, (u64)F.n, nblk, F.plan, F.codes, F.trees, F.offs, F.done, F.O.min_gain, F.O.prefer_flat, zenc_flat16(), dplans ? direct : (const u8 *)nullptr, direct);
+    return 0;
+}
+
+// most blocks of a frame with a frame's tree without a histogram (k_zenc_frame_quick); the planner takes what that leaves
+static int frame_quick(ZencFrame &F)
+{
+    naf_gpu_ctx *c = F.c; const u32 nblk = F.nblk;
+    float *fstat = arena_new<float>(c, 8); if (!fstat) return NAF_GPU_ENOMEM;
+    int rc = zenc_done_map(F, true); if (rc) return rc;
+    LAUNCH(c, "zenc_frame_stats", k_zenc_frame_stats, 1, 256, 0, (const u32 *)F.fhist, (const u16 *)F.fcodes, fstat);
+    u32 *tally = arena_new<u32>(c, 2); if (!tally) return NAF_GPU_ENOMEM;
+    HIP_TRY(c, hipMemsetAsync(tally, 0, 8, c->stream));
+    const u32 qs = nblk / 512 ? nblk / 512 : 1u;                      // (a dry run over ~512 blocks decides whether the pass over all of them is worth its read)
+    LAUNCH(c, "zenc_frame_quick", k_zenc_frame_quick, cdiv(nblk, qs), 256, 0, F.src, (u64)F.n, nblk, F.plan, F.codes, F.offs, F.done, (const ZEncPlan *)F.fplan, (const u16 *)F.fcodes, (const float *)fstat, F.O.min_gain, qs, tally, (const u32 *)nullptr);
+    LAUNCH(c, "zenc_frame_quick", k_zenc_frame_quick, nblk, 256, 0, F.src, (u64)F.n, nblk, F.plan, F.codes, F.offs, F.done, (const ZEncPlan *)F.fplan, (const u16 *)F.fcodes, (const float *)fstat, F.O.min_gain, 0u, (u32 *)nullptr, (const u32 *)tally);
+    return 0;
+}
+// The sampled blocks' trees (a frame of enough blocks to sample) and, of their summed histogram, the frame's tree: level 1 without the
+// match finder and without direct blocks.
+static int frame_tree_build(ZencFrame &F)
+{
+    naf_gpu_ctx *c = F.c;
+    F.frame_tree = F.O.frame_tree_allowed && F.cache && !F.use_lz && !F.direct;
+    if (F.frame_tree) {
+        F.fhist = arena_new<u32>(c, 256 + 2); F.fplan = arena_new<ZEncPlan>(c, 1); F.fcodes = arena_new<u16>(c, 256); F.ftree = (u8 *)arena_alloc(c, ZENC_TREE_SLOT);
+        if (!F.fhist || !F.fplan || !F.fcodes || !F.ftree) return NAF_GPU_ENOMEM;
+        HIP_TRY(c, hipMemsetAsync(F.fhist, 0, 258 * 4, c->stream));
+        HIP_TRY(c, hipMemsetAsync(F.fplan, 0, sizeof(ZEncPlan), c->stream));
+        HIP_TRY(c, hipMemsetAsync(F.fcodes, 0, 512, c->stream));
+    }
+    if (F.cache) {
+        PlanCall p = plan_call_blocks(F, "zenc_plan_sample", ZENC_CACHE_ENTRIES);
+        p.cache = F.cache; p.sample_stride = F.sample_stride; p.fhist = F.fhist;
+        launch_plan(F, p);
+    }
+    if (!F.frame_tree) return 0;
+    u8 *fblock = (u8 *)arena_alloc(c, ZENC_FRAME_BLOCK + 64); if (!fblock) return NAF_GPU_ENOMEM;
+    LAUNCH(c, "zenc_frame_block", k_zenc_frame_block, 1, 256, 0, (const u32 *)F.fhist, fblock, F.fhist + 256);
+    // (no flat preference: the code of the summed histogram as it is, with its tree description -- FSE-coded by k_zenc_tree where
+    // the weights reach past symbol 127, a mask stream's units, like any other block's)
+    u8 *fwt = (u8 *)arena_alloc(c, 256); if (!fwt) return NAF_GPU_ENOMEM;
+    PlanCall p = plan_call("zenc_plan_frame", 1);
+    p.src = fblock; p.nblk = 1; p.plan = F.fplan; p.codes = F.fcodes; p.trees = F.ftree; p.blk_len = F.fhist + 256; p.wt_defer = fwt;
+    launch_plan(F, p);
+    launch_tree(c, 1, F.fplan, F.ftree, nullptr, fwt, 0);
+    LAUNCH(c, "zenc_frame_ratio", k_zenc_frame_ratio, 1, 256, 0, F.fhist, (const u16 *)F.fcodes);
+    return F.O.frame_quick ? frame_quick(F) : 0;
+}
+
+// the match finder's buffers; and the blocks of zero-terminated names a lane per line settles (k_lz_parse_lines) in FRONT of the planner:
+// a block that kernel takes is coded with its matches or, should that come out larger, Raw -- the planner's histogram of its bytes, code
+// and tree (the literal-only coding k_lz_choose would weigh against the matches) are not made at all
+static int lz_buffers(ZencFrame &F)
+{
+    naf_gpu_ctx *c = F.c; const u32 nblk = F.nblk; const u64 bs = F.bs; LzBufs &B = F.B;
+    if (!F.lz_on) return 0;
+    B.slot = bs; B.seq_slot = bs / 4 + 2; B.of = nullptr; B.ofv = nullptr;
+    B.lits = (u8 *)arena_alloc(c, (size_t)nblk * B.slot + 64); B.seqbuf = (u8 *)arena_alloc(c, (size_t)nblk * B.slot + 64);
+    B.ll = arena_new<u16>(c, (size_t)nblk * B.seq_slot + 8); B.ml = arena_new<u16>(c, (size_t)nblk * B.seq_slot + 8);   // + 8: read in groups of eight
+    if (F.lzx) B.ofv = arena_new<u32>(c, (size_t)nblk * B.seq_slot + 8); else B.of = arena_new<u16>(c, (size_t)nblk * B.seq_slot + 8);
+    B.nseq = arena_new<u32>(c, nblk); B.nlit = arena_new<u32>(c, nblk); B.seq_bytes = arena_new<u32>(c, nblk);
+    if (!B.lits || !B.seqbuf || !B.ll || !B.ml || (!B.of && !B.ofv) || !B.nseq || !B.nlit || !B.seq_bytes) return NAF_GPU_ENOMEM;
+    if (F.lzx || !F.O.lz_lines || bs > 32768 || nblk < 64) return 0;
+    F.lz_fallback = (u8 *)arena_alloc(c, nblk); if (!F.lz_fallback) return NAF_GPU_ENOMEM;
+    int rc = zenc_done_map(F, true); if (rc) return rc;
+    const u32 line_div = bs > 16384 ? 16u : 8u, ml_slots = 2 * (u32)(bs / line_div) + 4;   // (at most two sequences a line, a line more than the terminators)
+    const u32 lines_lds = F.lz_buf + 4 * ml_slots + 2 * (u32)(bs / line_div + 2);            // 19 KiB for blocks of 8 KiB, 53 for 32
+    LAUNCH(c, "zenc_lz_lines", k_lz_parse_lines, nblk, 64, lines_lds, F.src, (u64)F.n, nblk, B, F.lz_buf, F.lz_fallback, F.plan, F.offs, F.done, line_div, ml_slots);
+    return 0;
+}
+
+// the planner over what is left, a workgroup a block; its tree descriptions by k_zenc_tree, a lane a block
+static int plan_blocks(ZencFrame &F)
+{
+    // (frames of a few blocks keep the tree with the planner: nothing to gain from a second launch)
+    F.wt_defer = (F.nblk >= 256 && F.O.tree_defer) ? (u8 *)arena_alloc(F.c, (size_t)F.nblk * 256) : nullptr;
+    PlanCall p = plan_call_blocks(F, "zenc_plan", F.nblk);
+    p.cache = F.cache; p.wt_defer = F.wt_defer; p.fplan = F.fplan; p.fcodes = F.fcodes; p.fratio = F.fhist ? F.fhist + 257 : nullptr; p.long_last = F.O.long_last;
+    launch_plan(F, p);
+    if (F.wt_defer) launch_tree(F.c, F.nblk, F.plan, F.trees, F.offs, F.wt_defer, F.O.min_gain);
+    return 0;
+}
+
+// the first block of every run of blocks under the frame's code carries its tree
+static int frame_tree_fix(ZencFrame &F)
+{
+    naf_gpu_ctx *c = F.c; const u32 nblk = F.nblk;
+    if (!F.frame_tree) return 0;
+    i32 *fv = arena_new<i32>(c, (size_t)nblk + 1); if (!fv) return NAF_GPU_ENOMEM;
+    LAUNCH(c, "zenc_frame_class", k_zenc_frame_class, cdiv(nblk, 256), 256, 0, (const ZEncPlan *)F.plan, nblk, fv);
+    int rcs = scan_inclusive_max_i32(c, fv, nblk); if (rcs) return rcs;
+    LAUNCH(c, "zenc_frame_fix", k_zenc_frame_fix, cdiv(nblk, 256), 256, 0, F.plan, nblk, (const i32 *)fv, (const ZEncPlan *)F.fplan, (const u8 *)F.ftree, F.trees, F.offs);
+    return 0;
+}
+
+// matches, their sequences sections, the plan of the literals they leave, and per block the smaller of the two codings
+static int match_finder(ZencFrame &F)
+{
+    naf_gpu_ctx *c = F.c; const u32 nblk = F.nblk; const size_t n = F.n; const LzBufs &B = F.B; ZWriteLz &L = F.J->L;
+    if (!F.lz_on) return 0;
+    if (!c->d_seqctab) {
+        SeqCTabs T; zenc_build_predefined(T);
+        HIP_TRY(c, hipMalloc(&c->d_seqctab, sizeof T));
+        HIP_TRY(c, hipMemcpy(c->d_seqctab, &T, sizeof T, hipMemcpyHostToDevice));
+    }
+    ZEncPlan *plan1 = arena_new<ZEncPlan>(c, nblk);
+    u16 *codes1 = arena_new<u16>(c, (size_t)nblk * 256); u8 *trees1 = (u8 *)arena_alloc(c, (size_t)nblk * ZENC_TREE_SLOT);
+    u8 *mode = (u8 *)arena_alloc(c, nblk);
+    if (!plan1 || !codes1 || !trees1 || !mode) return NAF_GPU_ENOMEM;
+    if (F.lzx) {
+        // table of first occurrences: one in eight positions is an anchor, epochs of half the window, load factor <= 1/2
+        LdmTab T; T.wlog = F.window_log; T.elog = T.wlog - 1; T.pad = 0;
+        const u64 E = 1ull << T.elog, span = n < E ? n : E;
+        u32 tl = 4; while ((1ull << tl) < span / 4 + 16) tl++;
+        T.tlog = tl;
+        const u64 n_ep = (n >> T.elog) + 1, entries = n_ep << T.tlog;
+        T.tab = arena_new<u32>(c, entries); if (!T.tab) return NAF_GPU_ENOMEM;
+        HIP_TRY(c, hipMemsetAsync(T.tab, 0xFF, entries * 4, c->stream));
+        LAUNCH(c, "zenc_ldm_insert", k_ldm_insert, cdiv(cdiv(n, 8), 256), 256, 0, F.src, (u64)n, T);
+        HIP_TRY(c, hipFuncSetAttribute((const void *)k_lzx_parse, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(F.lz_buf + (2u << LZ_HASH_LOG))));   // above 64 KiB
+        LAUNCH(c, "zenc_lz_parse", k_lzx_parse, nblk, 64, F.lz_buf + (2u << LZ_HASH_LOG), F.src, (u64)n, nblk, B, F.lz_buf, T);
+        LAUNCH(c, "zenc_lz_seqenc", k_lzx_seqenc, nblk, 64, 0, nblk, B, (const SeqCTabs *)c->d_seqctab);
+    } else {
+        // the table's size is LDS a wavefront holds for the whole block: what bounds the blocks in flight per CU -- and what is left
+        // of a CU for the kernels of the other streams (2^11 and 2^10 entries measured: DESIGN.md section 8)
+        const u32 hash_log = LZ_HASH_LOG;
+        // (names against the name in front, a lane each: k_lz_parse_lines above; what that left to the hash table's walk is marked in `lz_fallback`)
+        LAUNCH(c, "zenc_lz_parse", k_lz_parse, nblk, 64, F.lz_buf + (2u << hash_log), F.src, (u64)n, nblk, B, F.lz_buf, hash_log, (const u8 *)F.lz_fallback);
+        LAUNCH(c, "zenc_lz_seqenc", k_lz_seqenc, cdiv(nblk, 64), 64, 0, nblk, B, (const SeqCTabs *)c->d_seqctab);
+    }
+    PlanCall p = plan_call("zenc_plan", nblk);
+    p.src = B.lits; p.n = (u64)n; p.nblk = nblk; p.plan = plan1; p.codes = codes1; p.trees = trees1; p.blk_len = B.nlit; p.slot = B.slot; p.min_gain = F.O.min_gain; p.wt_defer = F.wt_defer;
+    launch_plan(F, p);
+    if (F.wt_defer) launch_tree(c, nblk, plan1, trees1, nullptr, F.wt_defer, F.O.min_gain);
+    LAUNCH(c, "zenc_lz_choose", k_lz_choose, cdiv(nblk, 256), 256, 0, nblk, (const ZEncPlan *)F.plan, (const ZEncPlan *)plan1, (const u32 *)B.nseq, (const u32 *)B.seq_bytes, mode, F.offs);
+    L.mode = mode; L.plan1 = plan1; L.codes1 = codes1; L.trees1 = trees1; L.B = B;
+    return 0;
+}
+
+// where each block goes (the frame's size behind the last offset), and what the writers need of the frame
+static int block_offsets(ZencFrame &F)
+{
+    ZencJob *J = F.J;
+    int rc = scan_exclusive_u64(F.c, F.offs, F.nblk, F.offs + F.nblk + 1); if (rc) return rc;
+    J->L.not_last = F.O.part && !F.O.part_last;
+    J->L.frame_split = (F.frame_tree && F.O.frame_write) ? 1u : 0u;
+    J->direct = F.direct != nullptr;
+    if (F.direct && F.dloc) J->dloc = *F.dloc;
+    J->block_bytes = (u32)F.bs; J->nblk = F.nblk; J->plan = F.plan; J->codes = F.codes; J->trees = F.trees; J->offs = F.offs; J->hdr = F.hdr; J->with_magic = F.O.with_magic; J->frame_wlog = F.frame_wlog;
+    return 0;
+}
+
 int zstd_encode_begin(naf_gpu_ctx *c, const u8 *d_src, size_t n, int level, int with_magic, int lz, int block_log_hint, int window_log, ZencJob **job, const u8 *direct, u32 nd, const ZencLoc *dloc)
 {
     ZencJob *J = new ZencJob; *job = J;                          // released by zstd_encode_finish
     memset(J, 0, sizeof *J);
     J->src = d_src; J->n = n;
-    const bool part = (with_magic & ZENC_PART) != 0, part_first = (with_magic & ZENC_PART_FIRST) != 0, part_last = (with_magic & ZENC_PART_LAST) != 0;
-    const u32 min_gain = (with_magic & ZENC_PREFER_RAW) ? 32u : 0u;
-    const bool frame_tree_ok = level <= 1 && (with_magic & ZENC_FRAME_TREE) != 0;
-    // (the same streams -- the mask -- keep their codes to 9 bits: this build's decoder then walks them with its single-level table)
-    u32 maxbits = (with_magic & ZENC_PREFER_RAW) ? 9u : (with_magic & ZENC_SHORT_CODES) ? 7u : (u32)ZENC_HUF_MAXBITS;
-    // ZENC_PREFER_FLAT: blocks of 2^k distinct symbols take k-bit codes unless Huffman coding saves a sixteenth of the block
-    // (NAF_GPU_PREFER_FLAT=0: never; =d: the threshold 1/d)
-    u32 prefer_flat = (with_magic & ZENC_PREFER_FLAT) ? 16u : 0u;
-    if (prefer_flat) { const char *pf = ctx_opt(c, "PREFER_FLAT"); if (pf && pf[0]) prefer_flat = (u32)atoi(pf); }
-    const u32 long_last = ((with_magic & ZENC_LONG_LAST) && (!part || part_last)) ? 1u : 0u;
-    with_magic &= ~(ZENC_PREFER_RAW | ZENC_PREFER_FLAT | ZENC_SHORT_CODES | ZENC_FRAME_TREE | ZENC_LONG_LAST);
-    if (part) with_magic = 0;
-    if (part && n == 0 && !part_last) {
-        J->empty = 1; J->hdr = part_first ? 2 : 0; J->frame_wlog = (u32)(window_log >= 10 ? window_log : 19);
-        return 0;
-    }
-    u32 block_log = 15;                                          // 32 KiB: 4 streams of 8 KiB; more streams = more decode parallelism
-    if (block_log_hint >= 10 && block_log_hint <= 17) block_log = (u32)block_log_hint;
-    const char *e = ctx_opt(c, "BLOCK_LOG");
-    if (e) { int v = atoi(e); if (v >= 10 && v <= 17) block_log = (u32)v; }
-    const char *el = ctx_opt(c, "LZ");                       // "0": never, "all": every stream (tests)
-    bool use_lz = lz || level >= 2;
-    if (el && !strcmp(el, "0")) use_lz = false;
-    if (el && !strcmp(el, "all")) use_lz = true;
-    // LZ-coded streams: 8 KiB blocks.  The decoder decodes and executes the sequences of a block serially -- a lane, then a wavefront per
-    // block whose LDS buffer is the block's size -- so smaller blocks are more lanes, more workgroups per CU and shorter chains; matches in
-    // ids / names / lengths are a few dozen bytes back anyway (a FASTQ's read names: the archive is no larger than with 16 KiB blocks).
-    if (use_lz && !e) block_log = (lz && block_log_hint >= 10 && block_log_hint <= 15) ? (u32)block_log_hint : 13u;   // (the hint of a caller that asked for the match finder itself: ennaf's comments and lengths of many records)
-    if (use_lz && block_log > 15) block_log = 15;                // LZ lengths and distances are kept in 16 bits
-    // cross-block matching (window_log >= 10; the host maps level / --long to it): 64 KiB blocks -- fewer block and table headers,
-    // and a repeat is cut less often; lengths still fit 16 bits (k_lzx_parse clamps a match at 65535)
-    const bool lzx = use_lz && window_log >= 10 && n >= 64;
-    if (window_log > 31) window_log = 31;
-    if (lzx) {
-        block_log = 16;
-        if (block_log > (u32)window_log) block_log = (u32)window_log;          // Block_Maximum_Size is the smaller of Window_Size and 128 KiB (3.1.1.2.4)
-    }
-    // The window announced in the frame header follows from the OPTIONS alone, not from this part's size: the header is written by the
-    // first part of a sharded / chunked frame, and a first part of a few bytes (the ids of a slice that is one chromosome) says
-    // nothing about the offsets the later parts use -- the reference's streaming decoder sizes its history from this field
-    const u32 frame_wlog = (use_lz && window_log >= 10) ? (u32)window_log : 19u;
-    u64 bs = 1ull << block_log;
-    u64 nblk64 = n ? (n + bs - 1) / bs : 1;
-    if (nblk64 > 0x7FFFFFFFull) return ctx_fail(c, NAF_GPU_EARG, "stream too large");
-    u32 nblk = (u32)nblk64;
-    u64 hdr = with_magic ? 6 : (part && !part_first) ? 0 : 2;
-    ZEncPlan *plan = arena_new<ZEncPlan>(c, nblk);
-    u16 *codes = arena_new<u16>(c, (size_t)nblk * 256); u8 *trees = (u8 *)arena_alloc(c, (size_t)nblk * ZENC_TREE_SLOT);
-    u64 *offs = arena_new<u64>(c, (size_t)nblk + 2);
-    // level 1 writes Huffman weights directly where the format allows it (up to 128 of them): FSE-coding them saves about a
-    // dozen bytes per block and costs one lane a serial pass per block
-    const u32 try_fse = level >= 2;
-    // tree descriptions of ZENC_CACHE_ENTRIES evenly spaced blocks first (worth a launch from a few thousand blocks up)
-    const u32 sample_stride = nblk >= 16 * ZENC_CACHE_ENTRIES ? nblk / ZENC_CACHE_ENTRIES : 0;
-    ZTreeCache *cache = sample_stride ? arena_new<ZTreeCache>(c, 1) : nullptr;
-    if (!plan || !codes || !trees || !offs || (sample_stride && !cache)) return NAF_GPU_ENOMEM;
-    if (cache) HIP_TRY(c, hipMemsetAsync(cache, 0, sizeof(ZTreeCache), c->stream));
-    // the packed 4-bit stream: blocks of pure A C G T near four bits of entropy are settled by a wave each, without the planner
-    u8 *done = nullptr;
-    if (direct && (use_lz || block_log != 15 || nblk != nd || n != (size_t)nd << 15 || prefer_flat < 2 || !zenc_flat16().tb))
-        return ctx_fail(c, NAF_GPU_EARG, "direct blocks: the stream must be %u blocks of 32 KiB coded without the match finder", nd);
-    if (prefer_flat >= 2 && n >= 2048 && zenc_flat16().tb) {
-        done = (u8 *)arena_alloc(c, nblk); if (!done) return NAF_GPU_ENOMEM;
-        bool dplans = false;
-        if (direct) {
-            // what k_zenc_flat_scan makes of a direct block, once, on the host
-            ZEncPlan pd; memset(&pd, 0, sizeof pd);
-            const u32 bn = 32768, perq = bn / 4;
-            pd.n = bn; pd.kind = ZK_RAW; pd.csize = 3 + bn;
-            for (u32 k = 0; k < 4; k++) pd.ssz[k] = (perq * 4 + 8) >> 3;
-            zenc_plan_finish(pd, bn, 4, zenc_flat16().tb, min_gain);
-            if (pd.kind == ZK_HUF) {
-                pd.pad = 2; dplans = true;
-                LAUNCH(c, "zenc_direct_plans", k_zenc_direct_plans, cdiv(nblk, 256), 256, 0, direct, nblk, pd, zenc_flat16(), plan, trees, offs, done);
-            }
-        }
-        LAUNCH(c, "zenc_flat_scan", k_zenc_flat_scan, (dplans && cdiv(nblk, ZENC_FLATSCAN_WAVES) > 16384u) ? 16384u : cdiv(nblk, ZENC_FLATSCAN_WAVES), 64 * ZENC_FLATSCAN_WAVES, 0, d_src, (u64)n, nblk, plan, codes, trees, offs, done, min_gain, prefer_flat, zenc_flat16(), dplans ? direct : (const u8 *)nullptr, direct);
-    }
-    // the frame's tree (k_zenc_plan): level 1 without the match finder, frames of enough blocks to sample; NAF_GPU_FRAME_TREE=0: a tree per block
-    const char *eft = ctx_opt(c, "FRAME_TREE");
-    const bool frame_tree = frame_tree_ok && cache && !use_lz && !direct && !(eft && eft[0] == '0');
-    u32 *fhist = nullptr; ZEncPlan *fplan = nullptr; u16 *fcodes = nullptr; u8 *ftree = nullptr;
-    if (frame_tree) {
-        fhist = arena_new<u32>(c, 256 + 2); fplan = arena_new<ZEncPlan>(c, 1); fcodes = arena_new<u16>(c, 256); ftree = (u8 *)arena_alloc(c, ZENC_TREE_SLOT);
-        if (!fhist || !fplan || !fcodes || !ftree) return NAF_GPU_ENOMEM;
-        HIP_TRY(c, hipMemsetAsync(fhist, 0, 258 * 4, c->stream));
-        HIP_TRY(c, hipMemsetAsync(fplan, 0, sizeof(ZEncPlan), c->stream));
-        HIP_TRY(c, hipMemsetAsync(fcodes, 0, 512, c->stream));
-    }
-    if (cache) LAUNCH(c, "zenc_plan_sample", k_zenc_plan, ZENC_CACHE_ENTRIES, 256, 0, d_src, (u64)n, nblk, plan, codes, trees, offs, (const u32 *)nullptr, (u64)0, cache, sample_stride, try_fse, min_gain, maxbits, prefer_flat, (const u8 *)done, (u8 *)nullptr, fhist, (const ZEncPlan *)nullptr, (const u16 *)nullptr);
-    if (frame_tree) {
-        u8 *fblock = (u8 *)arena_alloc(c, ZENC_FRAME_BLOCK + 64); if (!fblock) return NAF_GPU_ENOMEM;
-        LAUNCH(c, "zenc_frame_block", k_zenc_frame_block, 1, 256, 0, (const u32 *)fhist, fblock, fhist + 256);
-        // (no flat preference: the code of the summed histogram as it is, with its tree description -- FSE-coded by k_zenc_tree where
-        // the weights reach past symbol 127, a mask stream's units, like any other block's)
-        u8 *fwt = (u8 *)arena_alloc(c, 256); if (!fwt) return NAF_GPU_ENOMEM;
-        LAUNCH(c, "zenc_plan_frame", k_zenc_plan, 1, 256, 0, (const u8 *)fblock, (u64)0, 1u, fplan, fcodes, ftree, (u64 *)nullptr, (const u32 *)(fhist + 256), (u64)0, (ZTreeCache *)nullptr, 0u, try_fse, 0u, maxbits, 0u, (const u8 *)nullptr, fwt, (u32 *)nullptr, (const ZEncPlan *)nullptr, (const u16 *)nullptr);
-        LAUNCH(c, "zenc_tree", k_zenc_tree, 1, 64, 64 * sizeof(ZTreeLane), 1u, fplan, ftree, (u64 *)nullptr, (const u8 *)fwt, 0u);
-        LAUNCH(c, "zenc_frame_ratio", k_zenc_frame_ratio, 1, 256, 0, fhist, (const u16 *)fcodes);
-        // most blocks of such a frame without a histogram (k_zenc_frame_quick); the planner below takes what that leaves
-        const char *fq = ctx_opt(c, "FRAME_QUICK");
-        if (!(fq && fq[0] == '0')) {
-            float *fstat = arena_new<float>(c, 8); if (!fstat) return NAF_GPU_ENOMEM;
-            if (!done) { done = (u8 *)arena_alloc(c, nblk); if (!done) return NAF_GPU_ENOMEM; HIP_TRY(c, hipMemsetAsync(done, 0, nblk, c->stream)); }
-            LAUNCH(c, "zenc_frame_stats", k_zenc_frame_stats, 1, 256, 0, (const u32 *)fhist, (const u16 *)fcodes, fstat);
-            u32 *tally = arena_new<u32>(c, 2); if (!tally) return NAF_GPU_ENOMEM;
-            HIP_TRY(c, hipMemsetAsync(tally, 0, 8, c->stream));
-            const u32 qs = nblk / 512 ? nblk / 512 : 1u;                      // (a dry run over ~512 blocks decides whether the pass over all of them is worth its read)
-            LAUNCH(c, "zenc_frame_quick", k_zenc_frame_quick, cdiv(nblk, qs), 256, 0, d_src, (u64)n, nblk, plan, codes, offs, done, (const ZEncPlan *)fplan, (const u16 *)fcodes, (const float *)fstat, min_gain, qs, tally, (const u32 *)nullptr);
-            LAUNCH(c, "zenc_frame_quick", k_zenc_frame_quick, nblk, 256, 0, d_src, (u64)n, nblk, plan, codes, offs, done, (const ZEncPlan *)fplan, (const u16 *)fcodes, (const float *)fstat, min_gain, 0u, (u32 *)nullptr, (const u32 *)tally);
-        }
-    }
-    // the match finder's buffers; and the blocks of zero-terminated names a lane per line settles (k_lz_parse_lines) in FRONT of the planner:
-    // a block that kernel takes is coded with its matches or, should that come out larger, Raw -- the planner's histogram of its bytes, code
-    // and tree (the literal-only coding k_lz_choose would weigh against the matches) are not made at all
-    LzBufs B; memset(&B, 0, sizeof B);
-    u8 *lz_fallback = nullptr;
-    const u32 lz_buf = (u32)((bs + 1 + 320 + 15) & ~15ull);               // a block of the even split holds at most bs bytes
-    if (use_lz && n >= 64) {
-        B.slot = bs; B.seq_slot = bs / 4 + 2; B.of = nullptr; B.ofv = nullptr;
-        B.lits = (u8 *)arena_alloc(c, (size_t)nblk * B.slot + 64); B.seqbuf = (u8 *)arena_alloc(c, (size_t)nblk * B.slot + 64);
-        B.ll = arena_new<u16>(c, (size_t)nblk * B.seq_slot + 8); B.ml = arena_new<u16>(c, (size_t)nblk * B.seq_slot + 8);   // + 8: read in groups of eight
-        if (lzx) B.ofv = arena_new<u32>(c, (size_t)nblk * B.seq_slot + 8); else B.of = arena_new<u16>(c, (size_t)nblk * B.seq_slot + 8);
-        B.nseq = arena_new<u32>(c, nblk); B.nlit = arena_new<u32>(c, nblk); B.seq_bytes = arena_new<u32>(c, nblk);
-        if (!B.lits || !B.seqbuf || !B.ll || !B.ml || (!B.of && !B.ofv) || !B.nseq || !B.nlit || !B.seq_bytes) return NAF_GPU_ENOMEM;
-        const char *ll_ = ctx_opt(c, "LZ_LINES");
-        if (!lzx && !(ll_ && ll_[0] == '0') && bs <= 32768 && nblk >= 64) {
-            lz_fallback = (u8 *)arena_alloc(c, nblk); if (!lz_fallback) return NAF_GPU_ENOMEM;
-            if (!done) { done = (u8 *)arena_alloc(c, nblk); if (!done) return NAF_GPU_ENOMEM; HIP_TRY(c, hipMemsetAsync(done, 0, nblk, c->stream)); }
-            const u32 line_div = bs > 16384 ? 16u : 8u, ml_slots = 2 * (u32)(bs / line_div) + 4;   // (at most two sequences a line, a line more than the terminators)
-            const u32 lines_lds = lz_buf + 4 * ml_slots + 2 * (u32)(bs / line_div + 2);              // 19 KiB for blocks of 8 KiB, 53 for 32
-            LAUNCH(c, "zenc_lz_lines", k_lz_parse_lines, nblk, 64, lines_lds, d_src, (u64)n, nblk, B, lz_buf, lz_fallback, plan, offs, done, line_div, ml_slots);
-        }
-    }
-    // (frames of a few blocks keep the tree with the planner: nothing to gain from a second launch)
-    const char *td = ctx_opt(c, "TREE_DEFER");
-    u8 *wt_defer = (nblk >= 256 && !(td && td[0] == '0')) ? (u8 *)arena_alloc(c, (size_t)nblk * 256) : nullptr;
-    LAUNCH(c, "zenc_plan", k_zenc_plan, nblk, 256, 0, d_src, (u64)n, nblk, plan, codes, trees, offs, (const u32 *)nullptr, (u64)0, cache, 0u, try_fse, min_gain, maxbits, prefer_flat, (const u8 *)done, wt_defer, (u32 *)nullptr, (const ZEncPlan *)fplan, (const u16 *)fcodes, (const u32 *)(fhist ? fhist + 257 : nullptr), long_last);
-    if (wt_defer) LAUNCH(c, "zenc_tree", k_zenc_tree, cdiv(nblk, 64), 64, 64 * sizeof(ZTreeLane), nblk, plan, trees, offs, (const u8 *)wt_defer, min_gain);
-    if (frame_tree) {
-        i32 *fv = arena_new<i32>(c, (size_t)nblk + 1); if (!fv) return NAF_GPU_ENOMEM;
-        LAUNCH(c, "zenc_frame_class", k_zenc_frame_class, cdiv(nblk, 256), 256, 0, (const ZEncPlan *)plan, nblk, fv);
-        int rcs = scan_inclusive_max_i32(c, fv, nblk); if (rcs) return rcs;
-        LAUNCH(c, "zenc_frame_fix", k_zenc_frame_fix, cdiv(nblk, 256), 256, 0, plan, nblk, (const i32 *)fv, (const ZEncPlan *)fplan, (const u8 *)ftree, trees, offs);
-    }
-    ZWriteLz &L = J->L;
-    L.not_last = part && !part_last;
-    { const char *fs = ctx_opt(c, "FRAME_WRITE"); L.frame_split = (frame_tree && !(fs && fs[0] == '0')) ? 1u : 0u; }   // (NAF_GPU_FRAME_WRITE=0: every block by the sixteen-table writer)
-    if (use_lz && n >= 64) {
-        if (!c->d_seqctab) {
-            SeqCTabs T; zenc_build_predefined(T);
-            HIP_TRY(c, hipMalloc(&c->d_seqctab, sizeof T));
-            HIP_TRY(c, hipMemcpy(c->d_seqctab, &T, sizeof T, hipMemcpyHostToDevice));
-        }
-        ZEncPlan *plan1 = arena_new<ZEncPlan>(c, nblk);
-        u16 *codes1 = arena_new<u16>(c, (size_t)nblk * 256); u8 *trees1 = (u8 *)arena_alloc(c, (size_t)nblk * ZENC_TREE_SLOT);
-        u8 *mode = (u8 *)arena_alloc(c, nblk);
-        if (!plan1 || !codes1 || !trees1 || !mode) return NAF_GPU_ENOMEM;
-        if (lzx) {
-            // table of first occurrences: one in eight positions is an anchor, epochs of half the window, load factor <= 1/2
-            LdmTab T; T.wlog = (u32)window_log; T.elog = T.wlog - 1; T.pad = 0;
-            const u64 E = 1ull << T.elog, span = n < E ? n : E;
-            u32 tl = 4; while ((1ull << tl) < span / 4 + 16) tl++;
-            T.tlog = tl;
-            const u64 n_ep = (n >> T.elog) + 1, entries = n_ep << T.tlog;
-            T.tab = arena_new<u32>(c, entries); if (!T.tab) return NAF_GPU_ENOMEM;
-            HIP_TRY(c, hipMemsetAsync(T.tab, 0xFF, entries * 4, c->stream));
-            LAUNCH(c, "zenc_ldm_insert", k_ldm_insert, cdiv(cdiv(n, 8), 256), 256, 0, d_src, (u64)n, T);
-            HIP_TRY(c, hipFuncSetAttribute((const void *)k_lzx_parse, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(lz_buf + (2u << LZ_HASH_LOG))));   // above 64 KiB
-            LAUNCH(c, "zenc_lz_parse", k_lzx_parse, nblk, 64, lz_buf + (2u << LZ_HASH_LOG), d_src, (u64)n, nblk, B, lz_buf, T);
-            LAUNCH(c, "zenc_lz_seqenc", k_lzx_seqenc, nblk, 64, 0, nblk, B, (const SeqCTabs *)c->d_seqctab);
-        } else {
-            // the table's size is LDS a wavefront holds for the whole block: what bounds the blocks in flight per CU -- and what is left
-            // of a CU for the kernels of the other streams (2^11 and 2^10 entries measured: DESIGN.md section 8)
-            const u32 hash_log = LZ_HASH_LOG;
-            // (names against the name in front, a lane each: k_lz_parse_lines above; what that left to the hash table's walk is marked in `lz_fallback`)
-            LAUNCH(c, "zenc_lz_parse", k_lz_parse, nblk, 64, lz_buf + (2u << hash_log), d_src, (u64)n, nblk, B, lz_buf, hash_log, (const u8 *)lz_fallback);
-            LAUNCH(c, "zenc_lz_seqenc", k_lz_seqenc, cdiv(nblk, 64), 64, 0, nblk, B, (const SeqCTabs *)c->d_seqctab);
-        }
-        LAUNCH(c, "zenc_plan", k_zenc_plan, nblk, 256, 0, (const u8 *)B.lits, (u64)n, nblk, plan1, codes1, trees1, (u64 *)nullptr, (const u32 *)B.nlit, B.slot, (ZTreeCache *)nullptr, 0u, try_fse, min_gain, maxbits, 0u, (const u8 *)nullptr, wt_defer);
-        if (wt_defer) LAUNCH(c, "zenc_tree", k_zenc_tree, cdiv(nblk, 64), 64, 64 * sizeof(ZTreeLane), nblk, plan1, trees1, (u64 *)nullptr, (const u8 *)wt_defer, min_gain);
-        LAUNCH(c, "zenc_lz_choose", k_lz_choose, cdiv(nblk, 256), 256, 0, nblk, (const ZEncPlan *)plan, (const ZEncPlan *)plan1, (const u32 *)B.nseq, (const u32 *)B.seq_bytes, mode, offs);
-        L.mode = mode; L.plan1 = plan1; L.codes1 = codes1; L.trees1 = trees1; L.B = B;
-    }
-    int rc = scan_exclusive_u64(c, offs, nblk, offs + nblk + 1); if (rc) return rc;
-    J->direct = direct != nullptr;
-    if (direct && dloc) J->dloc = *dloc;
-    J->block_bytes = (u32)bs; J->nblk = nblk; J->plan = plan; J->codes = codes; J->trees = trees; J->offs = offs; J->hdr = hdr; J->with_magic = with_magic; J->frame_wlog = frame_wlog;
-    return 0;
+    ZencFrame F; memset(&F, 0, sizeof F);
+    F.c = c; F.src = d_src; F.n = n; F.J = J; F.direct = direct; F.nd = nd; F.dloc = dloc;
+    zenc_options(c, level, with_magic, lz, block_log_hint, window_log, F.O);
+    int rc = zenc_geometry(F);
+    if (rc) return rc == ZENC_EMPTY_PART ? 0 : rc;
+    if ((rc = plan_buffers(F))) return rc;
+    if ((rc = flat_blocks(F))) return rc;
+    if ((rc = frame_tree_build(F))) return rc;
+    if ((rc = lz_buffers(F))) return rc;
+    if ((rc = plan_blocks(F))) return rc;
+    if ((rc = frame_tree_fix(F))) return rc;
+    if ((rc = match_finder(F))) return rc;
+    return block_offsets(F);
 }
 
 // The second half: the frame's size is read back (before the write when a hook places the frame, after it otherwise) and the blocks
@@ -1789,49 +1941,93 @@ int zstd_encode_finish(naf_gpu_ctx *c, ZencJob *J, u8 *d_dst, size_t cap, size_t
     delete J;
     return rc;
 }
+// ---- the phases of zenc_finish
+static int finish_empty(naf_gpu_ctx *c, ZencJob *J, u8 *d_dst, size_t cap, size_t *out_len, const ZencPlace *place)
+{
+    const u64 hdr = J->hdr;
+    if (place && !(d_dst = place->fn(place->ud, hdr))) return NAF_GPU_ECAP;
+    if (!place && cap < hdr) return ctx_fail(c, NAF_GPU_ECAP, "zstd_compress capacity %zu too small", cap);
+    if (hdr) LAUNCH(c, "zenc_frame_header", k_zenc_frame_header, 1, 64, 0, d_dst, 0, J->frame_wlog);
+    *out_len = hdr;
+    return 0;
+}
+// the bytes of the blocks: what a caller read back before, else this call's one read-back
+static int zenc_total(naf_gpu_ctx *c, const ZencJob *J, u64 *total)
+{
+    if (J->have_total) { *total = J->known_total; return 0; }
+    return ctx_readback(c, total, J->offs + J->nblk + 1, 8);
+}
+// where the frame goes: the caller's buffer of enough bytes, or what the hook says once it hears the size
+static int finish_place(naf_gpu_ctx *c, ZencJob *J, u8 **d_dst, size_t cap, const ZencPlace *place, u64 *total)
+{
+    const u64 bound = J->hdr + J->n + 3ull * J->nblk;
+    if (!place) return cap < bound ? ctx_fail(c, NAF_GPU_ECAP, "zstd_compress capacity %zu too small (bound %llu)", cap, (unsigned long long)bound) : 0;
+    int rc = zenc_total(c, J, total); if (rc) return rc;
+    return (*d_dst = place->fn(place->ud, J->hdr + *total)) ? 0 : NAF_GPU_ECAP;
+}
+// A writer of blocks on `on`'s stream: the arguments k_zenc_write<> and k_zenc_write_wave share, written once; `last` is what the kernel
+// takes behind them.  Not timed on a stream that is not the job's own.
+template <typename Kernel, typename Last>
+static void launch_writer(naf_gpu_ctx *on, bool timed, const char *name, Kernel kern, u32 grid, u32 block, u32 lds, const ZencJob *J, u8 *d_dst, const Last &last)
+{
+    if (timed) ktime_begin(on, name);
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(block), lds, on->stream, J->src, (u64)J->n, J->nblk, (const ZEncPlan *)J->plan, (const u16 *)J->codes, (const u8 *)J->trees, (const u64 *)J->offs, d_dst, J->hdr, last);
+    if (timed) ktime_end(on);
+}
+static void write_wave(naf_gpu_ctx *on, bool timed, const ZencJob *J, u8 *d_dst)
+{
+    launch_writer(on, timed, "zenc_write_wave", k_zenc_write_wave, cdiv(J->nblk, ZWW_BLOCKS), 256, 512u + 4u * ZWW_OBUF, J, d_dst, J->L.not_last);
+}
+static void write_blocks(naf_gpu_ctx *c, ZencJob *J, u8 *d_dst)
+{
+    // few blocks of general codes (a frame of direct blocks, a short frame): a wavefront per stream for those
+    J->L.wave_general = (!J->L.mode && J->block_bytes <= 32768u && (J->direct || J->nblk <= 2048u)) ? 1u : 0u;
+    if (J->L.frame_split) launch_writer(c, true, "zenc_write", k_zenc_write<true>, cdiv(J->nblk, ZENC_BLOCKS_PER_WG), 64, 0, J, d_dst, J->L);
+    launch_writer(c, true, "zenc_write", k_zenc_write<false>, cdiv(J->nblk, ZENC_BLOCKS_PER_WG), 64, 0, J, d_dst, J->L);
+}
+static int write_direct(naf_gpu_ctx *c, const ZencJob *J, u8 *d_dst)
+{
+    const u32 nblk = J->nblk;
+    if (J->direct && J->dloc.loc) LAUNCH(c, "zenc_write_direct", k_zenc_write_direct_loc, nblk, 256, 0, J->dloc, nblk, (const ZEncPlan *)J->plan, (const u8 *)J->trees, (const u64 *)J->offs, d_dst, J->hdr, J->L.not_last);
+    else if (J->direct) LAUNCH(c, "zenc_write_direct", k_zenc_write_direct, nblk, 256, 0, J->src, nblk, (const ZEncPlan *)J->plan, (const u8 *)J->trees, (const u64 *)J->offs, d_dst, J->hdr, J->L.not_last);
+    return 0;
+}
+// A frame of direct blocks whose size is known already: the few blocks of general codes beside the gather, on the look's idle stream,
+// instead of 60 us in front of it.  That stream waits for the caller's fork event only, NOT for this job's planning: so the stream is
+// taken only where the size was read back on the job's own stream (own_sync: zstd_encode_size -- the planning has finished), not
+// where a caller handed a total in (zstd_encode_set_total: read back on whatever stream).  nullptr: on the job's stream like the rest.
+static naf_gpu_ctx *beside_stream(naf_gpu_ctx *c, const ZencJob *J)
+{
+    if (!(J->L.wave_general && J->direct && J->own_sync && c->side3 && c->split_ev[ZSPLIT_MAX - 1])) return nullptr;
+    return hipStreamWaitEvent(c->side3->stream, c->fork_ev, 0) == hipSuccess ? c->side3 : nullptr;
+}
+// fork (beside_stream), the writer on `aux`, its event; the direct blocks on the job's stream meanwhile; the join -- which is waited
+// for whatever became of the direct blocks
+static int write_beside(naf_gpu_ctx *c, naf_gpu_ctx *aux, const ZencJob *J, u8 *d_dst)
+{
+    write_wave(aux, false, J, d_dst);
+    if (hipGetLastError() != hipSuccess || hipEventRecord(c->split_ev[ZSPLIT_MAX - 1], aux->stream) != hipSuccess) return ctx_fail(c, NAF_GPU_EHIP, "zenc_write_wave beside the gather: launch failed");
+    const int rc = write_direct(c, J, d_dst);
+    if (hipStreamWaitEvent(c->stream, c->split_ev[ZSPLIT_MAX - 1], 0) != hipSuccess && !rc) return ctx_fail(c, NAF_GPU_EHIP, "zenc_write_wave beside the gather: join failed");
+    return rc;
+}
 static int zenc_finish(naf_gpu_ctx *c, ZencJob *J, u8 *d_dst, size_t cap, size_t *out_len, const ZencPlace *place)
 {
-    const u64 hdr = J->hdr; const u32 nblk = J->nblk;
-    if (J->empty) {
-        if (place && !(d_dst = place->fn(place->ud, hdr))) return NAF_GPU_ECAP;
-        if (!place && cap < hdr) return ctx_fail(c, NAF_GPU_ECAP, "zstd_compress capacity %zu too small", cap);
-        if (hdr) LAUNCH(c, "zenc_frame_header", k_zenc_frame_header, 1, 64, 0, d_dst, 0, J->frame_wlog);
-        *out_len = hdr;
-        return 0;
-    }
-    if (!place && cap < hdr + J->n + 3ull * nblk) return ctx_fail(c, NAF_GPU_ECAP, "zstd_compress capacity %zu too small (bound %llu)", cap, (unsigned long long)(hdr + J->n + 3ull * nblk));
+    if (J->empty) return finish_empty(c, J, d_dst, cap, out_len, place);
     int rc;
     u64 total = 0;
-    if (place) {
-        if (J->have_total) total = J->known_total;
-        else if ((rc = ctx_readback(c, &total, J->offs + nblk + 1, 8))) return rc;
-        if (!(d_dst = place->fn(place->ud, hdr + total))) return NAF_GPU_ECAP;
+    if ((rc = finish_place(c, J, &d_dst, cap, place, &total))) return rc;
+    if (J->hdr) LAUNCH(c, "zenc_frame_header", k_zenc_frame_header, 1, 64, 0, d_dst, J->with_magic, J->frame_wlog);
+    write_blocks(c, J, d_dst);
+    naf_gpu_ctx *aux = beside_stream(c, J);
+    if (aux) rc = write_beside(c, aux, J, d_dst);
+    else {
+        if (J->L.wave_general) write_wave(c, true, J, d_dst);
+        rc = write_direct(c, J, d_dst);
     }
-    if (hdr) LAUNCH(c, "zenc_frame_header", k_zenc_frame_header, 1, 64, 0, d_dst, J->with_magic, J->frame_wlog);
-    {
-        // few blocks of general codes (a frame of direct blocks, a short frame): a wavefront per stream for those
-        J->L.wave_general = (!J->L.mode && J->block_bytes <= 32768u && (J->direct || nblk <= 2048u)) ? 1u : 0u;
-    }
-    if (J->L.frame_split) LAUNCH(c, "zenc_write", k_zenc_write<true>, cdiv(nblk, ZENC_BLOCKS_PER_WG), 64, 0, J->src, (u64)J->n, nblk, (const ZEncPlan *)J->plan, (const u16 *)J->codes, (const u8 *)J->trees,
-           (const u64 *)J->offs, d_dst, hdr, J->L);
-    LAUNCH(c, "zenc_write", k_zenc_write<false>, cdiv(nblk, ZENC_BLOCKS_PER_WG), 64, 0, J->src, (u64)J->n, nblk, (const ZEncPlan *)J->plan, (const u16 *)J->codes, (const u8 *)J->trees,
-           (const u64 *)J->offs, d_dst, hdr, J->L);
-    // (a frame of direct blocks whose size is known already -- nothing of this stream is in flight: the few blocks of general codes beside the gather,
-    // on the look's idle stream, instead of 60 us in front of it)
-    naf_gpu_ctx *aux = (J->L.wave_general && J->direct && J->have_total && c->side3 && c->split_ev[ZSPLIT_MAX - 1]) ? c->side3 : nullptr;
-    if (aux && hipStreamWaitEvent(aux->stream, c->fork_ev, 0) != hipSuccess) aux = nullptr;
-    if (aux) {
-        hipLaunchKernelGGL(k_zenc_write_wave, dim3(cdiv(nblk, ZWW_BLOCKS)), dim3(256), 512u + 4u * ZWW_OBUF, aux->stream, J->src, (u64)J->n, nblk, (const ZEncPlan *)J->plan, (const u16 *)J->codes, (const u8 *)J->trees,
-                           (const u64 *)J->offs, d_dst, hdr, J->L.not_last);
-        if (hipGetLastError() != hipSuccess || hipEventRecord(c->split_ev[ZSPLIT_MAX - 1], aux->stream) != hipSuccess) return ctx_fail(c, NAF_GPU_EHIP, "zenc_write_wave beside the gather: launch failed");
-    } else
-    if (J->L.wave_general) LAUNCH(c, "zenc_write_wave", k_zenc_write_wave, cdiv(nblk, ZWW_BLOCKS), 256, 512u + 4u * ZWW_OBUF, J->src, (u64)J->n, nblk, (const ZEncPlan *)J->plan, (const u16 *)J->codes, (const u8 *)J->trees,
-           (const u64 *)J->offs, d_dst, hdr, J->L.not_last);
-    if (J->direct && J->dloc.loc) LAUNCH(c, "zenc_write_direct", k_zenc_write_direct_loc, nblk, 256, 0, J->dloc, nblk, (const ZEncPlan *)J->plan, (const u8 *)J->trees, (const u64 *)J->offs, d_dst, hdr, J->L.not_last);
-    else if (J->direct) LAUNCH(c, "zenc_write_direct", k_zenc_write_direct, nblk, 256, 0, J->src, nblk, (const ZEncPlan *)J->plan, (const u8 *)J->trees, (const u64 *)J->offs, d_dst, hdr, J->L.not_last);
-    if (aux && hipStreamWaitEvent(c->stream, c->split_ev[ZSPLIT_MAX - 1], 0) != hipSuccess) return ctx_fail(c, NAF_GPU_EHIP, "zenc_write_wave beside the gather: join failed");
-    if (!place) { if (J->have_total) total = J->known_total; else if ((rc = ctx_readback(c, &total, J->offs + nblk + 1, 8))) return rc; }
-    *out_len = hdr + total;
+    if (rc) return rc;
+    if (!place && (rc = zenc_total(c, J, &total))) return rc;
+    *out_len = J->hdr + total;
     return 0;
 }
 // The size of the frame a begun job will write (its header and its blocks), read back ONCE and kept for zstd_encode_finish: a caller that
@@ -1845,7 +2041,7 @@ int zstd_encode_size(naf_gpu_ctx *c, ZencJob *J, size_t *frame_len)
     if (J->empty) { *frame_len = J->hdr; return 0; }
     if (!J->have_total) {
         u64 t = 0; int rc = ctx_readback(c, &t, J->offs + J->nblk + 1, 8); if (rc) return rc;
-        J->known_total = t; J->have_total = 1;
+        J->known_total = t; J->have_total = 1; J->own_sync = 1;
     }
     *frame_len = J->hdr + J->known_total;
     return 0;
